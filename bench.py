@@ -6,7 +6,17 @@ directory image, then inflate the resulting payloads.  `value` = raw bytes / (de
 all ranks (max over ranks of the timed region).  Ranks own disjoint files (shards partition one-per-rank, SURVEY.md
 section 8e): weak scaling, no data-path collective.
 
-With no --workload the run covers BOTH headline configurations and prints ONE JSON line:
+A plain run (no --full) does only what the headline figure needs: it builds the batch, warms up, times --steps steps, writes
+the last step's outputs if --dump-outputs DIR is given, and prints ONE JSON line (metric, value, unit, ms_per_step,
+higher_is_better, dtype, config).  With no --workload that is BASELINE configs[2] (below).  Everything else -- the second
+headline configuration, the direction split, per-kernel times and roofline, verification, the CPU baseline and the e2e legs --
+runs with --full only, exactly as described below.
+
+--dump-outputs DIR writes, for each timed workload, what its last timed step handed back as DIR/<workload>_<name>.npy (float32 /
+float64, 64 MB at most in all; see dump_outputs): per-chunk lengths, status and checksums of the payloads and the decoded bytes,
+and the whole bytes of a fixed, seeded sample of chunks.  The inputs are the same on every run with the same arguments.
+
+With --full and no --workload the run covers BOTH headline configurations and prints ONE JSON line:
   top level   BASELINE configs[2]: 10 000 x 256 KiB text-like files (50 000 chunks; the LZ77 + Huffman kernels) -- the line's `value`
   "random"    BASELINE configs[1]: 10 000 x 256 KiB incompressible files (stored-block path), same fields
   "e2e"       the drop-in CLI (`main compress` + `main decompress`) on the same two directories and on a 4x larger text one: banner seconds,
@@ -14,7 +24,7 @@ With no --workload the run covers BOTH headline configurations and prints ONE JS
 Other workloads on request: --workload small_files (configs[3]: ~370 000 image-like files, ~2.5 GB) and
 --workload one_file --decompress-only (configs[4] scaled to fit: ONE file, its records split over the ranks).
 
-Every line also carries
+Every --full line also carries
   roofline      dominant kernel's (raw + payload) bytes per launch / its mean launch duration, measured with HIP events on
                 the codec's own stream, against the 8 TB/s HBM peak; plus whole-direction fractions against 8.0 and 6.29 TB/s
   verified      outside the timed region: every decoded byte compared with the input on the device (not lengths), and
@@ -52,7 +62,12 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--workload", default="both", choices=["both", "random", "text", "small_files", "one_file"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (second workload, direction split, per-kernel times, "
+                         "roofline, verification, CPU baseline, e2e legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<workload>_<name>.npy")
+    ap.add_argument("--workload", default="both", choices=["both", "random", "text", "small_files", "one_file"],
+                    help="both: text (the headline), and with --full also random")
     ap.add_argument("--files", type=int, default=None, help="files per GPU (default 10000; small_files: 370000)")
     ap.add_argument("--file-bytes", type=int, default=262144)
     ap.add_argument("--one-file-bytes", type=int, default=8 << 30, help="one_file: size of the single file (BASELINE: 64 GiB)")
@@ -315,6 +330,54 @@ def e2e_legs(args):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ outputs of the timed step
+DUMP_MAX_CHUNKS = 131072       # per-chunk figures of at most this many chunks (a fixed, seeded sample beyond)
+DUMP_SAMPLE_CHUNKS = 32        # chunks whose whole payload and decoded bytes are written
+DUMP_SEED = 1234
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _masked_rows(torch, buf, lens, rows):
+    """Slots `rows` of a [chunk][STRIDE] byte buffer as int64, bytes at or beyond the chunk's length zeroed (they are not output)."""
+    col = torch.arange(STRIDE, device=buf.device, dtype=torch.int64).view(1, -1)
+    x = buf.view(-1, STRIDE)[rows].to(torch.int64)
+    return x * (col < lens[rows].to(torch.int64).view(-1, 1)), col
+
+
+def _row_sums(torch, buf, lens, rows):
+    """(len(rows), 2) float64: sum of a chunk's valid bytes and sum of byte * (position + 1) -- both exact in float64 (< 2^40)."""
+    out = []
+    for c0 in range(0, rows.numel(), 512):
+        x, col = _masked_rows(torch, buf, lens, rows[c0:c0 + 512])
+        out.append(torch.stack([x.sum(1), (x * (col + 1)).sum(1)], 1).cpu())
+    return torch.cat(out).double().numpy() if out else torch.zeros((0, 2), dtype=torch.float64).numpy()
+
+
+def dump_outputs(torch, out_dir, prefix, with_payloads, d_out, d_olen, d_back, d_blen, d_stat):
+    """What one timed step hands its caller -- the payloads and their lengths (deflate), the decoded bytes, their lengths and the
+    per-chunk status (inflate) -- as out_dir/<prefix>_<name>.npy: per-chunk lengths, status and checksums for every chunk (or a
+    fixed, seeded sample of DUMP_MAX_CHUNKS), and the whole bytes of DUMP_SAMPLE_CHUNKS seeded chunks.  with_payloads=False: the
+    step was inflate only (the payloads were its input).  Returns the bytes written."""
+    import numpy as np
+    n = d_blen.numel()
+    rng = np.random.RandomState(DUMP_SEED)
+    idx = np.arange(n) if n <= DUMP_MAX_CHUNKS else np.sort(rng.choice(n, DUMP_MAX_CHUNKS, replace=False))
+    pick = np.sort(rng.choice(n, min(n, DUMP_SAMPLE_CHUNKS), replace=False))
+    rows = torch.from_numpy(idx).to(d_blen.device)
+    prow = torch.from_numpy(pick).to(d_blen.device)
+    arrays = {"chunk_index": idx.astype(np.float64), "sample_index": pick.astype(np.float64)}
+    parts = [("decoded", d_back, d_blen)] + ([("payload", d_out, d_olen)] if with_payloads else [])
+    for nm, buf, lens in parts:
+        arrays[nm + "_len"] = lens[rows].cpu().numpy().astype(np.float32)
+        arrays[nm + "_sums"] = _row_sums(torch, buf, lens, rows)
+        arrays[nm + "_sample"] = _masked_rows(torch, buf, lens, prow)[0].to(torch.float32).cpu().numpy()
+    arrays["inflate_status"] = d_stat[rows].cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for nm, a in arrays.items():
+        np.save(os.path.join(out_dir, "%s_%s.npy" % (prefix, nm)), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 # ------------------------------------------------------------------------------------------------ verification
 def verify_bytes(torch, d_in, d_len, d_olen, d_back, d_blen, d_stat):
     """Every chunk, on the device: the decoded bytes are the input's bytes.  A chunk either comes back whole, or it is one
@@ -410,7 +473,8 @@ def run_workload(args, torch, dist, codec, dev, world, rank, name):
         cpu_bytes = min(total, args.cpu_sample_one_file_bytes)
 
         cpu_rows = min(n, (cpu_bytes + CHUNK - 1) // CHUNK)
-        head_host = view[:cpu_rows, :CHUNK].cpu().numpy()          # (rank 0's first records = the file's first bytes)
+        # (rank 0's first records = the file's first bytes; only the CPU baseline of a --full run reads them)
+        head_host = view[:cpu_rows, :CHUNK].cpu().numpy() if args.full else None
 
         def populate(src):          # the file's first cpu_bytes bytes: the same records, in the same order
             blob = head_host.tobytes()[:cpu_bytes]
@@ -462,6 +526,30 @@ def run_workload(args, torch, dist, codec, dev, world, rank, name):
         dist.all_gather(every, mine)
         per_rank_ms = [round(float(x.item()) / args.steps * 1e3, 3) for x in every]
         elapsed = max(float(x.item()) for x in every)
+    raw_all = raw_bytes
+    if world > 1:
+        tot = torch.tensor([float(raw_bytes)], dtype=torch.float64, device=cpu_dev if args.rehearse_on_one_gpu else dev)
+        dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+        raw_all = float(tot.item())
+
+    res = dumped = None
+    if rank == 0:
+        if args.dump_outputs:           # (rank 0's share of a multi-rank job)
+            dumped = dump_outputs(torch, args.dump_outputs, name, not decompress_only, d_out, d_olen, d_back, d_blen, d_stat)
+        res = {
+            "value": round(raw_all * args.steps / elapsed / 1e9, 3), "unit": "GB/s",
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "ms_per_step_by_rank": per_rank_ms, "scaling": scaling,
+            "config": {"workload": desc, "chunk_bytes": CHUNK, "max_batch_chunks": args.max_batch,
+                       "parallelism": ("record-range-per-gpu x%d" if name == "one_file" else "shard-per-gpu x%d") % world,
+                       **({"scope_note": "device-resident inflate of the record ranges only.  Through the CLI (zwz_decompress_dir_ranked) ONE file is bounded by its "
+                                         "single MD5 stream (~0.65 GB/s on one host core, the reference's verification.cpp:6-30 semantics): a 64 GiB file takes "
+                                         "~105 s there whatever N is -- see DESIGN.md section 5"} if name == "one_file" else {}),
+                       "timed": "inflate only" if decompress_only else "deflate + inflate"},
+        }
+    if not args.full:
+        del d_in, d_out, d_back
+        torch.cuda.empty_cache()
+        return res, dumped
 
     # direction split + per-kernel times (untimed extra passes, HIP events on the codec's stream)
     fence()
@@ -483,17 +571,12 @@ def run_workload(args, torch, dist, codec, dev, world, rank, name):
     verified["oracle"] = verify_oracle_sample(torch, args.oracle_sample, d_in, d_len, d_out, d_olen, d_back, d_blen)
     verified["ok"] = bool(verified["length_rule_ok"] and verified["chunks_with_wrong_bytes"] == 0 and
                           verified["oracle"]["payload_mismatches"] == 0 and verified["oracle"]["decode_mismatches"] == 0)
-    raw_all = raw_bytes
     if world > 1:
-        tot = torch.tensor([float(raw_bytes)], dtype=torch.float64, device=cpu_dev if args.rehearse_on_one_gpu else dev)
-        dist.all_reduce(tot, op=dist.ReduceOp.SUM)
-        raw_all = float(tot.item())
         flag = torch.tensor([0.0 if verified["ok"] else 1.0], dtype=torch.float64, device=cpu_dev if args.rehearse_on_one_gpu else dev)
         dist.all_reduce(flag, op=dist.ReduceOp.SUM)
         verified["ranks_failed"] = int(flag.item())
         verified["ok"] = verified["ok"] and flag.item() == 0
 
-    res = None
     if rank == 0:
         launches_per_pass = (n + args.max_batch - 1) // args.max_batch
         timed = {k: v for k, v in stage.items() if not (decompress_only and k != "inflate")}
@@ -514,15 +597,7 @@ def run_workload(args, torch, dist, codec, dev, world, rank, name):
             got = [per_kernel[k]["hbm_bytes_per_launch"] for k in stage_kernels.get(dom, [dom]) if k in per_kernel]
             traffic = sum(got) if got else None
         comp_s, dec_s = c1 - c0, c2 - c1
-        res = {
-            "value": round(raw_all * args.steps / elapsed / 1e9, 3), "unit": "GB/s",
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "ms_per_step_by_rank": per_rank_ms, "scaling": scaling,
-            "config": {"workload": desc, "chunk_bytes": CHUNK, "max_batch_chunks": args.max_batch,
-                       "parallelism": ("record-range-per-gpu x%d" if name == "one_file" else "shard-per-gpu x%d") % world,
-                       **({"scope_note": "device-resident inflate of the record ranges only.  Through the CLI (zwz_decompress_dir_ranked) ONE file is bounded by its "
-                                         "single MD5 stream (~0.65 GB/s on one host core, the reference's verification.cpp:6-30 semantics): a 64 GiB file takes "
-                                         "~105 s there whatever N is -- see DESIGN.md section 5"} if name == "one_file" else {}),
-                       "timed": "inflate only" if decompress_only else "deflate + inflate"},
+        res.update({
             "compress_GBps": round(raw_bytes / comp_s / 1e9, 3), "decompress_GBps": round(raw_bytes / dec_s / 1e9, 3),
             "payload_ratio": round(payload_bytes / raw_bytes, 4), "verified": verified,
             "stage_ms_per_pass": {k: round(v / prof_passes, 3) for k, v in stage.items()},
@@ -535,7 +610,7 @@ def run_workload(args, torch, dist, codec, dev, world, rank, name):
                          "compress_frac_of_6.29TBps": round((raw_bytes + payload_bytes) / comp_s / 1e9 / HBM_ACHIEVABLE_GBS, 5),
                          "decompress_frac_of_8TBps": round((payload_bytes + back_bytes) / dec_s / 1e9 / HBM_PEAK_GBS, 5),
                          "decompress_frac_of_6.29TBps": round((payload_bytes + back_bytes) / dec_s / 1e9 / HBM_ACHIEVABLE_GBS, 5)},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             try:
                 if cpu_files:
@@ -546,7 +621,7 @@ def run_workload(args, torch, dist, codec, dev, world, rank, name):
                 res["cpu_baseline"] = {"value": None, "unit": "GB/s", "cores": 0, "kind": "reference", "sample": None, "note": "CPU baseline failed: %r" % (e,)}
     del d_in, d_out, d_back
     torch.cuda.empty_cache()
-    return res
+    return res, dumped
 
 
 def main():
@@ -596,9 +671,18 @@ def main():
         dist.barrier()
     codec = zwz.Codec(local, args.max_batch)
 
-    # (both: the text-like configuration first -- it is the line's `value` -- then the incompressible one)
-    names = ["text", "random"] if args.workload == "both" else [args.workload]
-    results = [run_workload(args, torch, dist, codec, dev, world, rank, nm) for nm in names]
+    # (both: the text-like configuration first -- it is the line's `value` -- then, with --full, the incompressible one)
+    if args.workload == "both":
+        names = ["text", "random"] if args.full else ["text"]
+    else:
+        names = [args.workload]
+    results, dumped = [], 0
+    for nm in names:
+        r, d = run_workload(args, torch, dist, codec, dev, world, rank, nm)
+        results.append(r)
+        dumped += d or 0
+    if dumped > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs wrote %d bytes, more than the %d allowed" % (dumped, DUMP_LIMIT_BYTES))
     if rank == 0:
         head = results[0]
         line = {"metric": "compress+decompress GB/s (raw bytes / (deflate + inflate time)), .zwz bit-exact",
@@ -627,10 +711,10 @@ def main():
             line["roofline_text_frac"] = line["roofline"]["frac"]
             line["value_note"] = ("value = BASELINE configs[2] (10 000 x 256 KiB text-like files: dynamic-Huffman blocks, the LZ77 + Huffman kernels); "
                                   "value_random = configs[1] (incompressible files: stored blocks) -- same size, same step.  Until round 4 `value` was configs[1].")
-    ok = all(r is None or r["verified"]["ok"] for r in results)
+    ok = not args.full or all(r is None or r["verified"]["ok"] for r in results)
     codec.close()
     e2e = None
-    if rank == 0 and world == 1 and args.workload == "both" and not args.no_e2e:
+    if rank == 0 and world == 1 and args.workload == "both" and args.full and not args.no_e2e:
         # What a user of the reference's command line sees (main.cpp:78-159): the product's `main compress` + `main decompress` on the same
         # 10 000 x 256 KiB directories, on this box's file system, page cache warm.  NOT `value`: file I/O, PCIe and the process's fixed
         # costs are in it.  The GPU workspace of the runs above is released first (two processes share the card for a moment).

@@ -532,7 +532,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     box's one GPU over gloo -- the same code the driver's --gpus 8 run goes through, minus RCCL (main.cpp:24-41,131,144 are
     the collectives it stands in for).  Not a measurement."""
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--files", "200", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse-on-one-gpu", "--files", "200", "--steps", "2",
                         "--warmup", "1", "--no-cpu-baseline", "--max-batch", "2048", "--oracle-sample", "64"],
                        capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -545,3 +545,31 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     assert d["random"]["verified"]["ok"] and len(d["random"]["ms_per_step_by_rank"]) == 2        # (the line's own fields are the text configuration's)
     assert d["value"] > 0 and d["value"] == d["value_text"] and d["value_random"] == d["random"]["value"] and d["scaling"] == "weak"
     assert "e2e" not in d                                                                            # the CLI legs are a one-rank affair
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_outputs(oracle, tmp_path):
+    """A plain bench.py run times the headline (text) workload only and prints the headline fields, nothing of --full; with
+    --dump-outputs the sampled chunks on disk are the oracle's payloads of the workload's own input bytes and decode back to them."""
+    import sys
+    import workloads
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--files", "200", "--steps", "3", "--warmup", "1",
+                        "--max-batch", "2048", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "GB/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "u8" and d["metric"].startswith("compress+decompress GB/s")
+    assert not {"verified", "random", "e2e", "roofline", "cpu_baseline", "stage_ms_per_pass"} & set(d)
+    files = sorted(os.listdir(out))
+    assert files and all(f.startswith("text_") for f in files) and sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    dump = {f[len("text_"):-4]: np.load(out / f) for f in files}
+    per_file = 262144 // CHUNK + 1
+    assert (dump["chunk_index"] == np.arange(200 * per_file)).all() and (dump["inflate_status"] == 0).all()
+    for j, k in enumerate(dump["sample_index"].astype(np.int64)):
+        f, part = divmod(int(k), per_file)
+        chunk = corpus.text_like(workloads.TEXT_SEED0 + f, 262144)[part * CHUNK:(part + 1) * CHUNK]
+        plen, blen = int(dump["payload_len"][k]), int(dump["decoded_len"][k])
+        assert dump["payload_sample"][j, :plen].astype(np.uint8).tobytes() == oracle.payload(chunk), k
+        assert blen == len(chunk) and dump["decoded_sample"][j, :blen].astype(np.uint8).tobytes() == chunk, k

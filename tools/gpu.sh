@@ -10,7 +10,7 @@
 #   tools/gpu.sh variant <tag> "<flags>" [bench args]  a build with other compile-time constants (libzwz_hip_exp.so too) and one bench run on it
 #   tools/gpu.sh soak   <tag> [chunks] [seed]          tools/soak_gpu.py
 #   tools/gpu.sh refresh <tag>                         the evidence behind DESIGN.md's tables: prof of both headline workloads at full
-#                                                      size -> profiles/<tag>_*_rocprofv3_summary.txt + profiles/traffic_*.json, then the default bench line
+#                                                      size -> profiles/<tag>_*_rocprofv3_summary.txt + profiles/traffic_*.json, then the --full bench line
 # Steps inside one call are joined with &&: nothing runs on the GPU after a step failed or timed out.
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -63,7 +63,7 @@ trace)
   TAG=${1:-t}; W=${2:-text}; F=${3:-2000}
   O=$R/gpurun_out/trace_${TAG}_$W; rm -rf $O; mkdir -p $O
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --workload $W --files $F > $O/trace.log 2>&1 || { echo "trace failed"; tail -20 $O/trace.log; exit 1; }
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --workload $W --files $F > $O/trace.log 2>&1 || { echo "trace failed"; tail -20 $O/trace.log; exit 1; }
   kernel_table $O/trace; tail -c 300 $O/trace.log ;;
 prof)
   TAG=${1:-p}; W=${2:-text}; F=${3:-10000}
@@ -71,7 +71,7 @@ prof)
   # so on the CPU side, delete gpurun_out/prof_<tag>_<workload> before a second run under the same tag)
   O=$R/gpurun_out/prof_${TAG}_$W; rm -rf $O; mkdir -p $O
   cd /tmp && export TMPDIR=/tmp
-  ARGS="$R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --workload $W --files $F"
+  ARGS="$R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --workload $W --files $F"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $ARGS > $O/trace.log 2>&1 && \
   timeout -k 10 400 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_ANY --output-format csv -d $O/pmc1 -- python3 $ARGS > $O/pmc1.log 2>&1 && \
   timeout -k 10 400 rocprofv3 --pmc SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU --output-format csv -d $O/pmc2 -- python3 $ARGS > $O/pmc2.log 2>&1 && \
@@ -83,7 +83,7 @@ times)
   case $K in band) D=ZWZ_BAND_EXP; E=ZWZ_BAND_TIMES;; match) D=ZWZ_MATCH_EXP; E=ZWZ_MATCH_TIMES;; parse) D=ZWZ_PARSE_EXP; E=ZWZ_PARSE_TIMES;;
              enc) D=ZWZ_ENC_EXP; E=ZWZ_ENC_TIMES;; inf) D=ZWZ_INF_EXP; E=ZWZ_INF_TIMES;; lazy) D=ZWZ_LAZY_EXP; E=ZWZ_LAZY_TIMES;; *) echo "times: band|match|parse|enc|inf|lazy"; exit 2;; esac
   make -C $PKG EXP_FLAGS="-D$D=$X" libzwz_hip_exp.so > $R/gpurun_out/exp_build.log 2>&1 || { echo "experiment build failed"; tail -30 $R/gpurun_out/exp_build.log; exit 1; }
-  cd $R && ZWZ_LIB=$PKG/libzwz_hip_exp.so env $E=1 timeout -k 10 400 python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --workload $W --files $F 2>&1 | grep -E "$E|EXPERIMENT|stage_ms" | cut -c1-700 ;;
+  cd $R && ZWZ_LIB=$PKG/libzwz_hip_exp.so env $E=1 timeout -k 10 400 python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --workload $W --files $F 2>&1 | grep -E "$E|EXPERIMENT|stage_ms" | cut -c1-700 ;;
 variant)   # <tag> "<compiler flags>" [bench.py args ...]: a build with other constants (e.g. -DZWZ_INF_WAVES=4) as libzwz_hip_exp.so, one bench run on it
   TAG=${1:-v}; FL=$2; shift; shift
   make -C $PKG EXP_FLAGS="$FL" libzwz_hip_exp.so > $R/gpurun_out/exp_build.log 2>&1 || { echo "variant build failed"; tail -30 $R/gpurun_out/exp_build.log; exit 1; }
@@ -105,9 +105,8 @@ refresh)
     cp gpurun_out/${TAG}_traffic_$w.json profiles/traffic_$w.json; done && \
   # (profiles/ on the GPU box is a scratch copy: bench.py below reads the fresh traffic files from it; on the CPU side copy
   #  gpurun_out/<tag>_traffic_*.json and gpurun_out/<tag>_*_rocprofv3_summary.txt into profiles/ and commit them)
-  timeout -k 10 900 python bench.py > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err; rc=$?
+  bash $R/tools/gpu.sh bench ${TAG} --full; rc=$?
   tail -c 300 gpurun_out/bench_${TAG}.err; grep -A12 "kernel stats" gpurun_out/${TAG}_text_rocprofv3_summary.txt | cut -c1-150
-  [ $rc -eq 0 ] && bench_table gpurun_out/bench_${TAG}.json
   exit $rc ;;
 *)
   sed -n 2,16p $0; exit 2 ;;
