@@ -52,7 +52,8 @@ typedef enum zwz_status {
     ZWZ_E_NO_DEVICE = -3, /* no usable gfx950 device (none visible, or it fails every one of zwz_ctx_create's self-tests: see zwz_ctx_set_option) */
     ZWZ_E_IO = -4,        /* file system error */
     ZWZ_E_NOMEM = -5,
-    ZWZ_E_FORMAT = -6     /* malformed .zwz shard */
+    ZWZ_E_FORMAT = -6,    /* malformed .zwz shard, or input that is not BGZF (zwz_bgzf_*) */
+    ZWZ_E_CHECKSUM = -7   /* a BGZF member's CRC-32 or ISIZE does not match its decoded bytes */
 } zwz_status;
 
 /* Per-chunk status written by the inflate entry points (the reference ignores zlib's return
@@ -63,6 +64,13 @@ typedef enum zwz_inflate_status {
     ZWZ_INF_DATA_ERROR = 2,  /* invalid stream: output up to the error kept */
     ZWZ_INF_OVERFLOW = 3     /* stream decodes past 65535 bytes (not producible by the reference) */
 } zwz_inflate_status;
+
+/* Per-member status of zwz_bgzf_decompress_dev beyond the inflate codes above (0 = the member decoded and matched). */
+typedef enum zwz_bgzf_member_status {
+    ZWZ_BGZF_BAD_MEMBER = 16,      /* the member's header or size does not parse (an offset list not made by zwz_bgzf_index) */
+    ZWZ_BGZF_ISIZE_MISMATCH = 17,  /* decoded length differs from the stored ISIZE */
+    ZWZ_BGZF_CRC_MISMATCH = 18     /* CRC-32 of the decoded bytes differs from the stored one */
+} zwz_bgzf_member_status;
 
 typedef struct zwz_ctx zwz_ctx;
 
@@ -178,6 +186,31 @@ int zwz_ctx_set_chunk_size(zwz_ctx *ctx, uint32_t bytes);
  * understood is reported on stderr and ignored).  ZWZ_E_INVALID for an unknown name or value; ZWZ_E_NO_DEVICE for a kernel form
  * that failed its self-test on this device at zwz_ctx_create -- it stays off ("auto" / "" then mean what the device can run). */
 int zwz_ctx_set_option(zwz_ctx *ctx, const char *name, const char *value);
+
+/* ---- BGZF (blocked gzip, SAM/BAM specification section 4.1): .gz files that gzip, zcat and htslib read -----------------------
+ * Compression cuts the input into blocks of 65280 bytes (htslib's BGZF_BLOCK_SIZE; the last one shorter, none for an empty input)
+ * and writes each as one gzip member: 1f 8b 08 04 | 00000000 | 00 ff | 06 00 | 'B' 'C' 02 00 | BSIZE-1 (u16 LE) | raw deflate |
+ * CRC-32 (LE) | ISIZE (LE), the raw deflate being bytes [2, len - 4) of the block's zlib 1.2.11 level-6 stream (the bytes of
+ * zwz_deflate_batch_dev), then the standard 28-byte EOF member.  Decompression accepts any BGZF: other extra subfields around BC,
+ * any deflate level, empty members anywhere (two BGZF files one after the other), a missing EOF member; it rejects (ZWZ_E_FORMAT,
+ * zwz_last_error() naming the member and its byte offset) a member without BC, a BSIZE past the end, trailing bytes that are not
+ * a member and ISIZE > 65535.  A CRC-32 or ISIZE mismatch is ZWZ_E_CHECKSUM.  All of it runs on the GPU but the header walk. */
+uint64_t zwz_bgzf_bound(uint64_t n);   /* worst-case compressed bytes for n input bytes, EOF member included */
+/* Asynchronous on the context's stream.  d_in 16-byte aligned and readable up to n rounded up to 16 (as every slot of
+ * zwz_deflate_batch_dev); out_cap >= zwz_bgzf_bound(n) (else ZWZ_E_INVALID).  *d_out_len (device u64) receives the total length. */
+int zwz_bgzf_compress_dev(zwz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_len);
+/* Host-only walk of a BGZF file in memory (no GPU): member_off[0..*n_members) and the total decoded size *raw_len.  member_off may
+ * be NULL to count only; with fewer than *n_members entries of cap the call is ZWZ_E_INVALID (*n_members, *raw_len still set). */
+int zwz_bgzf_index(const uint8_t *gz, uint64_t n, uint64_t *member_off, uint32_t cap, uint32_t *n_members, uint64_t *raw_len);
+/* Asynchronous.  d_gz (gz_len bytes, 16-byte aligned) and d_member_off (device copies of zwz_bgzf_index's offsets) describe the
+ * members; d_out holds raw_len bytes; *d_out_len (device u64) receives the decoded length; d_status[i] per member: 0, an inflate
+ * code (zwz_inflate_status) or a zwz_bgzf_member_status. */
+int zwz_bgzf_decompress_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len, const uint64_t *d_member_off, uint32_t n_members,
+                            uint8_t *d_out, uint64_t *d_out_len, uint32_t *d_status);
+/* Whole files of any size, streamed in slices through pinned staging (reading, the GPU and writing overlap).  dst is written as
+ * <dst>.part and renamed only on success; on failure no dst is left. */
+int zwz_bgzf_compress_file(zwz_ctx *ctx, const char *src, const char *dst);
+int zwz_bgzf_decompress_file(zwz_ctx *ctx, const char *src, const char *dst);
 
 #ifdef __cplusplus
 }

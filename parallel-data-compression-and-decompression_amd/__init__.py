@@ -10,6 +10,9 @@ Names and argument meaning follow the reference:
 plus the batch form of the two zlib call sites (compression.cpp:119-134, decompression.cpp:16-36):
     Codec.deflate_chunks / Codec.inflate_chunks                (host bytes)
     Codec.deflate_dev / Codec.inflate_dev                      (device-resident torch tensors)
+and BGZF (blocked gzip, readable by gzip / zcat / htslib; no reference counterpart):
+    Codec.bgzf_compress / Codec.bgzf_decompress                (bytes or a CUDA uint8 tensor)
+    Codec.bgzf_compress_file / Codec.bgzf_decompress_file      (whole files, streamed)
 
 There is no CPU fallback: importing works anywhere (so the build can be checked), but every codec
 call needs the HIP library and a GPU and raises ZwzError otherwise.
@@ -75,11 +78,22 @@ def lib():
         L.zwz_decompress_dir_ranked.argtypes = [vp, c.c_char_p, c.c_char_p, c.c_int, c.c_int, ALLGATHER_FN, vp, c.POINTER(c.c_int)]
         L.zwz_ctx_set_chunk_size.argtypes = [vp, u32]
         L.zwz_ctx_set_option.argtypes = [vp, c.c_char_p, c.c_char_p]
+        L.zwz_bgzf_bound.restype = u64
+        L.zwz_bgzf_bound.argtypes = [u64]
+        L.zwz_bgzf_compress_dev.argtypes = [vp, vp, u64, vp, u64, vp]
+        L.zwz_bgzf_index.argtypes = [vp, u64, vp, u32, c.POINTER(u32), c.POINTER(u64)]
+        L.zwz_bgzf_decompress_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp]
+        L.zwz_bgzf_compress_file.argtypes = [vp, c.c_char_p, c.c_char_p]
+        L.zwz_bgzf_decompress_file.argtypes = [vp, c.c_char_p, c.c_char_p]
         _lib = L
     return _lib
 
 
 E_FORMAT = -6
+E_CHECKSUM = -7
+BGZF_BLOCK_SIZE = 65280     # raw bytes per BGZF member (htslib's BGZF_BLOCK_SIZE)
+# per-member status of zwz_bgzf_decompress_dev beyond the inflate codes (include/zwz.h)
+BGZF_BAD_MEMBER, BGZF_ISIZE_MISMATCH, BGZF_CRC_MISMATCH = 16, 17, 18
 
 
 def _check(rc, what, **extra):
@@ -220,6 +234,66 @@ class Codec:
         _check(rc, "zwz_decompress_dir", md5_mismatches=bad.value)
         return bad.value
 
+    # ---- BGZF (include/zwz.h: zwz_bgzf_*) -------------------------------------------------------
+    # bgzf_compress / bgzf_decompress hold their buffers in torch tensors.  torch loads its own HIP runtime, which must open the GPU
+    # before this codec's library does: touch the device through torch (torch.zeros(1, device="cuda")) before creating the Codec.
+    def bgzf_compress(self, data):
+        """bytes -> BGZF bytes; a CUDA uint8 tensor -> a CUDA uint8 tensor of the BGZF stream (on this codec's device)."""
+        import torch
+        as_tensor = isinstance(data, torch.Tensor)
+        d_in = _device_input(torch, data, self.device)
+        n = data.numel() if as_tensor else len(data)
+        cap = lib().zwz_bgzf_bound(n)
+        d_out = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+        d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+        torch.cuda.synchronize(d_in.device)
+        _check(lib().zwz_bgzf_compress_dev(self._h, d_in.data_ptr(), n, d_out.data_ptr(), cap, d_len.data_ptr()), "zwz_bgzf_compress_dev")
+        self.sync()
+        n_out = int(d_len.item())
+        if n_out < 0:       # ~0: a member body reached the deflate slot's length (include/zwz.h; not producible from 65 280-byte blocks)
+            raise ZwzError("zwz_bgzf_compress_dev: a member body was cut")
+        out = d_out[:n_out]
+        return out if as_tensor else out.cpu().numpy().tobytes()
+
+    def bgzf_decompress(self, data):
+        """BGZF bytes -> bytes; a CUDA uint8 tensor -> a CUDA uint8 tensor.  The member headers are walked on the host (a tensor's
+        bytes are copied there for it); everything else runs on the GPU.  ZwzError with status E_FORMAT / E_CHECKSUM on damage."""
+        import numpy as np
+        import torch
+        as_tensor = isinstance(data, torch.Tensor)
+        host = data.detach().cpu().numpy().tobytes() if as_tensor else bytes(data)
+        count, raw = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        _check(lib().zwz_bgzf_index(host, len(host), None, 0, ctypes.byref(count), ctypes.byref(raw)), "zwz_bgzf_index")
+        offs = np.zeros(max(count.value, 1), dtype=np.uint64)
+        _check(lib().zwz_bgzf_index(host, len(host), offs.ctypes.data, count.value, ctypes.byref(count), ctypes.byref(raw)), "zwz_bgzf_index")
+        dev = torch.device("cuda", self.device)
+        d_gz = _device_input(torch, data if as_tensor else host, self.device)
+        d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
+        d_out = torch.empty(max(raw.value, 1), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(count.value, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        _check(lib().zwz_bgzf_decompress_dev(self._h, d_gz.data_ptr(), len(host), d_off.data_ptr(), count.value, d_out.data_ptr(),
+                                             d_len.data_ptr(), d_st.data_ptr()), "zwz_bgzf_decompress_dev")
+        self.sync()
+        st = d_st[:count.value].cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if len(bad):
+            i, s = int(bad[0]), int(st[bad[0]])
+            code = E_CHECKSUM if s in (BGZF_ISIZE_MISMATCH, BGZF_CRC_MISMATCH) else E_FORMAT
+            err = ZwzError("zwz_bgzf_decompress_dev: member %d at byte offset %d: status %d" % (i, int(offs[i]), s))
+            err.status = code
+            raise err
+        out = d_out[:int(d_len.item())]
+        return out if as_tensor else out.cpu().numpy().tobytes()
+
+    def bgzf_compress_file(self, src, dst):
+        """src -> dst as BGZF, streamed through pinned staging (any size); dst appears only on success."""
+        _check(lib().zwz_bgzf_compress_file(self._h, os.fsencode(src), os.fsencode(dst)), "zwz_bgzf_compress_file")
+
+    def bgzf_decompress_file(self, src, dst):
+        _check(lib().zwz_bgzf_decompress_file(self._h, os.fsencode(src), os.fsencode(dst)), "zwz_bgzf_decompress_file")
+
     def set_option(self, name, value):
         """Test / experiment switches of this context (include/zwz.h: zwz_ctx_set_option): "match" = auto | walk | band | lazy |
         autoband | autolazy, "plan" = wave | serial, "inflate_header" = wave | serial.  Every choice produces the same bytes; a form that
@@ -230,6 +304,26 @@ class Codec:
         """Raw bytes per Chunk for do_compression (0 = the reference's 65535).  Opt-in, not bit-exact with the reference's
         shards; LOSSLESS_CHUNK_SIZE never truncates."""
         _check(lib().zwz_ctx_set_chunk_size(self._h, nbytes), "zwz_ctx_set_chunk_size")
+
+
+def _device_input(torch, data, device):
+    """A 16-byte aligned CUDA uint8 tensor holding `data` and readable up to its length rounded up to 16 (the kernels read whole
+    16-byte vectors): a suitable tensor as it is, anything else copied."""
+    if isinstance(data, torch.Tensor):
+        if data.dtype != torch.uint8 or not data.is_cuda:
+            raise ValueError("expected a CUDA uint8 tensor")
+        t = data.reshape(-1)
+        room = t.untyped_storage().nbytes() - t.storage_offset()
+        if t.is_contiguous() and t.data_ptr() % 16 == 0 and room >= (t.numel() + 15) // 16 * 16 and t.device.index == device:
+            return t
+        out = torch.empty((t.numel() + 15) // 16 * 16 or 16, dtype=torch.uint8, device=torch.device("cuda", device))
+        out[:t.numel()].copy_(t)
+        return out
+    n = len(data)
+    buf = torch.zeros((n + 15) // 16 * 16 or 16, dtype=torch.uint8)
+    if n:
+        buf[:n] = torch.frombuffer(bytearray(data), dtype=torch.uint8)
+    return buf.to(torch.device("cuda", device))
 
 
 def sort_files_by_size(path):
@@ -264,3 +358,34 @@ def do_compression(input_dir, output_dir, file_record, world_rank, world_size=1)
 
 def do_decompression(input_dir, output_dir, world_rank=0, world_size=1, allgather=None):
     return _codec().do_decompression(input_dir, output_dir, world_rank, world_size, allgather)
+
+
+def bgzf_bound(n):
+    """Worst-case BGZF size of n input bytes (EOF member included); needs no GPU."""
+    return lib().zwz_bgzf_bound(n)
+
+
+def bgzf_index(gz):
+    """(member offsets, total decoded bytes) of a BGZF byte string, walked on the host (no GPU)."""
+    import numpy as np
+    count, raw = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    _check(lib().zwz_bgzf_index(gz, len(gz), None, 0, ctypes.byref(count), ctypes.byref(raw)), "zwz_bgzf_index")
+    offs = np.zeros(max(count.value, 1), dtype=np.uint64)
+    _check(lib().zwz_bgzf_index(gz, len(gz), offs.ctypes.data, count.value, ctypes.byref(count), ctypes.byref(raw)), "zwz_bgzf_index")
+    return [int(o) for o in offs[:count.value]], raw.value
+
+
+def bgzf_compress(data):
+    return _codec().bgzf_compress(data)
+
+
+def bgzf_decompress(data):
+    return _codec().bgzf_decompress(data)
+
+
+def bgzf_compress_file(src, dst):
+    _codec().bgzf_compress_file(src, dst)
+
+
+def bgzf_decompress_file(src, dst):
+    _codec().bgzf_decompress_file(src, dst)

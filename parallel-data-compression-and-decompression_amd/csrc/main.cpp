@@ -321,6 +321,23 @@ int exchange_cb(void* user, const uint64_t* mine, uint64_t* all, uint32_t count)
     return x->nc->on ? x->nc->allgather(mine, all, count) : x->rv->allgather(mine, all, count);
 }
 
+// `main bgzip <src file> <dst file>` / `main bgunzip <src file> <dst file>`: BGZF (blocked gzip) of one file, one process, one GPU.
+// Exit 0 on success, 2 on a CRC-32 / ISIZE mismatch, 1 on any other failure.
+int bgzf_main(const std::string& op, const char* src, const char* dst, int world_size, int device) {
+    if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", op.c_str(), world_size); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    zwz_ctx* ctx = nullptr;
+    int rc = zwz_ctx_create(device, 0, &ctx);
+    if (rc == ZWZ_OK) rc = op == "bgzip" ? zwz_bgzf_compress_file(ctx, src, dst) : zwz_bgzf_decompress_file(ctx, src, dst);
+    zwz_ctx_destroy(ctx);
+    if (rc != ZWZ_OK) {
+        fprintf(stderr, "%s %s: %s (%s)\n", op.c_str(), src, zwz_strerror(rc), zwz_last_error());
+        return rc == ZWZ_E_CHECKSUM ? 2 : 1;
+    }
+    printf("%s %s -> %s in %.3f s\n", op.c_str(), src, dst, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -335,6 +352,11 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     std::string operation = argv[1], source_path = argv[2], output_path = argv[3];
+    if (operation == "bgzip" || operation == "bgunzip") {
+        int n = 0;
+        const int dev = zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0;
+        return bgzf_main(operation, argv[2], argv[3], world_size, dev);
+    }
     if (!source_path.empty() && source_path.back() == '/') source_path.pop_back();   // main.cpp:72-76
     if (!output_path.empty() && output_path.back() == '/') output_path.pop_back();
     printf("source_path: %s\noutput_path: %s\n", source_path.c_str(), output_path.c_str());

@@ -203,6 +203,7 @@ const char* zwz_strerror(int s) {
         case ZWZ_E_IO: return "I/O error";
         case ZWZ_E_NOMEM: return "out of memory";
         case ZWZ_E_FORMAT: return "malformed .zwz shard";
+        case ZWZ_E_CHECKSUM: return "BGZF checksum mismatch (CRC-32 or ISIZE)";
         default: return "unknown status";
     }
 }
@@ -320,6 +321,8 @@ void zwz_ctx_destroy(zwz_ctx* c) {
     if (c->inf_order) (void)hipFree(c->inf_order);
     if (c->d_stage) (void)hipFree(c->d_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->bgzf_ws) (void)hipFree(c->bgzf_ws);
+    if (c->crc_tables) (void)hipFree(c->crc_tables);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_inf) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);

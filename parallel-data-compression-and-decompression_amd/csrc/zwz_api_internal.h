@@ -30,6 +30,10 @@ struct zwz_ctx {
     hipEvent_t ev[zwz::kNumDeflateStages + 1] = {};
     hipEvent_t ev_inf[2] = {};
     float stage_ms[ZWZ_NUM_STAGES] = {};
+    // BGZF (zwz_bgzf.cpp): slots and per-member arrays for bgzf_cap members, grown lazily; the CRC tables, built once
+    void* bgzf_ws = nullptr;
+    uint32_t bgzf_cap = 0;
+    void* crc_tables = nullptr;
 };
 
 namespace zwz {
