@@ -160,10 +160,16 @@ ZWZ_HD int decode_symbol(BitReader& br, const uint16_t* fast, uint32_t fast_bits
     if (kFmt == 1u) e = unpack_lit_entry(e); else if (kFmt == 2u) e = unpack_dist_entry(e);
     uint32_t l = e & 15u;
     if (e != 0 && l <= br.bits) { br.drop(l); return (int)(e >> 4); }
-    // slow path: canonical walk bit by bit (long codes, invalid codes, or the stream's last bits)
+    // slow path: canonical walk bit by bit (long codes, invalid codes, or the stream's last bits).  Bits that no code can complete
+    // any more are invalid as soon as they are read, however much input is left: zlib's tables mark them after the first bit of an
+    // empty or one-code table, after the fifth of fixed distance codes 30 / 31.
     int code = 0, first = 0, index = 0;
     for (uint32_t len = 1; len <= 15; len++) {
-        if (br.bits < len) return -1;
+        if (br.bits < len) {
+            if (len == 1) return -1;
+            for (uint32_t l = len; l <= 15; l++) if (count[l]) return -1;
+            return -2;
+        }
         code |= (int)((br.hold >> (len - 1)) & 1u);
         int c = count[len];
         if (code - c < first) { br.drop(len); return sorted[index + (code - first)]; }
@@ -246,6 +252,13 @@ ZWZ_HD bool inflate_dyn_lengths(InflateState& st, const InflateTables& t, uint8_
     return true;
 }
 
+// zlib's verdict on a code-length code that is not complete (build_decode_table's rc != 0): an error -- unless it has no codes at
+// all, which zlib accepts and decodes as a length of zero per bit, so that the block fails only at its missing end-of-block code,
+// nlen + ndist bits on, or for want of input before them.
+ZWZ_HD uint32_t inflate_cl_verdict(const InflateState& st, uint32_t max_len, uint32_t nsyms) {
+    return max_len == 0 && st.br.bits + 8u * (st.br.n - st.br.pos) < nsyms ? kInfNeedInput : kInfDataError;
+}
+
 ZWZ_HD bool inflate_table_ok(InflateState& st, int rc, uint32_t max_len, bool literal) {
     if (rc < 0 || (rc > 0 && (literal ? max_len != 1 : max_len > 1))) { st.status = kInfDataError; return false; }
     return true;
@@ -295,7 +308,7 @@ ZWZ_HD uint32_t inflate_block_rest(InflateState& st, InflateTables* tp, uint8_t*
     uint8_t cl[19];
     if (!inflate_dyn_begin(st, cl, nlen, ndist)) return kBlkStop;
     // the code-length code reuses the distance-table slots (7-bit fast index fits in 8)
-    if (build_decode_table(cl, 19, t.dist_fast, 7, t.dist_count, t.dist_sym, max_len) != 0) { st.status = kInfDataError; return kBlkStop; }
+    if (build_decode_table(cl, 19, t.dist_fast, 7, t.dist_count, t.dist_sym, max_len) != 0) { st.status = inflate_cl_verdict(st, max_len, nlen + ndist); return kBlkStop; }
     if (!inflate_dyn_lengths(st, t, lens, nlen, ndist)) return kBlkStop;
     int lr = build_decode_table(lens, nlen, t.lit_fast, kLitFastBits, t.lit_count, t.lit_sym, max_len, t.lit_walk);
     if (!inflate_table_ok(st, lr, max_len, true)) return kBlkStop;

@@ -2067,7 +2067,9 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     uint32_t fenced = 0;      // every output byte below this offset is visible to the whole wave
     while (go) {
         uint32_t kind = kBlkStop, soff = 0, slen = 0, opos = 0;
-        top_up(st.br.pos);
+        // from the header's first bit: the reader's byte position runs up to 8 bytes ahead of it, and a ring filled for that position can
+        // have let the bytes of a header that starts just before a 1 KiB boundary go (the wave reads the header and the block from the ring)
+        top_up(st.br.bit_pos() >> 3);
         {   // the block header: lane 0 reads the bits, the wave builds the tables (inflate_core.h: inflate_block_rest, in its pieces)
             uint32_t v = 0, ok = 0;
             if (lane == 0) { opos = st.out_pos; ok = inflate_block_type(st, v) ? 1u : 0u; }
@@ -2088,7 +2090,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                         // the code-length code reuses the distance-table slots (7-bit fast index fits in 8)
                         if (wave_build_decode_table(cl, 19u, m.t.dist_fast, 7u, m.t.dist_count, m.t.dist_sym, max_len, nullptr, m.batch) != 0) {
-                            if (lane == 0) st.status = kInfDataError;
+                            if (lane == 0) st.status = inflate_cl_verdict(st, max_len, nlen + ndist);
                             good = 0;
                         }
                     }
@@ -2210,7 +2212,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                     const uint32_t nb = skip + (is_len ? de & 31u : 0u);
                     if (near_end_s) {                                             // (scalar: the payload's last bits -- a symbol that would reach past them, or starts past them)
                         const int32_t avail = (int32_t)total_bits - (int32_t)(a0 + r * 64u);
-                        if (avail <= 0 || (kind <= kEob && (int32_t)nb > avail)) kind = kNeed;
+                        if (avail <= 0 || ((kind <= kEob || kind == kErr) && (int32_t)nb > avail)) kind = kNeed;   // (286 / 287 only once all their bits are there)
                     }
                     inf[r] = kind | (nb << 3);
                 }

@@ -278,9 +278,10 @@ extern "C" uint32_t emu_inflate(const uint8_t* in, uint32_t n, uint8_t* out, uin
             uint32_t kind = inflate_block_header(st, t, lens, src, len);
             if (kind == kBlkStop) break;
             if (kind == kBlkStored) {
-                if (st.out_pos + len > cap) { st.status = kInfOverflow; break; }
-                memcpy(out + st.out_pos, in + src, len);
-                st.out_pos += len;
+                const uint32_t cp = len < cap - st.out_pos ? len : cap - st.out_pos;   // the kernel cuts a stored block at the slot's end
+                memcpy(out + st.out_pos, in + src, cp);
+                st.out_pos += cp;
+                if (cp < len) st.status = kInfOverflow;
                 if (st.status != kInfRunning) break;
             } else {
                 bool done = false;
@@ -323,7 +324,7 @@ SlotView packed_slot(const uint8_t* in, uint32_t n, const InflateTables& tp, uin
     SlotView v;
     v.kind = is_len ? de >> 13 : e >> 13;
     v.nb = skip + (is_len ? de & 31u : 0u);
-    if (avail <= 0 || (v.kind <= kEob && (int32_t)v.nb > avail)) v.kind = kNeed;
+    if (avail <= 0 || ((v.kind <= kEob || v.kind == kErr) && (int32_t)v.nb > avail)) v.kind = kNeed;
     // the value pass (kernel: "the symbol's value, decoded here and only here")
     const uint32_t s = (e >> 4) & 511u, c = (s - 257u) & 31u, xb = length_extra_bits(c);
     const uint32_t len = length_base(c) + 3u + ((uint32_t)(bits >> ((skip - xb) & 15u)) & ((1u << xb) - 1u));
@@ -362,7 +363,10 @@ extern "C" uint32_t emu_packed_window_check(const uint8_t* in, uint32_t n, uint6
                 if (k != k2 || d2 != done || sp.status != st.status || sp.out_pos != st.out_pos || (!done && sp.br.bit_pos() != st.br.bit_pos()) || (k && (b1[0] != b2[0] || p1[0] != p2[0]))) bad++;
                 const SlotView v = packed_slot(in, n, tp, bp);
                 (*n_syms)++;
-                if (v.kind == kSlow || v.kind == kNeed || v.kind == kErr) { (*n_slow)++; continue; }      // the kernel stops the round here and asks the sequential decoder
+                // need / error: the kernel stops the block with that status itself -- the sequential decoder must agree
+                if (v.kind == kNeed && !(k == 0 && done && st.status == kInfNeedInput)) bad++;
+                if (v.kind == kErr && !(k == 0 && done && st.status == kInfDataError)) bad++;
+                if (v.kind == kSlow || v.kind == kNeed || v.kind == kErr) { (*n_slow)++; continue; }      // slow: the kernel asks the sequential decoder
                 if (k == 1) {                                            // a literal or a match was decoded
                     const bool want_match = b1[0] >= 256u;
                     if (v.kind != (want_match ? kMatch : kLit) || v.value != b1[0] || bp + v.nb != st.br.bit_pos()) bad++;
@@ -462,9 +466,10 @@ extern "C" uint32_t emu_inflate_bytewise(const uint8_t* in, uint32_t n, uint8_t*
             uint32_t kind = inflate_block_header(st, t, lens, src, len);
             if (kind == kBlkStop) break;
             if (kind == kBlkStored) {
-                if (st.out_pos + len > cap) { st.status = kInfOverflow; break; }
-                memcpy(out + st.out_pos, in + src, len);
-                st.out_pos += len;
+                const uint32_t cp = len < cap - st.out_pos ? len : cap - st.out_pos;   // the kernel cuts a stored block at the slot's end
+                memcpy(out + st.out_pos, in + src, cp);
+                st.out_pos += cp;
+                if (cp < len) st.status = kInfOverflow;
                 if (st.status != kInfRunning) break;
             } else {
                 bool done = false;

@@ -21,6 +21,9 @@ def load():
     lib.emu_inflate.restype = ctypes.c_uint32
     lib.emu_inflate.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32,
                                 ctypes.POINTER(ctypes.c_uint32)]
+    lib.emu_inflate_bytewise.restype = ctypes.c_uint32
+    lib.emu_inflate_bytewise.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32,
+                                         ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]
     lib.emu_band_records.restype = ctypes.c_uint32
     lib.emu_band_records.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.emu_plan_split_check.restype = ctypes.c_uint32
@@ -50,4 +53,12 @@ def inflate(lib, payload: bytes, cap: int = 65535):
     out = ctypes.create_string_buffer(cap + 8)
     st = ctypes.c_uint32()
     n = lib.emu_inflate(payload, len(payload), out, cap, ctypes.byref(st))
+    return out.raw[:n], st.value
+
+
+def inflate_bytewise(lib, payload: bytes, cap: int = 65535, batch_syms: int = 64):
+    """emu_inflate with the kernel's batch copy (one output byte per lane, owners by binary search)."""
+    out = ctypes.create_string_buffer(cap + 8)
+    st = ctypes.c_uint32()
+    n = lib.emu_inflate_bytewise(payload, len(payload), out, cap, ctypes.byref(st), batch_syms)
     return out.raw[:n], st.value
