@@ -212,6 +212,30 @@ int zwz_bgzf_decompress_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len, 
 int zwz_bgzf_compress_file(zwz_ctx *ctx, const char *src, const char *dst);
 int zwz_bgzf_decompress_file(zwz_ctx *ctx, const char *src, const char *dst);
 
+/* ---- BGZF random access: the .gzi index and range reads ---------------------------------------------------------------------
+ * .gzi (htslib's bgzf_index_dump layout; what `bgzip -i` / `bgzip -r` write): a u64 LE count, then count pairs of u64 LE
+ * (compressed offset of a member, decoded offset of its first byte).  The first member, (0, 0), is implied and not stored.
+ * Written here: one entry for every member after the first, in file order, except a last member that decodes to nothing (the EOF
+ * member); empty members elsewhere (the EOF member of the first of two concatenated files) get one.  Read here: indexes with or
+ * without entries for empty members, a trailing EOF member's included.  A .gzi whose length is not 8 + 16 * count, whose
+ * compressed offsets are not strictly increasing from above 0, or whose decoded offsets decrease is ZWZ_E_FORMAT. */
+/* Host only (no GPU): the .gzi bytes of a BGZF buffer; gzi == NULL gives the size in *gzi_len only (cap too small: ZWZ_E_INVALID).
+ * The same strict walk and ZWZ_E_FORMAT messages as zwz_bgzf_index. */
+int zwz_bgzf_gzi(const uint8_t *gz, uint64_t n, uint8_t *gzi, uint64_t cap, uint64_t *gzi_len);
+/* The same for a file of any size, streamed in bounded memory (`bgzip -r`); written as <dst_gzi>.part, renamed on success. */
+int zwz_bgzf_gzi_file(const char *src, const char *dst_gzi);
+/* ranges: k pairs (decoded offset, length) in host memory.  d_out (device) receives their bytes concatenated in the given order:
+ * sum of the lengths.  Ranges may overlap, repeat, come in any order and be empty; an empty range at the very end is valid.  A
+ * range past the end of the decoded data, or whose offset + length overflows, is ZWZ_E_INVALID naming the range.  Only members
+ * holding a requested byte are read, decoded and checked (header, BSIZE within gz_len, inflate, CRC-32, ISIZE, and the decoded
+ * length against the next index entry).  d_gz as for zwz_bgzf_decompress_dev.  Synchronous: returns after the GPU work, with the
+ * first bad touched member reported as zwz_bgzf_decompress_file reports it (ZWZ_E_CHECKSUM / ZWZ_E_FORMAT). */
+int zwz_bgzf_read_ranges_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len, const uint8_t *gzi, uint64_t gzi_len,
+                             const uint64_t *ranges, uint32_t k, uint8_t *d_out);
+/* The same from a file into host memory.  With a .gzi only the touched members are read (one pread per run of consecutive
+ * entries); gzi_path == NULL walks the member headers from the start until the last requested byte is covered. */
+int zwz_bgzf_read_ranges_file(zwz_ctx *ctx, const char *src, const char *gzi_path, const uint64_t *ranges, uint32_t k, uint8_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ plus the batch form of the two zlib call sites (compression.cpp:119-134, decompr
 and BGZF (blocked gzip, readable by gzip / zcat / htslib; no reference counterpart):
     Codec.bgzf_compress / Codec.bgzf_decompress                (bytes or a CUDA uint8 tensor)
     Codec.bgzf_compress_file / Codec.bgzf_decompress_file      (whole files, streamed)
+    bgzf_gzi / bgzf_gzi_file                                   (the .gzi index, host only)
+    Codec.bgzf_read_ranges / Codec.bgzf_read_ranges_file       (random access: decoded byte ranges)
 
 There is no CPU fallback: importing works anywhere (so the build can be checked), but every codec
 call needs the HIP library and a GPU and raises ZwzError otherwise.
@@ -85,10 +87,15 @@ def lib():
         L.zwz_bgzf_decompress_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp]
         L.zwz_bgzf_compress_file.argtypes = [vp, c.c_char_p, c.c_char_p]
         L.zwz_bgzf_decompress_file.argtypes = [vp, c.c_char_p, c.c_char_p]
+        L.zwz_bgzf_gzi.argtypes = [vp, u64, vp, u64, c.POINTER(u64)]
+        L.zwz_bgzf_gzi_file.argtypes = [c.c_char_p, c.c_char_p]
+        L.zwz_bgzf_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp]
+        L.zwz_bgzf_read_ranges_file.argtypes = [vp, c.c_char_p, c.c_char_p, vp, u32, vp]
         _lib = L
     return _lib
 
 
+E_INVALID = -1
 E_FORMAT = -6
 E_CHECKSUM = -7
 BGZF_BLOCK_SIZE = 65280     # raw bytes per BGZF member (htslib's BGZF_BLOCK_SIZE)
@@ -294,6 +301,39 @@ class Codec:
     def bgzf_decompress_file(self, src, dst):
         _check(lib().zwz_bgzf_decompress_file(self._h, os.fsencode(src), os.fsencode(dst)), "zwz_bgzf_decompress_file")
 
+    def bgzf_read_ranges(self, gz, ranges, gzi=None):
+        """Decoded byte ranges [(offset, length), ...] of a BGZF stream: bytes -> a list of bytes; a CUDA uint8 tensor -> one CUDA tensor
+        of the ranges concatenated.  gzi: the stream's .gzi bytes (None: built on the host from the stream).  Only the members holding
+        a requested byte are decoded and checked."""
+        import numpy as np
+        import torch
+        as_tensor = isinstance(gz, torch.Tensor)
+        if gzi is None:
+            gzi = bgzf_gzi(gz.detach().cpu().numpy().tobytes() if as_tensor else bytes(gz))
+        rng = _ranges(np, ranges)
+        total = int(rng[:, 1].sum()) if len(rng) else 0
+        dev = torch.device("cuda", self.device)
+        d_gz = _device_input(torch, gz, self.device)
+        n = gz.numel() if as_tensor else len(gz)
+        d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        _check(lib().zwz_bgzf_read_ranges_dev(self._h, d_gz.data_ptr(), n, bytes(gzi), len(gzi), rng.ctypes.data, len(rng), d_out.data_ptr()),
+               "zwz_bgzf_read_ranges_dev")
+        if as_tensor:
+            return d_out[:total]
+        return _split(d_out[:total].cpu().numpy().tobytes(), rng)
+
+    def bgzf_read_ranges_file(self, src, ranges, gzi=None):
+        """Decoded byte ranges of a BGZF file -> a list of bytes.  gzi: path of its .gzi (only the touched members are read); None:
+        the member headers are walked up to the last requested byte."""
+        import numpy as np
+        rng = _ranges(np, ranges)
+        total = int(rng[:, 1].sum()) if len(rng) else 0
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        _check(lib().zwz_bgzf_read_ranges_file(self._h, os.fsencode(src), None if gzi is None else os.fsencode(gzi), rng.ctypes.data, len(rng),
+                                               out.ctypes.data), "zwz_bgzf_read_ranges_file")
+        return _split(out[:total].tobytes(), rng)
+
     def set_option(self, name, value):
         """Test / experiment switches of this context (include/zwz.h: zwz_ctx_set_option): "match" = auto | walk | band | lazy |
         autoband | autolazy, "plan" = wave | serial, "inflate_header" = wave | serial.  Every choice produces the same bytes; a form that
@@ -324,6 +364,24 @@ def _device_input(torch, data, device):
     if n:
         buf[:n] = torch.frombuffer(bytearray(data), dtype=torch.uint8)
     return buf.to(torch.device("cuda", device))
+
+
+def _ranges(np, ranges):
+    """[(offset, length), ...] -> a C-contiguous (k, 2) uint64 array (ZwzError for a negative value)."""
+    rows = [(int(a), int(b)) for a, b in ranges]
+    if any(a < 0 or b < 0 for a, b in rows):
+        err = ZwzError("bgzf ranges: offsets and lengths are not negative")
+        err.status = E_INVALID
+        raise err
+    return np.ascontiguousarray(np.array(rows, dtype=np.uint64).reshape(-1, 2))
+
+
+def _split(blob, rng):
+    out, o = [], 0
+    for n in rng[:, 1].tolist():
+        out.append(blob[o:o + n])
+        o += n
+    return out
 
 
 def sort_files_by_size(path):
@@ -389,3 +447,18 @@ def bgzf_compress_file(src, dst):
 
 def bgzf_decompress_file(src, dst):
     _codec().bgzf_decompress_file(src, dst)
+
+
+def bgzf_gzi(gz):
+    """The .gzi index (include/zwz.h) of a BGZF byte string, built on the host (no GPU)."""
+    gz = bytes(gz)
+    n = ctypes.c_uint64(0)
+    _check(lib().zwz_bgzf_gzi(gz, len(gz), None, 0, ctypes.byref(n)), "zwz_bgzf_gzi")
+    buf = ctypes.create_string_buffer(n.value)
+    _check(lib().zwz_bgzf_gzi(gz, len(gz), buf, n.value, ctypes.byref(n)), "zwz_bgzf_gzi")
+    return buf.raw[:n.value]
+
+
+def bgzf_gzi_file(src, dst):
+    """src's .gzi written to dst, streamed (`bgzip -r`; no GPU); dst appears only on success."""
+    _check(lib().zwz_bgzf_gzi_file(os.fsencode(src), os.fsencode(dst)), "zwz_bgzf_gzi_file")

@@ -14,6 +14,7 @@
 //     a publication that names its nonce, i.e. one written by a rank 0 that has seen THIS process;
 //   * completion markers carry rank 0's nonce and the rank's return code; rank 0 fails if a rank failed or never arrived.
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -338,6 +339,139 @@ int bgzf_main(const std::string& op, const char* src, const char* dst, int world
     return 0;
 }
 
+void bgzf_usage(const char* argv0) {
+    fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n", argv0, argv0,
+            argv0);
+}
+
+bool parse_u64(const char* s, uint64_t* v) {
+    if (!s || !*s || *s < '0' || *s > '9') return false;
+    errno = 0;
+    char* end = nullptr;
+    const unsigned long long x = strtoull(s, &end, 10);
+    if (errno || *end) return false;
+    *v = x;
+    return true;
+}
+
+bool exists(const std::string& p) { struct stat st {}; return stat(p.c_str(), &st) == 0; }
+
+// Decoded bytes [off, off + size) of src (size ~0: to the end) to dst, in pieces of bounded size, through <dst>.part.
+int bgzf_range_to_file(zwz_ctx* ctx, const char* src, const char* dst, uint64_t off, uint64_t size, bool to_end) {
+    std::string gzi = std::string(src) + ".gzi", tmp_gzi;
+    bool have_gzi = exists(gzi);
+    if (to_end) {
+        // the end of the data: the last entry's decoded offset + what the members from its compressed offset on decode to
+        if (!have_gzi) {
+            tmp_gzi = std::string(dst) + ".gzi.part";
+            if (int rc = zwz_bgzf_gzi_file(src, tmp_gzi.c_str())) return rc;
+            gzi = tmp_gzi;                              // (used for the reads too, removed at the end)
+            have_gzi = true;
+        }
+        std::vector<uint8_t> g, tail;
+        FILE* f = fopen(gzi.c_str(), "rb");
+        int rc = f ? ZWZ_OK : ZWZ_E_IO;
+        uint64_t last_c = 0, last_u = 0;
+        if (f) {
+            uint8_t cnt[8] = {};
+            if (fread(cnt, 1, 8, f) == 8) {
+                uint64_t k = 0;
+                for (int i = 7; i >= 0; i--) k = k << 8 | cnt[i];
+                uint8_t e[16];
+                if (k && fseek(f, (long)(8 + 16 * (k - 1)), SEEK_SET) == 0 && fread(e, 1, 16, f) == 16)
+                    for (int i = 7; i >= 0; i--) { last_c = last_c << 8 | e[i]; last_u = last_u << 8 | e[8 + i]; }
+            }
+            fclose(f);
+        }
+        FILE* s = rc ? nullptr : fopen(src, "rb");
+        if (!rc && !s) rc = ZWZ_E_IO;
+        if (s) {
+            if (fseeko(s, (off_t)last_c, SEEK_SET) == 0) {
+                tail.resize(3u << 16);                  // the last entry's member, the EOF member and more: a stale index is refused below
+                tail.resize(fread(tail.data(), 1, tail.size(), s));
+            }
+            fclose(s);
+        }
+        uint32_t members = 0;
+        uint64_t raw = 0;
+        if (!rc) rc = zwz_bgzf_index(tail.data(), tail.size(), nullptr, 0, &members, &raw);
+        const uint64_t end = last_u + raw;
+        if (!rc && off > end) { fprintf(stderr, "bgunzip: --offset %llu is past the end of the data (%llu bytes)\n", (unsigned long long)off, (unsigned long long)end); rc = ZWZ_E_INVALID; }
+        if (rc && !tmp_gzi.empty()) unlink(tmp_gzi.c_str());
+        if (rc) return rc;
+        size = end - off;
+    }
+    const std::string part = std::string(dst) + ".part";
+    FILE* out = fopen(part.c_str(), "wb");
+    if (!out) { fprintf(stderr, "cannot create %s\n", part.c_str()); return ZWZ_E_IO; }
+    constexpr uint64_t kPiece = 64ull << 20;
+    std::vector<uint8_t> buf((size_t)std::min<uint64_t>(size ? size : 1, kPiece));
+    int rc = ZWZ_OK;
+    uint64_t done = 0;
+    do {
+        const uint64_t n = std::min<uint64_t>(size - done, kPiece);
+        const uint64_t r[2] = {off + done, n};
+        rc = zwz_bgzf_read_ranges_file(ctx, src, have_gzi ? gzi.c_str() : nullptr, r, 1, buf.data());
+        if (!rc && n && fwrite(buf.data(), 1, n, out) != n) rc = ZWZ_E_IO;
+        done += n;
+    } while (!rc && done < size);
+    if (fclose(out) != 0 && !rc) rc = ZWZ_E_IO;
+    if (!rc && rename(part.c_str(), dst) != 0) rc = ZWZ_E_IO;
+    if (rc) unlink(part.c_str());
+    if (!tmp_gzi.empty()) unlink(tmp_gzi.c_str());
+    return rc;
+}
+
+// `main bgzip <src> <dst> --index` (also <dst>.gzi), `main bgindex <src.gz>` (<src.gz>.gzi), `main bgunzip <src> <dst> --offset B
+// [--size S]` (decoded bytes [B, B + S) or [B, end)).  Flags after the operands; a flag that is not known, or a malformed number,
+// prints the usage and exits 1.  Exit codes as bgzf_main's.
+int bgzf_ext_main(int argc, char* argv[], int world_size, int device) {
+    const std::string op = argv[1];
+    if (op == "bgindex") {
+        if (argc != 3) { bgzf_usage(argv[0]); return 1; }
+        const std::string dst = std::string(argv[2]) + ".gzi";
+        const int rc = zwz_bgzf_gzi_file(argv[2], dst.c_str());
+        if (rc) { fprintf(stderr, "bgindex %s: %s (%s)\n", argv[2], zwz_strerror(rc), zwz_last_error()); return rc == ZWZ_E_CHECKSUM ? 2 : 1; }
+        printf("bgindex %s -> %s\n", argv[2], dst.c_str());
+        return 0;
+    }
+    bool index = false, have_off = false, have_size = false;
+    uint64_t off = 0, size = 0;
+    for (int i = 4; i < argc; i++) {
+        const std::string a = argv[i];
+        if (op == "bgzip" && a == "--index") index = true;
+        else if (op == "bgunzip" && a == "--offset" && i + 1 < argc && parse_u64(argv[i + 1], &off)) { have_off = true; i++; }
+        else if (op == "bgunzip" && a == "--size" && i + 1 < argc && parse_u64(argv[i + 1], &size)) { have_size = true; i++; }
+        else { bgzf_usage(argv[0]); return 1; }
+    }
+    if (have_size && !have_off) { bgzf_usage(argv[0]); return 1; }
+    if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", op.c_str(), world_size); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    zwz_ctx* ctx = nullptr;
+    int rc = zwz_ctx_create(device, 0, &ctx);
+    if (rc == ZWZ_OK) {
+        if (op == "bgzip") {
+            rc = zwz_bgzf_compress_file(ctx, argv[2], argv[3]);
+            if (rc == ZWZ_OK) rc = zwz_bgzf_gzi_file(argv[3], (std::string(argv[3]) + ".gzi").c_str());
+        } else {
+            rc = bgzf_range_to_file(ctx, argv[2], argv[3], off, size, !have_size);
+        }
+    }
+    zwz_ctx_destroy(ctx);
+    if (rc != ZWZ_OK) {
+        fprintf(stderr, "%s %s: %s (%s)\n", op.c_str(), argv[2], zwz_strerror(rc), zwz_last_error());
+        return rc == ZWZ_E_CHECKSUM ? 2 : 1;
+    }
+    printf("%s %s -> %s%s in %.3f s\n", op.c_str(), argv[2], argv[3], index ? " (+ .gzi)" : "",
+           std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}
+
+bool has_dash_arg(int argc, char* argv[]) {
+    for (int i = 4; i < argc; i++) if (argv[i][0] == '-') return true;
+    return false;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -347,6 +481,11 @@ int main(int argc, char* argv[]) {
     static const char* const dev_vars[] = {"ZWZ_DEVICE", "LOCAL_RANK", "OMPI_COMM_WORLD_LOCAL_RANK", nullptr};
     const int world_rank = env_int(rank_vars, 0), world_size = env_int(size_vars, 1);
 
+    if (argc >= 2 && std::string(argv[1]) == "bgindex") {
+        int n = 0;
+        const int dev = zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0;
+        return bgzf_ext_main(argc, argv, world_size, dev);
+    }
     if (argc < 4) {   // main.cpp:88-92
         fprintf(stderr, "Usage: %s <compress/decompress> <source directory path> <output directory path>\n", argv[0]);
         return 1;
@@ -355,6 +494,7 @@ int main(int argc, char* argv[]) {
     if (operation == "bgzip" || operation == "bgunzip") {
         int n = 0;
         const int dev = zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0;
+        if (has_dash_arg(argc, argv)) return bgzf_ext_main(argc, argv, world_size, dev);
         return bgzf_main(operation, argv[2], argv[3], world_size, dev);
     }
     if (!source_path.empty() && source_path.back() == '/') source_path.pop_back();   // main.cpp:72-76

@@ -323,6 +323,8 @@ void zwz_ctx_destroy(zwz_ctx* c) {
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->bgzf_ws) (void)hipFree(c->bgzf_ws);
     if (c->crc_tables) (void)hipFree(c->crc_tables);
+    if (c->rr_dev) (void)hipFree(c->rr_dev);
+    if (c->rr_host) (void)hipHostFree(c->rr_host);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_inf) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);

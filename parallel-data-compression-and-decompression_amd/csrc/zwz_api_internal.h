@@ -34,6 +34,10 @@ struct zwz_ctx {
     void* bgzf_ws = nullptr;
     uint32_t bgzf_cap = 0;
     void* crc_tables = nullptr;
+    // range reads (zwz_bgzf_read_ranges_*): the plan of one call, pinned on the host and its device copy, grown to the largest call
+    void* rr_host = nullptr;
+    void* rr_dev = nullptr;
+    size_t rr_cap = 0;
 };
 
 namespace zwz {

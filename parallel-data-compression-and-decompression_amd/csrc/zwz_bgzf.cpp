@@ -1,12 +1,18 @@
 // zwz_bgzf.cpp -- BGZF entry points of include/zwz.h: the host walk of member headers, the device drivers around the codec
 // (crc32_blocks + zwz_deflate_batch_dev + bgzf_scan + bgzf_pack; bgzf_gather + inflate + bgzf_scan + bgzf_verify_compact), and
-// whole-file streaming through pinned staging with reading, the GPU and writing overlapped.
+// whole-file streaming through pinned staging with reading, the GPU and writing overlapped.  Random access: the .gzi index
+// (writer, streamed writer, reader), the planning of range reads and their device path (bgzf_gather_list + inflate +
+// bgzf_verify_extract) for data in device memory or in a file.
+#include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include "zwz_api_internal.h"
 #include "zwz_bgzf.h"
@@ -25,14 +31,15 @@ inline uint32_t le32(const uint8_t* p) { return le16(p) | le16(p + 2) << 16; }
 
 // Walks the members of gz[0, n).  Strict (partial = false): anything that is not a whole member is ZWZ_E_FORMAT.  partial: stops
 // (ZWZ_OK) before a member that does not end inside the buffer -- the file reader's slice boundary.  Also stops after `limit` members.
-// offs[] (may be null) receives up to cap offsets; *count counts every member walked; *consumed = the end of the last one.
-// `at` is the buffer's offset in the file, for messages.
-int bgzf_walk(const uint8_t* gz, uint64_t n, uint64_t at, bool partial, uint64_t limit, uint64_t* offs, uint64_t cap, uint64_t* count,
-              uint64_t* raw, uint64_t* consumed) {
+// on_member(k, offset, isize) sees every member walked; *count counts them; *consumed = the end of the last one.  `at` is the buffer's
+// offset in the file and k0 the number of members in front of it, for messages.
+template <class F>
+int bgzf_walk_each(const uint8_t* gz, uint64_t n, uint64_t at, uint64_t k0, bool partial, uint64_t limit, F&& on_member, uint64_t* count,
+                   uint64_t* raw, uint64_t* consumed) {
     uint64_t o = 0, k = 0, total = 0;
     auto fail = [&](const char* what, uint64_t v) {
-        if (v == ~0ull) set_error("bgzf: member %llu at byte offset %llu: %s", (unsigned long long)k, (unsigned long long)(at + o), what);
-        else set_error("bgzf: member %llu at byte offset %llu: %s %llu", (unsigned long long)k, (unsigned long long)(at + o), what, (unsigned long long)v);
+        if (v == ~0ull) set_error("bgzf: member %llu at byte offset %llu: %s", (unsigned long long)(k0 + k), (unsigned long long)(at + o), what);
+        else set_error("bgzf: member %llu at byte offset %llu: %s %llu", (unsigned long long)(k0 + k), (unsigned long long)(at + o), what, (unsigned long long)v);
         *count = k; *raw = total; *consumed = o;
         return ZWZ_E_FORMAT;
     };
@@ -40,7 +47,7 @@ int bgzf_walk(const uint8_t* gz, uint64_t n, uint64_t at, bool partial, uint64_t
         const uint64_t avail = n - o;
         const uint8_t* m = gz + o;
         if (m[0] != 0x1f || (avail > 1 && m[1] != 0x8b) || (avail > 2 && m[2] != 8))
-            return fail(k ? "trailing bytes that are not a gzip member" : "not gzip (bad magic or method)", ~0ull);
+            return fail(k0 + k ? "trailing bytes that are not a gzip member" : "not gzip (bad magic or method)", ~0ull);
         if (avail < 12) { if (partial) break; return fail("truncated member header", ~0ull); }
         const uint32_t flg = m[3];
         if (!(flg & 4u)) return fail("no extra field: a plain gzip member, not BGZF", ~0ull);
@@ -61,13 +68,20 @@ int bgzf_walk(const uint8_t* gz, uint64_t n, uint64_t at, bool partial, uint64_t
         if (bsize > avail) { if (partial) break; return fail("BSIZE runs past the end of the input:", bsize); }
         const uint32_t isize = le32(m + bsize - 4);
         if (isize > kBgzfMaxIsize) return fail("ISIZE above 65535:", isize);
-        if (offs && k < cap) offs[k] = o;
+        on_member(k, o, isize);
         total += isize;
         k++;
         o += bsize;
     }
     *count = k; *raw = total; *consumed = o;
     return ZWZ_OK;
+}
+
+// offs[] (may be null) receives up to cap member offsets
+int bgzf_walk(const uint8_t* gz, uint64_t n, uint64_t at, bool partial, uint64_t limit, uint64_t* offs, uint64_t cap, uint64_t* count,
+              uint64_t* raw, uint64_t* consumed) {
+    return bgzf_walk_each(gz, n, at, 0, partial, limit, [&](uint64_t k, uint64_t o, uint32_t) { if (offs && k < cap) offs[k] = o; }, count, raw,
+                          consumed);
 }
 
 struct BgzfView {
@@ -226,6 +240,275 @@ struct FileJob {
 
 #define HIPJOB(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { job.join(); return hip_fail(e_, #x); } } while (0)
 
+// ---- .gzi index and range reads ----------------------------------------------------------------------------------------------------
+
+constexpr size_t kWalkBuf = 4u << 20;               // bytes of file a streamed walk holds (a member is at most 65 536 bytes)
+constexpr size_t kRangeOutSlice = 16u << 20;        // decoded bytes of one slice of the file range reader (>= one member)
+
+inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | (uint64_t)le32(p + 4) << 32; }
+inline void put64(uint8_t* p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (8 * i)); }
+
+// The writer's rule: one entry (compressed offset, decoded offset) per member after the first, in file order, except a last member
+// that decodes to nothing (the EOF member).  An entry is held back until the next member shows it is not the last.
+struct GziBuilder {
+    uint64_t raw = 0, members = 0, entries = 0;
+    bool held = false, held_empty = false;
+    uint64_t hc = 0, hu = 0;
+    std::vector<uint8_t> buf;                       // serialised entries not yet flushed
+    void emit() { uint8_t e[16]; put64(e, hc); put64(e + 8, hu); buf.insert(buf.end(), e, e + 16); entries++; held = false; }
+    void member(uint64_t coff, uint32_t isize) {
+        if (held) emit();
+        if (members++) { held = true; held_empty = isize == 0; hc = coff; hu = raw; }
+        raw += isize;
+    }
+    void finish() { if (held && !held_empty) emit(); held = false; }
+};
+
+// Walks the members of an open file from its start with kWalkBuf bytes of memory: on_member(offset, isize) for each, until the end of
+// the file or until stop() returns true (asked after every buffer).
+template <class F, class S>
+int walk_file(FILE* in, F&& on_member, S&& stop) {
+    std::vector<uint8_t> buf(kWalkBuf);
+    size_t have = 0;
+    bool eof = false;
+    uint64_t at = 0, k0 = 0;
+    for (;;) {
+        if (!eof) {
+            bool io_err = false;
+            const size_t got = read_full(in, buf.data() + have, kWalkBuf - have, &io_err);
+            if (io_err) { set_error("read error"); return ZWZ_E_IO; }
+            eof = have + got < kWalkBuf;
+            have += got;
+        }
+        if (!have) return ZWZ_OK;
+        uint64_t count = 0, raw = 0, used = 0;
+        if (int rc = bgzf_walk_each(buf.data(), have, at, k0, !eof, ~0ull, [&](uint64_t, uint64_t o, uint32_t isize) { on_member(at + o, isize); },
+                                    &count, &raw, &used))
+            return rc;
+        if (!count) { set_error("bgzf: cannot split the input at byte offset %llu", (unsigned long long)at); return ZWZ_E_FORMAT; }
+        memmove(buf.data(), buf.data() + used, have - used);
+        have -= used;
+        at += used;
+        k0 += count;
+        if (stop()) return ZWZ_OK;
+    }
+}
+
+// A parsed .gzi: entry 0 is the implied (0, 0); coff strictly increasing, uoff not decreasing.
+struct GziIndex { std::vector<uint64_t> coff, uoff; };
+
+int parse_gzi(const uint8_t* g, uint64_t n, GziIndex* ix) {
+    if (n < 8 || !g) { set_error("gzi: %llu bytes, shorter than its 8-byte entry count", (unsigned long long)n); return ZWZ_E_FORMAT; }
+    const uint64_t count = le64(g);
+    if ((n - 8) % 16 || (n - 8) / 16 != count) {
+        set_error("gzi: %llu bytes do not hold the %llu entries its count gives", (unsigned long long)n, (unsigned long long)count);
+        return ZWZ_E_FORMAT;
+    }
+    ix->coff.assign(1, 0);
+    ix->uoff.assign(1, 0);
+    ix->coff.reserve(count + 1);
+    ix->uoff.reserve(count + 1);
+    for (uint64_t i = 0; i < count; i++) {
+        const uint64_t c = le64(g + 8 + 16 * i), u = le64(g + 16 + 16 * i);
+        if (c <= ix->coff.back()) {
+            set_error("gzi: entry %llu: compressed offset %llu does not follow %llu", (unsigned long long)(i + 1), (unsigned long long)c,
+                      (unsigned long long)ix->coff.back());
+            return ZWZ_E_FORMAT;
+        }
+        if (u < ix->uoff.back()) {
+            set_error("gzi: entry %llu: decoded offset %llu below the previous %llu", (unsigned long long)(i + 1), (unsigned long long)u,
+                      (unsigned long long)ix->uoff.back());
+            return ZWZ_E_FORMAT;
+        }
+        ix->coff.push_back(c);
+        ix->uoff.push_back(u);
+    }
+    return ZWZ_OK;
+}
+
+// The pieces of k ranges against an index, in compressed sparse rows over the touched members (index entries holding at least one
+// requested byte, ascending).  Within a member the pieces of at least kWavePieceMax bytes come first (nlong of them).
+struct RangePlan {
+    std::vector<uint32_t> member;                   // touched index entries
+    std::vector<uint32_t> expect;                   // decoded length the index implies (kNoExpect: the last entry)
+    std::vector<uint32_t> row, nlong;               // member t's pieces: [row[t], row[t + 1]), the first nlong[t] long
+    std::vector<RangePiece> piece;                  // dst = place in the concatenated output
+    std::vector<uint32_t> prange;                   // the range each piece belongs to
+    uint64_t total = 0;                             // output bytes
+};
+
+int range_past_end(uint32_t r, uint64_t a, uint64_t len) {
+    set_error("bgzf: range %u (offset %llu, length %llu) runs past the end of the decoded data", r, (unsigned long long)a, (unsigned long long)len);
+    return ZWZ_E_INVALID;
+}
+
+int plan_ranges(const GziIndex& ix, const uint64_t* ranges, uint32_t k, RangePlan* P) {
+    struct Raw { uint32_t j, r, off, len; uint64_t dst; };
+    const uint64_t* uo = ix.uoff.data();
+    const size_t N = ix.uoff.size(), last = N - 1;
+    std::vector<Raw> raw;
+    raw.reserve(k);
+    uint64_t dst = 0;
+    auto add = [&](size_t j, uint32_t r, uint64_t lo, uint64_t hi) {
+        // (pieces of an entry whose span exceeds what a member can hold are clamped to a place no block reaches: the kernel does not copy them)
+        const uint64_t off = lo - uo[j], len = hi - lo;
+        raw.push_back({(uint32_t)j, r, (uint32_t)std::min<uint64_t>(off, kBgzfSlot), (uint32_t)std::min<uint64_t>(len, kBgzfSlot), dst});
+    };
+    for (uint32_t r = 0; r < k; r++) {
+        const uint64_t a = ranges[2 * r], len = ranges[2 * r + 1];
+        if (len > ~0ull - a) {
+            set_error("bgzf: range %u (offset %llu, length %llu): offset + length overflows", r, (unsigned long long)a, (unsigned long long)len);
+            return ZWZ_E_INVALID;
+        }
+        const uint64_t b = a + len;
+        if (N == 0) { if (b) return range_past_end(r, a, len); continue; }
+        // the last entry's member holds at most kBgzfMaxIsize bytes: a range beyond that is past the end without looking further
+        if (b > uo[last] && b - uo[last] > kBgzfMaxIsize) return range_past_end(r, a, len);
+        if (!len) {
+            if (a > uo[last]) add(last, r, a, a);       // the device checks a against the last member's length
+            continue;
+        }
+        const size_t j0 = std::upper_bound(ix.uoff.begin(), ix.uoff.end(), a) - ix.uoff.begin() - 1;
+        const size_t j1 = std::upper_bound(ix.uoff.begin() + j0, ix.uoff.end(), b - 1) - ix.uoff.begin() - 1;
+        for (size_t j = j0; j <= j1; j++) {
+            const uint64_t lo = std::max(a, uo[j]), hi = j < last ? std::min(b, uo[j + 1]) : b;
+            if (hi > lo) { add(j, r, lo, hi); dst += hi - lo; }
+        }
+        if (raw.size() > 0xfffffff0ull) { set_error("bgzf: more than 2^32 - 16 pieces"); return ZWZ_E_INVALID; }
+    }
+    P->total = dst;
+    // counting sort by entry: long pieces from the front of a member's rows, short ones behind them
+    std::vector<uint32_t> cnt(N + 1, 0), cntl(N, 0);
+    for (const Raw& q : raw) { cnt[q.j]++; if (q.len >= kWavePieceMax) cntl[q.j]++; }
+    P->member.clear(); P->expect.clear(); P->row.assign(1, 0); P->nlong.clear();
+    std::vector<uint32_t> cur_long(N), cur_short(N);
+    for (size_t j = 0; j < N; j++) {
+        if (!cnt[j]) continue;
+        P->member.push_back((uint32_t)j);
+        P->expect.push_back(j < last ? (uint32_t)std::min<uint64_t>(uo[j + 1] - uo[j], kBgzfSlot) : kNoExpect);
+        cur_long[j] = P->row.back();
+        cur_short[j] = P->row.back() + cntl[j];
+        P->nlong.push_back(cntl[j]);
+        P->row.push_back(P->row.back() + cnt[j]);
+    }
+    P->piece.resize(raw.size());
+    P->prange.resize(raw.size());
+    for (const Raw& q : raw) {
+        const uint32_t at = q.len >= kWavePieceMax ? cur_long[q.j]++ : cur_short[q.j]++;
+        P->piece[at] = {q.dst, q.off, q.len};
+        P->prange[at] = q.r;
+    }
+    return ZWZ_OK;
+}
+
+// One slice of a plan: touched members [t0, t1) and pieces [p0, p1) of theirs (all of them, or a part of one member's).
+struct Slice { uint32_t t0, t1, p0, p1; };
+
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+// moff, mend (u64); expect, nlong, status, bad, row (u32; row has m + 1); pieces
+inline size_t slice_bytes(uint32_t m, uint32_t np) { return align16(16 * (size_t)m + 20 * (size_t)m + 4) + 16 * (size_t)np; }
+
+struct SliceView { uint64_t *moff, *mend; uint32_t *expect, *nlong, *status, *bad, *row; RangePiece* piece; };
+SliceView slice_view(uint8_t* p, uint32_t m) {
+    SliceView v;
+    v.moff = reinterpret_cast<uint64_t*>(p); v.mend = v.moff + m;
+    v.expect = reinterpret_cast<uint32_t*>(v.mend + m); v.nlong = v.expect + m; v.status = v.nlong + m; v.bad = v.status + m; v.row = v.bad + m;
+    v.piece = reinterpret_cast<RangePiece*>(p + align16(36 * (size_t)m + 4));
+    return v;
+}
+
+int ensure_rr(zwz_ctx* c, size_t bytes) {
+    if (bytes <= c->rr_cap) return ZWZ_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->rr_dev) { (void)hipFree(c->rr_dev); c->rr_dev = nullptr; }
+    if (c->rr_host) { (void)hipHostFree(c->rr_host); c->rr_host = nullptr; }
+    c->rr_cap = 0;
+    const size_t cap = (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);
+    HIPCHK(hipHostMalloc(&c->rr_host, cap, hipHostMallocDefault));
+    HIPCHK(hipMalloc(&c->rr_dev, cap));
+    c->rr_cap = cap;
+    return ZWZ_OK;
+}
+
+// Packs slice S at h (pinned; its device copy at d) and queues it: one upload, bgzf_gather_list, inflate, bgzf_verify_extract, and the
+// status and bad-piece words back into h.  moff / mend: where touched member t starts and how far it may be read in d_gz.  compact:
+// the slice's pieces go to d_out one after the other (their output offsets stay in the plan) instead of to their place in the output.
+int queue_slice(zwz_ctx* c, const RangePlan& P, const Slice& S, const uint64_t* moff, const uint64_t* mend, uint8_t* h, uint8_t* d,
+                const uint8_t* d_gz, uint64_t gz_len, uint8_t* d_out, bool compact) {
+    const uint32_t m = S.t1 - S.t0, np = S.p1 - S.p0;
+    const SliceView hv = slice_view(h, m), dv = slice_view(d, m);
+    uint64_t o = 0;
+    hv.row[0] = 0;
+    for (uint32_t i = 0; i < m; i++) {
+        const uint32_t t = S.t0 + i;
+        const uint32_t rs = std::max(P.row[t], S.p0), re = std::min(P.row[t + 1], S.p1);
+        const uint32_t ls = std::min(std::max(P.row[t] + P.nlong[t], rs), re);
+        hv.moff[i] = moff[t]; hv.mend[i] = mend ? mend[t] : gz_len;
+        hv.expect[i] = P.expect[t]; hv.nlong[i] = ls - rs; hv.status[i] = 0; hv.bad[i] = ~0u;
+        hv.row[i + 1] = re - S.p0;
+    }
+    for (uint32_t p = 0; p < np; p++) {
+        hv.piece[p] = P.piece[S.p0 + p];
+        if (compact) { hv.piece[p].dst = o; o += hv.piece[p].len; }
+    }
+    const BgzfView v = bgzf_view(c);
+    const CrcTables* tab = static_cast<const CrcTables*>(c->crc_tables);
+    HIPCHK(hipMemcpyAsync(d, h, slice_bytes(m, np), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_bgzf_gather_list(d_gz, gz_len, dv.moff, dv.mend, m, v.slots_a, v.off, v.len, v.crc, v.isize, dv.status, c->stream));
+    if (int rc = zwz_inflate_batch_dev(c, v.slots_a, v.off, v.len, m, v.slots_b, kBgzfSlot, v.olen, v.st)) return rc;
+    HIPCHK(launch_bgzf_verify_extract(tab, v.slots_b, v.olen, v.st, v.crc, v.isize, dv.expect, dv.row, dv.nlong, dv.piece, m, d_out, dv.status, dv.bad,
+                                      c->cu_count, c->stream));
+    HIPCHK(hipMemcpyAsync(hv.status, dv.status, 8 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+    return ZWZ_OK;
+}
+
+// After the slice ran: the first touched member that failed (as check_status reports it), else the first range past the end.
+int slice_verdict(const RangePlan& P, const GziIndex& ix, const Slice& S, const uint8_t* h, const uint64_t* ranges) {
+    const uint32_t m = S.t1 - S.t0;
+    const SliceView hv = slice_view(const_cast<uint8_t*>(h), m);
+    for (uint32_t i = 0; i < m; i++) {
+        const uint32_t j = P.member[S.t0 + i], st = hv.status[i];
+        if (st == kBgzfIndexMismatch) {
+            set_error("bgzf: member %u at byte offset %llu: decoded length differs from the .gzi index", j, (unsigned long long)ix.coff[j]);
+            return ZWZ_E_FORMAT;
+        }
+        if (st) {
+            const uint64_t off = ix.coff[j];
+            return check_status(&st, 1, &off, 0, j);
+        }
+        if (hv.bad[i] != ~0u) {
+            const uint32_t r = P.prange[S.p0 + hv.bad[i]];
+            return range_past_end(r, ranges[2 * r], ranges[2 * r + 1]);
+        }
+    }
+    return ZWZ_OK;
+}
+
+int read_file_bytes(const char* path, std::vector<uint8_t>* out) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { set_error("cannot open %s", path); return ZWZ_E_IO; }
+    out->clear();
+    uint8_t tmp[1 << 16];
+    size_t k;
+    while ((k = fread(tmp, 1, sizeof tmp, f)) > 0) out->insert(out->end(), tmp, tmp + k);
+    const bool bad = ferror(f);
+    fclose(f);
+    if (bad) { set_error("read error on %s", path); return ZWZ_E_IO; }
+    return ZWZ_OK;
+}
+
+// Buffers of one file range read, released whatever the outcome.
+struct RangeFileJob {
+    int fd = -1;
+    void* h[2] = {};                 // pinned: packed members, decoded pieces
+    void* d[2] = {};
+    ~RangeFileJob() {
+        for (void* p : h) if (p) (void)hipHostFree(p);
+        for (void* p : d) if (p) (void)hipFree(p);
+        if (fd >= 0) close(fd);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -361,6 +644,188 @@ int zwz_bgzf_decompress_file(zwz_ctx* c, const char* src, const char* dst) {
         member0 += count;
     }
     return job.commit(dst);
+}
+
+int zwz_bgzf_gzi(const uint8_t* gz, uint64_t n, uint8_t* gzi, uint64_t cap, uint64_t* gzi_len) {
+    if ((n && !gz) || !gzi_len) return ZWZ_E_INVALID;
+    *gzi_len = 0;
+    GziBuilder b;
+    uint64_t count = 0, raw = 0, used = 0;
+    if (int rc = bgzf_walk_each(gz, n, 0, 0, false, ~0ull, [&](uint64_t, uint64_t o, uint32_t isize) { b.member(o, isize); }, &count, &raw, &used))
+        return rc;
+    b.finish();
+    *gzi_len = 8 + b.buf.size();
+    if (!gzi) return ZWZ_OK;
+    if (cap < *gzi_len) { set_error("zwz_bgzf_gzi: %llu bytes, room for %llu", (unsigned long long)*gzi_len, (unsigned long long)cap); return ZWZ_E_INVALID; }
+    put64(gzi, b.entries);
+    if (!b.buf.empty()) memcpy(gzi + 8, b.buf.data(), b.buf.size());
+    return ZWZ_OK;
+}
+
+int zwz_bgzf_gzi_file(const char* src, const char* dst_gzi) {
+    if (!src || !dst_gzi) return ZWZ_E_INVALID;
+    FileJob job;
+    if (int rc = job.open(src, dst_gzi)) return rc;
+    GziBuilder b;
+    bool werr = fwrite("\0\0\0\0\0\0\0\0", 1, 8, job.out) != 8;          // the count, rewritten at the end
+    auto flush = [&] { if (!b.buf.empty() && fwrite(b.buf.data(), 1, b.buf.size(), job.out) != b.buf.size()) werr = true; b.buf.clear(); };
+    const int rc = walk_file(job.in, [&](uint64_t o, uint32_t isize) { b.member(o, isize); if (b.buf.size() >= (1u << 20)) flush(); },
+                             [] { return false; });
+    if (rc) return rc;
+    b.finish();
+    flush();
+    uint8_t cnt[8];
+    put64(cnt, b.entries);
+    if (werr || fseek(job.out, 0, SEEK_SET) != 0 || fwrite(cnt, 1, 8, job.out) != 8) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
+    return job.commit(dst_gzi);
+}
+
+int zwz_bgzf_read_ranges_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, const uint8_t* gzi, uint64_t gzi_len, const uint64_t* ranges, uint32_t k,
+                             uint8_t* d_out) {
+    if (!c || (k && !ranges) || (gzi_len && !gzi) || (gz_len && !d_gz) || ((uintptr_t)d_gz & 15u)) return ZWZ_E_INVALID;
+    GziIndex ix;
+    if (int rc = parse_gzi(gzi, gzi_len, &ix)) return rc;
+    RangePlan P;
+    if (int rc = plan_ranges(ix, ranges, k, &P)) return rc;
+    if (P.total && !d_out) return ZWZ_E_INVALID;
+    const uint32_t T = (uint32_t)P.member.size();
+    if (!T) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const uint32_t M = T < c->max_batch ? T : c->max_batch;
+    if (int rc = ensure_bgzf(c, M)) return rc;
+    // every slice packs into its own part of the plan buffers: the host fills slice s + 1 while the device runs slice s
+    std::vector<Slice> slices;
+    std::vector<size_t> at;
+    size_t bytes = 0;
+    for (uint32_t t0 = 0; t0 < T; t0 += M) {
+        const uint32_t t1 = T - t0 < M ? T : t0 + M;
+        slices.push_back({t0, t1, P.row[t0], P.row[t1]});
+        at.push_back(bytes);
+        bytes += align16(slice_bytes(t1 - t0, P.row[t1] - P.row[t0]));
+    }
+    if (int rc = ensure_rr(c, bytes)) return rc;
+    std::vector<uint64_t> moff(T);
+    for (uint32_t t = 0; t < T; t++) moff[t] = ix.coff[P.member[t]];
+    uint8_t* h = static_cast<uint8_t*>(c->rr_host);
+    uint8_t* d = static_cast<uint8_t*>(c->rr_dev);
+    for (size_t s = 0; s < slices.size(); s++)
+        if (int rc = queue_slice(c, P, slices[s], moff.data(), nullptr, h + at[s], d + at[s], d_gz, gz_len, d_out, false)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t s = 0; s < slices.size(); s++)
+        if (int rc = slice_verdict(P, ix, slices[s], h + at[s], ranges)) return rc;
+    return ZWZ_OK;
+}
+
+// Touched members are read with one pread per run of consecutive index entries, into pinned staging of at most kFileSliceBlocks
+// members; each slice of members (and at most kRangeOutSlice decoded bytes) runs through the device path and its pieces are copied
+// to their places in out.
+int zwz_bgzf_read_ranges_file(zwz_ctx* c, const char* src, const char* gzi_path, const uint64_t* ranges, uint32_t k, uint8_t* out) {
+    if (!c || !src || (k && !ranges)) return ZWZ_E_INVALID;
+    GziIndex ix;
+    if (gzi_path) {
+        std::vector<uint8_t> g;
+        if (int rc = read_file_bytes(gzi_path, &g)) return rc;
+        if (int rc = parse_gzi(g.data(), g.size(), &ix)) return rc;
+    } else {
+        // the index of the members up to the last requested byte, from a walk of the headers
+        uint64_t need = 0;
+        for (uint32_t r = 0; r < k; r++) need = std::max(need, ranges[2 * r] + std::min<uint64_t>(ranges[2 * r + 1], ~0ull - ranges[2 * r]));
+        FILE* f = fopen(src, "rb");
+        if (!f) { set_error("cannot open %s", src); return ZWZ_E_IO; }
+        uint64_t raw = 0;
+        const int rc = walk_file(f, [&](uint64_t o, uint32_t isize) { ix.coff.push_back(o); ix.uoff.push_back(raw); raw += isize; },
+                                 [&] { return raw > need; });
+        fclose(f);
+        if (rc) return rc;
+    }
+    RangePlan P;
+    if (int rc = plan_ranges(ix, ranges, k, &P)) return rc;
+    if (P.total && !out) return ZWZ_E_INVALID;
+    const uint32_t T = (uint32_t)P.member.size();
+    if (!T) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    RangeFileJob job;
+    job.fd = open(src, O_RDONLY);
+    if (job.fd < 0) { set_error("cannot open %s", src); return ZWZ_E_IO; }
+    struct stat stt {};
+    if (fstat(job.fd, &stt) != 0) { set_error("cannot stat %s", src); return ZWZ_E_IO; }
+    const uint64_t fsize = (uint64_t)stt.st_size;
+    // member t's bytes in the file: [coff, end), end = the next entry's offset (at most a member's 65 536 bytes further), or the file's end
+    const size_t last = ix.coff.size() - 1;
+    std::vector<uint64_t> fend(T);
+    for (uint32_t t = 0; t < T; t++) {
+        const size_t j = P.member[t];
+        const uint64_t s0 = ix.coff[j];
+        uint64_t e = std::min<uint64_t>(s0 + kBgzfSlot, fsize);
+        if (j < last) e = std::min(e, ix.coff[j + 1]);
+        fend[t] = s0 >= fsize ? s0 : e;                     // (an entry past the file's end: nothing to read, the member does not parse)
+    }
+    const uint32_t S = c->max_batch < kFileSliceBlocks ? c->max_batch : kFileSliceBlocks;
+    const size_t B = (size_t)S * kBgzfSlot;
+    HIPCHK(hipHostMalloc(&job.h[0], B + 16, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(&job.h[1], kRangeOutSlice + 16, hipHostMallocDefault));
+    HIPCHK(hipMalloc(&job.d[0], B + 16));
+    HIPCHK(hipMalloc(&job.d[1], kRangeOutSlice + 16));
+    if (int rc = ensure_bgzf(c, S)) return rc;
+    uint8_t* hin = static_cast<uint8_t*>(job.h[0]);
+    uint8_t* hout = static_cast<uint8_t*>(job.h[1]);
+    std::vector<uint64_t> moff(T), mend(T);
+    uint32_t t = 0, p = 0;
+    while (t < T) {
+        // the slice: whole members while they fit S and kRangeOutSlice, or a part of one member's pieces that alone exceed kRangeOutSlice
+        // (every piece is at most 65 536 bytes: a part holds at least one).  Its first member may continue one cut before.
+        Slice sl{t, t, p, p};
+        uint64_t obytes = 0;
+        while (sl.t1 < T && sl.t1 - sl.t0 < S) {
+            const uint32_t q0 = sl.t1 == t ? p : P.row[sl.t1];
+            uint64_t mb = 0;
+            for (uint32_t q = q0; q < P.row[sl.t1 + 1]; q++) mb += P.piece[q].len;
+            if (obytes + mb <= kRangeOutSlice) { obytes += mb; sl.t1++; sl.p1 = P.row[sl.t1]; continue; }
+            if (sl.t1 == sl.t0) {
+                uint32_t q = q0;
+                while (q < P.row[sl.t1 + 1] && obytes + P.piece[q].len <= kRangeOutSlice) obytes += P.piece[q++].len;
+                sl.t1++;
+                sl.p1 = q;
+            }
+            break;
+        }
+        // read the slice's members: one pread per run of consecutive entries
+        uint64_t packed = 0;
+        for (uint32_t i = sl.t0; i < sl.t1;) {
+            uint32_t e = i + 1;
+            while (e < sl.t1 && P.member[e] == P.member[e - 1] + 1 && fend[e - 1] == ix.coff[P.member[e]]) e++;
+            const uint64_t start = ix.coff[P.member[i]], len = fend[e - 1] - start;
+            size_t got = 0;
+            while (got < len) {
+                const ssize_t r = pread(job.fd, hin + packed + got, len - got, (off_t)(start + got));
+                if (r < 0) { set_error("read error on %s", src); return ZWZ_E_IO; }
+                if (r == 0) break;
+                got += (size_t)r;
+            }
+            for (uint32_t q = i; q < e; q++) {
+                moff[q] = packed + (ix.coff[P.member[q]] - start);
+                mend[q] = std::min(packed + (fend[q] - start), packed + got);
+            }
+            packed += got;
+            i = e;
+        }
+        uint8_t* d_in = static_cast<uint8_t*>(job.d[0]);
+        uint8_t* d_dec = static_cast<uint8_t*>(job.d[1]);
+        const uint32_t m = sl.t1 - sl.t0, np = sl.p1 - sl.p0;
+        if (int rc = ensure_rr(c, slice_bytes(m, np))) return rc;
+        HIPCHK(hipMemcpyAsync(d_in, hin, packed, hipMemcpyHostToDevice, c->stream));
+        if (int rc = queue_slice(c, P, sl, moff.data(), mend.data(), static_cast<uint8_t*>(c->rr_host), static_cast<uint8_t*>(c->rr_dev), d_in, packed,
+                                 d_dec, true))
+            return rc;
+        if (obytes) HIPCHK(hipMemcpyAsync(hout, d_dec, obytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (int rc = slice_verdict(P, ix, sl, static_cast<const uint8_t*>(c->rr_host), ranges)) return rc;
+        uint64_t o = 0;
+        for (uint32_t q = sl.p0; q < sl.p1; q++) { memcpy(out + P.piece[q].dst, hout + o, P.piece[q].len); o += P.piece[q].len; }
+        p = sl.p1;
+        t = p < P.row[sl.t1] ? sl.t1 - 1 : sl.t1;         // a member cut in parts: its next part opens the next slice
+    }
+    return ZWZ_OK;
 }
 
 }  // extern "C"

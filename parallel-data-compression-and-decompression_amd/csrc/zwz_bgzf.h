@@ -17,6 +17,12 @@ constexpr uint32_t kBgzfThreads = 256;        // lanes of the CRC workgroup (crc
 // member body is ever cut; bgzf_scan still flags a stream that reaches the slot's length (the output length then reads ~0).
 static_assert(kBgzfBlock + 5u * 5u + 6u + 16u < 65535u, "a BGZF block's level-6 stream always fits the deflate slot");
 
+// Range reads: one piece is len bytes at offset off of a touched member's decoded block, bound for out + dst
+struct RangePiece { uint64_t dst; uint32_t off; uint32_t len; };
+constexpr uint32_t kNoExpect = 0xffffffffu;       // no index entry follows the member: its decoded length is not known in advance
+constexpr uint32_t kBgzfIndexMismatch = 32;       // member status (internal): decoded length differs from what the .gzi implies
+constexpr uint32_t kWavePieceMax = 4096;          // pieces of at least this many bytes go with the workgroup, shorter ones with a wave
+
 extern const uint8_t kBgzfEof[kBgzfEofBytes];
 
 // CRC tables in device memory (crc_core.h): slicing tables, the lane stride's multiplier, every lane's closing shift.
@@ -43,5 +49,15 @@ hipError_t launch_bgzf_gather(const uint8_t* gz, uint64_t gz_len, const uint64_t
 hipError_t launch_bgzf_verify_compact(const CrcTables* t, const uint8_t* slots, const uint32_t* olen, const uint32_t* inf_status, const uint32_t* crc,
                                       const uint32_t* isize, const uint64_t* ooff, uint32_t m, uint8_t* out, uint32_t* status, uint32_t cu_count,
                                       hipStream_t s);
+
+// touched members: member i at gz + moff[i], readable up to min(mend[i], gz_len) (mend may be null: gz_len).  The header is parsed
+// and bounds-checked on the device; then as launch_bgzf_gather for slot i (status[i] = 0 or ZWZ_BGZF_BAD_MEMBER)
+hipError_t launch_bgzf_gather_list(const uint8_t* gz, uint64_t gz_len, const uint64_t* moff, const uint64_t* mend, uint32_t m, uint8_t* slots,
+                                   uint64_t* in_off, uint32_t* in_len, uint32_t* crc, uint32_t* isize, uint32_t* status, hipStream_t s);
+// checks decoded slot i (status[i]: first failure wins; kBgzfIndexMismatch when the length is not expect[i]) and copies its pieces
+// [row[i], row[i + 1]) -- the first nlong[i] of them >= kWavePieceMax bytes -- to out; bad_piece[i] = smallest piece past the block's end
+hipError_t launch_bgzf_verify_extract(const CrcTables* t, const uint8_t* slots, const uint32_t* olen, const uint32_t* inf_status, const uint32_t* crc,
+                                      const uint32_t* isize, const uint32_t* expect, const uint32_t* row, const uint32_t* nlong, const RangePiece* pieces,
+                                      uint32_t m, uint8_t* out, uint32_t* status, uint32_t* bad_piece, uint32_t cu_count, hipStream_t s);
 
 }  // namespace zwz

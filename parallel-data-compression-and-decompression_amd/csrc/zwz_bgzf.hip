@@ -113,16 +113,17 @@ __global__ void __launch_bounds__(kScanThreads) bgzf_scan_kernel(const uint32_t*
     if (t == 0) { *base = carry; if (bad) *err = 1; }
 }
 
-// Copies len bytes src -> dst with the workgroup.  Every whole 16-byte aligned vector of dst is one store, its bytes gathered from
-// four or five aligned source dwords with v_alignbyte (the source's misalignment against dst is the same for every vector); the
-// partly covered vectors at both ends go byte by byte.  Reads up to 3 bytes past src + len: callers keep those readable.
-__device__ void wg_copy(uint8_t* dst, const uint8_t* src, uint32_t len) {
+// Copies len bytes src -> dst with `lanes` lanes, this one being `lane`.  Every whole 16-byte aligned vector of dst is one store, its
+// bytes gathered from four or five aligned source dwords with v_alignbyte (the source's misalignment against dst is the same for
+// every vector); the partly covered vectors at both ends go byte by byte.  Reads up to 3 bytes past src + len: callers keep those
+// readable.
+__device__ void lanes_copy(uint8_t* dst, const uint8_t* src, uint32_t len, uint32_t lane, uint32_t lanes) {
     if (!len) return;
     const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + len, v0 = d0 & ~(uintptr_t)15;
     const uint32_t nv = (uint32_t)((((d1 + 15) & ~(uintptr_t)15) - v0) >> 4);
     const uintptr_t delta = reinterpret_cast<uintptr_t>(src) - d0;        // (modular) source address of dst byte a: a + delta
     const uint32_t r = (uint32_t)(delta & 3u);
-    for (uint32_t j = threadIdx.x; j < nv; j += blockDim.x) {
+    for (uint32_t j = lane; j < nv; j += lanes) {
         const uintptr_t D = v0 + ((uintptr_t)j << 4);
         if (D >= d0 && D + 16 <= d1) {
             const uint32_t* w = reinterpret_cast<const uint32_t*>((D + delta) & ~(uintptr_t)3);
@@ -142,6 +143,9 @@ __device__ void wg_copy(uint8_t* dst, const uint8_t* src, uint32_t len) {
         }
     }
 }
+
+// The workgroup's copy (every lane of the block)
+__device__ __forceinline__ void wg_copy(uint8_t* dst, const uint8_t* src, uint32_t len) { lanes_copy(dst, src, len, threadIdx.x, blockDim.x); }
 
 __device__ __forceinline__ void put_le32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 __device__ __forceinline__ uint32_t get_le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
@@ -217,6 +221,80 @@ __global__ void __launch_bounds__(kBgzfThreads) bgzf_verify_compact_kernel(const
     }
 }
 
+// Range reads (zwz_bgzf_read_ranges_*): touched member i starts at gz + moff[i] and may use bytes up to min(mend[i], gz_len) (mend null:
+// gz_len).  Its header is parsed here as the host walk parses it -- magic, flags, XLEN, the BC subfield -- so the end comes from BSIZE,
+// never from the index; then the body goes behind 78 9c into slot i as bgzf_gather_kernel does.
+__global__ void __launch_bounds__(256) bgzf_gather_list_kernel(const uint8_t* gz, uint64_t gz_len, const uint64_t* moff, const uint64_t* mend,
+                                                               uint8_t* slots, uint64_t* in_off, uint32_t* in_len, uint32_t* crc, uint32_t* isize,
+                                                               uint32_t* status) {
+    __shared__ uint32_t body_start, body_len, ok;
+    const uint32_t i = blockIdx.x;
+    const uint64_t o = moff[i], lim = mend ? min(mend[i], gz_len) : gz_len;
+    uint8_t* slot = slots + (size_t)i * kBgzfSlot;
+    if (threadIdx.x == 0) {
+        const uint8_t* p = gz + o;
+        uint32_t xlen = 0, bsize = 0;
+        bool good = o < lim && lim - o >= 12 && p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && (p[3] & 4u) && !(p[3] & ~5u);
+        if (good) { xlen = get_le16(p + 10); good = lim - o >= 12ull + xlen; }
+        for (uint32_t x = 0; good && x < xlen;) {
+            const uint8_t* f = p + 12 + x;
+            const uint32_t slen = xlen - x < 4 ? 0u : get_le16(f + 2);
+            if (xlen - x < 4 || 4u + slen > xlen - x) { good = false; break; }
+            if (f[0] == 'B' && f[1] == 'C' && slen == 2) bsize = get_le16(f + 4) + 1u;
+            x += 4 + slen;
+        }
+        good = good && bsize >= 12u + xlen + kBgzfTrailer && bsize <= lim - o;
+        const uint32_t isz = good ? get_le32(p + bsize - 4) : 0u;
+        good = good && isz <= kBgzfMaxIsize;
+        body_start = 12 + xlen;
+        body_len = good ? bsize - 12u - xlen - kBgzfTrailer : 0u;
+        ok = good;
+        slot[0] = 0x78; slot[1] = 0x9c;
+        in_off[i] = (uint64_t)i * kBgzfSlot;
+        in_len[i] = 2 + body_len;
+        crc[i] = good ? get_le32(p + bsize - 8) : 0u;
+        isize[i] = good ? isz : 0u;
+        status[i] = good ? 0u : (uint32_t)ZWZ_BGZF_BAD_MEMBER;
+    }
+    __syncthreads();
+    if (ok) wg_copy(slot + 2, gz + o + body_start, body_len);
+}
+
+// Check of decoded slot i (inflate status, ISIZE, CRC-32, and the length the index implies: expect[i] unless kNoExpect) into status[i],
+// then its pieces row[i] .. row[i + 1] - 1 to out.  The first nlong[i] of them are at least kWavePieceMax bytes and go with the
+// whole workgroup; each of the rest goes with one wave, the four waves taking turns.  A piece past the decoded length is not copied:
+// the smallest such piece index goes to bad_piece[i] (initialised to ~0 by the caller).
+__global__ void __launch_bounds__(kBgzfThreads) bgzf_verify_extract_kernel(const CrcTables* tab, const uint8_t* slots, const uint32_t* olen,
+                                                                           const uint32_t* inf_status, const uint32_t* crc, const uint32_t* isize,
+                                                                           const uint32_t* expect, const uint32_t* row, const uint32_t* nlong,
+                                                                           const RangePiece* pieces, uint32_t m, uint8_t* out, uint32_t* status,
+                                                                           uint32_t* bad_piece) {
+    __shared__ CrcLds s;
+    crc_load_tables(s, tab);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) {
+        const uint8_t* slot = slots + (size_t)i * kBgzfSlot;
+        const uint32_t L = min(olen[i], kBgzfMaxIsize);
+        const uint32_t c = crc_block_wg(s, slot, L);
+        if (threadIdx.x == 0 && status[i] == 0) {
+            const uint32_t st = inf_status[i], e = expect[i];
+            status[i] = st != ZWZ_INF_END ? st : L != isize[i] ? (uint32_t)ZWZ_BGZF_ISIZE_MISMATCH : c != crc[i] ? (uint32_t)ZWZ_BGZF_CRC_MISMATCH
+                      : e != kNoExpect && L != e ? kBgzfIndexMismatch : 0u;
+        }
+        const uint32_t p0 = row[i], pl = p0 + nlong[i], p1 = row[i + 1];
+        for (uint32_t p = p0; p < pl; p++) {
+            const RangePiece q = pieces[p];
+            if ((uint64_t)q.off + q.len > L) { if (threadIdx.x == 0) atomicMin(&bad_piece[i], p); continue; }
+            wg_copy(out + q.dst, slot + q.off, q.len);
+        }
+        for (uint32_t p = pl + wave; p < p1; p += kBgzfThreads / 64) {
+            const RangePiece q = pieces[p];
+            if ((uint64_t)q.off + q.len > L) { if (lane == 0) atomicMin(&bad_piece[i], p); continue; }
+            lanes_copy(out + q.dst, slot + q.off, q.len, lane, 64);
+        }
+    }
+}
+
 uint32_t persistent_grid(uint32_t m, uint32_t cu_count) {
     const uint32_t g = (cu_count ? cu_count : 256u) * 4u;     // four 21-KiB table copies a CU
     return m < g ? m : g;
@@ -272,6 +350,22 @@ hipError_t launch_bgzf_verify_compact(const CrcTables* t, const uint8_t* slots, 
                                       hipStream_t s) {
     if (!m) return hipSuccess;
     bgzf_verify_compact_kernel<<<persistent_grid(m, cu_count), kBgzfThreads, 0, s>>>(t, slots, olen, inf_status, crc, isize, ooff, m, out, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_bgzf_gather_list(const uint8_t* gz, uint64_t gz_len, const uint64_t* moff, const uint64_t* mend, uint32_t m, uint8_t* slots,
+                                   uint64_t* in_off, uint32_t* in_len, uint32_t* crc, uint32_t* isize, uint32_t* status, hipStream_t s) {
+    if (!m) return hipSuccess;
+    bgzf_gather_list_kernel<<<m, 256, 0, s>>>(gz, gz_len, moff, mend, slots, in_off, in_len, crc, isize, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_bgzf_verify_extract(const CrcTables* t, const uint8_t* slots, const uint32_t* olen, const uint32_t* inf_status, const uint32_t* crc,
+                                      const uint32_t* isize, const uint32_t* expect, const uint32_t* row, const uint32_t* nlong, const RangePiece* pieces,
+                                      uint32_t m, uint8_t* out, uint32_t* status, uint32_t* bad_piece, uint32_t cu_count, hipStream_t s) {
+    if (!m) return hipSuccess;
+    bgzf_verify_extract_kernel<<<persistent_grid(m, cu_count), kBgzfThreads, 0, s>>>(t, slots, olen, inf_status, crc, isize, expect, row, nlong, pieces,
+                                                                                     m, out, status, bad_piece);
     return hipGetLastError();
 }
 
