@@ -90,6 +90,8 @@ public:
         std::unique_lock<std::mutex> l(m_);
         done_cv_.wait(l, [&] { return g.pending.load() == 0; });
     }
+    // workers actually started: the thread-limit fallback above may leave fewer than were asked for
+    size_t size() const { return workers_.size(); }
     bool failed(std::string* why = nullptr) {
         std::lock_guard<std::mutex> l(m_);
         if (why) *why = failure_;
@@ -767,14 +769,16 @@ struct DecodeSink {
     // The same digest, taken WHILE the file is being written: the hash trails the writers -- it reads what `durable` says is on disk,
     // waits when it has caught up, and ends when the file is `complete` and read to its end.  One MD5 stream is ~0.8 GB/s (an 8 GiB
     // file: 10.9 s, tools/one_file_e2e.py), the decode of the same file 1.2 s: started behind the last record, the hash ADDED its time;
-    // started with the first slice it hides the decode.
-    void hash_trailing(uint32_t inst, const std::atomic<uint64_t>& durable, const std::atomic<int>& complete) const {
+    // started with the first slice it hides the decode.  `abandoned`: the decode stopped before the file was complete (an error
+    // left the slice loop); the hash then ends without a verdict -- nothing would ever make the file complete.
+    void hash_trailing(uint32_t inst, const std::atomic<uint64_t>& durable, const std::atomic<int>& complete, const std::atomic<int>& abandoned) const {
         Md5 m;
         const std::string file_path = path_of(inst);
         const int fd = open(file_path.c_str(), O_RDONLY);
         std::vector<uint8_t> buf(4 << 20);
         uint64_t off = 0;
         while (fd >= 0) {
+            if (abandoned.load(std::memory_order_acquire)) { close(fd); return; }
             const int fin = complete.load(std::memory_order_acquire);        // (read BEFORE durable: a complete file's durable is final)
             const uint64_t upto = durable.load(std::memory_order_acquire);
             if (off < upto) {
@@ -815,7 +819,8 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
     for (uint32_t i = 0; i < insts.size(); i++) for (const Rec& r : insts[i].order) jobs.push_back({i, r});
     struct OutState { FILE* f = nullptr; int fd = -1; uint64_t written = 0; Md5 md5; uint32_t remaining = 0; bool failed = false; bool deferred = false;
                       int32_t gpu_md5 = -1;         // index into its slice's GPU digest list, or -1: hashed by the task that writes it
-                      std::atomic<uint64_t> durable{0}; std::atomic<int> complete{0}; bool hashing = false; };   // a spanning file's trailing hash (DecodeSink::hash_trailing)
+                      std::atomic<uint64_t> durable{0}; std::atomic<int> complete{0}; bool hashing = false;     // a spanning file's trailing hash (DecodeSink::hash_trailing)
+                      std::atomic<int> abandoned{0}; };                                                         // ... told to stop: the decode ended early
     std::vector<OutState> outs(insts.size());
     // SURVEY.md section 8 f1, second call site (decompression.cpp:136): a file decoded whole within one slice (and no longer than the
     // 64 chunks a lane is asked to hash on the compress side) sits in consecutive output slots on the device -- its MD5 is taken
@@ -848,6 +853,11 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
     struct FreeSlices { Slices& s; ~FreeSlices() { free_slices(s); } } free_sl{sl};      // behind the Drain: released once the tasks are done, whatever the way out
     Pool::Group fill_group[2], write_group, md5_group;
     Drain drain{pool, {&fill_group[0], &fill_group[1], &write_group, &md5_group}};
+    // A trailing hash ends only when its file is complete.  On every way out of the slice loop that leaves a file incomplete -- an
+    // error `break`, an exception unwinding through write_slice -- its hash is told to give up, BEFORE anything waits for md5_group:
+    // called below on an error, and by this guard (declared after the Drain: destroyed, and so run, before the Drain waits).
+    auto abandon_hashes = [&outs] { for (OutState& o : outs) if (o.hashing && !o.complete.load()) o.abandoned.store(1, std::memory_order_release); };
+    struct Abandon { decltype(abandon_hashes)& f; ~Abandon() { f(); } } abandon{abandon_hashes};
     // MD5 is one sequential stream per file (~0.65 GB/s).  A file decoded within one slice is hashed by the task that
     // writes it, from the staging buffer; a file that spans slices would hold every slice back for its hash (three
     // 384 MiB files: 2.1 s, slower than the reference), so it is hashed afterwards, from the file just written, by a
@@ -937,6 +947,16 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
         const int b = (int)(s & 1u);
         const uint32_t g0 = s * cap, g1 = std::min(T, g0 + cap);
         std::vector<uint32_t> finished;          // spanning files whose last record is in this slice
+        // (call with the writes of `finished` done) closed, final length published, hash completed or started
+        auto finish_spanning = [&] {
+            for (uint32_t inst : finished) {
+                OutState& o = outs[inst];
+                if (o.fd >= 0) { o.durable.store(o.written, std::memory_order_release); close(o.fd); o.fd = -1; }
+                if (o.hashing) o.complete.store(1, std::memory_order_release);
+                else pool.submit(md5_group, [&sink, inst] { sink.hash_from_disk(inst); }, /*background=*/true);     // (one worker, or a file that could not be created)
+            }
+            finished.clear();
+        };
         uint32_t g = g0;
         while (g < g1) {
             uint32_t e = g;
@@ -944,7 +964,9 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
             const uint32_t inst = jobs[g].inst, a0 = g, a1 = e;
             OutState& os = outs[inst];
             if (shared_path[inst]) {            // rare: in shard order, nothing else of this path in flight (see shared_path)
-                pool.wait(write_group); pool.wait(md5_group);
+                // a spanning file that ended earlier in this slice is complete once its writes are: its trailing hash (in md5_group)
+                // would otherwise wait for the end of the slice, and this thread for it
+                pool.wait(write_group); finish_spanning(); pool.wait(md5_group);
                 if (!os.f && !os.failed && os.remaining == (uint32_t)insts[inst].order.size()) open_out(inst);
                 for (uint32_t k = a0; k < a1; k++) {
                     const uint8_t* src = sl.h_out[b] + (size_t)(k - g0) * ZWZ_DEV_STRIDE;
@@ -994,23 +1016,26 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
             g = e;
         }
         { const double t0 = since(); pool.wait(write_group); t_write_wait += since() - t0; }   // the next slice of a file must follow this one
-        // what this slice wrote of the spanning files is on disk now: their hashes (started with a file's first slice) may read on
+        // what this slice wrote of the spanning files is on disk now: their hashes (started with a file's first slice) may read on.
+        // A trailing hash occupies its worker until the file is complete, i.e. until slices behind this one are written -- by the
+        // other workers.  With one worker there are none: spanning files are then hashed from disk after their last record.
+        const bool trailing = pool.size() >= 2;
         for (uint32_t g2 = g0; g2 < g1;) {
             uint32_t e2 = g2;
             while (e2 < g1 && jobs[e2].inst == jobs[g2].inst) e2++;
             OutState& o = outs[jobs[g2].inst];
             if (o.deferred && !shared_path[jobs[g2].inst] && o.fd >= 0) {
                 o.durable.store(o.written, std::memory_order_release);
-                if (!o.hashing) { o.hashing = true; const uint32_t inst = jobs[g2].inst; pool.submit(md5_group, [&sink, &outs, inst] { sink.hash_trailing(inst, outs[inst].durable, outs[inst].complete); }, /*background=*/true); }
+                if (!o.hashing && trailing) {
+                    o.hashing = true;
+                    const uint32_t inst = jobs[g2].inst;
+                    pool.submit(md5_group, [&sink, &outs, inst] { sink.hash_trailing(inst, outs[inst].durable, outs[inst].complete, outs[inst].abandoned); },
+                                /*background=*/true);
+                }
             }
             g2 = e2;
         }
-        for (uint32_t inst : finished) {
-            OutState& o = outs[inst];
-            if (o.fd >= 0) { close(o.fd); o.fd = -1; }
-            if (o.hashing) o.complete.store(1, std::memory_order_release);
-            else pool.submit(md5_group, [&sink, inst] { sink.hash_from_disk(inst); }, /*background=*/true);     // (a file that could not be created: reports as before)
-        }
+        finish_spanning();
     };
 
     if (nslices && rc == ZWZ_OK) start_fill(0);
@@ -1028,6 +1053,7 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
         t_gpu_wait += since() - t0;
         if (e != hipSuccess) rc = hip_fail(e, "hipEventSynchronize"); else write_slice(nslices - 1);
     }
+    if (rc != ZWZ_OK) abandon_hashes();           // (before the wait for md5_group below)
     const double t_slices = since();
     pool.wait(fill_group[0]); pool.wait(fill_group[1]); pool.wait(md5_group);
     if (timeline()) fprintf(stderr, "zwz: decode: %u records of %zu files in %u slices done at %.3f s (waited %.3f s for the GPU, %.3f s for the writers); "

@@ -98,3 +98,72 @@ def edge_shards(good):
         "cut_header": good[:spans[k][0] + 6],
         "empty": b"",
     }
+
+
+
+def flip_digit(hexdigest):
+    """The same digest wrong in one hex digit (bytes in, bytes out)."""
+    i = sum(hexdigest) % 32
+    return hexdigest[:i] + (b"1" if hexdigest[i:i + 1] == b"0" else b"0") + hexdigest[i + 1:]
+
+
+def file_records(path, payloads, md5):
+    """The records of one file, chunks ascending, the digest behind the last."""
+    return [(path, seq, int(seq + 1 == len(payloads)), p, md5 if seq + 1 == len(payloads) else None)
+            for seq, p in enumerate(payloads)]
+
+
+def decode_alone(oracle, path, payloads, workdir, tag):
+    """What the reference's decoder makes of one file's records: a one-file shard through oracle.decompress_shard."""
+    import os
+    one, out = os.path.join(workdir, "one_%s.zwz" % tag), os.path.join(workdir, "one_%s" % tag)
+    os.makedirs(workdir, exist_ok=True)
+    with open(one, "wb") as f:
+        f.write(serialise(file_records(path, payloads, b"0" * 32)))
+    oracle.decompress_shard(one, out)
+    with open(os.path.join(out, path.decode()), "rb") as f:
+        return f.read()
+
+
+def instances(blob):
+    """-> [(path, [payload, ...], stored digest)] of a shard whose records are in order (every file's chunks ascending,
+    its last record behind the others): one entry per file instance, a repeated path once per instance."""
+    out, cur = [], {}
+    for path, seq, last, payload, md5 in parse(blob):
+        payloads = cur.setdefault(path, [])
+        assert seq == len(payloads), (path, seq)
+        payloads.append(payload)
+        if last:
+            out.append((path, cur.pop(path), md5))
+    assert not cur, sorted(cur)
+    return out
+
+
+def verdicts(oracle, blob, workdir):
+    """The reference's verdict for every file instance of an in-order shard, each instance decoded on its own:
+    -> [(path, decoded bytes, stored digest, "match" | "mismatch")] in shard order."""
+    import hashlib
+    out = []
+    for i, (path, payloads, stored) in enumerate(instances(blob)):
+        decoded = decode_alone(oracle, path, payloads, workdir, "v%d" % i)
+        out.append((path, decoded, stored, "match" if hashlib.md5(decoded).hexdigest().encode() == stored else "mismatch"))
+    return out
+
+
+def build_shard(oracle, files, workdir):
+    """A .zwz shard from a list of files, with the MD5 each one stores chosen: files = [(path bytes, [payload, ...],
+    "right" | "wrong"), ...], records in list order, chunks ascending.  "right" is the MD5 of what the reference's
+    decoder makes of the file's records (oracle.decompress_shard, so a cut payload that decodes short still verifies);
+    "wrong" is that digest with one hex digit changed.  Two passes: every file is first decoded on its own, from a
+    one-file shard (a path may occur twice with different payloads), then the digests go into the records.
+    -> (shard bytes, [(path, decoded bytes, stored digest, "match" | "mismatch")] in list order)."""
+    import hashlib
+    recs, table = [], []
+    for i, (path, payloads, digest) in enumerate(files):
+        assert payloads and digest in ("right", "wrong"), (path, digest)
+        decoded = decode_alone(oracle, path, payloads, workdir, "b%d" % i)
+        right = hashlib.md5(decoded).hexdigest().encode()
+        stored = right if digest == "right" else flip_digit(right)
+        recs += file_records(path, payloads, stored)
+        table.append((path, decoded, stored, "match" if digest == "right" else "mismatch"))
+    return serialise(recs), table
