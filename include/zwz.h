@@ -236,6 +236,40 @@ int zwz_bgzf_read_ranges_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len,
  * entries); gzi_path == NULL walks the member headers from the start until the last requested byte is covered. */
 int zwz_bgzf_read_ranges_file(zwz_ctx *ctx, const char *src, const char *gzi_path, const uint64_t *ranges, uint32_t k, uint8_t *out);
 
+/* ---- DEFLATE streams of any size: raw, zlib and gzip ---------------------------------------------------------------------------
+ * Decodes a batch of n independent streams in one pass on the GPU, one wave per stream (a single stream is not faster than one
+ * wave; the call pays off on batches of thousands).  Stream i is d_in_len[i] bytes at d_in + d_in_off[i], wrapped as `wrap` says:
+ *   ZWZ_WRAP_RAW   RFC 1951 DEFLATE data alone; bytes after the final block are ignored
+ *   ZWZ_WRAP_ZLIB  RFC 1950: header, DEFLATE data, Adler-32; bytes after the Adler-32 are ignored
+ *   ZWZ_WRAP_GZIP  RFC 1952: one or more members, each a header (FEXTRA, FNAME, FCOMMENT, FHCRC), DEFLATE data, CRC-32 and ISIZE.
+ *                  Zero bytes between and after members are skipped; a following 1f 8b starts another member, any other byte is
+ *                  ZWZ_STREAM_TRAILING.  Every member starts with an empty window.  An input with no member (empty, or zeros only)
+ *                  is status 1.
+ * Output i goes to d_out + d_out_off[i], at most d_out_cap[i] bytes; d_out_len[i] receives the decoded length (also on failure:
+ * everything decoded before the stop, as libz emits it) and d_status[i] the verdict, libz 1.2.11's:
+ * 0..3 as in zwz_inflate_status, 3 meaning that the output would pass d_out_cap[i], or a zwz_stream_status.  A checksum mismatch in an earlier
+ * member beats whatever stopped a later one, as libz stops at the first bad member.  A byte outside
+ * [d_out_off[i], d_out_off[i] + d_out_cap[i]) is never written.
+ * Limits (the kernel's 32-bit bit and byte positions): d_in_len[i] < 2^29 and d_out_cap[i] < 2^32, else ZWZ_STREAM_TOO_LARGE with
+ * nothing read or written.
+ * Alignment: d_in, d_out and every d_in_off[i], d_out_off[i] are multiples of 16; stream i is readable up to its length rounded up to
+ * 16; output ranges do not overlap.  All arrays are device memory on the context's GPU.  Asynchronous on the context's stream.
+ * ZWZ_E_INVALID for a null pointer, a misaligned d_in / d_out or an unknown wrap; problems of one stream only through d_status.
+ * Preset dictionaries (FDICT) are ZWZ_STREAM_BAD_HEADER.  The context's "inflate_header" option applies here too. */
+#define ZWZ_WRAP_RAW  0
+#define ZWZ_WRAP_ZLIB 1
+#define ZWZ_WRAP_GZIP 2
+typedef enum zwz_stream_status {      /* 0..3 mean what zwz_inflate_status means */
+    ZWZ_STREAM_BAD_HEADER = 32,   /* not this wrapper, FDICT set, unknown method or flags, window > 32K, header CRC mismatch */
+    ZWZ_STREAM_CHECKSUM   = 33,   /* Adler-32 / CRC-32 mismatch */
+    ZWZ_STREAM_LENGTH     = 34,   /* gzip ISIZE mismatch */
+    ZWZ_STREAM_TRAILING   = 35,   /* gzip: bytes after a member that are neither zero padding nor another member */
+    ZWZ_STREAM_TOO_LARGE  = 36    /* d_in_len[i] >= 2^29 or d_out_cap[i] >= 2^32: nothing read or written */
+} zwz_stream_status;
+int zwz_inflate_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
+                            uint32_t n, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
+                            uint64_t *d_out_len, uint32_t *d_status);
+
 #ifdef __cplusplus
 }
 #endif

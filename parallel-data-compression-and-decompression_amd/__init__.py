@@ -15,6 +15,8 @@ and BGZF (blocked gzip, readable by gzip / zcat / htslib; no reference counterpa
     Codec.bgzf_compress_file / Codec.bgzf_decompress_file      (whole files, streamed)
     bgzf_gzi / bgzf_gzi_file                                   (the .gzi index, host only)
     Codec.bgzf_read_ranges / Codec.bgzf_read_ranges_file       (random access: decoded byte ranges)
+and ordinary DEFLATE data of any size, a batch of independent streams in one launch (no reference counterpart):
+    Codec.inflate_streams / Codec.inflate_streams_dev          (raw, zlib or gzip; bytes or device tensors)
 
 There is no CPU fallback: importing works anywhere (so the build can be checked), but every codec
 call needs the HIP library and a GPU and raises ZwzError otherwise.
@@ -91,6 +93,7 @@ def lib():
         L.zwz_bgzf_gzi_file.argtypes = [c.c_char_p, c.c_char_p]
         L.zwz_bgzf_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp]
         L.zwz_bgzf_read_ranges_file.argtypes = [vp, c.c_char_p, c.c_char_p, vp, u32, vp]
+        L.zwz_inflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -101,6 +104,12 @@ E_CHECKSUM = -7
 BGZF_BLOCK_SIZE = 65280     # raw bytes per BGZF member (htslib's BGZF_BLOCK_SIZE)
 # per-member status of zwz_bgzf_decompress_dev beyond the inflate codes (include/zwz.h)
 BGZF_BAD_MEMBER, BGZF_ISIZE_MISMATCH, BGZF_CRC_MISMATCH = 16, 17, 18
+# zwz_inflate_streams_dev (include/zwz.h): wrappers, and per-stream statuses beyond the inflate codes 0..3
+WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2
+WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP}
+STREAM_END, STREAM_NEED_INPUT, STREAM_DATA_ERROR, STREAM_OVERFLOW = 0, 1, 2, 3
+STREAM_BAD_HEADER, STREAM_CHECKSUM, STREAM_LENGTH, STREAM_TRAILING, STREAM_TOO_LARGE = 32, 33, 34, 35, 36
+STREAM_MAX_IN, STREAM_MAX_OUT = 1 << 29, 1 << 32
 
 
 def _check(rc, what, **extra):
@@ -211,6 +220,78 @@ class Codec:
         n = d_len.numel()
         _check(lib().zwz_inflate_batch_dev(self._h, d_in.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, d_out.data_ptr(),
                                            out_stride, d_out_len.data_ptr(), d_status.data_ptr()), "zwz_inflate_batch_dev")
+
+    def inflate_streams_dev(self, wrap, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status):
+        """zwz_inflate_streams_dev on device tensors (offsets, lengths, capacities and d_out_len int64, d_status int32; include/zwz.h
+        has the alignment rules).  wrap: "raw" | "zlib" | "gzip" or WRAP_*.  Asynchronous; never raises for a stream's status."""
+        n = d_in_len.numel()
+        _check(lib().zwz_inflate_streams_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), n,
+                                             d_out.data_ptr(), d_out_off.data_ptr(), d_out_cap.data_ptr(), d_out_len.data_ptr(),
+                                             d_status.data_ptr()), "zwz_inflate_streams_dev")
+
+    def _streams_once(self, torch, np, wrap, streams, caps):
+        """One call over host streams with the given capacities -> (statuses, [bytes])."""
+        n = len(streams)
+        dev = torch.device("cuda", self.device)
+        lens = np.array([len(s) for s in streams], dtype=np.int64)
+        offs = np.zeros(n, dtype=np.int64)
+        if n:
+            offs[1:] = np.cumsum((lens[:-1] + 15) // 16 * 16)
+        total_in = int(offs[-1] + (lens[-1] + 15) // 16 * 16) if n else 0
+        blob = np.zeros(max(total_in, 16), dtype=np.uint8)
+        for i, s in enumerate(streams):
+            blob[offs[i]:offs[i] + len(s)] = np.frombuffer(s, dtype=np.uint8)
+        cap = np.array(caps, dtype=np.int64)
+        ooff = np.zeros(n, dtype=np.int64)
+        if n:
+            ooff[1:] = np.cumsum((cap[:-1] + 15) // 16 * 16)
+        total_out = int(ooff[-1] + (cap[-1] + 15) // 16 * 16) if n else 0
+        d_in = torch.from_numpy(blob).to(dev)
+        d_out = torch.empty(max(total_out, 16), dtype=torch.uint8, device=dev)
+        t = lambda a: torch.from_numpy(a).to(dev)
+        d_off, d_len, d_ooff, d_cap = t(offs), t(lens), t(ooff), t(cap)
+        d_olen = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.inflate_streams_dev(wrap, d_in, d_off, d_len, d_out, d_ooff, d_cap, d_olen, d_st)
+        self.sync()
+        st = d_st[:n].cpu().numpy()
+        olen = d_olen[:n].cpu().numpy()
+        host = d_out.cpu().numpy()
+        return [int(x) for x in st], [host[ooff[i]:ooff[i] + olen[i]].tobytes() for i in range(n)]
+
+    def inflate_streams(self, streams, wrap="gzip", out_sizes=None):
+        """[bytes] -> [decoded bytes]: a batch of independent raw / zlib / gzip streams of any size in one pass on the GPU.  Raises
+        ZwzError for the first failing stream, naming its index and status (.index, .stream_status), as zlib.decompress raises.
+        out_sizes: each stream's decoded size if known; without it capacities are guessed (gzip: ISIZE from the last 4 bytes; zlib,
+        raw: max(4 x input, 64 KiB)), and streams that come back with status 3 are decoded again by themselves with double the
+        capacity, up to 2^32 - 1."""
+        import numpy as np
+        import torch
+        w = WRAPS.get(wrap, wrap)
+        if w not in (WRAP_RAW, WRAP_ZLIB, WRAP_GZIP):
+            raise ValueError("wrap must be raw, zlib or gzip")
+        streams = [bytes(s) for s in streams]
+        if out_sizes is not None:
+            caps, grow = [int(c) for c in out_sizes], False
+        else:
+            caps, grow = [], True
+            for s in streams:
+                guess = max(4 * len(s), 1 << 16)
+                if w == WRAP_GZIP and len(s) >= 4:
+                    guess = max(int.from_bytes(s[-4:], "little"), 1)
+                caps.append(min(guess, STREAM_MAX_OUT - 1))
+        st, out = self._streams_once(torch, np, w, streams, caps)
+        for i in range(len(streams)):
+            while grow and st[i] == STREAM_OVERFLOW and caps[i] < STREAM_MAX_OUT - 1:
+                caps[i] = min(2 * caps[i], STREAM_MAX_OUT - 1)
+                s1, o1 = self._streams_once(torch, np, w, [streams[i]], [caps[i]])
+                st[i], out[i] = s1[0], o1[0]
+            if st[i] != STREAM_END:
+                err = ZwzError("inflate_streams: stream %d: status %d" % (i, st[i]))
+                err.status, err.index, err.stream_status = E_FORMAT, i, st[i]
+                raise err
+        return out
 
     # ---- directory level -----------------------------------------------------------------------
     def do_compression(self, input_dir, output_dir, file_record, world_rank, world_size=1):

@@ -322,9 +322,11 @@ ZWZ_HD uint32_t inflate_block_rest(InflateState& st, InflateTables* tp, uint8_t*
 // Returns the symbol count; *block_done is set at end-of-block or when decoding stops.
 // out_cap bounds the output slot (65535): a symbol that would cross it stops with kInfOverflow.
 // kPacked: t's two fast tables are in the device's packed form (see pack_lit_entry).
-template <bool kPacked = false>
+// kStream (zwz_inflate_streams_dev): out_cap is any 32-bit capacity, and a match may not reach before `origin`, the first output byte
+// of the current gzip member (libz starts every member with an empty window).
+template <bool kPacked = false, bool kStream = false>
 ZWZ_HD uint32_t inflate_decode_batch(InflateState& st, const InflateTables& t, uint32_t out_cap, uint32_t* batch,
-                                     uint32_t* pos, bool& block_done, uint32_t max_syms = kBatch) {
+                                     uint32_t* pos, bool& block_done, uint32_t max_syms = kBatch, uint32_t origin = 0) {
     BitReader& br = st.br;
     uint32_t k = 0;
     block_done = false;
@@ -348,8 +350,13 @@ ZWZ_HD uint32_t inflate_decode_batch(InflateState& st, const InflateTables& t, u
         xb = dist_extra_bits((uint32_t)ds);
         if (!br.take(xb, xv)) { st.status = kInfNeedInput; block_done = true; break; }
         uint32_t dist = dist_base((uint32_t)ds) + 1u + xv;
-        if (dist > st.out_pos) { st.status = kInfDataError; block_done = true; break; }  // too far back
-        if (st.out_pos + len > out_cap) { st.status = kInfOverflow; block_done = true; break; }
+        if constexpr (kStream) {
+            if (dist > st.out_pos - origin) { st.status = kInfDataError; block_done = true; break; }
+            if (len > out_cap - st.out_pos) { st.status = kInfOverflow; block_done = true; break; }   // (no wrap: out_pos <= out_cap)
+        } else {
+            if (dist > st.out_pos) { st.status = kInfDataError; block_done = true; break; }  // too far back
+            if (st.out_pos + len > out_cap) { st.status = kInfOverflow; block_done = true; break; }
+        }
         batch[k] = (len << 16) | dist; pos[k] = st.out_pos; k++; st.out_pos += len;
     }
     return k;

@@ -1,6 +1,7 @@
 // zwz_api.cpp -- C ABI (include/zwz.h) over the kernel pipeline: context, workspace, batch slicing,
 // pinned staging for host buffers.  No CPU codec lives here: without a GPU every entry point fails.
 #include "zwz_api_internal.h"
+#include "zwz_bgzf.h"
 
 #include <cstdarg>
 #include <chrono>
@@ -319,6 +320,7 @@ void zwz_ctx_destroy(zwz_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->workspace) (void)hipFree(c->workspace);
     if (c->inf_order) (void)hipFree(c->inf_order);
+    if (c->stream_rec) (void)hipFree(c->stream_rec);
     if (c->d_stage) (void)hipFree(c->d_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->bgzf_ws) (void)hipFree(c->bgzf_ws);
@@ -417,6 +419,38 @@ int zwz_inflate_batch_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_
         HIPCHK(hipEventElapsedTime(&ms, c->ev_inf[0], c->ev_inf[1]));
         c->stage_ms[kNumDeflateStages] += ms;
     }
+    return ZWZ_OK;
+}
+
+int zwz_inflate_streams_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n,
+                            uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, uint32_t* d_status) {
+    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    if (n && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status)) return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return ZWZ_E_INVALID;
+    if (n == 0) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (n > c->inf_order_cap || n > c->stream_rec_cap) {   // scratch: the launch order, and what the decode hands the check
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (n > c->inf_order_cap) {
+            if (c->inf_order) { (void)hipFree(c->inf_order); c->inf_order = nullptr; c->inf_order_cap = 0; }
+            HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->inf_order), (size_t)n * sizeof(uint4)));
+            c->inf_order_cap = n;
+        }
+        if (n > c->stream_rec_cap) {
+            if (c->stream_rec) { (void)hipFree(c->stream_rec); c->stream_rec = nullptr; c->stream_rec_cap = 0; }
+            HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->stream_rec), (size_t)n * sizeof(uint4)));
+            c->stream_rec_cap = n;
+        }
+    }
+    if (wrap == ZWZ_WRAP_GZIP && !c->crc_tables) {
+        HIPCHK(hipMalloc(&c->crc_tables, sizeof(CrcTables)));
+        HIPCHK(launch_crc_tables(static_cast<CrcTables*>(c->crc_tables), c->stream));
+    }
+    InflateStreamArgs a{d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, c->inf_order, c->stream_rec,
+                        (uint32_t)wrap, c->inflate_serial_header};
+    HIPCHK(launch_inflate_streams(a, c->stream));
+    HIPCHK(launch_stream_check(static_cast<const CrcTables*>(c->crc_tables), d_out, d_out_off, c->stream_rec, n, (uint32_t)wrap, d_status,
+                               c->cu_count, c->stream));
     return ZWZ_OK;
 }
 

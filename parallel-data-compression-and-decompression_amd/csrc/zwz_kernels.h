@@ -136,6 +136,19 @@ struct InflateArgs {
     uint4* order;              // n entries of scratch (the launch fills it: (offset, length, chunk) by payload length, longest first), or null: as they come
     uint32_t serial_header;    // 1: block headers and tables by lane 0 alone (inflate_block_rest) -- no ordered LDS adds
 };
+// zwz_inflate_streams_dev: per-stream output ranges and what inflate_kernel's stream form hands stream_check_kernel
+struct StreamParams {
+    const uint64_t* out_off; const uint64_t* out_cap; uint64_t* out_len;
+    uint4* rec;                // per stream (checked length, expected checksum, has a checksum, provisional status): stream_core.h's StreamRecord
+    uint32_t wrap;             // stream_core.h: kWrapRaw / kWrapZlib / kWrapGzip
+};
+struct InflateStreamArgs {
+    const uint8_t* in; const uint64_t* in_off; const uint64_t* in_len; uint32_t n;
+    uint8_t* out; const uint64_t* out_off; const uint64_t* out_cap; uint64_t* out_len; uint32_t* status;
+    uint4* order;              // n entries of scratch, as InflateArgs::order (never null here)
+    uint4* rec;                // n entries of scratch
+    uint32_t wrap, serial_header;
+};
 // match_mode: auto = lz_dense_list decides per chunk between links + lz_match (+ lz_parse) and sort + lz_lazy; walk / band / lazy = every chunk through
 // that search; autoband / autolazy = the per-chunk choice with the band + lz_parse / lz_lazy for the chain-heavy ones.  Same bytes whichever runs.
 enum : uint32_t { kMatchAuto = 0, kMatchWalk = 1, kMatchBand = 2, kMatchLazy = 3, kMatchAutoBand = 4, kMatchAutoLazy = 5 };
@@ -173,6 +186,11 @@ hipError_t launch_lazy(const DeflateArgs& a, hipStream_t s);
 uint32_t exp_flags_lazy();
 hipError_t launch_plan(const DeflateArgs& a, hipStream_t s);                             // zwz_plan.hip
 hipError_t launch_inflate(const InflateArgs& a, hipStream_t s);
+hipError_t launch_inflate_streams(const InflateStreamArgs& a, hipStream_t s);      // order + inflate_kernel's stream form (statuses provisional)
+struct CrcTables;                                                                  // zwz_bgzf.h
+// zwz_stream.hip: the checksum of every stream's checked output (rec) and its final status
+hipError_t launch_stream_check(const CrcTables* tab, const uint8_t* out, const uint64_t* out_off, const uint4* rec, uint32_t n,
+                               uint32_t wrap, uint32_t* status, uint32_t cu_count, hipStream_t s);
 hipError_t launch_md5_files(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* files, uint32_t n_files,
                             uint32_t* digests, hipStream_t s);
 

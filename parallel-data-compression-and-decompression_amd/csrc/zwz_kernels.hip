@@ -30,6 +30,7 @@
 
 #include "huff_core.h"
 #include "inflate_core.h"
+#include "stream_core.h"
 #include "lz_core.h"
 #include "zwz_md5.h"
 #include "zwz_kernels.h"
@@ -2020,12 +2021,17 @@ struct InflateWaveMem {
 // kSerialHeader: block headers and tables by lane 0 alone (inflate_block_rest) -- the form that does not depend on the lane order of the
 // returning LDS add; chosen per context when its known-answer test of the wave-built tables fails (zwz_api.cpp), never otherwise.  A
 // template parameter, not a kernel argument: the production kernel's code is untouched by the other form's.
-template <bool kSerialHeader>
+// kStream (zwz_inflate_streams_dev, stream_core.h): a raw, zlib or gzip stream of any size instead of a chunk.  Output goes to
+// out + sp.out_off[i] and is bounded by sp.out_cap[i] instead of the 65 535-byte slot; the wrapper's header is read from global memory
+// before the first block, the trailer after every final block, and a gzip stream goes on with its next member, whose matches may not
+// reach before its first output byte (`origin`).  The chunk forms (kStream = false) compile as they did before this parameter existed.
+template <bool kSerialHeader, bool kStream>
 __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                   const uint32_t* __restrict__ in_len, uint32_t n,
                                                                   uint8_t* __restrict__ out, uint64_t out_stride,
                                                                   uint32_t* __restrict__ out_len, uint32_t* __restrict__ status,
-                                                                  const uint4* __restrict__ order /* (offset, length, chunk) longest payloads first, or null */) {
+                                                                  const uint4* __restrict__ order /* (offset, length, chunk) longest payloads first, or null */,
+                                                                  StreamParams sp) {
     __shared__ InflateWaveMem s_mem[kInflateThreads / 64];
     const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
     const uint32_t slot = blockIdx.x * (kInflateThreads / 64) + wave;
@@ -2036,7 +2042,19 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     const uint32_t chunk = oe.w;
     InflateWaveMem& m = s_mem[wave];
     const uint8_t* src = in + (order ? ((uint64_t)oe.y << 32 | oe.x) : in_off[chunk]);   // 16-byte aligned (API contract)
-    uint8_t* dst = out + (size_t)chunk * out_stride;
+    uint8_t* dst;
+    uint32_t cap = kChunk;                             // output bound
+    if constexpr (kStream) {
+        const uint64_t cap64 = sp.out_cap[chunk];
+        if (oe.z >= kStreamMaxIn || cap64 >= kStreamMaxOut) {     // (the order clips a 64-bit length to 32 bits)
+            if (lane == 0) { sp.out_len[chunk] = 0; status[chunk] = kStrTooLarge; sp.rec[chunk] = make_uint4(0, 0, 0, kStrTooLarge); }
+            return;
+        }
+        dst = out + sp.out_off[chunk];
+        cap = (uint32_t)cap64;
+    } else {
+        dst = out + (size_t)chunk * out_stride;
+    }
     const uint32_t nin = order ? oe.z : in_len[chunk];
     const uint32_t nin16 = (nin + 15u) & ~15u;         // readable extent (API contract)
 
@@ -2062,8 +2080,46 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
 #endif
     top_up(0);
     uint32_t go = 0;
-    if (lane == 0) go = inflate_begin(st, m.ring, nin, kInfRing - 1u) ? 1u : 0u;
-    go = __builtin_amdgcn_readfirstlane(go);
+    uint32_t origin = 0;                               // kStream: the current gzip member's first output byte
+    StreamRecord rec{0, 0, 0, kInfRunning};
+    // kStream: the first byte at or after q that is not zero, or nin (the zeros around gzip members), the wave 1 KiB a step
+    auto skip_zeros = [&](uint32_t q) -> uint32_t {
+        q = __builtin_amdgcn_readfirstlane(q);
+        while (q < nin) {
+            const uint32_t base = q & ~15u, o = base + lane * 16u;
+            uint32_t hit = 0xffffffffu;
+            if (o < nin16) {
+                const uint4 v = *reinterpret_cast<const uint4*>(src + o);
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (uint32_t b = 16; b-- > 0;) {
+                    const uint32_t at = o + b;
+                    if (((w[b >> 2] >> (8u * (b & 3u))) & 255u) && at >= q && at < nin) hit = at;
+                }
+            }
+            const uint64_t any = __ballot(hit != 0xffffffffu);
+            if (any) return (uint32_t)__builtin_amdgcn_readlane((int)hit, (int)__builtin_ctzll(any));
+            q = base + 64u * 16u;
+        }
+        return nin;
+    };
+    if constexpr (kStream) {
+        const uint32_t nz = sp.wrap == kWrapGzip ? skip_zeros(0) : nin;
+        uint32_t body = 0, sst = kInfRunning;
+        if (lane == 0) {
+            sst = stream_begin(sp.wrap, src, nin, nz, &body);
+            st.br.init(m.ring, nin, kInfRing - 1u); st.out_pos = 0; st.last = 0; st.status = sst;
+        }
+        body = __builtin_amdgcn_readfirstlane(body);
+        go = __builtin_amdgcn_readfirstlane(sst) == kInfRunning;
+        if (go) {
+            top_up(body);
+            if (lane == 0) st.br.seek_bit(body * 8u);
+        }
+    } else {
+        if (lane == 0) go = inflate_begin(st, m.ring, nin, kInfRing - 1u) ? 1u : 0u;
+        go = __builtin_amdgcn_readfirstlane(go);
+    }
     uint32_t fenced = 0;      // every output byte below this offset is visible to the whole wave
     while (go) {
         uint32_t kind = kBlkStop, soff = 0, slen = 0, opos = 0;
@@ -2131,7 +2187,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         if (kind == kBlkStored) {
             soff = __builtin_amdgcn_readfirstlane(soff); slen = __builtin_amdgcn_readfirstlane(slen);
             opos = __builtin_amdgcn_readfirstlane(opos);
-            uint32_t room = kChunk - opos, cp = slen < room ? slen : room;
+            uint32_t room = cap - opos, cp = slen < room ? slen : room;
             // stored bytes: whole 16-byte vectors of output, each from five aligned input words shifted by the two
             // ranges' relative misalignment (a 5-byte block header sits between them); bytes at the ragged ends singly.
             // (One byte per lane per trip moved 1.7 TB/s with 5 k waves in flight; this is ~10x fewer instructions.)
@@ -2297,8 +2353,13 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                     const uint32_t ol = is_lit + is_match * mlen;
                     const uint32_t sc = wave_scan_incl(ol);
                     const uint32_t pos = opos_u + sc - ol;
-                    const uint32_t ends = have & ((uint32_t)(kd >= kEob) | (is_lit & (uint32_t)(pos >= kChunk)) |
-                                                  (is_match & ((uint32_t)((v & 0xffffu) > pos) | (uint32_t)(pos + mlen > kChunk))));
+                    uint32_t ends;
+                    if constexpr (kStream)    // (pos <= cap up to the first symbol that ends the round: no wrap where it counts)
+                        ends = have & ((uint32_t)(kd >= kEob) | (is_lit & (uint32_t)(pos >= cap)) |
+                                       (is_match & ((uint32_t)((v & 0xffffu) > pos - origin) | (uint32_t)(mlen > cap - pos))));
+                    else
+                        ends = have & ((uint32_t)(kd >= kEob) | (is_lit & (uint32_t)(pos >= kChunk)) |
+                                       (is_match & ((uint32_t)((v & 0xffffu) > pos) | (uint32_t)(pos + mlen > kChunk))));
                     const uint64_t C = __ballot(ends != 0);
                     if (C) {                                               // wave-uniform: the round ends at this symbol
                         const uint32_t lc = (uint32_t)__builtin_ctzll(C);
@@ -2308,7 +2369,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                         cur = c_off;
                         k = lc;
                         if (c_kind == kLit) { stop = kErr; stop_status = kInfOverflow; }
-                        else if (c_kind == kMatch) { stop = kErr; stop_status = (c_val & 0xffffu) > opos_new ? kInfDataError : kInfOverflow; }
+                        else if (c_kind == kMatch) { stop = kErr; stop_status = (c_val & 0xffffu) > opos_new - origin ? kInfDataError : kInfOverflow; }
                         else if (c_kind == kEob) { cur += c_nb; stop = kEob; }
                         else { stop = c_kind; if (c_kind == kNeed) stop_status = kInfNeedInput; else if (c_kind == kErr) stop_status = kInfDataError; }
                     } else if (nsym > kBatch) {                            // batch full: the next round starts at symbol kBatch
@@ -2409,7 +2470,8 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                     if (lane == 0) {
                         st.br.seek_bit(bp); st.out_pos = opos_u;
                         bool d;
-                        k1 = inflate_decode_batch<true>(st, m.t, kChunk, m.batch, m.pos, d, 1u);
+                        if constexpr (kStream) k1 = inflate_decode_batch<true, true>(st, m.t, cap, m.batch, m.pos, d, 1u, origin);
+                        else k1 = inflate_decode_batch<true>(st, m.t, kChunk, m.batch, m.pos, d, 1u);
                         d1 = d; nbp = st.br.bit_pos(); nop = st.out_pos; stt = st.status;
                     }
                     k1 = __builtin_amdgcn_readfirstlane(k1); d1 = __builtin_amdgcn_readfirstlane(d1);
@@ -2443,11 +2505,41 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
             }
             if (__builtin_amdgcn_readfirstlane(halt)) break;
         }
-        uint32_t fin = 0;
-        if (lane == 0 && st.last) { st.status = kInfEnd; fin = 1; }
-        if (__builtin_amdgcn_readfirstlane(fin)) break;
+        if constexpr (kStream) {
+            // the end of a member: its trailer; a gzip stream goes on behind the zeros that may follow with its next member
+            uint32_t more = 0, next = 0;
+            if (lane == 0 && st.last) {
+                const uint32_t q = (st.br.bit_pos() + 7u) >> 3;
+                st.status = stream_trailer(sp.wrap, src, nin, q, st.out_pos, st.out_pos - origin, rec, &next);
+                more = st.status == kInfRunning;
+                if (!more) rec.status = st.status;
+            }
+            if (__builtin_amdgcn_readfirstlane(more)) {
+                const uint32_t nz = skip_zeros(next);
+                uint32_t body = 0, sst = kInfRunning;
+                if (lane == 0) { sst = gzip_next_member(src, nin, nz, &body); st.status = sst; st.last = 0; }
+                body = __builtin_amdgcn_readfirstlane(body);
+                if (__builtin_amdgcn_readfirstlane(sst) != kInfRunning) break;
+                origin = __builtin_amdgcn_readfirstlane(st.out_pos);
+                top_up(body);
+                if (lane == 0) st.br.seek_bit(body * 8u);
+                continue;
+            }
+            if (__builtin_amdgcn_readfirstlane((uint32_t)(st.status != kInfRunning))) break;
+        } else {
+            uint32_t fin = 0;
+            if (lane == 0 && st.last) { st.status = kInfEnd; fin = 1; }
+            if (__builtin_amdgcn_readfirstlane(fin)) break;
+        }
     }
-    if (lane == 0) { out_len[chunk] = st.out_pos; status[chunk] = st.status; }
+    if constexpr (kStream) {
+        if (lane == 0) {
+            sp.out_len[chunk] = st.out_pos; status[chunk] = st.status;
+            sp.rec[chunk] = make_uint4(rec.checked, rec.expect, rec.has_check, st.status);
+        }
+    } else {
+        if (lane == 0) { out_len[chunk] = st.out_pos; status[chunk] = st.status; }
+    }
 #if ZWZ_INF_EXP & 16
     ZWZ_ISTAMP(6);                                                            // stored blocks, the sequential decoder, the rest
     if (lane == 0) for (uint32_t ph = 0; ph < 8; ph++) atomicAdd(&g_inf_times[ph], (unsigned long long)(iacc_[ph] >> 8));
@@ -2733,12 +2825,24 @@ hipError_t launch_md5_files(const uint8_t* in, const uint64_t* in_off, const uin
 // A chunk is one wave's work from start to end, and a full-size chunk takes a lone wave milliseconds: in a batch of mixed sizes the
 // long ones must start first or they are the batch's tail (370 000 image-like files: the few 64 KB chunks among the 7 KB ones).
 // Counting sort of the chunk numbers by payload length (256-byte classes), longest first; one workgroup, ~20 us per 50 000.
-__global__ __launch_bounds__(1024) void inflate_order_kernel(const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ in_len, uint32_t n, uint4* __restrict__ order) {
+// Streams (Len = uint64_t, zwz_inflate_streams_dev): lengths clipped to 32 bits, log-spaced classes -- four per power of two -- as
+// 256-byte classes saturate at 64 KiB.
+template <typename Len>
+__global__ __launch_bounds__(1024) void inflate_order_kernel(const uint64_t* __restrict__ in_off, const Len* __restrict__ in_len_, uint32_t n, uint4* __restrict__ order) {
     __shared__ uint32_t s_bin[256];
     const uint32_t tid = threadIdx.x;
     if (tid < 256u) s_bin[tid] = 0;
     __syncthreads();
-    auto cls = [](uint32_t len) { const uint32_t c = len >> 8; return 255u - (c < 255u ? c : 255u); };      // longest first
+    constexpr bool kLog = sizeof(Len) == 8;
+    auto in_len = [&](uint32_t i) -> uint32_t { const Len v = in_len_[i]; return kLog && v > (Len)0xffffffffu ? 0xffffffffu : (uint32_t)v; };
+    auto cls = [](uint32_t len) {
+        if constexpr (kLog) {
+            const uint32_t l = len ? 32u - (uint32_t)__builtin_clz(len) : 0u;                      // bits: 0..32
+            return 255u - (4u * l + (l >= 3u ? (len >> (l - 3u)) & 3u : 0u));                       // <= 131
+        } else {
+            const uint32_t c = len >> 8; return 255u - (c < 255u ? c : 255u);                        // longest first
+        }
+    };
     // (lanes of a wave that share a class add to its counter as one: a batch of equal-sized chunks would otherwise be
     // 50 000 additions to the same LDS word, one after the other)
     // (.. and a wave whose lanes are of MANY classes -- 370 000 log-normal files: thirty classes a wave, thirty turns of the loop below, 3.4 ms a
@@ -2765,14 +2869,14 @@ __global__ __launch_bounds__(1024) void inflate_order_kernel(const uint64_t* __r
         }
         return slot;
     };
-    for (uint32_t i = tid; i - tid < n; i += 1024u) (void)grouped_add(i < n ? cls(in_len[i]) : 0u, i < n);
+    for (uint32_t i = tid; i - tid < n; i += 1024u) (void)grouped_add(i < n ? cls(in_len(i)) : 0u, i < n);
     __syncthreads();
     // A batch of one or two sizes (incompressible files: full chunks and 4-byte tails) keeps the order it came in: there is no
     // tail to shorten, and its copies, which run at HBM speed, lost a fifth of it when neighbouring slots were no longer
     // neighbouring waves.
     const bool keep = __syncthreads_count(tid < 256u && s_bin[tid] != 0u) <= 2;
     if (keep) {
-        for (uint32_t i = tid; i < n; i += 1024u) { const uint64_t off = in_off[i]; order[i] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), in_len[i], i); }
+        for (uint32_t i = tid; i < n; i += 1024u) { const uint64_t off = in_off[i]; order[i] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), in_len(i), i); }
         return;
     }
     if (tid < 64u) {                                                       // exclusive scan of the 256 counts by one wave, four a lane
@@ -2782,7 +2886,7 @@ __global__ __launch_bounds__(1024) void inflate_order_kernel(const uint64_t* __r
     }
     __syncthreads();
     for (uint32_t i = tid; i - tid < n; i += 1024u) {
-        const uint32_t len = i < n ? in_len[i] : 0u;
+        const uint32_t len = i < n ? in_len(i) : 0u;
         const uint32_t slot = grouped_add(cls(len), i < n);
         if (i < n) { const uint64_t off = in_off[i]; order[slot] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), len, i); }
     }
@@ -2791,11 +2895,11 @@ __global__ __launch_bounds__(1024) void inflate_order_kernel(const uint64_t* __r
 hipError_t launch_inflate(const InflateArgs& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
     const uint32_t per = kInflateThreads / 64;
-    if (a.order) hipLaunchKernelGGL(inflate_order_kernel, dim3(1), dim3(1024), 0, s, a.in_off, a.in_len, a.n, a.order);
-    if (a.serial_header) hipLaunchKernelGGL(inflate_kernel<true>, dim3((a.n + per - 1) / per), dim3(kInflateThreads), 0, s, a.in, a.in_off, a.in_len, a.n, a.out,
-                                            a.out_stride, a.out_len, a.status, (const uint4*)a.order);
-    else hipLaunchKernelGGL(inflate_kernel<false>, dim3((a.n + per - 1) / per), dim3(kInflateThreads), 0, s, a.in, a.in_off, a.in_len, a.n, a.out,
-                            a.out_stride, a.out_len, a.status, (const uint4*)a.order);
+    if (a.order) hipLaunchKernelGGL(inflate_order_kernel<uint32_t>, dim3(1), dim3(1024), 0, s, a.in_off, a.in_len, a.n, a.order);
+    if (a.serial_header) hipLaunchKernelGGL((inflate_kernel<true, false>), dim3((a.n + per - 1) / per), dim3(kInflateThreads), 0, s, a.in, a.in_off, a.in_len, a.n, a.out,
+                                            a.out_stride, a.out_len, a.status, (const uint4*)a.order, StreamParams{});
+    else hipLaunchKernelGGL((inflate_kernel<false, false>), dim3((a.n + per - 1) / per), dim3(kInflateThreads), 0, s, a.in, a.in_off, a.in_len, a.n, a.out,
+                            a.out_stride, a.out_len, a.status, (const uint4*)a.order, StreamParams{});
 #if ZWZ_INF_EXP & 16
     if (getenv("ZWZ_INF_TIMES")) {
         unsigned long long h[8], z[8] = {0};
@@ -2805,6 +2909,18 @@ hipError_t launch_inflate(const InflateArgs& a, hipStream_t s) {
         fprintf(stderr, "ZWZ_INF_TIMES n=%u header=%llu decode=%llu orbit=%llu symbols=%llu owners=%llu copy=%llu other=%llu\n", a.n, h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
     }
 #endif
+    return hipGetLastError();
+}
+
+hipError_t launch_inflate_streams(const InflateStreamArgs& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    const uint32_t per = kInflateThreads / 64;
+    hipLaunchKernelGGL(inflate_order_kernel<uint64_t>, dim3(1), dim3(1024), 0, s, a.in_off, a.in_len, a.n, a.order);
+    const StreamParams sp{a.out_off, a.out_cap, a.out_len, a.rec, a.wrap};
+    if (a.serial_header) hipLaunchKernelGGL((inflate_kernel<true, true>), dim3((a.n + per - 1) / per), dim3(kInflateThreads), 0, s, a.in, a.in_off, nullptr, a.n, a.out,
+                                            0, nullptr, a.status, (const uint4*)a.order, sp);
+    else hipLaunchKernelGGL((inflate_kernel<false, true>), dim3((a.n + per - 1) / per), dim3(kInflateThreads), 0, s, a.in, a.in_off, nullptr, a.n, a.out,
+                            0, nullptr, a.status, (const uint4*)a.order, sp);
     return hipGetLastError();
 }
 
