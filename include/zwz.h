@@ -270,6 +270,31 @@ int zwz_inflate_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const u
                             uint32_t n, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
                             uint64_t *d_out_len, uint32_t *d_status);
 
+/* ---- DEFLATE streams of any size, written: raw, zlib and gzip ------------------------------------------------------------------
+ * Compresses a batch of n independent inputs into n ordinary streams that any inflate reads.  Stream i is, byte for byte, what
+ * libz 1.2.11 writes at level 6 (windowBits -15 / 15 / 31 for ZWZ_WRAP_RAW / _ZLIB / _GZIP) when every 65280 bytes of input are
+ * followed by deflate(Z_FULL_FLUSH) and the last by deflate(Z_FINISH): every piece of 65280 bytes is compressed by itself (the bytes of
+ * zwz_deflate_batch_dev), its last block made non-final and followed by an empty stored block (00 00 ff ff on a byte boundary), and
+ * the stream ends with 03 00 and the trailer.  zlib: 78 9c ... Adler-32; gzip: 1f 8b 08 00 00 00 00 00 00 03 ... CRC-32, ISIZE; an
+ * empty input is header, 03 00, trailer.  The pieces of one long stream are as parallel as a batch of short ones.
+ * Input i is in_len[i] bytes at d_in + in_off[i]; output i goes to d_out + out_off[i], at most out_cap[i] bytes.  d_out_len[i]
+ * receives the length the stream needs, whether it fitted or not, and d_status[i] 0 or ZWZ_INF_OVERFLOW (3) when that is more than
+ * out_cap[i]; what then lies in the range is undefined, and no byte outside [out_off[i], out_off[i] + out_cap[i]) is ever written.
+ * out_cap[i] >= zwz_deflate_stream_bound(in_len[i], wrap) never overflows.  (Status 2 would mean that the codec's own block records
+ * contradict the stream it wrote from them; no input is known to cause it.)
+ * in_off, in_len, out_off, out_cap are HOST arrays (the launch sizes depend on them; they may be reused when the call returns);
+ * d_in, d_out, d_out_len and d_status are device memory.  Asynchronous on the context's stream.
+ * Alignment: d_in, d_out and every in_off[i], out_off[i] are multiples of 16; input i is readable up to its length rounded up to 16;
+ * output ranges do not overlap.  Lengths are 64-bit and not limited; pieces are counted in 64 bits, and a call may hold at most
+ * 2^46 of them (2^62 bytes).  ZWZ_E_INVALID for a null pointer, a misaligned pointer or offset, or an unknown wrap. */
+uint64_t zwz_deflate_stream_bound(uint64_t n, int wrap);   /* worst-case output bytes for one stream of n input bytes; 1.0009 n */
+int zwz_deflate_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
+                            uint8_t *d_out, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *d_out_len,
+                            uint32_t *d_status);
+/* One file of any size as one stream, in slices through pinned staging (reading, the GPU and writing overlap; the checksum and the
+ * position carry from slice to slice).  dst is written as <dst>.part and renamed only on success; on failure no dst is left. */
+int zwz_deflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst);
+
 #ifdef __cplusplus
 }
 #endif

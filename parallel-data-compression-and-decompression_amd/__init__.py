@@ -17,6 +17,8 @@ and BGZF (blocked gzip, readable by gzip / zcat / htslib; no reference counterpa
     Codec.bgzf_read_ranges / Codec.bgzf_read_ranges_file       (random access: decoded byte ranges)
 and ordinary DEFLATE data of any size, a batch of independent streams in one launch (no reference counterpart):
     Codec.inflate_streams / Codec.inflate_streams_dev          (raw, zlib or gzip; bytes or device tensors)
+    Codec.deflate_streams / Codec.deflate_streams_dev          (the way there: libz's level-6 full-flush streams, any size)
+    Codec.deflate_stream_file, deflate_stream_bound            (one file as one .gz / zlib / raw stream)
 
 There is no CPU fallback: importing works anywhere (so the build can be checked), but every codec
 call needs the HIP library and a GPU and raises ZwzError otherwise.
@@ -94,6 +96,10 @@ def lib():
         L.zwz_bgzf_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp]
         L.zwz_bgzf_read_ranges_file.argtypes = [vp, c.c_char_p, c.c_char_p, vp, u32, vp]
         L.zwz_inflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.zwz_deflate_stream_bound.restype = u64
+        L.zwz_deflate_stream_bound.argtypes = [u64, c.c_int]
+        L.zwz_deflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.zwz_deflate_stream_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
         _lib = L
     return _lib
 
@@ -292,6 +298,58 @@ class Codec:
                 err.status, err.index, err.stream_status = E_FORMAT, i, st[i]
                 raise err
         return out
+
+    def deflate_streams_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status):
+        """zwz_deflate_streams_dev: d_in / d_out uint8 device tensors, d_out_len int64 and d_status int32 device tensors; in_off, in_len,
+        out_off, out_cap HOST sequences or numpy arrays (include/zwz.h has the alignment rules).  wrap: "raw" | "zlib" | "gzip" or
+        WRAP_*.  Asynchronous; an output that does not fit is status 3 with the needed length in d_out_len, never an exception."""
+        import numpy as np
+        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
+        n = arr[1].size
+        if any(a.size != n for a in arr):
+            raise ValueError("in_off, in_len, out_off and out_cap must have one entry per stream")
+        _check(lib().zwz_deflate_streams_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n,
+                                             d_out.data_ptr(), arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(),
+                                             d_status.data_ptr()), "zwz_deflate_streams_dev")
+
+    def deflate_streams(self, buffers, wrap="gzip"):
+        """[bytes] -> [bytes]: every buffer as one raw / zlib / gzip stream of its own, all in one pass on the GPU.  Each is what libz
+        writes at level 6 with a full flush after every 65 280 bytes, so zlib.decompress / gzip.decompress read it."""
+        import numpy as np
+        import torch
+        w = WRAPS.get(wrap, wrap)
+        if w not in (WRAP_RAW, WRAP_ZLIB, WRAP_GZIP):
+            raise ValueError("wrap must be raw, zlib or gzip")
+        buffers = [bytes(b) for b in buffers]
+        n = len(buffers)
+        if n == 0:
+            return []
+        dev = torch.device("cuda", self.device)
+        up = lambda a: (a + 15) // 16 * 16
+        lens = np.array([len(b) for b in buffers], dtype=np.int64)
+        caps = np.array([deflate_stream_bound(int(k), w) for k in lens], dtype=np.int64)
+        offs, ooff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        offs[1:] = np.cumsum(up(lens[:-1]))
+        ooff[1:] = np.cumsum(up(caps[:-1]))
+        blob = np.zeros(max(int(offs[-1] + up(lens[-1])), 16), dtype=np.uint8)
+        for i, b in enumerate(buffers):
+            blob[offs[i]:offs[i] + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        d_in = torch.from_numpy(blob).to(dev)
+        d_out = torch.empty(int(ooff[-1] + up(caps[-1])), dtype=torch.uint8, device=dev)
+        d_olen = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.deflate_streams_dev(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st)
+        self.sync()
+        st, olen, host = d_st.cpu().numpy(), d_olen.cpu().numpy(), d_out.cpu().numpy()
+        for i in range(n):
+            if st[i] != 0:
+                raise ZwzError("deflate_streams: stream %d needs %d bytes, above its bound of %d" % (i, olen[i], caps[i]))
+        return [host[ooff[i]:ooff[i] + olen[i]].tobytes() for i in range(n)]
+
+    def deflate_stream_file(self, src, dst, wrap="gzip"):
+        """One file of any size as one gzip (.gz), zlib or raw DEFLATE stream, streamed through the GPU in slices."""
+        _check(lib().zwz_deflate_stream_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst)), "zwz_deflate_stream_file")
 
     # ---- directory level -----------------------------------------------------------------------
     def do_compression(self, input_dir, output_dir, file_record, world_rank, world_size=1):
@@ -497,6 +555,11 @@ def do_compression(input_dir, output_dir, file_record, world_rank, world_size=1)
 
 def do_decompression(input_dir, output_dir, world_rank=0, world_size=1, allgather=None):
     return _codec().do_decompression(input_dir, output_dir, world_rank, world_size, allgather)
+
+
+def deflate_stream_bound(n, wrap="gzip"):
+    """Worst-case size of one stream of n input bytes from Codec.deflate_streams (about 1.0009 n); needs no GPU."""
+    return lib().zwz_deflate_stream_bound(n, WRAPS.get(wrap, wrap))
 
 
 def bgzf_bound(n):

@@ -1,0 +1,130 @@
+// dstream_core.h -- the portable half of zwz_deflate_streams_dev: how the level-6 streams of independent pieces become one raw, zlib
+// or gzip stream of any size.  Host + device, so that a CPU build (tests/emu_dstream) pins every formula here against libz.
+//
+// The output is what libz 1.2.11 writes when every kPieceBytes of input are followed by deflate(Z_FULL_FLUSH) and the last by
+// deflate(Z_FINISH).  A full flush with all input consumed clears libz's hash and window, so each piece is compressed as if alone,
+// and its share of the output differs from its own Z_FINISH raw stream -- bytes [2, len - 4) of zwz_deflate_batch_dev's slot -- in
+// two places only:
+//   * the BFINAL bit of its last block's header is 0;
+//   * after the last block's end-of-block code (or a stored block's last data byte) come the three header bits 000 of an empty
+//     stored block, zero bits up to a byte boundary, and LEN / NLEN = 00 00 ff ff.  The Z_FINISH stream pads with zero bits at the
+//     same place, so its bytes are kept and the marker adds 4 bytes when the block ends 1 to 5 bits into a byte, else 5.
+// After the last piece's marker Z_FINISH writes 03 00 (an empty final static block, padded) and the wrapper's trailer.
+#pragma once
+#include "crc_core.h"
+#include "huff_core.h"
+#include "stream_core.h"
+
+namespace zwz {
+
+constexpr uint32_t kPieceBytes = 65280;       // input bytes per piece: BGZF's block, whose level-6 stream always fits the deflate slot
+constexpr uint32_t kGzipHeaderBytes = 10;     // 1f 8b 08 00 | mtime 0 | 00 | 03 (libz's deflate with no gz_header: OS_CODE 3)
+
+ZWZ_HD uint32_t dstream_header_bytes(uint32_t wrap) { return wrap == kWrapZlib ? 2u : wrap == kWrapGzip ? kGzipHeaderBytes : 0u; }
+ZWZ_HD uint32_t dstream_trailer_bytes(uint32_t wrap) { return wrap == kWrapZlib ? 4u : wrap == kWrapGzip ? 8u : 0u; }
+ZWZ_HD uint32_t dstream_header_byte(uint32_t wrap, uint32_t i) {
+    if (wrap == kWrapZlib) return i == 0 ? 0x78u : 0x9cu;
+    return i == 0 ? 0x1fu : i == 1 ? 0x8bu : i == 2 ? 0x08u : i == 9 ? 0x03u : 0u;
+}
+// Byte i of what follows the last marker: 03 00, then Adler-32 big-endian (zlib) or CRC-32 and ISIZE little-endian (gzip).
+ZWZ_HD uint32_t dstream_tail_byte(uint32_t wrap, uint32_t i, uint32_t check, uint64_t total_in) {
+    if (i < 2) return i == 0 ? 0x03u : 0u;
+    i -= 2;
+    if (wrap == kWrapZlib) return (check >> (24u - 8u * i)) & 255u;
+    return i < 4 ? (check >> (8u * i)) & 255u : ((uint32_t)total_in >> (8u * (i - 4u))) & 255u;
+}
+ZWZ_HD uint32_t dstream_check_init(uint32_t wrap) { return wrap == kWrapZlib ? 1u : 0u; }     // adler32("") / crc32("")
+
+// Where a piece's zlib stream is spliced, in bits from the start of its slot (the 16 bits of 78 9c included): the header of its last
+// block (whose first bit is BFINAL), and the end of that block before the final padding.  Walks the blocks as the encoder lays them
+// out (encode_kernel's thread 0): headers bit-contiguous, a stored block's LEN at the next byte boundary.
+struct SplicePoints { uint32_t hdr_bit, end_bit; };
+template <class BlockFn>    // block(b, type, hdr_bits, body_bits, stored_bytes)
+ZWZ_HD SplicePoints splice_points(uint32_t n_blocks, BlockFn&& block) {
+    uint64_t bit = 16;
+    SplicePoints sp{16u, 16u};
+    for (uint32_t b = 0; b < n_blocks; b++) {
+        uint32_t type, hdr_bits, body_bits, stored_bytes;
+        block(b, type, hdr_bits, body_bits, stored_bytes);
+        sp.hdr_bit = (uint32_t)bit;
+        bit += hdr_bits;
+        if (type == kStored) bit = ((bit + 7) & ~7ull) + 32u + 8ull * stored_bytes;
+        else bit += body_bits;
+    }
+    sp.end_bit = (uint32_t)bit;
+    return sp;
+}
+// Bytes a piece contributes: its raw stream through the marker's padding, then 00 00 ff ff.  The source bytes are slot[2, 2 + n - 4)
+// with the BFINAL bit cleared; where the marker's three bits open a new byte that byte is zero.
+ZWZ_HD uint32_t spliced_bytes(uint32_t end_bit) { return (end_bit - 16u + 3u + 7u) / 8u + 4u; }
+ZWZ_HD uint32_t spliced_source_bytes(uint32_t end_bit) { return (end_bit - 16u + 7u) / 8u; }
+
+// Worst case of spliced_bytes for a piece of L <= kPieceBytes input bytes.  A piece has at most L / kSymsPerBlock + 1 blocks (one per
+// kSymsPerBlock symbols, and a symbol covers at least a byte).  libz stores a block of n bytes unless the coded form is shorter than
+// n + 4 bytes, header bits included, so a block takes at most 3 + 7 + 32 + 8n = 8n + 42 bits (stored, behind up to 7 bits of
+// padding).  The exception is a block that may not be stored because the window has slid: it is flushed at or after kSlidePos
+// and starts before kWSize, so only a piece of at least kSlidePos bytes has one, it has only one, and that block holds
+// n > kSlidePos - kWSize = 32 506 bytes in S <= kSymsPerBlock symbols.  libz takes the static code when that is shorter, so the
+// block costs at most its static length: 3 header bits, 7 for the end-of-block code, at most 9 for a literal -- one more than its
+// byte -- and for a match of length l at most 22 bits for l = 3 (farther than kTooFar it is not taken), 25 for l <= 10 and 31
+// above: always at least l - 1 bits less than its 8 l.  With m matches the literals add at most S - m bits and the matches save at
+// least n - S, so the block takes at most 8n + 10 + 2 * 16 383 - 32 507 = 8n + 269 bits: 227 more than the 8n + 42 counted already.
+ZWZ_HD uint32_t piece_bound(uint32_t L) {
+    const uint32_t nb = L / kSymsPerBlock + 1u;
+    const uint32_t bits = 42u * nb + (L >= kSlidePos ? 227u : 0u);
+    return L + (bits + 3u + 7u) / 8u + 4u;
+}
+// header + pieces * (worst piece + marker) + 03 00 + trailer; an empty input has no piece.  1.0009 n for large n.
+ZWZ_HD uint64_t dstream_bound(uint64_t n, uint32_t wrap) {
+    const uint64_t full = n / kPieceBytes;
+    const uint32_t rest = (uint32_t)(n % kPieceBytes);
+    return dstream_header_bytes(wrap) + full * piece_bound(kPieceBytes) + (rest ? piece_bound(rest) : 0u) + 2u + dstream_trailer_bytes(wrap);
+}
+
+// ---- checksums of a concatenation -----------------------------------------------------------------------------------------------
+// Both checksums are monoids under "append": join(l, r, p) is the checksum of A || B from those of A and B and a parameter p that
+// depends on |B| alone; pof(n) is that parameter for n bytes and pjoin(p, q) the parameter of the two lengths added.  The identity
+// (the checksum of nothing) on the left leaves r unchanged whatever p is, which is what lets a wave pad a short row of pieces
+// at the front.
+struct AdlerSum {       // Adler-32 as B << 16 | A; p = |B| mod 65521
+    static ZWZ_HD uint32_t identity() { return 1u; }
+    static ZWZ_HD uint32_t pof(uint64_t n) { return (uint32_t)(n % kAdlerMod); }
+    static ZWZ_HD uint32_t pjoin(uint32_t p, uint32_t q) { return (p + q) % kAdlerMod; }
+    static ZWZ_HD uint32_t join(uint32_t l, uint32_t r, uint32_t p) {
+        const uint32_t a1 = l & 0xffffu, b1 = l >> 16, a2 = r & 0xffffu, b2 = r >> 16;
+        const uint32_t a = (a1 + a2 + kAdlerMod - 1u) % kAdlerMod;                               // A1 + A2 - 1
+        const uint32_t b = (b1 + b2 + (p * ((a1 + kAdlerMod - 1u) % kAdlerMod)) % kAdlerMod) % kAdlerMod;   // B1 + B2 + |B| (A1 - 1); p * (..) < 2^32
+        return b << 16 | a;
+    }
+};
+struct CrcSum {         // CRC-32; p = x^(8 |B|) mod P (crc_core.h: zlib's crc32_combine)
+    static ZWZ_HD uint32_t identity() { return 0u; }
+    static ZWZ_HD uint32_t pof(uint64_t n) { return crc_xpow8n(n); }
+    static ZWZ_HD uint32_t pjoin(uint32_t p, uint32_t q) { return crc_mulmod(p, q); }
+    static ZWZ_HD uint32_t join(uint32_t l, uint32_t r, uint32_t p) { return crc_mulmod(l, p) ^ r; }
+};
+// The parameter of k blocks of the length p stands for, by doubling
+template <class Sum>
+ZWZ_HD uint32_t sum_ptimes(uint32_t p, uint32_t k) {
+    uint32_t r = Sum::pof(0);
+    while (k) {
+        if (k & 1u) r = Sum::pjoin(r, p);
+        p = Sum::pjoin(p, p);
+        k >>= 1;
+    }
+    return r;
+}
+// A row of kSumRow checksums of equal-length blocks (parameter p1 each), identities in front of a short row, folded as a wave folds
+// it: at distance d = 1, 2, 4, ... every 2d-th entry takes in its neighbour d further on, whose d blocks have the parameter p1 d times.
+constexpr uint32_t kSumRow = 64;
+template <class Sum>
+inline uint32_t sum_fold_row_host(uint32_t* v, uint32_t p1) {
+    uint32_t pd = p1;
+    for (uint32_t d = 1; d < kSumRow; d <<= 1) {
+        for (uint32_t l = 0; l < kSumRow; l += 2 * d) v[l] = Sum::join(v[l], v[l + d], pd);
+        pd = Sum::pjoin(pd, pd);
+    }
+    return v[0];
+}
+
+}  // namespace zwz

@@ -327,6 +327,10 @@ void zwz_ctx_destroy(zwz_ctx* c) {
     if (c->crc_tables) (void)hipFree(c->crc_tables);
     if (c->rr_dev) (void)hipFree(c->rr_dev);
     if (c->rr_host) (void)hipHostFree(c->rr_host);
+    if (c->ds_ws) (void)hipFree(c->ds_ws);
+    if (c->ds_dev) (void)hipFree(c->ds_dev);
+    if (c->ds_host) (void)hipHostFree(c->ds_host);
+    if (c->ds_copied) (void)hipEventDestroy(c->ds_copied);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_inf) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);

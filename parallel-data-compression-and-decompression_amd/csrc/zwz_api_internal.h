@@ -40,6 +40,14 @@ struct zwz_ctx {
     void* rr_host = nullptr;
     void* rr_dev = nullptr;
     size_t rr_cap = 0;
+    // stream deflate (zwz_dstream.cpp): slots and per-piece arrays for ds_cap pieces; the per-stream arrays of one call for ds_streams
+    // streams, pinned on the host and on the device; ds_copied: the last call's copy out of the pinned arrays has run
+    void* ds_ws = nullptr;
+    uint32_t ds_cap = 0;
+    void* ds_host = nullptr;
+    void* ds_dev = nullptr;
+    uint32_t ds_streams = 0;
+    hipEvent_t ds_copied = nullptr;
 };
 
 namespace zwz {

@@ -1,0 +1,36 @@
+// zwz_dstream.h -- zwz_deflate_streams_dev: the kernels that turn the deflate slots of independent pieces into whole raw, zlib or gzip
+// streams (zwz_dstream.hip) and their host driver (zwz_dstream.cpp).  dstream_core.h has the format.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "zwz_kernels.h"
+
+namespace zwz {
+
+// Per stream, device memory.  Stream i's pieces are pfirst[i] .. pfirst[i + 1] - 1, counted over the whole call (n + 1 entries).
+struct DstreamStreams {
+    const uint64_t *in_off, *in_len, *out_off, *out_cap, *pfirst;
+    uint64_t* xs;              // the scan's value at the stream's first piece, for its pieces in later slices
+    uint32_t* chk;             // the checksum of the stream's pieces so far
+    uint32_t n;
+};
+// Per piece of one slice: piece p of the slice is piece g0 + p of the call
+struct DstreamPieces {
+    uint8_t* slots;            // ZWZ_DEV_STRIDE bytes each: the piece's zlib stream
+    uint64_t *off, *x;         // its input; bytes of spliced output in front of it (over the whole call)
+    uint32_t *len, *olen, *crc, *sidx, *slen, *hbit, *ebit;   // input, slot and spliced lengths; CRC-32 (gzip); stream; dstream_core.h's SplicePoints
+};
+struct DstreamOut { uint8_t* out; uint64_t* out_len; uint32_t* status; uint32_t wrap; uint32_t partial; };   // partial: pieces only (no header, no 03 00, no trailer)
+
+hipError_t launch_dstream_begin(const DstreamStreams& S, const DstreamOut& O, hipStream_t s);
+hipError_t launch_dstream_layout(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, hipStream_t s);
+hipError_t launch_dstream_size(const ChunkInfo* info, const BlockInfo* blocks, const BlockOut* plans, const DstreamPieces& P, uint32_t m, uint32_t* err,
+                               hipStream_t s);   // *err = 1 if a piece's records contradict its slot
+// streams s0 .. s0 + ns - 1 are those with a piece in the slice
+hipError_t launch_dstream_combine(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, uint32_t s0, uint32_t ns, uint32_t wrap,
+                                  hipStream_t s);
+hipError_t launch_dstream_pack(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamOut& O, const uint32_t* err,
+                               hipStream_t s);
+
+}  // namespace zwz

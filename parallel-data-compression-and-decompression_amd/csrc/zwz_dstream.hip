@@ -1,0 +1,181 @@
+// zwz_dstream.hip -- the device half of zwz_deflate_streams_dev on gfx950.  The codec is untouched: every piece of at most kPieceBytes
+// goes through zwz_deflate_batch_dev into its slot, and the kernels here cut the batch into pieces (layout), find where each piece's
+// stream is spliced from the block records the encoder itself was laid out by (size), fold the pieces' checksums into their streams'
+// (combine) and move every piece once, with its marker, to its place in its stream (pack).  dstream_core.h has the format and the
+// arithmetic; the scan between size and pack is BGZF's (launch_bgzf_scan).
+#include "../../include/zwz.h"
+#include "copy_wg.h"
+#include "dstream_core.h"
+#include "zwz_device.h"
+#include "zwz_dstream.h"
+
+namespace zwz {
+
+namespace {
+
+// Streams without input are complete here (header, 03 00, trailer); the others start their running checksum.
+__global__ void __launch_bounds__(256) dstream_begin_kernel(DstreamStreams S, DstreamOut O) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S.n) return;
+    const uint32_t init = dstream_check_init(O.wrap);
+    S.chk[i] = init;
+    S.xs[i] = 0;
+    if (S.in_len[i]) return;
+    const uint32_t hdr = O.partial ? 0u : dstream_header_bytes(O.wrap), tail = O.partial ? 0u : 2u + dstream_trailer_bytes(O.wrap);
+    const bool fits = hdr + tail <= S.out_cap[i];
+    if (fits) {
+        uint8_t* dst = O.out + S.out_off[i];
+        for (uint32_t b = 0; b < hdr; b++) dst[b] = (uint8_t)dstream_header_byte(O.wrap, b);
+        for (uint32_t b = 0; b < tail; b++) dst[hdr + b] = (uint8_t)dstream_tail_byte(O.wrap, b, init, 0);
+    }
+    O.out_len[i] = hdr + tail;
+    O.status[i] = fits ? 0u : (uint32_t)ZWZ_INF_OVERFLOW;
+}
+
+// Piece g0 + p: its stream is the last one whose first piece is not behind it (streams without pieces share their successor's first).
+__global__ void __launch_bounds__(256) dstream_layout_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, uint32_t m) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    const uint64_t g = g0 + p;
+    uint32_t lo = 0, hi = S.n;                     // pfirst[lo] <= g < pfirst[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (S.pfirst[mid] <= g) lo = mid; else hi = mid;
+    }
+    const uint64_t at = (g - S.pfirst[lo]) * kPieceBytes, left = S.in_len[lo] - at;
+    P.off[p] = S.in_off[lo] + at;
+    P.len[p] = (uint32_t)min<uint64_t>(left, kPieceBytes);
+    P.sidx[p] = lo;
+}
+
+// (The records are the ones the slot's stream was written from; should they ever contradict its length, *err is set, the piece gets
+// harmless splice points and its stream ends with status ZWZ_INF_DATA_ERROR.)
+__global__ void __launch_bounds__(256) dstream_size_kernel(const ChunkInfo* info, const BlockInfo* blocks, const BlockOut* plans, DstreamPieces P,
+                                                           uint32_t m, uint32_t* err) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    const BlockInfo* bi = blocks + (size_t)p * kMaxBlocks;
+    const BlockOut* bo = plans + (size_t)p * kMaxBlocks;
+    const SplicePoints sp_ = splice_points(min(info[p].n_blocks, kMaxBlocks), [&](uint32_t b, uint32_t& type, uint32_t& hdr_bits, uint32_t& body_bits, uint32_t& stored) {
+        type = bo[b].type; hdr_bits = bo[b].hdr_bits; body_bits = bo[b].body_bits; stored = bi[b].end - bi[b].start;
+    });
+    SplicePoints sp = sp_;
+    if (2u + spliced_source_bytes(sp.end_bit) + 4u != P.olen[p] || sp.hdr_bit >= sp.end_bit) { *err = 1; sp.hdr_bit = 16; sp.end_bit = 16; }
+    P.hbit[p] = sp.hdr_bit;
+    P.ebit[p] = sp.end_bit;
+    P.slen[p] = spliced_bytes(sp.end_bit);
+}
+
+// One wave per stream with a piece in the slice: the checksums of its pieces there, in order, joined onto the stream's running value.
+// All but the last of them are kPieceBytes long (only a stream's last piece is shorter).  Lane l joins K = ceil(full / 64) consecutive
+// ones one after the other -- the short share is lane 0's, padded in front with nothing -- and the 64 lanes' values, each now the
+// checksum of K pieces, are folded pairwise at distances 1, 2, 4, ... with the parameter of K, 2K, 4K, ... pieces
+// (dstream_core.h: sum_fold_row_host is that fold on the host).  A stream of 8 192 pieces a slice costs 128 + 6 joins deep instead of 8 192.
+// The last piece is joined by its own length.
+template <class Sum, bool kFromSlot>
+__global__ void __launch_bounds__(256) dstream_combine_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, uint32_t m, uint32_t s0, uint32_t ns) {
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = lane_id();
+    if (wave >= ns) return;
+    const uint32_t s = s0 + wave;
+    const uint64_t lo = max(S.pfirst[s], g0), hi = min(S.pfirst[s + 1], g0 + m);
+    if (hi <= lo) return;
+    const uint32_t p0 = (uint32_t)(lo - g0), cnt = (uint32_t)(hi - lo), full = cnt - 1u;
+    auto value = [&](uint32_t p) -> uint32_t {
+        if (!kFromSlot) return P.crc[p];
+        const uint8_t* a = P.slots + (size_t)p * ZWZ_DEV_STRIDE + P.olen[p] - 4u;        // the slot's Adler-32, big-endian
+        return (uint32_t)a[0] << 24 | (uint32_t)a[1] << 16 | (uint32_t)a[2] << 8 | (uint32_t)a[3];
+    };
+    uint32_t acc = S.chk[s];
+    if (full) {
+        const uint32_t p1 = Sum::pof(kPieceBytes), K = (full + kSumRow - 1u) / kSumRow, pad = K * kSumRow - full;
+        uint32_t x = Sum::identity();
+        for (uint32_t j = 0; j < K; j++) {
+            const uint32_t v = lane * K + j;
+            if (v >= pad) x = Sum::join(x, value(p0 + v - pad), p1);
+        }
+        uint32_t pd = sum_ptimes<Sum>(p1, K);
+#pragma unroll
+        for (uint32_t k = 0; k < 6; k++) {
+            const uint32_t d = 1u << k, y = (uint32_t)__shfl_down((int)x, d, 64);
+            if ((lane & (2u * d - 1u)) == 0) x = Sum::join(x, y, pd);
+            pd = Sum::pjoin(pd, pd);
+        }
+        x = (uint32_t)__shfl((int)x, 0, 64);
+        acc = Sum::join(acc, x, sum_ptimes<Sum>(p1, full));
+    }
+    acc = Sum::join(acc, value(p0 + full), Sum::pof(P.len[p0 + full]));
+    if (lane == 0) S.chk[s] = acc;
+}
+
+// One workgroup per piece.  Thread 0 first makes the slot's bytes [2, 2 + slen) the piece's share of the stream -- BFINAL cleared, the
+// marker behind the last block (over the slot's Adler-32, which dstream_combine_kernel has read) -- then the workgroup copies them
+// to their place.  A stream's first piece also writes the header and its last the tail, the length and the status.  Nothing is
+// written that would end behind the stream's capacity.
+__global__ void __launch_bounds__(256) dstream_pack_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, DstreamOut O, const uint32_t* err) {
+    const uint32_t p = blockIdx.x, t = threadIdx.x;
+    const uint32_t s = P.sidx[p], slen = P.slen[p];
+    const uint64_t g = g0 + p, pf = S.pfirst[s];
+    uint8_t* slot = P.slots + (size_t)p * ZWZ_DEV_STRIDE;
+    if (t == 0) {
+        const uint32_t hbit = P.hbit[p], src = spliced_source_bytes(P.ebit[p]);
+        slot[hbit >> 3] &= (uint8_t)~(1u << (hbit & 7u));
+        if (slen - 4u > src) slot[2u + src] = 0;
+        uint8_t* mk = slot + 2u + slen - 4u;
+        mk[0] = 0; mk[1] = 0; mk[2] = 0xff; mk[3] = 0xff;
+    }
+    const bool first = g == pf, last = g + 1 == S.pfirst[s + 1];
+    const uint64_t xs = pf >= g0 ? P.x[pf - g0] : S.xs[s];
+    const uint32_t hdr = O.partial ? 0u : dstream_header_bytes(O.wrap), tail = O.partial ? 0u : 2u + dstream_trailer_bytes(O.wrap);
+    const uint64_t start = hdr + (P.x[p] - xs), end = start + slen, cap = S.out_cap[s];
+    uint8_t* dst = O.out + S.out_off[s];
+    if (first) {
+        if (t == 0) S.xs[s] = P.x[p];              // (read by this stream's pieces in later slices only)
+        if (t < hdr && hdr <= cap) dst[t] = (uint8_t)dstream_header_byte(O.wrap, t);
+    }
+    if (last) {
+        const uint64_t total = end + tail;
+        if (t == 0) { O.out_len[s] = total; O.status[s] = *err ? (uint32_t)ZWZ_INF_DATA_ERROR : total > cap ? (uint32_t)ZWZ_INF_OVERFLOW : 0u; }
+        if (t >= 64u && t - 64u < tail && total <= cap) dst[end + (t - 64u)] = (uint8_t)dstream_tail_byte(O.wrap, t - 64u, S.chk[s], S.in_len[s]);
+    }
+    __syncthreads();
+    if (end <= cap) wg_copy(dst + start, slot + 2, slen);
+}
+
+}  // namespace
+
+hipError_t launch_dstream_begin(const DstreamStreams& S, const DstreamOut& O, hipStream_t s) {
+    if (!S.n) return hipSuccess;
+    dstream_begin_kernel<<<(S.n + 255u) / 256u, 256, 0, s>>>(S, O);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstream_layout(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, hipStream_t s) {
+    if (!m) return hipSuccess;
+    dstream_layout_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, g0, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstream_size(const ChunkInfo* info, const BlockInfo* blocks, const BlockOut* plans, const DstreamPieces& P, uint32_t m, uint32_t* err,
+                               hipStream_t s) {
+    if (!m) return hipSuccess;
+    dstream_size_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(info, blocks, plans, P, m, err);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstream_combine(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, uint32_t s0, uint32_t ns, uint32_t wrap,
+                                  hipStream_t s) {
+    if (!m || !ns || wrap == kWrapRaw) return hipSuccess;
+    const uint32_t grid = (ns + 3u) / 4u;
+    if (wrap == kWrapZlib) dstream_combine_kernel<AdlerSum, true><<<grid, 256, 0, s>>>(S, P, g0, m, s0, ns);
+    else dstream_combine_kernel<CrcSum, false><<<grid, 256, 0, s>>>(S, P, g0, m, s0, ns);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstream_pack(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamOut& O, const uint32_t* err,
+                               hipStream_t s) {
+    if (!m) return hipSuccess;
+    dstream_pack_kernel<<<m, 256, 0, s>>>(S, P, g0, O, err);
+    return hipGetLastError();
+}
+
+}  // namespace zwz
