@@ -184,7 +184,9 @@ int zwz_ctx_set_chunk_size(zwz_ctx *ctx, uint32_t bytes);
  *   "inflate_header"  "wave" (default) | "serial"   a block's decoding tables by the whole wave, or by lane 0
  * Defaults come from ZWZ_MATCH / ZWZ_PLAN / ZWZ_INFLATE_HEADER, read once in zwz_ctx_create (never per launch; a value that is not
  * understood is reported on stderr and ignored).  ZWZ_E_INVALID for an unknown name or value; ZWZ_E_NO_DEVICE for a kernel form
- * that failed its self-test on this device at zwz_ctx_create -- it stays off ("auto" / "" then mean what the device can run). */
+ * that failed its self-test on this device at zwz_ctx_create -- it stays off ("auto" / "" then mean what the device can run).
+ * "split_min_bytes", "split_budget" and "split_max_candidates" (decimal numbers) belong to zwz_inflate_split_streams_dev and are
+ * described there; they decide which streams are decoded in pieces, never what is decoded. */
 int zwz_ctx_set_option(zwz_ctx *ctx, const char *name, const char *value);
 
 /* ---- BGZF (blocked gzip, SAM/BAM specification section 4.1): .gz files that gzip, zcat and htslib read -----------------------
@@ -269,6 +271,46 @@ typedef enum zwz_stream_status {      /* 0..3 mean what zwz_inflate_status means
 int zwz_inflate_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
                             uint32_t n, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
                             uint64_t *d_out_len, uint32_t *d_status);
+
+/* ---- One long stream, decoded in parallel at its full-flush points ------------------------------------------------------------
+ * Arguments, alignment rules, limits (ZWZ_STREAM_TOO_LARGE included) and PER-STREAM RESULTS exactly those of
+ * zwz_inflate_streams_dev: the same decoded bytes, d_out_len[i] and d_status[i] for every input, good or damaged.  What differs is
+ * the time a long stream takes.  A flush point is an empty stored block, 00 00 ff ff on a byte boundary, and after a FULL flush
+ * nothing refers back across it, so a stream that has such points -- what zwz_deflate_streams_dev and `main gzip` write (one every
+ * 65280 input bytes), pigz -i, libz callers that use Z_FULL_FLUSH -- is decoded by one wave per piece between two of them instead
+ * of one wave in all.  Per stream: the candidates (the body's first byte and every byte behind the four marker bytes) are found by
+ * a scan of the input; one wave per candidate decodes from there with an empty window and only counts; the chain of true piece
+ * starts is followed from the body's first byte; if it reaches the final block, the trailer is fine and the counts fit the
+ * capacity, one wave per piece writes its bytes in place and the checksum is computed from pieces of the output in parallel.
+ * Every other stream -- no flush points, sync flushes (the pieces refer back), a damaged or cut stream, a second gzip member or
+ * trailing bytes, a header other than fine, an output above the capacity -- is decoded by zwz_inflate_streams_dev's own path and
+ * gets that path's results.
+ * d_segments (device, n entries, may be NULL): the pieces of stream i decoded in parallel, 0 for a stream that took the other path.
+ * Context options (zwz_ctx_set_option, decimal values, "" restores the default; "split_slice_bytes" belongs to the file function below):
+ *   "split_min_bytes"       65536    streams shorter than this are not scanned
+ *   "split_budget"          4194304  input bytes one measuring wave may read; a piece longer than this sends its stream the other way
+ *   "split_max_candidates"  131072   a stream with more candidates is not measured (2^32 output bytes in pieces of 65280 are 65794)
+ * so the work on hostile input is bounded by candidates x budget per stream, whatever its length.  Device memory beyond input and
+ * output: 12 bytes per 4096 input bytes for the scan, 20 + log2(candidates of the longest chain) words per candidate that is
+ * measured, 40 bytes per piece decoded and 16 per 65280 output bytes for the checksum.  One call measures at most 8 Mi candidates
+ * (streams beyond that take the other path): about 1.2 GB at the worst.  The context keeps its largest workspace until it is
+ * destroyed.
+ * NOT asynchronous: the launch sizes depend on what the scan finds, so the call waits for the context's stream three times; the
+ * last kernels are still queued when it returns (zwz_ctx_sync before reading results, as for zwz_inflate_streams_dev). */
+int zwz_inflate_split_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
+                                  uint32_t n, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
+                                  uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_segments);
+/* One file of any size holding ONE raw, zlib or gzip stream -> its decoded bytes: the way back from zwz_deflate_stream_file and
+ * `main gzip`.  The compressed file passes through the device in slices of "split_slice_bytes" (context option, default 67108864,
+ * 4096 .. 2^28); per slice the pieces that end inside it are found and decoded as above and written, and the next slice starts where
+ * the chain stands.  Sizes are 64-bit: no 2^29 or 2^32 limit for a file that splits; a piece must fit a slice and its decoded bytes
+ * four slices (at least 4 MiB).  A file in which no piece ends cleanly before any byte was written (no flush points, sync flushes,
+ * another wrapper) is decoded as one stream by zwz_inflate_streams_dev's path if it is shorter than 2^29 bytes.  Otherwise, and if
+ * the chain breaks later (a cut or damaged file), ZWZ_E_FORMAT with zwz_last_error() naming the compressed offset.  A CRC-32,
+ * Adler-32 or ISIZE that does not match is ZWZ_E_CHECKSUM.  When bytes other than zeros follow the first gzip member of a file
+ * that splits, a file shorter than 2^29 bytes is decoded again by that one-stream path (which reads further members and names
+ * garbage); a longer one is ZWZ_E_FORMAT, its further members are not read.  dst is written as dst.part and renamed on success only.  Synchronous. */
+int zwz_inflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst);
 
 /* ---- DEFLATE streams of any size, written: raw, zlib and gzip ------------------------------------------------------------------
  * Compresses a batch of n independent inputs into n ordinary streams that any inflate reads.  Stream i is, byte for byte, what

@@ -17,6 +17,8 @@ and BGZF (blocked gzip, readable by gzip / zcat / htslib; no reference counterpa
     Codec.bgzf_read_ranges / Codec.bgzf_read_ranges_file       (random access: decoded byte ranges)
 and ordinary DEFLATE data of any size, a batch of independent streams in one launch (no reference counterpart):
     Codec.inflate_streams / Codec.inflate_streams_dev          (raw, zlib or gzip; bytes or device tensors)
+    Codec.inflate_stream / Codec.inflate_split_streams_dev     (one long stream with full-flush points: a wave per piece)
+    Codec.inflate_stream_file                                  (one file of any size, in slices; `main gunzip`)
     Codec.deflate_streams / Codec.deflate_streams_dev          (the way there: libz's level-6 full-flush streams, any size)
     Codec.deflate_stream_file, deflate_stream_bound            (one file as one .gz / zlib / raw stream)
 
@@ -96,6 +98,8 @@ def lib():
         L.zwz_bgzf_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp]
         L.zwz_bgzf_read_ranges_file.argtypes = [vp, c.c_char_p, c.c_char_p, vp, u32, vp]
         L.zwz_inflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.zwz_inflate_split_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+        L.zwz_inflate_stream_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
         L.zwz_deflate_stream_bound.restype = u64
         L.zwz_deflate_stream_bound.argtypes = [u64, c.c_int]
         L.zwz_deflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
@@ -235,7 +239,29 @@ class Codec:
                                              d_out.data_ptr(), d_out_off.data_ptr(), d_out_cap.data_ptr(), d_out_len.data_ptr(),
                                              d_status.data_ptr()), "zwz_inflate_streams_dev")
 
-    def _streams_once(self, torch, np, wrap, streams, caps):
+    def inflate_split_streams_dev(self, wrap, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_segments=None):
+        """zwz_inflate_split_streams_dev: arguments and per-stream results exactly those of inflate_streams_dev; a stream with full-flush
+        points (what deflate_streams writes, pigz -i, libz callers that flush fully) is decoded by one wave per piece.  d_segments
+        (int32, optional) receives the pieces decoded in parallel, 0 for a stream that took the one-wave path.  Waits for the
+        context's stream while it runs; the results are complete after sync()."""
+        n = d_in_len.numel()
+        _check(lib().zwz_inflate_split_streams_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), n,
+                                                   d_out.data_ptr(), d_out_off.data_ptr(), d_out_cap.data_ptr(), d_out_len.data_ptr(),
+                                                   d_status.data_ptr(), d_segments.data_ptr() if d_segments is not None else None),
+               "zwz_inflate_split_streams_dev")
+
+    def inflate_stream(self, data, wrap="gzip", out_size=None):
+        """bytes -> decoded bytes of ONE raw / zlib / gzip stream through the split decode: as fast as a batch when the stream has
+        full-flush points, the one-wave path otherwise.  Capacity guessed and regrown as inflate_streams does; raises ZwzError
+        (.stream_status) as inflate_streams does."""
+        return self.inflate_streams([data], wrap, None if out_size is None else [out_size], split=True)[0]
+
+    def inflate_stream_file(self, src, dst, wrap="gzip"):
+        """One file holding one raw / zlib / gzip stream of any size -> dst (zwz_inflate_stream_file; `main gunzip`).  ZwzError with
+        status E_FORMAT / E_CHECKSUM on a damaged file; dst then does not appear."""
+        _check(lib().zwz_inflate_stream_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst)), "zwz_inflate_stream_file")
+
+    def _streams_once(self, torch, np, wrap, streams, caps, split=False):
         """One call over host streams with the given capacities -> (statuses, [bytes])."""
         n = len(streams)
         dev = torch.device("cuda", self.device)
@@ -259,19 +285,19 @@ class Codec:
         d_olen = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
         d_st = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
-        self.inflate_streams_dev(wrap, d_in, d_off, d_len, d_out, d_ooff, d_cap, d_olen, d_st)
+        (self.inflate_split_streams_dev if split else self.inflate_streams_dev)(wrap, d_in, d_off, d_len, d_out, d_ooff, d_cap, d_olen, d_st)
         self.sync()
         st = d_st[:n].cpu().numpy()
         olen = d_olen[:n].cpu().numpy()
         host = d_out.cpu().numpy()
         return [int(x) for x in st], [host[ooff[i]:ooff[i] + olen[i]].tobytes() for i in range(n)]
 
-    def inflate_streams(self, streams, wrap="gzip", out_sizes=None):
+    def inflate_streams(self, streams, wrap="gzip", out_sizes=None, split=False):
         """[bytes] -> [decoded bytes]: a batch of independent raw / zlib / gzip streams of any size in one pass on the GPU.  Raises
         ZwzError for the first failing stream, naming its index and status (.index, .stream_status), as zlib.decompress raises.
         out_sizes: each stream's decoded size if known; without it capacities are guessed (gzip: ISIZE from the last 4 bytes; zlib,
         raw: max(4 x input, 64 KiB)), and streams that come back with status 3 are decoded again by themselves with double the
-        capacity, up to 2^32 - 1."""
+        capacity, up to 2^32 - 1.  split: through zwz_inflate_split_streams_dev (same results)."""
         import numpy as np
         import torch
         w = WRAPS.get(wrap, wrap)
@@ -287,11 +313,11 @@ class Codec:
                 if w == WRAP_GZIP and len(s) >= 4:
                     guess = max(int.from_bytes(s[-4:], "little"), 1)
                 caps.append(min(guess, STREAM_MAX_OUT - 1))
-        st, out = self._streams_once(torch, np, w, streams, caps)
+        st, out = self._streams_once(torch, np, w, streams, caps, split)
         for i in range(len(streams)):
             while grow and st[i] == STREAM_OVERFLOW and caps[i] < STREAM_MAX_OUT - 1:
                 caps[i] = min(2 * caps[i], STREAM_MAX_OUT - 1)
-                s1, o1 = self._streams_once(torch, np, w, [streams[i]], [caps[i]])
+                s1, o1 = self._streams_once(torch, np, w, [streams[i]], [caps[i]], split)
                 st[i], out[i] = s1[0], o1[0]
             if st[i] != STREAM_END:
                 err = ZwzError("inflate_streams: stream %d: status %d" % (i, st[i]))
@@ -476,7 +502,8 @@ class Codec:
     def set_option(self, name, value):
         """Test / experiment switches of this context (include/zwz.h: zwz_ctx_set_option): "match" = auto | walk | band | lazy |
         autoband | autolazy, "plan" = wave | serial, "inflate_header" = wave | serial.  Every choice produces the same bytes; a form that
-        failed its self-test on this device is refused."""
+        failed its self-test on this device is refused.  "split_min_bytes", "split_budget", "split_max_candidates" (decimal strings):
+        the limits of inflate_split_streams_dev."""
         _check(lib().zwz_ctx_set_option(self._h, name.encode(), value.encode()), "zwz_ctx_set_option")
 
     def set_chunk_size(self, nbytes):
@@ -555,6 +582,14 @@ def do_compression(input_dir, output_dir, file_record, world_rank, world_size=1)
 
 def do_decompression(input_dir, output_dir, world_rank=0, world_size=1, allgather=None):
     return _codec().do_decompression(input_dir, output_dir, world_rank, world_size, allgather)
+
+
+def inflate_stream(data, wrap="gzip", out_size=None):
+    return _codec().inflate_stream(data, wrap, out_size)
+
+
+def inflate_stream_file(src, dst, wrap="gzip"):
+    return _codec().inflate_stream_file(src, dst, wrap)
 
 
 def deflate_stream_bound(n, wrap="gzip"):

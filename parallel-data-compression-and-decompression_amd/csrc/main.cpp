@@ -341,12 +341,14 @@ int bgzf_main(const std::string& op, const char* src, const char* dst, int world
 
 void bgzf_usage(const char* argv0) {
     fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n"
-            "       %s gzip <src> <dst> [--zlib|--raw]\n", argv0, argv0, argv0, argv0);
+            "       %s gzip <src> <dst> [--zlib|--raw]\n       %s gunzip <src> <dst> [--zlib|--raw]\n", argv0, argv0, argv0, argv0, argv0);
 }
 
 // `main gzip <src file> <dst file> [--zlib|--raw]`: one file as one ordinary gzip (zlib, raw DEFLATE) stream, one process, one GPU.
+// `main gunzip <src file> <dst file> [--zlib|--raw]`: the way back (zwz_inflate_stream_file), for any stream other encoders wrote too.
 int gzip_main(int argc, char** argv, int world_size, int device) {
-    if (world_size > 1) { fprintf(stderr, "gzip: single process only (world size %d in the environment)\n", world_size); return 1; }
+    const bool back = std::string(argv[1]) == "gunzip";
+    if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", argv[1], world_size); return 1; }
     int wrap = ZWZ_WRAP_GZIP;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
@@ -357,10 +359,10 @@ int gzip_main(int argc, char** argv, int world_size, int device) {
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
-    if (rc == ZWZ_OK) rc = zwz_deflate_stream_file(ctx, wrap, argv[2], argv[3]);
+    if (rc == ZWZ_OK) rc = back ? zwz_inflate_stream_file(ctx, wrap, argv[2], argv[3]) : zwz_deflate_stream_file(ctx, wrap, argv[2], argv[3]);
     zwz_ctx_destroy(ctx);
-    if (rc != ZWZ_OK) { fprintf(stderr, "gzip %s: %s (%s)\n", argv[2], zwz_strerror(rc), zwz_last_error()); return 1; }
-    printf("gzip %s -> %s in %.3f s\n", argv[2], argv[3], std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    if (rc != ZWZ_OK) { fprintf(stderr, "%s %s: %s (%s)\n", argv[1], argv[2], zwz_strerror(rc), zwz_last_error()); return 1; }
+    printf("%s %s -> %s in %.3f s\n", argv[1], argv[2], argv[3], std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     return 0;
 }
 
@@ -511,7 +513,7 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     std::string operation = argv[1], source_path = argv[2], output_path = argv[3];
-    if (operation == "gzip") {
+    if (operation == "gzip" || operation == "gunzip") {
         int n = 0;
         return gzip_main(argc, argv, world_size, zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0);
     }

@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -246,6 +247,7 @@ int zwz_ctx_create(int device, uint32_t max_batch, zwz_ctx** out) {
         if (const char* v = getenv(var)) if (zwz_ctx_set_option(c, option, v) != ZWZ_OK) fprintf(stderr, "zwz: %s=%s is not a value of option \"%s\": ignored\n", var, v, option);
     };
     from_env("ZWZ_MATCH", "match"); from_env("ZWZ_PLAN", "plan"); from_env("ZWZ_INFLATE_HEADER", "inflate_header");
+    from_env("ZWZ_SPLIT_SLICE_BYTES", "split_slice_bytes");      // (for `main gunzip`: the slice of zwz_inflate_stream_file)
     const bool tl = getenv("ZWZ_TIMELINE") != nullptr || getenv("ZWZ_VERBOSE") != nullptr;
     const auto t_create = std::chrono::steady_clock::now();
     auto mark = [&](const char* what) { if (tl) fprintf(stderr, "zwz: context: %s at +%.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_create).count()); };
@@ -310,6 +312,19 @@ int zwz_ctx_set_option(zwz_ctx* c, const char* name, const char* value) {
     } else if (n == "inflate_header") {
         if (v == "wave" || v.empty()) { if (c->forbidden & kForbidInflateWave) { if (v.empty()) return ZWZ_OK; return refuse("inflate_header"); } c->inflate_serial_header = 0; }
         else if (v == "serial") c->inflate_serial_header = 1; else return ZWZ_E_INVALID;
+    } else if (n == "split_slice_bytes") {
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v.c_str(), &end, 10);
+        if (!v.empty() && (*end || end == v.c_str() || x < 4096 || x > (1ull << 28))) return ZWZ_E_INVALID;
+        c->split_slice_bytes = v.empty() ? kSplitSliceBytes : (uint32_t)x & ~15u;
+    } else if (n == "split_min_bytes" || n == "split_budget" || n == "split_max_candidates") {
+        // zwz_inflate_split_streams_dev (split_core.h): an empty value restores the default
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v.c_str(), &end, 10);
+        if ((!v.empty() && (*end || end == v.c_str())) || x > 0x7fffffffull) return ZWZ_E_INVALID;
+        if (n == "split_min_bytes") c->split_min_bytes = v.empty() ? kSplitMinBytes : (uint32_t)x;
+        else if (n == "split_budget") { if (!v.empty() && x < 16) return ZWZ_E_INVALID; c->split_budget = v.empty() ? kSplitBudget : (uint32_t)x; }
+        else { if (!v.empty() && x < 2) return ZWZ_E_INVALID; c->split_max_candidates = v.empty() ? kSplitMaxCandidates : (uint32_t)x; }
     } else return ZWZ_E_INVALID;
     return ZWZ_OK;
 }
@@ -331,6 +346,8 @@ void zwz_ctx_destroy(zwz_ctx* c) {
     if (c->ds_dev) (void)hipFree(c->ds_dev);
     if (c->ds_host) (void)hipHostFree(c->ds_host);
     if (c->ds_copied) (void)hipEventDestroy(c->ds_copied);
+    for (auto& w : c->split_ws) if (w) (void)hipFree(w);
+    if (c->split_host) (void)hipHostFree(c->split_host);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_inf) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/zwz.h"
+#include "split_core.h"
 #include "zwz_kernels.h"
 
 struct zwz_ctx {
@@ -48,6 +49,14 @@ struct zwz_ctx {
     void* ds_dev = nullptr;
     uint32_t ds_streams = 0;
     hipEvent_t ds_copied = nullptr;
+    // split inflate (zwz_split.cpp): options "split_min_bytes", "split_budget", "split_max_candidates" (split_core.h's defaults); device
+    // workspaces of one call, grown to the largest seen: per stream and scan tile / per candidate / per chain segment and checksum piece
+    uint32_t split_min_bytes = zwz::kSplitMinBytes, split_budget = zwz::kSplitBudget, split_max_candidates = zwz::kSplitMaxCandidates;
+    uint32_t split_slice_bytes = zwz::kSplitSliceBytes;      // zwz_inflate_stream_file: "split_slice_bytes"
+    void* split_ws[3] = {};
+    size_t split_ws_cap[3] = {};
+    void* split_host = nullptr;      // pinned: the per-stream arrays a call uploads (read by copies that may still be queued when it returns)
+    size_t split_host_cap = 0;
 };
 
 namespace zwz {

@@ -141,6 +141,18 @@ struct StreamParams {
     const uint64_t* out_off; const uint64_t* out_cap; uint64_t* out_len;
     uint4* rec;                // per stream (checked length, expected checksum, has a checksum, provisional status): stream_core.h's StreamRecord
     uint32_t wrap;             // stream_core.h: kWrapRaw / kWrapZlib / kWrapGzip
+    // the split forms (split_core.h), appended so that the stream form's arguments lie where they lay
+    const uint4* seg;          // per segment: (p & 15, stream, first output byte within the stream's range, count); measuring: (p & 15, stream, -, p & ~15)
+    uint4* meas;               // measuring form: a SegMeasure per segment
+    uint32_t* bad;             // segment form: set for a stream one of whose segments did not end as measured
+};
+// zwz_inflate_split_streams_dev: one wave per segment.  seg_in_off[i] = the stream's offset + (p & ~15), seg_in_len[i] = the bytes the wave may read from there
+struct InflateSplitArgs {
+    const uint8_t* in; const uint64_t* seg_in_off; const uint64_t* seg_in_len; uint32_t n;
+    uint8_t* out; const uint64_t* out_off;
+    uint4* order;              // n entries of scratch
+    const uint4* seg; uint4* meas; uint32_t* bad;
+    uint32_t measure, serial_header;
 };
 struct InflateStreamArgs {
     const uint8_t* in; const uint64_t* in_off; const uint64_t* in_len; uint32_t n;
@@ -187,6 +199,7 @@ uint32_t exp_flags_lazy();
 hipError_t launch_plan(const DeflateArgs& a, hipStream_t s);                             // zwz_plan.hip
 hipError_t launch_inflate(const InflateArgs& a, hipStream_t s);
 hipError_t launch_inflate_streams(const InflateStreamArgs& a, hipStream_t s);      // order + inflate_kernel's stream form (statuses provisional)
+hipError_t launch_inflate_split(const InflateSplitArgs& a, hipStream_t s);         // order + inflate_kernel's measuring or segment form
 struct CrcTables;                                                                  // zwz_bgzf.h
 // zwz_stream.hip: the checksum of every stream's checked output (rec) and its final status
 hipError_t launch_stream_check(const CrcTables* tab, const uint8_t* out, const uint64_t* out_off, const uint4* rec, uint32_t n,

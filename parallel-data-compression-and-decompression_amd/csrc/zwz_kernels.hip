@@ -31,6 +31,7 @@
 #include "huff_core.h"
 #include "inflate_core.h"
 #include "stream_core.h"
+#include "split_core.h"
 #include "lz_core.h"
 #include "zwz_md5.h"
 #include "zwz_kernels.h"
@@ -2025,7 +2026,12 @@ struct InflateWaveMem {
 // out + sp.out_off[i] and is bounded by sp.out_cap[i] instead of the 65 535-byte slot; the wrapper's header is read from global memory
 // before the first block, the trailer after every final block, and a gzip stream goes on with its next member, whose matches may not
 // reach before its first output byte (`origin`).  The chunk forms (kStream = false) compile as they did before this parameter existed.
-template <bool kSerialHeader, bool kStream>
+// kSplit (zwz_inflate_split_streams_dev, split_core.h; with kStream): the wave's unit is a SEGMENT of a stream, sp.seg[i], that starts at a
+// byte-aligned block -- no wrapper header, no trailer, no second member -- and ends by split_stop's rule.  1, the measuring form: output
+// is counted, never written (no stored copy, no owner map, no byte copy), and sp.meas[i] says how the segment ended.  2, the segment
+// form: output goes to its place in the stream's range, which starts at any byte address -- dst is that address rounded down to 16, its
+// low four bits are the first position and the origin -- and is bounded by the measured count.  0 compiles as before the parameter.
+template <bool kSerialHeader, bool kStream, uint32_t kSplit = 0>
 __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                   const uint32_t* __restrict__ in_len, uint32_t n,
                                                                   uint8_t* __restrict__ out, uint64_t out_stride,
@@ -2044,7 +2050,15 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     const uint8_t* src = in + (order ? ((uint64_t)oe.y << 32 | oe.x) : in_off[chunk]);   // 16-byte aligned (API contract)
     uint8_t* dst;
     uint32_t cap = kChunk;                             // output bound
-    if constexpr (kStream) {
+    uint32_t seg_body = 0, seg_start = 0, seg_base = 0, seg_stream = 0, seg_fin = kSegBad;   // kSplit
+    if constexpr (kSplit != 0) {
+        static_assert(kStream, "the split forms are stream forms");
+        const uint4 sgv = sp.seg[chunk];               // (p & 15, stream, first output byte in the stream's range | -, count | p & ~15)
+        const uint4 sg = make_uint4(__builtin_amdgcn_readfirstlane(sgv.x), __builtin_amdgcn_readfirstlane(sgv.y), __builtin_amdgcn_readfirstlane(sgv.z), __builtin_amdgcn_readfirstlane(sgv.w));   // (wave-uniform: scalar registers)
+        seg_body = sg.x; seg_stream = sg.y;
+        if constexpr (kSplit == 1) { dst = nullptr; cap = kSplitMeasureCap; seg_base = sg.w; }
+        else { dst = out + sp.out_off[seg_stream] + (sg.z & ~15u); seg_start = sg.z & 15u; cap = seg_start + sg.w; }
+    } else if constexpr (kStream) {
         const uint64_t cap64 = sp.out_cap[chunk];
         if (oe.z >= kStreamMaxIn || cap64 >= kStreamMaxOut) {     // (the order clips a 64-bit length to 32 bits)
             if (lane == 0) { sp.out_len[chunk] = 0; status[chunk] = kStrTooLarge; sp.rec[chunk] = make_uint4(0, 0, 0, kStrTooLarge); }
@@ -2082,6 +2096,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     uint32_t go = 0;
     uint32_t origin = 0;                               // kStream: the current gzip member's first output byte
     StreamRecord rec{0, 0, 0, kInfRunning};
+    if constexpr (kSplit == 2) origin = seg_start;
     // kStream: the first byte at or after q that is not zero, or nin (the zeros around gzip members), the wave 1 KiB a step
     auto skip_zeros = [&](uint32_t q) -> uint32_t {
         q = __builtin_amdgcn_readfirstlane(q);
@@ -2103,7 +2118,10 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         }
         return nin;
     };
-    if constexpr (kStream) {
+    if constexpr (kSplit != 0) {
+        if (lane == 0) { st.br.init(m.ring, nin, kInfRing - 1u); st.out_pos = seg_start; st.last = 0; st.status = kInfRunning; st.br.seek_bit(seg_body * 8u); }
+        go = 1;                                        // (seg_body < 16: top_up(0) has the bytes)
+    } else if constexpr (kStream) {
         const uint32_t nz = sp.wrap == kWrapGzip ? skip_zeros(0) : nin;
         uint32_t body = 0, sst = kInfRunning;
         if (lane == 0) {
@@ -2191,7 +2209,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
             // stored bytes: whole 16-byte vectors of output, each from five aligned input words shifted by the two
             // ranges' relative misalignment (a 5-byte block header sits between them); bytes at the ragged ends singly.
             // (One byte per lane per trip moved 1.7 TB/s with 5 k waves in flight; this is ~10x fewer instructions.)
-            {
+            if constexpr (kSplit != 1) {
                 const uint32_t head = min(cp, (16u - (opos & 15u)) & 15u);               // dst + opos + head is 16-byte aligned (dst is)
                 if (lane < head) dst[opos + lane] = src[soff + lane];
                 const uint32_t s0 = soff + head, d0 = opos + head, sh = s0 & 3u;
@@ -2401,6 +2419,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                 // marks its first byte with 1 + its index, a max-scan carries the marks forward -- so a lookup is one LDS byte;
                 // larger batches search the symbols' start offsets (6 dependent LDS reads).  It matters where matches a few
                 // bytes back refer to each other (smooth "image-like" data): every hop of the chase below is such a lookup.
+                if constexpr (kSplit != 1) {
                 const bool mapped = bbytes <= kOwnCap;                             // wave-uniform
                 if (mapped) {
                     for (uint32_t i = lane; i < (bbytes + 15u) >> 4; i += 64u) reinterpret_cast<uint4*>(m.ownb)[i] = make_uint4(0, 0, 0, 0);
@@ -2462,6 +2481,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                     if (in) dst[pos] = lit ? (uint8_t)ov : __hip_atomic_load(&dst[src], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     (void)need_fence;
                 }
+                }
                 ZWZ_ISTAMP(5);                                                // the bytes
                 if (stop == kEob) block_done = 1;
                 else if (stop == kSlow) {
@@ -2478,7 +2498,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                     bp = __builtin_amdgcn_readfirstlane(nbp); opos_u = __builtin_amdgcn_readfirstlane(nop);
                     stt = __builtin_amdgcn_readfirstlane(stt);
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    if (k1) {
+                    if constexpr (kSplit != 1) if (k1) {
                         const uint32_t mv = m.batch[0], mp = m.pos[0];
                         if (mv < 256u) { if (lane == 0) dst[mp] = (uint8_t)mv; }
                         else {
@@ -2505,7 +2525,12 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
             }
             if (__builtin_amdgcn_readfirstlane(halt)) break;
         }
-        if constexpr (kStream) {
+        if constexpr (kSplit != 0) {
+            uint32_t fin = kSegBad;
+            if (lane == 0) fin = split_stop(st.last, kind == kBlkStored && slen == 0u);
+            seg_fin = __builtin_amdgcn_readfirstlane(fin);
+            if (seg_fin != kSegBad) break;
+        } else if constexpr (kStream) {
             // the end of a member: its trailer; a gzip stream goes on behind the zeros that may follow with its next member
             uint32_t more = 0, next = 0;
             if (lane == 0 && st.last) {
@@ -2532,7 +2557,11 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
             if (__builtin_amdgcn_readfirstlane(fin)) break;
         }
     }
-    if constexpr (kStream) {
+    if constexpr (kSplit == 1) {
+        if (lane == 0) sp.meas[chunk] = make_uint4(seg_fin, seg_base + ((st.br.bit_pos() + 7u) >> 3), st.out_pos, st.status);
+    } else if constexpr (kSplit == 2) {
+        if (lane == 0 && !(seg_fin != kSegBad && st.out_pos == cap)) sp.bad[seg_stream] = 1;      // (cannot happen: the measuring form decoded the same bits)
+    } else if constexpr (kStream) {
         if (lane == 0) {
             sp.out_len[chunk] = st.out_pos; status[chunk] = st.status;
             sp.rec[chunk] = make_uint4(rec.checked, rec.expect, rec.has_check, st.status);
@@ -2921,6 +2950,20 @@ hipError_t launch_inflate_streams(const InflateStreamArgs& a, hipStream_t s) {
                                             0, nullptr, a.status, (const uint4*)a.order, sp);
     else hipLaunchKernelGGL((inflate_kernel<false, true>), dim3((a.n + per - 1) / per), dim3(kInflateThreads), 0, s, a.in, a.in_off, nullptr, a.n, a.out,
                             0, nullptr, a.status, (const uint4*)a.order, sp);
+    return hipGetLastError();
+}
+
+hipError_t launch_inflate_split(const InflateSplitArgs& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    const uint32_t per = kInflateThreads / 64;
+    hipLaunchKernelGGL(inflate_order_kernel<uint64_t>, dim3(1), dim3(1024), 0, s, a.seg_in_off, a.seg_in_len, a.n, a.order);
+    StreamParams sp{};
+    sp.out_off = a.out_off; sp.seg = a.seg; sp.meas = a.meas; sp.bad = a.bad;
+    const dim3 grid((a.n + per - 1) / per), block(kInflateThreads);
+#define ZWZ_SPLIT_LAUNCH(h, k) hipLaunchKernelGGL((inflate_kernel<h, true, k>), grid, block, 0, s, a.in, a.seg_in_off, nullptr, a.n, a.out, 0, nullptr, nullptr, (const uint4*)a.order, sp)
+    if (a.measure) { if (a.serial_header) ZWZ_SPLIT_LAUNCH(true, 1); else ZWZ_SPLIT_LAUNCH(false, 1); }
+    else { if (a.serial_header) ZWZ_SPLIT_LAUNCH(true, 2); else ZWZ_SPLIT_LAUNCH(false, 2); }
+#undef ZWZ_SPLIT_LAUNCH
     return hipGetLastError();
 }
 

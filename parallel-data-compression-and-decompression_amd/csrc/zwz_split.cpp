@@ -1,0 +1,354 @@
+// zwz_split.cpp -- zwz_inflate_split_streams_dev of include/zwz.h: the host driver of the split decode (split_core.h).  The launch
+// sizes depend on what the scan and the chains give, so the call waits for the context's stream three times: for the batch's sizes,
+// for the candidates per stream, and for the chains' verdicts.  Streams that do not split go through zwz_inflate_streams_dev as they
+// are; the splitting ones are handed to it with a length of zero and get their results behind it.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "dstream_core.h"
+#include "zwz_api_internal.h"
+#include "zwz_bgzf.h"
+#include "zwz_filejob.h"
+#include "zwz_split.h"
+
+using namespace zwz;
+
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
+
+namespace {
+
+constexpr uint64_t kSplitMaxKept = 8u << 20;        // kept candidates of one call: the workspace is (levels + 20) words each
+
+struct Carver {
+    uint8_t* p;
+    template <class T> T* take(size_t count) { T* r = reinterpret_cast<T*>(p); p += (count * sizeof(T) + 255) & ~(size_t)255; return r; }
+};
+inline size_t padded(size_t count, size_t size) { return (count * size + 255) & ~(size_t)255; }
+
+int ensure_ws(zwz_ctx* c, int which, size_t bytes) {
+    if (bytes <= c->split_ws_cap[which]) return ZWZ_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->split_ws[which]) { (void)hipFree(c->split_ws[which]); c->split_ws[which] = nullptr; c->split_ws_cap[which] = 0; }
+    HIPCHK(hipMalloc(&c->split_ws[which], bytes));
+    c->split_ws_cap[which] = bytes;
+    return ZWZ_OK;
+}
+
+// One slice of a file (zwz_inflate_stream_file): the stream is raw DEFLATE data that starts at a known block start p0 and need not end
+// in the slice.  Decoded is the longest prefix of the chain that ends cleanly inside the slice and fits the output staging; nothing
+// falls back.  Results (after the call, which then returns synchronised): segments decoded, their bytes, where the prefix ends in
+// the slice, how its last segment ended, the checksum of the bytes.
+struct SlicePart { uint32_t p0; uint32_t nseg, total, end, kind, chk; };
+
+int split_call(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+               uint32_t n, uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+               uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_segments, SlicePart* part) {
+    hipStream_t st = c->stream;
+    auto fall_back = [&](const uint64_t* lens) {
+        if (part) return (int)ZWZ_OK;
+        return zwz_inflate_streams_dev(c, wrap, d_in, d_in_off, lens, n, d_out, d_out_off, d_out_cap, d_out_len, d_status);
+    };
+    const uint32_t min_bytes = part ? 1u : c->split_min_bytes;
+    if (part) { part->nseg = 0; part->total = 0; part->end = part->p0; part->kind = kSegBad; part->chk = 0; }
+
+    // 1. the sizes: which streams are scanned at all, and their tiles
+    std::vector<uint64_t> h_len(n), h_cap(n);
+    HIPCHK(hipMemcpyAsync(h_len.data(), d_in_len, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_cap.data(), d_out_cap, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (d_segments) HIPCHK(hipMemsetAsync(d_segments, 0, n * sizeof(uint32_t), st));
+    if ((size_t)(n + 1) * 24 > c->split_host_cap) {
+        if (c->split_host) { (void)hipHostFree(c->split_host); c->split_host = nullptr; c->split_host_cap = 0; }
+        HIPCHK(hipHostMalloc(&c->split_host, (size_t)(n + 1) * 24, hipHostMallocDefault));
+        c->split_host_cap = (size_t)(n + 1) * 24;
+    }
+    uint64_t* fb_len = static_cast<uint64_t*>(c->split_host);
+    uint32_t* tile_first = reinterpret_cast<uint32_t*>(fb_len + n + 1);
+    uint32_t *kbase = tile_first + n + 1, *dbase = kbase + n + 1, *pbase = dbase + n + 1;
+    uint64_t tiles = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        tile_first[i] = (uint32_t)tiles;
+        if (h_len[i] < kStreamMaxIn && h_cap[i] < kStreamMaxOut && h_len[i] >= min_bytes && h_len[i]) tiles += (h_len[i] + kSplitTile - 1) / kSplitTile;
+        if (tiles > 0x7fffffffull) return fall_back(d_in_len);          // (2^43 bytes of input in one call)
+    }
+    tile_first[n] = (uint32_t)tiles;
+    if (!tiles) return fall_back(d_in_len);
+
+    // per stream: body, tile_first, cfirst, kbase, dbase, pbase, res, bad, the lengths handed to the fallback; per tile: count, offset
+    {
+        const size_t bytes = 7 * padded(n + 1, 4) + 2 * padded(n + 1, 8) + 2 * padded(n, 16) + padded(tiles, 4) + padded(tiles, 8) + 256;
+        const int rc = ensure_ws(c, 0, bytes);
+        if (rc) return rc;
+    }
+    Carver w0{static_cast<uint8_t*>(c->split_ws[0])};
+    SplitStreams S{};
+    S.in = d_in; S.in_off = d_in_off; S.in_len = d_in_len; S.out_cap = d_out_cap; S.n = n; S.wrap = (uint32_t)wrap;
+    S.body = w0.take<uint32_t>(n + 1);
+    uint32_t* d_tile_first = w0.take<uint32_t>(n + 1);
+    uint32_t* d_kbase = w0.take<uint32_t>(n + 1);
+    uint32_t* d_dbase = w0.take<uint32_t>(n + 1);
+    uint32_t* d_pbase = w0.take<uint32_t>(n + 1);
+    uint32_t* d_bad = w0.take<uint32_t>(n + 1);
+    S.cfirst = w0.take<uint64_t>(n + 1);
+    uint64_t* d_fb_len = w0.take<uint64_t>(n + 1);
+    uint4* d_res = w0.take<uint4>(n);
+    uint4* d_res2 = w0.take<uint4>(n);
+    uint32_t* d_chk = w0.take<uint32_t>(n + 1);
+    S.tile_cnt = w0.take<uint32_t>(tiles);
+    S.tile_off = w0.take<uint64_t>(tiles);
+    S.base = w0.take<uint64_t>(2);
+    S.tile_first = d_tile_first; S.kbase = d_kbase; S.n_tiles = (uint32_t)tiles;
+    HIPCHK(hipMemcpyAsync(d_tile_first, tile_first, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), st));
+    if (part) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(S.body), (int)part->p0, 1, st));      // (the body starts where the last slice's chain ended)
+    else HIPCHK(launch_split_head(S, min_bytes, st));
+    HIPCHK(launch_split_count(S, st));
+
+    // 2. the candidates per stream: which streams are measured
+    std::vector<uint64_t> cfirst(n + 1);
+    HIPCHK(hipMemcpyAsync(cfirst.data(), S.cfirst, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    uint64_t kept = 0;
+    uint32_t longest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        kbase[i] = (uint32_t)kept;
+        const uint64_t cnt = cfirst[i + 1] - cfirst[i];
+        if (cnt >= (part ? 1u : 2u) && cnt <= c->split_max_candidates && kept + cnt <= kSplitMaxKept) { kept += cnt; longest = std::max(longest, (uint32_t)cnt); }
+    }
+    kbase[n] = (uint32_t)kept;
+    if (!kept) return fall_back(d_in_len);
+    const uint32_t m = (uint32_t)kept, levels = split_levels(longest);
+    {
+        const size_t bytes = (5 + levels) * padded(m, 4) + 2 * padded(m, 8) + 3 * padded(m, 16) + 256;
+        const int rc = ensure_ws(c, 1, bytes);
+        if (rc) return rc;
+    }
+    Carver w1{static_cast<uint8_t*>(c->split_ws[1])};
+    SplitCands C{};
+    C.m = m;
+    C.pos = w1.take<uint32_t>(m); C.mark = w1.take<uint32_t>(m); C.ostart = w1.take<uint32_t>(m); C.rank = w1.take<uint32_t>(m);
+    C.jump = w1.take<uint32_t>((size_t)levels * m);
+    C.in_off = w1.take<uint64_t>(m); C.in_len = w1.take<uint64_t>(m);
+    C.seg = w1.take<uint4>(m); C.meas = w1.take<uint4>(m);
+    uint4* d_order = w1.take<uint4>(m);
+    HIPCHK(hipMemcpyAsync(d_kbase, kbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(launch_split_write(S, C, c->split_budget, st));
+    {
+        InflateSplitArgs a{d_in, C.in_off, C.in_len, m, nullptr, nullptr, d_order, C.seg, C.meas, nullptr, 1u, c->inflate_serial_header};
+        HIPCHK(launch_inflate_split(a, st));
+    }
+    HIPCHK(launch_split_resolve(S, C, levels, d_res, part ? 1u : 0u, part ? h_cap[0] : 0, d_res2, st));
+
+    // 3. the chains' verdicts: the segments to decode, the checksum pieces, and who falls back
+    std::vector<uint4> res(n);
+    HIPCHK(hipMemcpyAsync(res.data(), d_res, n * sizeof(uint4), hipMemcpyDeviceToHost, st));
+    uint4 res2{};
+    if (part) HIPCHK(hipMemcpyAsync(&res2, d_res2, sizeof(uint4), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n; i++) fb_len[i] = h_len[i];
+    uint64_t nd = 0, np = 0;
+    uint32_t n_fall = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        dbase[i] = (uint32_t)nd; pbase[i] = (uint32_t)np;
+        if (res[i].x) { nd += res[i].y; if (wrap != ZWZ_WRAP_RAW) np += ((uint64_t)res[i].z + kPieceBytes - 1) / kPieceBytes; fb_len[i] = 0; }
+        else n_fall++;
+    }
+    dbase[n] = (uint32_t)nd; pbase[n] = (uint32_t)np;
+    if (!nd) return fall_back(d_in_len);
+    // The stream path runs over the whole batch with the splitting streams' lengths set to zero: a wave each that ends at once and
+    // writes status 1 and length 0 for them.  Their real results are written by split_finish_kernel further down.  Both are queued on
+    // the context's stream in this order, and the call's correctness depends on that: the later write wins.
+    if (n_fall && !part) {
+        HIPCHK(hipMemcpyAsync(d_fb_len, fb_len, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        const int rc = fall_back(d_fb_len);
+        if (rc) return rc;
+    }
+    if (wrap == ZWZ_WRAP_GZIP && !c->crc_tables) {
+        HIPCHK(hipMalloc(&c->crc_tables, sizeof(CrcTables)));
+        HIPCHK(launch_crc_tables(static_cast<CrcTables*>(c->crc_tables), st));
+    }
+    {
+        const size_t bytes = 3 * padded(nd, 8) + padded(nd, 16) + padded(np, 8) + 2 * padded(np, 4) + 256;
+        const int rc = ensure_ws(c, 2, bytes);
+        if (rc) return rc;
+    }
+    Carver w2{static_cast<uint8_t*>(c->split_ws[2])};
+    SplitDecode D{};
+    D.res = d_res; D.dbase = d_dbase;
+    D.in_off = w2.take<uint64_t>(nd); D.in_len = w2.take<uint64_t>(nd); D.seg = w2.take<uint4>(nd);
+    SplitPieces P{};
+    P.pbase = d_pbase; P.p = (uint32_t)np;
+    P.off = w2.take<uint64_t>(np); P.len = w2.take<uint32_t>(np); P.val = w2.take<uint32_t>(np);
+    HIPCHK(hipMemcpyAsync(d_dbase, dbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_pbase, pbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(launch_split_emit(S, C, D, st));
+    {
+        InflateSplitArgs a{d_in, D.in_off, D.in_len, (uint32_t)nd, d_out, d_out_off, d_order, D.seg, nullptr, d_bad, 0u, c->inflate_serial_header};
+        HIPCHK(launch_inflate_split(a, st));
+    }
+    HIPCHK(launch_split_finish(S, D, P, static_cast<const CrcTables*>(c->crc_tables), d_out, d_out_off, d_bad, d_out_len, d_status, d_segments,
+                               part ? d_chk : nullptr, c->cu_count, st));
+    if (part) {
+        HIPCHK(hipMemcpyAsync(&part->chk, d_chk, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        uint32_t bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (bad) { set_error("split inflate: a segment did not decode as it was measured"); return ZWZ_E_FORMAT; }
+        part->nseg = res[0].y; part->total = res[0].z; part->end = res2.x; part->kind = res2.y;
+    }
+    return ZWZ_OK;
+}
+
+}  // namespace
+
+extern "C" int zwz_inflate_split_streams_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                             uint32_t n, uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                             uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_segments) {
+    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    if (n && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status)) return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return ZWZ_E_INVALID;
+    if (n == 0) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return split_call(c, wrap, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_segments, nullptr);
+}
+
+// One file of any size.  The device holds a slice of the compressed file at a time; split_call decodes the chain segments that end
+// inside it and fit the output staging, the host writes them (a writer thread, two pinned buffers), joins their checksum onto the
+// file's and goes on with a slice that starts at the chain's position, rounded down to 16: the bytes behind it are kept, the rest is
+// read.  A chain that makes no progress in a whole slice is broken: before any byte was written the file goes through the one-stream
+// path if it fits its limits, later it is ZWZ_E_FORMAT.
+extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, const char* dst) {
+    if (!c || !src || !dst || wrap_ < ZWZ_WRAP_RAW || wrap_ > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    const uint32_t wrap = (uint32_t)wrap_;
+    HIPCHK(hipSetDevice(c->device));
+    FileJob job;
+    if (int rc = job.open(src, dst)) return rc;
+    const size_t S = c->split_slice_bytes, O = std::max<size_t>(4 * S, 4u << 20);
+    HIPCHK(hipHostMalloc(&job.h[0], S + 32, hipHostMallocDefault));
+    for (int i = 2; i < 4; i++) HIPCHK(hipHostMalloc(&job.h[i], O, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc(&job.h[4], 64, hipHostMallocDefault));
+    HIPCHK(hipMalloc(&job.d[0], S + 32));
+    HIPCHK(hipMalloc(&job.d[1], O + 16));
+    HIPCHK(hipMalloc(&job.d[2], 64));
+    uint8_t* hin = static_cast<uint8_t*>(job.h[0]);
+    uint8_t* d_in = static_cast<uint8_t*>(job.d[0]); uint8_t* d_out = static_cast<uint8_t*>(job.d[1]);
+    uint64_t* d_par = static_cast<uint64_t*>(job.d[2]);           // in_off, in_len, out_off, out_cap, out_len, (status, segments)
+    uint64_t* h_par = static_cast<uint64_t*>(job.h[4]);
+    bool io_err = false;
+    uint64_t base = 0;                    // file offset of hin[0], a multiple of 16
+    size_t have = read_full(job.in, hin, S, &io_err);
+    if (io_err) { set_error("read error on %s", src); return ZWZ_E_IO; }
+    bool eof = have < S;
+    uint32_t p0 = 0;
+    bool chain_ok = true;
+    {
+        uint32_t nz = 0;
+        while (nz < have && hin[nz] == 0) nz++;
+        chain_ok = have && stream_begin(wrap, hin, (uint32_t)have, wrap == kWrapGzip ? (nz ? (uint32_t)have : 0u) : (uint32_t)have, &p0) == kInfRunning && p0 < have;
+    }
+    uint32_t check = dstream_check_init(wrap);
+    uint64_t total = 0, at = p0;          // decoded bytes written; file offset of the chain's position
+    uint32_t kind = kSegBad;
+    int b = 0;
+    while (chain_ok) {
+        memset(hin + have, 0, 32);
+        h_par[0] = 0; h_par[1] = have; h_par[2] = 0; h_par[3] = O;
+        HIPJOB(hipMemcpyAsync(d_in, hin, (have + 31) & ~(size_t)15, hipMemcpyHostToDevice, c->stream));
+        HIPJOB(hipMemcpyAsync(d_par, h_par, 32, hipMemcpyHostToDevice, c->stream));
+        SlicePart part{};
+        part.p0 = (uint32_t)(at - base);
+        if (int rc = split_call(c, wrap_, d_in, d_par, d_par + 1, 1, d_out, d_par + 2, d_par + 3, d_par + 4, reinterpret_cast<uint32_t*>(d_par + 5), nullptr, &part)) { job.join(); return rc; }
+        if (!part.nseg) { chain_ok = false; break; }             // no segment ends inside a whole slice (or its input does)
+        uint8_t* hout = static_cast<uint8_t*>(job.h[2 + b]);
+        if (int rc = job.finish_write()) return rc;               // (two writes back: this buffer is free)
+        HIPJOB(hipMemcpyAsync(hout, d_out, part.total, hipMemcpyDeviceToHost, c->stream));
+        HIPJOB(hipStreamSynchronize(c->stream));
+        job.start_write(hout, part.total);
+        b ^= 1;
+        if (wrap == kWrapZlib) check = AdlerSum::join(check, part.chk, AdlerSum::pof(part.total));
+        else if (wrap == kWrapGzip) check = CrcSum::join(check, part.chk, CrcSum::pof(part.total));
+        total += part.total;
+        at = base + part.end;
+        kind = part.kind;
+        if (kind == kSegFinal) break;
+        // the next slice: from the chain's position rounded down to 16
+        const uint64_t nbase = at & ~15ull;
+        const size_t keep = (size_t)(base + have - nbase);
+        if (keep == have && eof) { chain_ok = false; break; }     // (cannot happen: a segment was decoded)
+        memmove(hin, hin + (nbase - base), keep);
+        base = nbase; have = keep;
+        if (!eof) {
+            const size_t got = read_full(job.in, hin + keep, S - keep, &io_err);
+            if (io_err) { job.join(); set_error("read error on %s", src); return ZWZ_E_IO; }
+            have += got;
+            eof = got < S - keep;
+        } else if (at >= base + have) { chain_ok = false; break; }   // the file ends at a flush point: no final block
+    }
+    if (int rc = job.finish_write()) return rc;
+    fseeko(job.in, 0, SEEK_END);
+    const uint64_t size = (uint64_t)ftello(job.in);
+    // the whole file as one stream through zwz_inflate_streams_dev, the capacity doubled until it fits; what was written is dropped
+    auto one_stream = [&]() -> int {
+        job.join();
+        if (fflush(job.out) != 0 || ftruncate(fileno(job.out), 0) != 0 || fseeko(job.out, 0, SEEK_SET) != 0) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
+        for (int i = 0; i < 4; i++) { if (job.h[i]) { (void)hipHostFree(job.h[i]); job.h[i] = nullptr; } if (i < 2 && job.d[i]) { (void)hipFree(job.d[i]); job.d[i] = nullptr; } }
+        std::vector<uint8_t> whole((size_t)size + 16, 0);
+        fseeko(job.in, 0, SEEK_SET);
+        if (read_full(job.in, whole.data(), (size_t)size, &io_err) != size || io_err) { set_error("read error on %s", src); return ZWZ_E_IO; }
+        HIPCHK(hipMalloc(&job.d[0], ((size_t)size + 31) & ~(size_t)15));
+        HIPCHK(hipMemcpy(job.d[0], whole.data(), ((size_t)size + 15) & ~(size_t)15, hipMemcpyHostToDevice));
+        uint64_t cap = std::max<uint64_t>(8 * size, 1u << 20);
+        for (;;) {
+            cap = std::min<uint64_t>(cap, kStreamMaxOut - 16);
+            if (job.d[1]) { (void)hipFree(job.d[1]); job.d[1] = nullptr; }
+            HIPCHK(hipMalloc(&job.d[1], cap + 16));
+            h_par[0] = 0; h_par[1] = size; h_par[2] = 0; h_par[3] = cap;
+            HIPCHK(hipMemcpy(d_par, h_par, 32, hipMemcpyHostToDevice));
+            if (int rc = zwz_inflate_streams_dev(c, wrap_, static_cast<uint8_t*>(job.d[0]), d_par, d_par + 1, 1, static_cast<uint8_t*>(job.d[1]), d_par + 2, d_par + 3,
+                                                 d_par + 4, reinterpret_cast<uint32_t*>(d_par + 5))) return rc;
+            HIPCHK(hipStreamSynchronize(c->stream));
+            HIPCHK(hipMemcpy(h_par + 4, d_par + 4, 16, hipMemcpyDeviceToHost));
+            const uint32_t status = (uint32_t)h_par[5];
+            if (status == kInfOverflow && cap < kStreamMaxOut - 16) { cap *= 2; continue; }
+            if (status == kStrChecksum || status == kStrLength) { set_error("zwz_inflate_stream_file: %s: %s mismatch", src, status == kStrLength ? "length" : "checksum"); return ZWZ_E_CHECKSUM; }
+            if (status != kInfEnd) { set_error("zwz_inflate_stream_file: %s: stream status %u after %llu decoded bytes", src, status, (unsigned long long)h_par[4]); return ZWZ_E_FORMAT; }
+            break;
+        }
+        std::vector<uint8_t> outv((size_t)h_par[4]);
+        if (!outv.empty()) HIPCHK(hipMemcpy(outv.data(), job.d[1], outv.size(), hipMemcpyDeviceToHost));
+        if (!outv.empty() && fwrite(outv.data(), 1, outv.size(), job.out) != outv.size()) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
+        return job.commit(dst);
+    };
+    if (!chain_ok || kind != kSegFinal) {
+        // the chain broke at `at`
+        if (total || size >= kStreamMaxIn) {
+            set_error("zwz_inflate_stream_file: %s: no block ends cleanly from compressed offset %llu on%s", src, (unsigned long long)at,
+                      total ? "" : " and the file is too large for the one-stream path");
+            return ZWZ_E_FORMAT;
+        }
+        return one_stream();              // nothing written yet
+    }
+    // the trailer behind the final block, and for gzip nothing but zero bytes behind it
+    if (wrap != kWrapRaw) {
+        uint8_t tr[8];
+        const size_t want = wrap == kWrapZlib ? 4 : 8;
+        fseeko(job.in, (off_t)at, SEEK_SET);
+        if (read_full(job.in, tr, want, &io_err) != want) { set_error("zwz_inflate_stream_file: %s ends inside its trailer at compressed offset %llu", src, (unsigned long long)at); return ZWZ_E_FORMAT; }
+        const uint32_t stored = wrap == kWrapZlib ? be32_at(tr) : le32_at(tr);
+        if (stored != check) { set_error("zwz_inflate_stream_file: %s: checksum mismatch", src); return ZWZ_E_CHECKSUM; }
+        if (wrap == kWrapGzip) {
+            if (le32_at(tr + 4) != (uint32_t)total) { set_error("zwz_inflate_stream_file: %s: length mismatch", src); return ZWZ_E_CHECKSUM; }
+            uint8_t buf[4096];
+            uint64_t q = at + 8;
+            for (size_t k; (k = fread(buf, 1, sizeof buf, job.in)) > 0; q += k)
+                for (size_t i = 0; i < k; i++)
+                    if (buf[i]) {
+                        if (size < kStreamMaxIn) return one_stream();      // another member, or garbage: that path reads the one and names the other
+                        set_error("zwz_inflate_stream_file: %s: bytes behind the first member at compressed offset %llu (further members of a file this large are not read)", src, (unsigned long long)(q + i));
+                        return ZWZ_E_FORMAT;
+                    }
+        }
+    }
+    return job.commit(dst);
+}

@@ -2,7 +2,7 @@
 # Registers, scratch, LDS and occupancy of every kernel (hipcc cross-compiles gfx950 on the CPU box): part of every kernel change --
 # a spill in one kernel has cost another kernel of the same file milliseconds before.   usage: tools/resources.sh [file.hip ...]
 cd "$(dirname "$0")/../parallel-data-compression-and-decompression_amd"
-for f in ${@:-csrc/zwz_kernels.hip csrc/zwz_band.hip csrc/zwz_plan.hip}; do
+for f in ${@:-csrc/zwz_kernels.hip csrc/zwz_band.hip csrc/zwz_plan.hip csrc/zwz_split.hip}; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $EXTRA -Rpass-analysis=kernel-resource-usage -c $f -o /dev/null 2>&1 | python3 -c '
 import re, sys
 cur = {}
