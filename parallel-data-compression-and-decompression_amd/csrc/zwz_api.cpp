@@ -33,8 +33,6 @@ int hip_fail(hipError_t e, const char* what) {
 
 using namespace zwz;
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
-
 namespace {
 
 // Known-answer test of lz_links, run once per context.  The kernel's feeders keep input loads in flight across several
@@ -333,21 +331,8 @@ void zwz_ctx_destroy(zwz_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->workspace) (void)hipFree(c->workspace);
-    if (c->inf_order) (void)hipFree(c->inf_order);
-    if (c->stream_rec) (void)hipFree(c->stream_rec);
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->bgzf_ws) (void)hipFree(c->bgzf_ws);
-    if (c->crc_tables) (void)hipFree(c->crc_tables);
-    if (c->rr_dev) (void)hipFree(c->rr_dev);
-    if (c->rr_host) (void)hipHostFree(c->rr_host);
-    if (c->ds_ws) (void)hipFree(c->ds_ws);
-    if (c->ds_dev) (void)hipFree(c->ds_dev);
-    if (c->ds_host) (void)hipHostFree(c->ds_host);
+    for (Buffer& b : c->buf) b.release();
     if (c->ds_copied) (void)hipEventDestroy(c->ds_copied);
-    for (auto& w : c->split_ws) if (w) (void)hipFree(w);
-    if (c->split_host) (void)hipHostFree(c->split_host);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_inf) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -383,12 +368,7 @@ int zwz_deflate_batch_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_
     {   // the workspace grows to the largest slice seen (never past max_batch): small jobs and pure
         // decompression never pay for the full ~5.6 GB
         const uint32_t want = n < c->max_batch ? n : c->max_batch;
-        if (want > c->ws_chunks) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (c->workspace) { (void)hipFree(c->workspace); c->workspace = nullptr; c->ws_chunks = 0; }
-            HIPCHK(hipMalloc(&c->workspace, (size_t)want * kWorkspaceBytesPerChunk + kTicketBytes + 8192));
-            c->ws_chunks = want;
-        }
+        if (int rc = ensure_workspace(c, want)) return rc;
     }
     for (uint32_t done = 0; done < n; done += c->max_batch) {
         const uint32_t m = n - done < c->max_batch ? n - done : c->max_batch;
@@ -424,13 +404,8 @@ int zwz_inflate_batch_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_
     if (!c || (n && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_len || !d_status))) return ZWZ_E_INVALID;
     if (out_stride < ZWZ_CHUNK_SIZE || ((uintptr_t)d_in & 15u)) return ZWZ_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
-    if (n > c->inf_order_cap) {     // scratch for the launch order (longest payloads first)
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->inf_order) { (void)hipFree(c->inf_order); c->inf_order = nullptr; c->inf_order_cap = 0; }
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->inf_order), (size_t)n * sizeof(uint4)));
-        c->inf_order_cap = n;
-    }
-    InflateArgs a{d_in, d_in_off, d_in_len, n, d_out, out_stride, d_out_len, d_status, c->inf_order, c->inflate_serial_header};
+    if (int rc = ensure_inf_order(c, n)) return rc;
+    InflateArgs a{d_in, d_in_off, d_in_len, n, d_out, out_stride, d_out_len, d_status, c->buf[kBufInfOrder].as<uint4>(), c->inflate_serial_header};
     if (c->profiling) HIPCHK(hipEventRecord(c->ev_inf[0], c->stream));
     HIPCHK(launch_inflate(a, c->stream));
     if (c->profiling) {
@@ -450,36 +425,22 @@ int zwz_inflate_streams_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uin
     if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return ZWZ_E_INVALID;
     if (n == 0) return ZWZ_OK;
     HIPCHK(hipSetDevice(c->device));
-    if (n > c->inf_order_cap || n > c->stream_rec_cap) {   // scratch: the launch order, and what the decode hands the check
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (n > c->inf_order_cap) {
-            if (c->inf_order) { (void)hipFree(c->inf_order); c->inf_order = nullptr; c->inf_order_cap = 0; }
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->inf_order), (size_t)n * sizeof(uint4)));
-            c->inf_order_cap = n;
-        }
-        if (n > c->stream_rec_cap) {
-            if (c->stream_rec) { (void)hipFree(c->stream_rec); c->stream_rec = nullptr; c->stream_rec_cap = 0; }
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->stream_rec), (size_t)n * sizeof(uint4)));
-            c->stream_rec_cap = n;
-        }
-    }
-    if (wrap == ZWZ_WRAP_GZIP && !c->crc_tables) {
-        HIPCHK(hipMalloc(&c->crc_tables, sizeof(CrcTables)));
-        HIPCHK(launch_crc_tables(static_cast<CrcTables*>(c->crc_tables), c->stream));
-    }
-    InflateStreamArgs a{d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, c->inf_order, c->stream_rec,
+    if (int rc = ensure_inf_order(c, n)) return rc;
+    if (int rc = c->buf[kBufStreamRec].reserve(c, n, (size_t)n * sizeof(uint4))) return rc;     // what the decode hands the check
+    if (wrap == ZWZ_WRAP_GZIP) if (int rc = ensure_crc_tables(c)) return rc;
+    uint4* rec = c->buf[kBufStreamRec].as<uint4>();
+    InflateStreamArgs a{d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, c->buf[kBufInfOrder].as<uint4>(), rec,
                         (uint32_t)wrap, c->inflate_serial_header};
     HIPCHK(launch_inflate_streams(a, c->stream));
-    HIPCHK(launch_stream_check(static_cast<const CrcTables*>(c->crc_tables), d_out, d_out_off, c->stream_rec, n, (uint32_t)wrap, d_status,
+    HIPCHK(launch_stream_check(c->buf[kBufCrcTables].as<const CrcTables>(), d_out, d_out_off, rec, n, (uint32_t)wrap, d_status,
                                c->cu_count, c->stream));
     return ZWZ_OK;
 }
 
 // ---- host-buffer variants: pack chunks into 65536-byte slots of a pinned buffer, one H2D, run,
-// one D2H, unpack at the reference's 65535-byte stride.
-int zwz_deflate_batch(zwz_ctx* c, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint8_t* out,
-                      uint32_t* out_len) {
-    if (!c || (n && (!in || !in_off || !in_len || !out || !out_len))) return ZWZ_E_INVALID;
+// one D2H, unpack at the reference's 65535-byte stride.  status = null: deflate, else inflate.
+static int batch_host(zwz_ctx* c, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint8_t* out,
+                      uint32_t* out_len, uint32_t* status) {
     for (uint32_t i = 0; i < n; i++) if (in_len[i] > ZWZ_CHUNK_SIZE) return ZWZ_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
     const uint32_t slice = c->max_batch;
@@ -487,7 +448,7 @@ int zwz_deflate_batch(zwz_ctx* c, const uint8_t* in, const uint64_t* in_off, con
         const uint32_t m = n - done < slice ? n - done : slice;
         int rc = ensure_staging(c, m);
         if (rc) return rc;
-        StageView v = stage_view(c, m);
+        StageView v = stage_view(c, 0);
         for (uint32_t i = 0; i < m; i++) {
             memcpy(v.h_in + (size_t)i * ZWZ_DEV_STRIDE, in + in_off[done + i], in_len[done + i]);
             v.h_off[i] = (uint64_t)i * ZWZ_DEV_STRIDE;
@@ -496,91 +457,114 @@ int zwz_deflate_batch(zwz_ctx* c, const uint8_t* in, const uint64_t* in_off, con
         HIPCHK(hipMemcpyAsync(v.d_in, v.h_in, (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(v.d_off, v.h_off, m * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(v.d_len, v.h_len, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        rc = zwz_deflate_batch_dev(c, v.d_in, v.d_off, v.d_len, m, v.d_out, ZWZ_DEV_STRIDE, v.d_olen);
+        rc = status ? zwz_inflate_batch_dev(c, v.d_in, v.d_off, v.d_len, m, v.d_out, ZWZ_DEV_STRIDE, v.d_olen, v.d_status)
+                    : zwz_deflate_batch_dev(c, v.d_in, v.d_off, v.d_len, m, v.d_out, ZWZ_DEV_STRIDE, v.d_olen);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(v.h_out, v.d_out, (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(v.h_olen, v.d_olen, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (status) HIPCHK(hipMemcpyAsync(v.h_status, v.d_status, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         for (uint32_t i = 0; i < m; i++) {
             out_len[done + i] = v.h_olen[i];
+            if (status) status[done + i] = v.h_status[i];
             memcpy(out + (size_t)(done + i) * ZWZ_CHUNK_SIZE, v.h_out + (size_t)i * ZWZ_DEV_STRIDE, v.h_olen[i]);
         }
     }
     return ZWZ_OK;
 }
 
+int zwz_deflate_batch(zwz_ctx* c, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint8_t* out,
+                      uint32_t* out_len) {
+    if (!c || (n && (!in || !in_off || !in_len || !out || !out_len))) return ZWZ_E_INVALID;
+    return batch_host(c, in, in_off, in_len, n, out, out_len, nullptr);
+}
+
 int zwz_inflate_batch(zwz_ctx* c, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint8_t* out,
                       uint32_t* out_len, uint32_t* status) {
     if (!c || (n && (!in || !in_off || !in_len || !out || !out_len || !status))) return ZWZ_E_INVALID;
-    for (uint32_t i = 0; i < n; i++) if (in_len[i] > ZWZ_CHUNK_SIZE) return ZWZ_E_INVALID;
-    HIPCHK(hipSetDevice(c->device));
-    const uint32_t slice = c->max_batch;
-    for (uint32_t done = 0; done < n; done += slice) {
-        const uint32_t m = n - done < slice ? n - done : slice;
-        int rc = ensure_staging(c, m);
-        if (rc) return rc;
-        StageView v = stage_view(c, m);
-        for (uint32_t i = 0; i < m; i++) {
-            memcpy(v.h_in + (size_t)i * ZWZ_DEV_STRIDE, in + in_off[done + i], in_len[done + i]);
-            v.h_off[i] = (uint64_t)i * ZWZ_DEV_STRIDE;
-            v.h_len[i] = in_len[done + i];
-        }
-        HIPCHK(hipMemcpyAsync(v.d_in, v.h_in, (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(v.d_off, v.h_off, m * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(v.d_len, v.h_len, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        rc = zwz_inflate_batch_dev(c, v.d_in, v.d_off, v.d_len, m, v.d_out, ZWZ_DEV_STRIDE, v.d_olen, v.d_status);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(v.h_out, v.d_out, (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(v.h_olen, v.d_olen, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(v.h_status, v.d_status, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (uint32_t i = 0; i < m; i++) {
-            out_len[done + i] = v.h_olen[i];
-            status[done + i] = v.h_status[i];
-            memcpy(out + (size_t)(done + i) * ZWZ_CHUNK_SIZE, v.h_out + (size_t)i * ZWZ_DEV_STRIDE, v.h_olen[i]);
-        }
-    }
-    return ZWZ_OK;
+    return batch_host(c, in, in_off, in_len, n, out, out_len, status);
 }
 
 }  // extern "C"
 
 namespace zwz {
 
-void carve_workspace(zwz_ctx* c, DeflateArgs& a) {
-    uint8_t* p = static_cast<uint8_t*>(c->workspace);
-    const size_t n = c->ws_chunks;
-    auto take = [&](size_t bytes) { uint8_t* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-    a.entries = reinterpret_cast<uint2*>(take(n * kEntryStride * sizeof(uint2)));
-    a.links = reinterpret_cast<uint16_t*>(take(n * kLinkStride * sizeof(uint16_t)));
-    a.has128 = reinterpret_cast<uint64_t*>(take(n * kMaskWords * 8));
-    a.sym = reinterpret_cast<uint64_t*>(take(n * kMaskWords * 8));
-    a.mst = reinterpret_cast<uint64_t*>(take(n * kMaskWords * 8));
-    a.perm = reinterpret_cast<uint16_t*>(take(n * kTile * sizeof(uint16_t)));
-    a.link_stat = reinterpret_cast<uint32_t*>(take(n * sizeof(uint32_t)));
-    a.tickets = reinterpret_cast<uint32_t*>(take(kTicketBytes));
-    a.sorted = reinterpret_cast<uint32_t*>(take(n * kSortedStride * sizeof(uint32_t)));
-    a.dense_list = reinterpret_cast<uint32_t*>(take(n * sizeof(uint32_t)));
-    a.sparse_list = reinterpret_cast<uint32_t*>(take(n * sizeof(uint32_t)));
-    a.cu_count = c->cu_count;
-    a.info = reinterpret_cast<ChunkInfo*>(take(n * sizeof(ChunkInfo)));
-    a.blocks = reinterpret_cast<BlockInfo*>(take(n * kMaxBlocks * sizeof(BlockInfo)));
-    a.plans = reinterpret_cast<BlockOut*>(take(n * kMaxBlocks * sizeof(BlockOut)));
+int Buffer::reserve(zwz_ctx* c, size_t want_count, size_t want_bytes) {
+    if (want_count <= count && want_bytes <= bytes) return ZWZ_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    release();
+    const hipError_t e = pinned ? hipHostMalloc(&p, want_bytes, hipHostMallocDefault) : hipMalloc(&p, want_bytes);
+    if (e != hipSuccess) { p = nullptr; return hip_fail(e, pinned ? "pinned buffer allocation" : "device buffer allocation"); }
+    bytes = want_bytes; count = want_count;
+    return ZWZ_OK;
+}
+
+void Buffer::release() {
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr; bytes = 0; count = 0;
+}
+
+int ensure_inf_order(zwz_ctx* c, uint32_t n) { return c->buf[kBufInfOrder].reserve(c, n, (size_t)n * sizeof(uint4)); }
+
+int ensure_crc_tables(zwz_ctx* c) {
+    Buffer& b = c->buf[kBufCrcTables];
+    if (b.p) return ZWZ_OK;
+    if (int rc = b.reserve(c, 1, sizeof(CrcTables))) return rc;
+    HIPCHK(launch_crc_tables(b.as<CrcTables>(), c->stream));
+    return ZWZ_OK;
+}
+
+// The deflate workspace for n chunks
+static void workspace_layout(Carver& w, size_t n, DeflateArgs& a) {
+    a.entries = w.take<uint2>(n * kEntryStride);
+    a.links = w.take<uint16_t>(n * kLinkStride);
+    a.has128 = w.take<uint64_t>(n * kMaskWords);
+    a.sym = w.take<uint64_t>(n * kMaskWords);
+    a.mst = w.take<uint64_t>(n * kMaskWords);
+    a.perm = w.take<uint16_t>(n * kTile);
+    a.link_stat = w.take<uint32_t>(n);
+    a.tickets = w.take<uint32_t>(kTicketBytes / sizeof(uint32_t));
+    a.sorted = w.take<uint32_t>(n * kSortedStride);
+    a.dense_list = w.take<uint32_t>(n);
+    a.sparse_list = w.take<uint32_t>(n);
+    a.info = w.take<ChunkInfo>(n);
+    a.blocks = w.take<BlockInfo>(n * kMaxBlocks);
+    a.plans = w.take<BlockOut>(n * kMaxBlocks);
     static_assert(kMaxBlocks * sizeof(BlockProbe) <= kLinkStride * sizeof(uint16_t), "probes alias the link array");
     a.probes = reinterpret_cast<BlockProbe*>(a.links);
 }
 
+int ensure_workspace(zwz_ctx* c, uint32_t chunks) {
+    DeflateArgs a;
+    return c->buf[kBufWorkspace].reserve(c, chunks, layout_bytes([&](Carver& w) { workspace_layout(w, chunks, a); }));
+}
+
+void carve_workspace(zwz_ctx* c, DeflateArgs& a) {
+    Carver w(c->buf[kBufWorkspace].p);
+    workspace_layout(w, c->buf[kBufWorkspace].count, a);
+    a.cu_count = c->cu_count;
+}
+
+static void stage_layout(Carver& w, size_t cap, size_t first, uint8_t*& in, uint8_t*& out, uint64_t*& off, uint32_t*& len, uint32_t*& olen, uint32_t*& st) {
+    in = w.take<uint8_t>(cap * ZWZ_DEV_STRIDE) + first * ZWZ_DEV_STRIDE;
+    out = w.take<uint8_t>(cap * ZWZ_DEV_STRIDE) + first * ZWZ_DEV_STRIDE;
+    off = w.take<uint64_t>(cap) + first;
+    len = w.take<uint32_t>(cap) + first; olen = w.take<uint32_t>(cap) + first; st = w.take<uint32_t>(cap) + first;
+}
+
+StageView stage_view(zwz_ctx* c, uint32_t first) {
+    StageView v;
+    Carver h(c->buf[kBufStageHost].p), d(c->buf[kBufStageDev].p);
+    stage_layout(h, c->buf[kBufStageHost].count, first, v.h_in, v.h_out, v.h_off, v.h_len, v.h_olen, v.h_status);
+    stage_layout(d, c->buf[kBufStageDev].count, first, v.d_in, v.d_out, v.d_off, v.d_len, v.d_olen, v.d_status);
+    return v;
+}
+
 int ensure_staging(zwz_ctx* c, uint32_t m) {
-    if (m <= c->stage_chunks) return ZWZ_OK;
-    if (c->d_stage) { (void)hipFree(c->d_stage); c->d_stage = nullptr; }
-    if (c->h_stage) { (void)hipHostFree(c->h_stage); c->h_stage = nullptr; }
-    c->stage_chunks = 0;
-    const size_t bytes = stage_bytes(m);
-    hipError_t e = hipMalloc(&c->d_stage, bytes);
-    if (e == hipSuccess) e = hipHostMalloc(&c->h_stage, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) return hip_fail(e, "staging allocation");
-    c->stage_chunks = m;
-    return ZWZ_OK;
+    StageView v;
+    const size_t bytes = layout_bytes([&](Carver& w) { stage_layout(w, m, 0, v.d_in, v.d_out, v.d_off, v.d_len, v.d_olen, v.d_status); });
+    if (int rc = c->buf[kBufStageDev].reserve(c, m, bytes)) return rc;
+    return c->buf[kBufStageHost].reserve(c, m, bytes);
 }
 
 }  // namespace zwz

@@ -6,20 +6,44 @@
 #include "split_core.h"
 #include "zwz_kernels.h"
 
+namespace zwz {
+
+// A grow-only allocation of the context, in device memory or pinned on the host.  `count` is the number of elements (chunks, members,
+// pieces, streams) the arrays in it were laid out for: a layout is always carved by that capacity, never by the current call's size.
+struct Buffer {
+    void* p = nullptr;
+    size_t bytes = 0, count = 0;
+    bool pinned = false;
+    // Returns at once if `count` elements and `bytes` bytes are reserved already.  Otherwise waits for the context's stream (queued
+    // work may still use the old allocation), frees it and allocates anew; on failure everything is left at zero.
+    int reserve(zwz_ctx* c, size_t count, size_t bytes);
+    void release();
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+enum BufId {
+    kBufWorkspace,       // deflate: carve_workspace's arrays, per chunk
+    kBufInfOrder,        // inflate's launch order ((offset, length, chunk) by payload length), a uint4 per chunk, stream or segment
+    kBufStreamRec,       // zwz_inflate_streams_dev: a StreamRecord per stream
+    kBufStageDev,        // staging of the host-buffer entry points and the directory pipeline (stage_view), and its pinned twin
+    kBufCrcTables,       // built on first use (ensure_crc_tables)
+    kBufBgzf,            // BGZF (zwz_bgzf.cpp): slots and per-member arrays
+    kBufRangeDev,        // range reads: the packed plan of one call, and its pinned twin
+    kBufPieces,          // stream deflate (zwz_dstream.cpp): slots and per-piece arrays
+    kBufStreamsDev,      // stream deflate: the per-stream arrays of one call, and their pinned twin
+    kBufSplit0, kBufSplit1, kBufSplit2,      // split inflate (zwz_split.cpp): per stream and scan tile / per candidate / per chain segment and checksum piece
+    kNumDeviceBufs,
+    kBufStageHost = kNumDeviceBufs, kBufRangeHost, kBufStreamsHost,
+    kBufSplitHost,       // split inflate: the per-stream arrays a call uploads (read by copies that may still be queued when it returns)
+    kNumBufs
+};
+
+}  // namespace zwz
+
 struct zwz_ctx {
     int device = 0;
     uint32_t max_batch = 0;
     hipStream_t stream = nullptr;
-    void* workspace = nullptr;
-    uint32_t ws_chunks = 0;          // chunks the workspace is currently sized for
-    uint4* inf_order = nullptr;      // inflate's launch order ((offset, length, chunk) by payload length), grown to the largest batch seen
-    uint32_t inf_order_cap = 0;
-    uint4* stream_rec = nullptr;     // zwz_inflate_streams_dev: a StreamRecord per stream, grown to the largest batch seen
-    uint32_t stream_rec_cap = 0;
-    // staging for the host-buffer entry points and the directory pipeline
-    void* d_stage = nullptr;
-    void* h_stage = nullptr;
-    uint32_t stage_chunks = 0;
     uint32_t cu_count = 0;
     uint32_t chunk_bytes = 0;        // raw bytes per Chunk for zwz_compress_dir; 0 = default (see chunk_bytes_for)
     // Switches (zwz_ctx_set_option; defaults from ZWZ_MATCH / ZWZ_PLAN / ZWZ_INFLATE_HEADER read ONCE at zwz_ctx_create, or forced by a
@@ -33,30 +57,13 @@ struct zwz_ctx {
     hipEvent_t ev[zwz::kNumDeflateStages + 1] = {};
     hipEvent_t ev_inf[2] = {};
     float stage_ms[ZWZ_NUM_STAGES] = {};
-    // BGZF (zwz_bgzf.cpp): slots and per-member arrays for bgzf_cap members, grown lazily; the CRC tables, built once
-    void* bgzf_ws = nullptr;
-    uint32_t bgzf_cap = 0;
-    void* crc_tables = nullptr;
-    // range reads (zwz_bgzf_read_ranges_*): the plan of one call, pinned on the host and its device copy, grown to the largest call
-    void* rr_host = nullptr;
-    void* rr_dev = nullptr;
-    size_t rr_cap = 0;
-    // stream deflate (zwz_dstream.cpp): slots and per-piece arrays for ds_cap pieces; the per-stream arrays of one call for ds_streams
-    // streams, pinned on the host and on the device; ds_copied: the last call's copy out of the pinned arrays has run
-    void* ds_ws = nullptr;
-    uint32_t ds_cap = 0;
-    void* ds_host = nullptr;
-    void* ds_dev = nullptr;
-    uint32_t ds_streams = 0;
-    hipEvent_t ds_copied = nullptr;
-    // split inflate (zwz_split.cpp): options "split_min_bytes", "split_budget", "split_max_candidates" (split_core.h's defaults); device
-    // workspaces of one call, grown to the largest seen: per stream and scan tile / per candidate / per chain segment and checksum piece
+    hipEvent_t ds_copied = nullptr;  // stream deflate: the last call's copy out of the pinned per-stream arrays (kBufStreamsHost) has run
+    // split inflate (zwz_split.cpp): options "split_min_bytes", "split_budget", "split_max_candidates" (split_core.h's defaults)
     uint32_t split_min_bytes = zwz::kSplitMinBytes, split_budget = zwz::kSplitBudget, split_max_candidates = zwz::kSplitMaxCandidates;
     uint32_t split_slice_bytes = zwz::kSplitSliceBytes;      // zwz_inflate_stream_file: "split_slice_bytes"
-    void* split_ws[3] = {};
-    size_t split_ws_cap[3] = {};
-    void* split_host = nullptr;      // pinned: the per-stream arrays a call uploads (read by copies that may still be queued when it returns)
-    size_t split_host_cap = 0;
+    // Every allocation that outlives a call: grown lazily to the largest call seen (Buffer::reserve), released by zwz_ctx_destroy
+    zwz::Buffer buf[zwz::kNumBufs];
+    zwz_ctx() { for (int i = zwz::kNumDeviceBufs; i < zwz::kNumBufs; i++) buf[i].pinned = true; }
 };
 
 namespace zwz {
@@ -65,8 +72,34 @@ enum : uint32_t { kForbidLinks = 1u, kForbidSort = 2u, kForbidPlanWave = 4u, kFo
 
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
+int ensure_workspace(zwz_ctx* c, uint32_t chunks);
 void carve_workspace(zwz_ctx* c, DeflateArgs& a);
 int ensure_staging(zwz_ctx* c, uint32_t chunks);
+int ensure_inf_order(zwz_ctx* c, uint32_t n);
+int ensure_crc_tables(zwz_ctx* c);            // builds the tables on first use, on the context's stream
+
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
+
+inline size_t round_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }   // a: a power of two
+
+// little-endian fields of a host buffer (le32_at / be32_at: stream_core.h)
+inline uint32_t le16_at(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+inline uint64_t le64_at(const uint8_t* p) { return (uint64_t)le32_at(p) | (uint64_t)le32_at(p + 4) << 32; }
+
+// Lays arrays out one after the other from `base`, each at a multiple of 256 bytes.  Every workspace has ONE layout function that
+// takes a Carver: run over base 0 it gives the bytes to reserve (layout_bytes), run over the buffer it gives the pointers, so the two
+// cannot disagree.  Offsets are integers: nothing is added to a null pointer.
+struct Carver {
+    uintptr_t base;
+    size_t used = 0;
+    explicit Carver(const void* p) : base(reinterpret_cast<uintptr_t>(p)) {}
+    template <class T> T* take(size_t count, size_t slack = 0) {
+        T* r = reinterpret_cast<T*>(base + used);
+        used += round_up(count * sizeof(T) + slack, 256);
+        return r;
+    }
+};
+template <class F> size_t layout_bytes(F&& layout) { Carver w(nullptr); layout(w); return w.used; }
 
 // One staging slice: input slots, output slots, offsets/lengths/status; same layout on host and device.
 struct StageView {
@@ -74,21 +107,7 @@ struct StageView {
     uint8_t *d_in, *d_out; uint64_t* d_off; uint32_t *d_len, *d_olen, *d_status;
 };
 
-inline size_t stage_bytes(uint32_t m) {
-    return 2 * (size_t)m * ZWZ_DEV_STRIDE + (size_t)m * (sizeof(uint64_t) + 3 * sizeof(uint32_t)) + 1024;
-}
-
-inline StageView stage_view(zwz_ctx* c, uint32_t /*m*/) {
-    const size_t cap = c->stage_chunks;
-    StageView v;
-    auto carve = [&](uint8_t* base, uint8_t*& in, uint8_t*& out, uint64_t*& off, uint32_t*& len, uint32_t*& olen, uint32_t*& st) {
-        in = base; out = in + cap * ZWZ_DEV_STRIDE;
-        off = reinterpret_cast<uint64_t*>(out + cap * ZWZ_DEV_STRIDE);
-        len = reinterpret_cast<uint32_t*>(off + cap); olen = len + cap; st = olen + cap;
-    };
-    carve(static_cast<uint8_t*>(c->h_stage), v.h_in, v.h_out, v.h_off, v.h_len, v.h_olen, v.h_status);
-    carve(static_cast<uint8_t*>(c->d_stage), v.d_in, v.d_out, v.d_off, v.d_len, v.d_olen, v.d_status);
-    return v;
-}
+// The staging arrays from chunk `first` on (the buffers are laid out for kBufStageDev's count)
+StageView stage_view(zwz_ctx* c, uint32_t first);
 
 }  // namespace zwz

@@ -20,15 +20,10 @@
 
 using namespace zwz;
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
-
 namespace {
 
 constexpr uint64_t kMemberMax = (uint64_t)ZWZ_CHUNK_SIZE + kBgzfHeader + kBgzfTrailer - 6u;   // the deflate slot's bytes, reframed
 constexpr uint32_t kFileSliceBlocks = 256;          // members per slice of the file functions: 16.7 MB of raw bytes
-
-inline uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
-inline uint32_t le32(const uint8_t* p) { return le16(p) | le16(p + 2) << 16; }
 
 // Walks the members of gz[0, n).  Strict (partial = false): anything that is not a whole member is ZWZ_E_FORMAT.  partial: stops
 // (ZWZ_OK) before a member that does not end inside the buffer -- the file reader's slice boundary.  Also stops after `limit` members.
@@ -53,21 +48,21 @@ int bgzf_walk_each(const uint8_t* gz, uint64_t n, uint64_t at, uint64_t k0, bool
         const uint32_t flg = m[3];
         if (!(flg & 4u)) return fail("no extra field: a plain gzip member, not BGZF", ~0ull);
         if (flg & ~5u) return fail("unsupported gzip header flags", flg);
-        const uint32_t xlen = le16(m + 10);
+        const uint32_t xlen = le16_at(m + 10);
         if (avail < 12ull + xlen) { if (partial) break; return fail("extra field runs past the end of the input", ~0ull); }
         uint32_t bsize = 0;
         for (uint32_t x = 0; x < xlen;) {
             if (xlen - x < 4) return fail("malformed extra field", ~0ull);
             const uint8_t* f = m + 12 + x;
-            const uint32_t slen = le16(f + 2);
+            const uint32_t slen = le16_at(f + 2);
             if (4u + slen > xlen - x) return fail("malformed extra field", ~0ull);
-            if (f[0] == 'B' && f[1] == 'C' && slen == 2) bsize = le16(f + 4) + 1u;
+            if (f[0] == 'B' && f[1] == 'C' && slen == 2) bsize = le16_at(f + 4) + 1u;
             x += 4 + slen;
         }
         if (!bsize) return fail("no BC subfield: not BGZF", ~0ull);
         if (bsize < 12u + xlen + kBgzfTrailer) return fail("BSIZE smaller than its header and trailer:", bsize);
         if (bsize > avail) { if (partial) break; return fail("BSIZE runs past the end of the input:", bsize); }
-        const uint32_t isize = le32(m + bsize - 4);
+        const uint32_t isize = le32_at(m + bsize - 4);
         if (isize > kBgzfMaxIsize) return fail("ISIZE above 65535:", isize);
         on_member(k, o, isize);
         total += isize;
@@ -91,35 +86,24 @@ struct BgzfView {
     uint32_t *len, *olen, *st, *crc, *isize, *err;
 };
 
-size_t bgzf_bytes(uint32_t m) { return 2 * (size_t)m * kBgzfSlot + (size_t)m * (2 * 8 + 5 * 4) + 4096; }
-
-BgzfView bgzf_view(zwz_ctx* c) {
-    const size_t m = c->bgzf_cap;
-    uint8_t* p = static_cast<uint8_t*>(c->bgzf_ws);
-    auto take = [&](size_t bytes) { uint8_t* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+BgzfView bgzf_layout(Carver& w, size_t m) {
     BgzfView v;
-    v.slots_a = take(m * kBgzfSlot);
-    v.slots_b = take(m * kBgzfSlot + 256);            // (wg_copy reads up to 3 bytes past a decoded block)
-    v.off = reinterpret_cast<uint64_t*>(take(m * 8)); v.moff = reinterpret_cast<uint64_t*>(take(m * 8));
-    v.len = reinterpret_cast<uint32_t*>(take(m * 4)); v.olen = reinterpret_cast<uint32_t*>(take(m * 4));
-    v.st = reinterpret_cast<uint32_t*>(take(m * 4)); v.crc = reinterpret_cast<uint32_t*>(take(m * 4));
-    v.isize = reinterpret_cast<uint32_t*>(take(m * 4));
-    v.base = reinterpret_cast<uint64_t*>(take(16)); v.err = reinterpret_cast<uint32_t*>(v.base + 1);
+    v.slots_a = w.take<uint8_t>(m * kBgzfSlot);
+    v.slots_b = w.take<uint8_t>(m * kBgzfSlot, 256);  // (wg_copy reads up to 3 bytes past a decoded block)
+    v.off = w.take<uint64_t>(m); v.moff = w.take<uint64_t>(m);
+    v.len = w.take<uint32_t>(m); v.olen = w.take<uint32_t>(m); v.st = w.take<uint32_t>(m); v.crc = w.take<uint32_t>(m); v.isize = w.take<uint32_t>(m);
+    v.base = w.take<uint64_t>(2); v.err = reinterpret_cast<uint32_t*>(v.base + 1);
     return v;
 }
 
+BgzfView bgzf_view(zwz_ctx* c) {
+    Carver w(c->buf[kBufBgzf].p);
+    return bgzf_layout(w, c->buf[kBufBgzf].count);
+}
+
 int ensure_bgzf(zwz_ctx* c, uint32_t m) {
-    if (!c->crc_tables) {
-        HIPCHK(hipMalloc(&c->crc_tables, sizeof(CrcTables)));
-        HIPCHK(launch_crc_tables(static_cast<CrcTables*>(c->crc_tables), c->stream));
-    }
-    if (m > c->bgzf_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->bgzf_ws) { (void)hipFree(c->bgzf_ws); c->bgzf_ws = nullptr; c->bgzf_cap = 0; }
-        HIPCHK(hipMalloc(&c->bgzf_ws, bgzf_bytes(m)));
-        c->bgzf_cap = m;
-    }
-    return ZWZ_OK;
+    if (int rc = ensure_crc_tables(c)) return rc;
+    return c->buf[kBufBgzf].reserve(c, m, layout_bytes([&](Carver& w) { bgzf_layout(w, m); }));
 }
 
 // The device part of compression, d_out_len = total bytes written (with or without the EOF member).  Arguments checked by the caller.
@@ -128,7 +112,7 @@ int compress_launch(zwz_ctx* c, const uint8_t* d_in, uint64_t n, uint8_t* d_out,
     const uint32_t M = (uint32_t)(nblocks < c->max_batch ? (nblocks ? nblocks : 1) : c->max_batch);
     if (int rc = ensure_bgzf(c, M)) return rc;
     const BgzfView v = bgzf_view(c);
-    const CrcTables* tab = static_cast<const CrcTables*>(c->crc_tables);
+    const CrcTables* tab = c->buf[kBufCrcTables].as<const CrcTables>();
     HIPCHK(hipMemsetAsync(v.base, 0, 16, c->stream));
     for (uint64_t first = 0; first < nblocks; first += M) {
         const uint32_t m = (uint32_t)(nblocks - first < M ? nblocks - first : M);
@@ -147,7 +131,7 @@ int decompress_launch(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, const ui
     const uint32_t M = n < c->max_batch ? (n ? n : 1u) : c->max_batch;
     if (int rc = ensure_bgzf(c, M)) return rc;
     const BgzfView v = bgzf_view(c);
-    const CrcTables* tab = static_cast<const CrcTables*>(c->crc_tables);
+    const CrcTables* tab = c->buf[kBufCrcTables].as<const CrcTables>();
     HIPCHK(hipMemsetAsync(v.base, 0, 16, c->stream));
     for (uint32_t first = 0; first < n; first += M) {
         const uint32_t m = n - first < M ? n - first : M;
@@ -188,7 +172,6 @@ int check_status(const uint32_t* st, uint32_t n, const uint64_t* offs, uint64_t 
 constexpr size_t kWalkBuf = 4u << 20;               // bytes of file a streamed walk holds (a member is at most 65 536 bytes)
 constexpr size_t kRangeOutSlice = 16u << 20;        // decoded bytes of one slice of the file range reader (>= one member)
 
-inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | (uint64_t)le32(p + 4) << 32; }
 inline void put64(uint8_t* p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (8 * i)); }
 
 // The writer's rule: one entry (compressed offset, decoded offset) per member after the first, in file order, except a last member
@@ -242,7 +225,7 @@ struct GziIndex { std::vector<uint64_t> coff, uoff; };
 
 int parse_gzi(const uint8_t* g, uint64_t n, GziIndex* ix) {
     if (n < 8 || !g) { set_error("gzi: %llu bytes, shorter than its 8-byte entry count", (unsigned long long)n); return ZWZ_E_FORMAT; }
-    const uint64_t count = le64(g);
+    const uint64_t count = le64_at(g);
     if ((n - 8) % 16 || (n - 8) / 16 != count) {
         set_error("gzi: %llu bytes do not hold the %llu entries its count gives", (unsigned long long)n, (unsigned long long)count);
         return ZWZ_E_FORMAT;
@@ -252,7 +235,7 @@ int parse_gzi(const uint8_t* g, uint64_t n, GziIndex* ix) {
     ix->coff.reserve(count + 1);
     ix->uoff.reserve(count + 1);
     for (uint64_t i = 0; i < count; i++) {
-        const uint64_t c = le64(g + 8 + 16 * i), u = le64(g + 16 + 16 * i);
+        const uint64_t c = le64_at(g + 8 + 16 * i), u = le64_at(g + 16 + 16 * i);
         if (c <= ix->coff.back()) {
             set_error("gzi: entry %llu: compressed offset %llu does not follow %llu", (unsigned long long)(i + 1), (unsigned long long)c,
                       (unsigned long long)ix->coff.back());
@@ -347,30 +330,23 @@ int plan_ranges(const GziIndex& ix, const uint64_t* ranges, uint32_t k, RangePla
 // One slice of a plan: touched members [t0, t1) and pieces [p0, p1) of theirs (all of them, or a part of one member's).
 struct Slice { uint32_t t0, t1, p0, p1; };
 
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 // moff, mend (u64); expect, nlong, status, bad, row (u32; row has m + 1); pieces
-inline size_t slice_bytes(uint32_t m, uint32_t np) { return align16(16 * (size_t)m + 20 * (size_t)m + 4) + 16 * (size_t)np; }
+inline size_t slice_bytes(uint32_t m, uint32_t np) { return round_up(16 * (size_t)m + 20 * (size_t)m + 4, 16) + 16 * (size_t)np; }
 
 struct SliceView { uint64_t *moff, *mend; uint32_t *expect, *nlong, *status, *bad, *row; RangePiece* piece; };
 SliceView slice_view(uint8_t* p, uint32_t m) {
     SliceView v;
     v.moff = reinterpret_cast<uint64_t*>(p); v.mend = v.moff + m;
     v.expect = reinterpret_cast<uint32_t*>(v.mend + m); v.nlong = v.expect + m; v.status = v.nlong + m; v.bad = v.status + m; v.row = v.bad + m;
-    v.piece = reinterpret_cast<RangePiece*>(p + align16(36 * (size_t)m + 4));
+    v.piece = reinterpret_cast<RangePiece*>(p + round_up(36 * (size_t)m + 4, 16));
     return v;
 }
 
+// (whole MiB: the file reader asks per slice, and must not reallocate for every slice a little larger than the last)
 int ensure_rr(zwz_ctx* c, size_t bytes) {
-    if (bytes <= c->rr_cap) return ZWZ_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->rr_dev) { (void)hipFree(c->rr_dev); c->rr_dev = nullptr; }
-    if (c->rr_host) { (void)hipHostFree(c->rr_host); c->rr_host = nullptr; }
-    c->rr_cap = 0;
-    const size_t cap = (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);
-    HIPCHK(hipHostMalloc(&c->rr_host, cap, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&c->rr_dev, cap));
-    c->rr_cap = cap;
-    return ZWZ_OK;
+    const size_t cap = round_up(bytes, (size_t)1 << 20);
+    if (int rc = c->buf[kBufRangeHost].reserve(c, 0, cap)) return rc;
+    return c->buf[kBufRangeDev].reserve(c, 0, cap);
 }
 
 // Packs slice S at h (pinned; its device copy at d) and queues it: one upload, bgzf_gather_list, inflate, bgzf_verify_extract, and the
@@ -395,7 +371,7 @@ int queue_slice(zwz_ctx* c, const RangePlan& P, const Slice& S, const uint64_t* 
         if (compact) { hv.piece[p].dst = o; o += hv.piece[p].len; }
     }
     const BgzfView v = bgzf_view(c);
-    const CrcTables* tab = static_cast<const CrcTables*>(c->crc_tables);
+    const CrcTables* tab = c->buf[kBufCrcTables].as<const CrcTables>();
     HIPCHK(hipMemcpyAsync(d, h, slice_bytes(m, np), hipMemcpyHostToDevice, c->stream));
     HIPCHK(launch_bgzf_gather_list(d_gz, gz_len, dv.moff, dv.mend, m, v.slots_a, v.off, v.len, v.crc, v.isize, dv.status, c->stream));
     if (int rc = zwz_inflate_batch_dev(c, v.slots_a, v.off, v.len, m, v.slots_b, kBgzfSlot, v.olen, v.st)) return rc;
@@ -440,18 +416,6 @@ int read_file_bytes(const char* path, std::vector<uint8_t>* out) {
     return ZWZ_OK;
 }
 
-// Buffers of one file range read, released whatever the outcome.
-struct RangeFileJob {
-    int fd = -1;
-    void* h[2] = {};                 // pinned: packed members, decoded pieces
-    void* d[2] = {};
-    ~RangeFileJob() {
-        for (void* p : h) if (p) (void)hipHostFree(p);
-        for (void* p : d) if (p) (void)hipFree(p);
-        if (fd >= 0) close(fd);
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -484,9 +448,7 @@ int zwz_bgzf_decompress_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, co
     return decompress_launch(c, d_gz, gz_len, d_member_off, n_members, d_out, d_out_len, d_status);
 }
 
-// Slice s: its input was read into hin[s & 1] while slice s - 1 ran; it runs while slice s + 1 is read into the other buffer and
-// slice s - 1's output is written from hout[(s - 1) & 1].  Every wait is a join of a thread that only does file I/O, or a stream
-// synchronisation that returns on a HIP error: no wait depends on another thread reaching a point.
+// run_slices' loop (zwz_filejob.h) over slices of whole blocks: the members of a slice, and the EOF member behind the last.
 int zwz_bgzf_compress_file(zwz_ctx* c, const char* src, const char* dst) {
     if (!c || !src || !dst) return ZWZ_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
@@ -494,36 +456,18 @@ int zwz_bgzf_compress_file(zwz_ctx* c, const char* src, const char* dst) {
     if (int rc = job.open(src, dst)) return rc;
     const uint32_t blocks = c->max_batch < kFileSliceBlocks ? c->max_batch : kFileSliceBlocks;
     const size_t S = (size_t)blocks * kBgzfBlock, O = zwz_bgzf_bound(S);
-    for (int i = 0; i < 2; i++) HIPCHK(hipHostMalloc(&job.h[i], S + 16, hipHostMallocDefault));
-    for (int i = 2; i < 4; i++) HIPCHK(hipHostMalloc(&job.h[i], O, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&job.h[4], 64, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&job.d[0], S + 16));
-    HIPCHK(hipMalloc(&job.d[1], O));
-    HIPCHK(hipMalloc(&job.d[2], 64));
-    uint8_t* d_in = static_cast<uint8_t*>(job.d[0]); uint8_t* d_out = static_cast<uint8_t*>(job.d[1]);
-    uint64_t* d_len = static_cast<uint64_t*>(job.d[2]); uint64_t* h_len = static_cast<uint64_t*>(job.h[4]);
-    size_t n = 0;
-    job.start_read(static_cast<uint8_t*>(job.h[0]), S);
-    if (int rc = job.finish_read(&n)) return rc;
-    for (int b = 0; n; b ^= 1) {
-        uint8_t* hin = static_cast<uint8_t*>(job.h[b]);
-        uint8_t* hout = static_cast<uint8_t*>(job.h[2 + b]);
-        HIPJOB(hipMemcpyAsync(d_in, hin, n, hipMemcpyHostToDevice, c->stream));
-        if (int rc = compress_launch(c, d_in, n, d_out, d_len, 0)) { job.join(); return rc; }
-        HIPJOB(hipMemcpyAsync(h_len, d_len, 8, hipMemcpyDeviceToHost, c->stream));
-        if (n == S) job.start_read(static_cast<uint8_t*>(job.h[b ^ 1]), S);     // (a short slice is the last one)
-        HIPJOB(hipStreamSynchronize(c->stream));
-        const uint64_t len = *h_len;
-        if (len > O) { job.join(); set_error("bgzf: a member body reached the deflate slot's length"); return ZWZ_E_FORMAT; }
-        HIPJOB(hipMemcpyAsync(hout, d_out, len, hipMemcpyDeviceToHost, c->stream));
-        HIPJOB(hipStreamSynchronize(c->stream));
-        if (int rc = job.finish_write()) { job.join(); return rc; }
-        job.start_write(hout, len);
-        size_t next = 0;
-        if (n == S) { if (int rc = job.finish_read(&next)) { job.join(); return rc; } }
-        n = next;
-    }
-    if (int rc = job.finish_write()) return rc;
+    if (int rc = job.alloc({S + 16, S + 16, O, O, 64}, {S + 16, O, 64})) return rc;
+    const int rc = run_slices(c, job, S,
+        [&](size_t n, SliceResult* d_res, SliceResult* h_res) {
+            if (int rc = compress_launch(c, job.dp(0), n, job.dp(1), &d_res->out_len, 0)) return rc;
+            HIPCHK(hipMemcpyAsync(&h_res->out_len, &d_res->out_len, 8, hipMemcpyDeviceToHost, c->stream));
+            return (int)ZWZ_OK;
+        },
+        [&](size_t, const SliceResult& r) {
+            if (r.out_len > O) { set_error("bgzf: a member body reached the deflate slot's length"); return (int)ZWZ_E_FORMAT; }
+            return (int)ZWZ_OK;
+        });
+    if (rc) return rc;
     if (fwrite(kBgzfEof, 1, kBgzfEofBytes, job.out) != kBgzfEofBytes) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
     return job.commit(dst);
 }
@@ -537,12 +481,8 @@ int zwz_bgzf_decompress_file(zwz_ctx* c, const char* src, const char* dst) {
     if (int rc = job.open(src, dst)) return rc;
     const uint32_t blocks = c->max_batch < kFileSliceBlocks ? c->max_batch : kFileSliceBlocks;
     const size_t B = (size_t)blocks * kBgzfSlot, R = (size_t)blocks * kBgzfMaxIsize;   // a member is at most 65536 bytes
-    for (int i = 0; i < 2; i++) HIPCHK(hipHostMalloc(&job.h[i], B, hipHostMallocDefault));
-    for (int i = 2; i < 4; i++) HIPCHK(hipHostMalloc(&job.h[i], R + 16, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&job.h[4], (size_t)blocks * (8 + 4) + 64, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&job.d[0], B + 16));
-    HIPCHK(hipMalloc(&job.d[1], R + 16));
-    HIPCHK(hipMalloc(&job.d[2], (size_t)blocks * (8 + 4) + 64));
+    const size_t small = (size_t)blocks * (8 + 4) + 64;
+    if (int rc = job.alloc({B, B, R + 16, R + 16, small}, {B + 16, R + 16, small})) return rc;
     uint8_t* d_gz = static_cast<uint8_t*>(job.d[0]); uint8_t* d_out = static_cast<uint8_t*>(job.d[1]);
     uint64_t* d_len = static_cast<uint64_t*>(job.d[2]); uint64_t* d_moff = d_len + 1; uint32_t* d_st = reinterpret_cast<uint32_t*>(d_moff + blocks);
     uint64_t* h_moff = static_cast<uint64_t*>(job.h[4]); uint32_t* h_st = reinterpret_cast<uint32_t*>(h_moff + blocks);
@@ -644,13 +584,13 @@ int zwz_bgzf_read_ranges_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, c
         const uint32_t t1 = T - t0 < M ? T : t0 + M;
         slices.push_back({t0, t1, P.row[t0], P.row[t1]});
         at.push_back(bytes);
-        bytes += align16(slice_bytes(t1 - t0, P.row[t1] - P.row[t0]));
+        bytes += round_up(slice_bytes(t1 - t0, P.row[t1] - P.row[t0]), 16);
     }
     if (int rc = ensure_rr(c, bytes)) return rc;
     std::vector<uint64_t> moff(T);
     for (uint32_t t = 0; t < T; t++) moff[t] = ix.coff[P.member[t]];
-    uint8_t* h = static_cast<uint8_t*>(c->rr_host);
-    uint8_t* d = static_cast<uint8_t*>(c->rr_dev);
+    uint8_t* h = c->buf[kBufRangeHost].as<uint8_t>();
+    uint8_t* d = c->buf[kBufRangeDev].as<uint8_t>();
     for (size_t s = 0; s < slices.size(); s++)
         if (int rc = queue_slice(c, P, slices[s], moff.data(), nullptr, h + at[s], d + at[s], d_gz, gz_len, d_out, false)) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -687,7 +627,7 @@ int zwz_bgzf_read_ranges_file(zwz_ctx* c, const char* src, const char* gzi_path,
     const uint32_t T = (uint32_t)P.member.size();
     if (!T) return ZWZ_OK;
     HIPCHK(hipSetDevice(c->device));
-    RangeFileJob job;
+    FileJob job;
     job.fd = open(src, O_RDONLY);
     if (job.fd < 0) { set_error("cannot open %s", src); return ZWZ_E_IO; }
     struct stat stt {};
@@ -705,10 +645,7 @@ int zwz_bgzf_read_ranges_file(zwz_ctx* c, const char* src, const char* gzi_path,
     }
     const uint32_t S = c->max_batch < kFileSliceBlocks ? c->max_batch : kFileSliceBlocks;
     const size_t B = (size_t)S * kBgzfSlot;
-    HIPCHK(hipHostMalloc(&job.h[0], B + 16, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&job.h[1], kRangeOutSlice + 16, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&job.d[0], B + 16));
-    HIPCHK(hipMalloc(&job.d[1], kRangeOutSlice + 16));
+    if (int rc = job.alloc({B + 16, kRangeOutSlice + 16}, {B + 16, kRangeOutSlice + 16})) return rc;    // packed members, decoded pieces
     if (int rc = ensure_bgzf(c, S)) return rc;
     uint8_t* hin = static_cast<uint8_t*>(job.h[0]);
     uint8_t* hout = static_cast<uint8_t*>(job.h[1]);
@@ -757,12 +694,12 @@ int zwz_bgzf_read_ranges_file(zwz_ctx* c, const char* src, const char* gzi_path,
         const uint32_t m = sl.t1 - sl.t0, np = sl.p1 - sl.p0;
         if (int rc = ensure_rr(c, slice_bytes(m, np))) return rc;
         HIPCHK(hipMemcpyAsync(d_in, hin, packed, hipMemcpyHostToDevice, c->stream));
-        if (int rc = queue_slice(c, P, sl, moff.data(), mend.data(), static_cast<uint8_t*>(c->rr_host), static_cast<uint8_t*>(c->rr_dev), d_in, packed,
+        if (int rc = queue_slice(c, P, sl, moff.data(), mend.data(), c->buf[kBufRangeHost].as<uint8_t>(), c->buf[kBufRangeDev].as<uint8_t>(), d_in, packed,
                                  d_dec, true))
             return rc;
         if (obytes) HIPCHK(hipMemcpyAsync(hout, d_dec, obytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (int rc = slice_verdict(P, ix, sl, static_cast<const uint8_t*>(c->rr_host), ranges)) return rc;
+        if (int rc = slice_verdict(P, ix, sl, c->buf[kBufRangeHost].as<const uint8_t>(), ranges)) return rc;
         uint64_t o = 0;
         for (uint32_t q = sl.p0; q < sl.p1; q++) { memcpy(out + P.piece[q].dst, hout + o, P.piece[q].len); o += P.piece[q].len; }
         p = sl.p1;

@@ -14,27 +14,24 @@
 
 using namespace zwz;
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
-
 namespace {
 
 constexpr uint32_t kFileSlicePieces = 256;          // pieces per slice of zwz_deflate_stream_file: 16.7 MB of input
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t pieces_bytes(uint32_t m) { return up256((size_t)m * ZWZ_DEV_STRIDE + 256) + 2 * up256((size_t)m * 8) + 7 * up256((size_t)m * 4) + 256; }
-
 struct PiecesView { DstreamPieces P; uint64_t* base; uint32_t* err; };
-PiecesView pieces_view(zwz_ctx* c) {
-    const size_t m = c->ds_cap;
-    uint8_t* p = static_cast<uint8_t*>(c->ds_ws);
-    auto take = [&](size_t bytes) { uint8_t* r = p; p += up256(bytes); return r; };
-    auto u32s = [&]() { return reinterpret_cast<uint32_t*>(take(m * 4)); };
+PiecesView pieces_layout(Carver& w, size_t m) {
     PiecesView v;
-    v.P.slots = take(m * ZWZ_DEV_STRIDE + 256);       // (wg_copy reads up to 3 bytes past a slot's bytes)
-    v.P.off = reinterpret_cast<uint64_t*>(take(m * 8)); v.P.x = reinterpret_cast<uint64_t*>(take(m * 8));
-    v.P.len = u32s(); v.P.olen = u32s(); v.P.crc = u32s(); v.P.sidx = u32s(); v.P.slen = u32s(); v.P.hbit = u32s(); v.P.ebit = u32s();
-    v.base = reinterpret_cast<uint64_t*>(take(16)); v.err = reinterpret_cast<uint32_t*>(v.base + 1);
+    v.P.slots = w.take<uint8_t>(m * ZWZ_DEV_STRIDE, 256);     // (wg_copy reads up to 3 bytes past a slot's bytes)
+    v.P.off = w.take<uint64_t>(m); v.P.x = w.take<uint64_t>(m);
+    v.P.len = w.take<uint32_t>(m); v.P.olen = w.take<uint32_t>(m); v.P.crc = w.take<uint32_t>(m); v.P.sidx = w.take<uint32_t>(m);
+    v.P.slen = w.take<uint32_t>(m); v.P.hbit = w.take<uint32_t>(m); v.P.ebit = w.take<uint32_t>(m);
+    v.base = w.take<uint64_t>(2); v.err = reinterpret_cast<uint32_t*>(v.base + 1);
     return v;
+}
+
+PiecesView pieces_view(zwz_ctx* c) {
+    Carver w(c->buf[kBufPieces].p);
+    return pieces_layout(w, c->buf[kBufPieces].count);
 }
 
 // in_off, in_len, out_off, out_cap (n each), pfirst (n + 1) -- copied from the host -- then xs (n) and chk (n)
@@ -42,26 +39,11 @@ size_t streams_host_bytes(uint32_t n) { return (5 * (size_t)n + 1) * 8; }
 size_t streams_dev_bytes(uint32_t n) { return streams_host_bytes(n) + (size_t)n * 8 + (size_t)n * 4 + 64; }
 
 int ensure_dstream(zwz_ctx* c, uint32_t pieces, uint32_t streams, bool crc) {
-    if (crc && !c->crc_tables) {
-        HIPCHK(hipMalloc(&c->crc_tables, sizeof(CrcTables)));
-        HIPCHK(launch_crc_tables(static_cast<CrcTables*>(c->crc_tables), c->stream));
-    }
+    if (crc) if (int rc = ensure_crc_tables(c)) return rc;
     if (!c->ds_copied) HIPCHK(hipEventCreateWithFlags(&c->ds_copied, hipEventDisableTiming));
-    if (pieces > c->ds_cap || streams > c->ds_streams) HIPCHK(hipStreamSynchronize(c->stream));
-    if (pieces > c->ds_cap) {
-        if (c->ds_ws) { (void)hipFree(c->ds_ws); c->ds_ws = nullptr; c->ds_cap = 0; }
-        HIPCHK(hipMalloc(&c->ds_ws, pieces_bytes(pieces)));
-        c->ds_cap = pieces;
-    }
-    if (streams > c->ds_streams) {
-        if (c->ds_dev) { (void)hipFree(c->ds_dev); c->ds_dev = nullptr; }
-        if (c->ds_host) { (void)hipHostFree(c->ds_host); c->ds_host = nullptr; }
-        c->ds_streams = 0;
-        HIPCHK(hipMalloc(&c->ds_dev, streams_dev_bytes(streams)));
-        HIPCHK(hipHostMalloc(&c->ds_host, streams_host_bytes(streams), hipHostMallocDefault));
-        c->ds_streams = streams;
-    }
-    return ZWZ_OK;
+    if (int rc = c->buf[kBufPieces].reserve(c, pieces, layout_bytes([&](Carver& w) { pieces_layout(w, pieces); }))) return rc;
+    if (int rc = c->buf[kBufStreamsDev].reserve(c, streams, streams_dev_bytes(streams))) return rc;
+    return c->buf[kBufStreamsHost].reserve(c, streams, streams_host_bytes(streams));
 }
 
 // The device part, arguments checked by the caller.  partial: every stream's pieces alone, and its checksum left in *d_chk (the file
@@ -83,11 +65,11 @@ int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_
     if (int rc = ensure_dstream(c, M, n, wrap == kWrapGzip)) return rc;
     // the pinned arrays may still be the source of the previous call's copy
     HIPCHK(hipEventSynchronize(c->ds_copied));
-    uint64_t* h = static_cast<uint64_t*>(c->ds_host);
+    uint64_t* h = c->buf[kBufStreamsHost].as<uint64_t>();
     memcpy(h, in_off, (size_t)n * 8); memcpy(h + n, in_len, (size_t)n * 8);
     memcpy(h + 2 * (size_t)n, out_off, (size_t)n * 8); memcpy(h + 3 * (size_t)n, out_cap, (size_t)n * 8);
     memcpy(h + 4 * (size_t)n, pfirst.data(), ((size_t)n + 1) * 8);
-    uint64_t* d = static_cast<uint64_t*>(c->ds_dev);
+    uint64_t* d = c->buf[kBufStreamsDev].as<uint64_t>();
     HIPCHK(hipMemcpyAsync(d, h, streams_host_bytes(n), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ds_copied, c->stream));
     DstreamStreams S;
@@ -96,7 +78,7 @@ int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_
     if (d_chk) *d_chk = S.chk;
     const DstreamOut O{d_out, d_out_len, d_status, wrap, partial ? 1u : 0u};
     const PiecesView v = pieces_view(c);
-    const CrcTables* tab = static_cast<const CrcTables*>(c->crc_tables);
+    const CrcTables* tab = c->buf[kBufCrcTables].as<const CrcTables>();
     HIPCHK(hipMemsetAsync(v.base, 0, 16, c->stream));
     HIPCHK(launch_dstream_begin(S, O, c->stream));
     uint32_t s0 = 0;                                  // the stream of the slice's first piece
@@ -144,50 +126,31 @@ int zwz_deflate_stream_file(zwz_ctx* c, int wrap_, const char* src, const char* 
     FileJob job;
     if (int rc = job.open(src, dst)) return rc;
     const uint32_t pieces = c->max_batch < kFileSlicePieces ? c->max_batch : kFileSlicePieces;
-    const size_t S = (size_t)pieces * kPieceBytes, O = ((size_t)pieces * piece_bound(kPieceBytes) + 15) & ~(size_t)15;
-    for (int i = 0; i < 2; i++) HIPCHK(hipHostMalloc(&job.h[i], S + 16, hipHostMallocDefault));
-    for (int i = 2; i < 4; i++) HIPCHK(hipHostMalloc(&job.h[i], O, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&job.h[4], 64, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&job.d[0], S + 16));
-    HIPCHK(hipMalloc(&job.d[1], O));
-    HIPCHK(hipMalloc(&job.d[2], 64));
-    uint8_t* d_in = static_cast<uint8_t*>(job.d[0]); uint8_t* d_out = static_cast<uint8_t*>(job.d[1]);
-    uint64_t* d_len = static_cast<uint64_t*>(job.d[2]); uint32_t* d_st = reinterpret_cast<uint32_t*>(d_len + 1);
-    uint64_t* h_len = static_cast<uint64_t*>(job.h[4]); uint32_t* h_st = reinterpret_cast<uint32_t*>(h_len + 1); uint32_t* h_chk = h_st + 1;
+    const size_t S = (size_t)pieces * kPieceBytes, O = round_up((size_t)pieces * piece_bound(kPieceBytes), 16);
+    if (int rc = job.alloc({S + 16, S + 16, O, O, 64}, {S + 16, O, 64})) return rc;
     uint8_t frame[kGzipHeaderBytes + 2 + 8];
     const uint32_t hdr = dstream_header_bytes(wrap);
     for (uint32_t i = 0; i < hdr; i++) frame[i] = (uint8_t)dstream_header_byte(wrap, i);
     if (hdr && fwrite(frame, 1, hdr, job.out) != hdr) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
     uint32_t check = dstream_check_init(wrap);
     uint64_t total_in = 0;
-    size_t n = 0;
-    job.start_read(static_cast<uint8_t*>(job.h[0]), S);
-    if (int rc = job.finish_read(&n)) return rc;
-    for (int b = 0; n; b ^= 1) {
-        uint8_t* hin = static_cast<uint8_t*>(job.h[b]);
-        uint8_t* hout = static_cast<uint8_t*>(job.h[2 + b]);
-        const uint64_t zero = 0, len = n, cap = O;
-        const uint32_t* d_chk = nullptr;
-        HIPJOB(hipMemcpyAsync(d_in, hin, n, hipMemcpyHostToDevice, c->stream));
-        if (int rc = dstream_launch(c, wrap, d_in, &zero, &len, 1, d_out, &zero, &cap, d_len, d_st, true, &d_chk)) { job.join(); return rc; }
-        HIPJOB(hipMemcpyAsync(h_len, d_len, 12, hipMemcpyDeviceToHost, c->stream));
-        HIPJOB(hipMemcpyAsync(h_chk, d_chk, 4, hipMemcpyDeviceToHost, c->stream));
-        if (n == S) job.start_read(static_cast<uint8_t*>(job.h[b ^ 1]), S);     // (a short slice is the last one)
-        HIPJOB(hipStreamSynchronize(c->stream));
-        const uint64_t out_len = *h_len;
-        if (*h_st || out_len > O) { job.join(); set_error("deflate stream: a slice needs %llu bytes, above its bound", (unsigned long long)out_len); return ZWZ_E_FORMAT; }
-        if (wrap == kWrapZlib) check = AdlerSum::join(check, *h_chk, AdlerSum::pof(n));
-        else if (wrap == kWrapGzip) check = CrcSum::join(check, *h_chk, CrcSum::pof(n));
-        total_in += n;
-        HIPJOB(hipMemcpyAsync(hout, d_out, out_len, hipMemcpyDeviceToHost, c->stream));
-        HIPJOB(hipStreamSynchronize(c->stream));
-        if (int rc = job.finish_write()) { job.join(); return rc; }
-        job.start_write(hout, out_len);
-        size_t next = 0;
-        if (n == S) { if (int rc = job.finish_read(&next)) { job.join(); return rc; } }
-        n = next;
-    }
-    if (int rc = job.finish_write()) return rc;
+    const int rc = run_slices(c, job, S,
+        [&](size_t n, SliceResult* d_res, SliceResult* h_res) {
+            const uint64_t zero = 0, len = n, cap = O;
+            const uint32_t* d_chk = nullptr;
+            if (int rc = dstream_launch(c, wrap, job.dp(0), &zero, &len, 1, job.dp(1), &zero, &cap, &d_res->out_len, &d_res->status, true, &d_chk)) return rc;
+            HIPCHK(hipMemcpyAsync(h_res, d_res, 12, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(&h_res->check, d_chk, 4, hipMemcpyDeviceToHost, c->stream));
+            return (int)ZWZ_OK;
+        },
+        [&](size_t n, const SliceResult& r) {
+            if (r.status || r.out_len > O) { set_error("deflate stream: a slice needs %llu bytes, above its bound", (unsigned long long)r.out_len); return (int)ZWZ_E_FORMAT; }
+            if (wrap == kWrapZlib) check = AdlerSum::join(check, r.check, AdlerSum::pof(n));
+            else if (wrap == kWrapGzip) check = CrcSum::join(check, r.check, CrcSum::pof(n));
+            total_in += n;
+            return (int)ZWZ_OK;
+        });
+    if (rc) return rc;
     const uint32_t tail = 2u + dstream_trailer_bytes(wrap);
     for (uint32_t i = 0; i < tail; i++) frame[i] = (uint8_t)dstream_tail_byte(wrap, i, check, total_in);
     if (fwrite(frame, 1, tail, job.out) != tail) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }

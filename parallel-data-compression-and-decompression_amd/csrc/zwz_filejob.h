@@ -1,9 +1,10 @@
-// zwz_filejob.h -- what the whole-file entry points share (zwz_bgzf.cpp, zwz_dstream.cpp): the open files, the pinned double buffers
-// and the reader and writer threads of one call.  Host code; include after zwz_api_internal.h.
+// zwz_filejob.h -- what the whole-file entry points share (zwz_bgzf.cpp, zwz_dstream.cpp, zwz_split.cpp): the open files, the pinned
+// double buffers and the reader and writer threads of one call, and the slice loop of the two compressing ones.  Host code.
 #pragma once
 #include <unistd.h>
 
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 #include <thread>
 
@@ -24,9 +25,10 @@ inline size_t read_full(FILE* f, uint8_t* p, size_t n, bool* io_err) {
 // Buffers and threads of one file call; everything is released (threads joined first) whatever the outcome.
 struct FileJob {
     FILE *in = nullptr, *out = nullptr;
+    int fd = -1;                     // (the range reader's input: pread)
     std::string part;
     void* h[5] = {};                 // pinned: two input buffers, two output buffers, small values
-    void* d[4] = {};
+    void* d[3] = {};                 // input, output, small values
     std::thread reader, writer;
     size_t read_got = 0; bool read_err = false; bool write_err = false;
     void join() { if (reader.joinable()) reader.join(); if (writer.joinable()) writer.join(); }
@@ -35,6 +37,7 @@ struct FileJob {
         for (void* p : h) if (p) (void)hipHostFree(p);
         for (void* p : d) if (p) (void)hipFree(p);
         if (in) fclose(in);
+        if (fd >= 0) close(fd);
         if (out) { fclose(out); unlink(part.c_str()); }
     }
     int open(const char* src, const char* dst) {
@@ -45,6 +48,16 @@ struct FileJob {
         if (!out) { set_error("cannot create %s", part.c_str()); return ZWZ_E_IO; }
         return ZWZ_OK;
     }
+    // The buffers of the call: h[i] of h_bytes[i] bytes, d[i] of d_bytes[i] (0: none).  Returns the first error.
+    int alloc(std::initializer_list<size_t> h_bytes, std::initializer_list<size_t> d_bytes) {
+        void** q = h;
+        for (size_t n : h_bytes) { if (n) HIPCHK(hipHostMalloc(q, n, hipHostMallocDefault)); q++; }
+        q = d;
+        for (size_t n : d_bytes) { if (n) HIPCHK(hipMalloc(q, n)); q++; }
+        return ZWZ_OK;
+    }
+    template <class T = uint8_t> T* hp(int i) const { return static_cast<T*>(h[i]); }
+    template <class T = uint8_t> T* dp(int i) const { return static_cast<T*>(d[i]); }
     void start_read(uint8_t* p, size_t n) { read_got = 0; read_err = false; reader = std::thread([this, p, n] { read_got = read_full(in, p, n, &read_err); }); }
     void start_write(const uint8_t* p, size_t n) { writer = std::thread([this, p, n] { if (n && fwrite(p, 1, n, out) != n) write_err = true; }); }
     int finish_read(size_t* got) {
@@ -69,5 +82,41 @@ struct FileJob {
 
 #define HIPJOB(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { job.join(); return hip_fail(e_, #x); } } while (0)
 
+// What a compressed slice hands back through h[4] / d[2]: the bytes it wrote, its status (0: fine) and its checksum where it has one
+struct SliceResult { uint64_t out_len; uint32_t status, check; };
+
+// The loop of zwz_bgzf_compress_file and zwz_deflate_stream_file over slices of S input bytes, buffers as FileJob::alloc({S.., S.., O, O,
+// small}, {S.., O, small}) gave them.  Slice s: its input was read into h[s & 1] while slice s - 1 ran; it runs while slice s + 1 is
+// read into the other buffer and slice s - 1's output is written from h[2 + ((s - 1) & 1)].  Every wait is a join of a thread that
+// only does file I/O, or a stream synchronisation that returns on a HIP error: no wait depends on another thread reaching a point.
+//   queue(n, d_res, h_res)  the slice's n bytes are on their way to d[0]: queue its work on the context's stream, output to d[1], and
+//                           the copy of its results into *h_res
+//   back(n, res)            the results have arrived: judge them (anything but ZWZ_OK ends the call)
+// Returns with the last write joined and checked.
+template <class Q, class B>
+int run_slices(zwz_ctx* c, FileJob& job, size_t S, Q&& queue, B&& back) {
+    SliceResult* res = job.hp<SliceResult>(4);
+    *res = SliceResult{};
+    size_t n = 0;
+    job.start_read(job.hp(0), S);
+    if (int rc = job.finish_read(&n)) return rc;
+    for (int b = 0; n; b ^= 1) {
+        uint8_t* hout = job.hp(2 + b);
+        HIPJOB(hipMemcpyAsync(job.d[0], job.h[b], n, hipMemcpyHostToDevice, c->stream));
+        if (int rc = queue(n, job.dp<SliceResult>(2), res)) { job.join(); return rc; }
+        if (n == S) job.start_read(job.hp(b ^ 1), S);     // (a short slice is the last one)
+        HIPJOB(hipStreamSynchronize(c->stream));
+        if (int rc = back(n, *res)) { job.join(); return rc; }
+        const uint64_t len = res->out_len;
+        HIPJOB(hipMemcpyAsync(hout, job.d[1], len, hipMemcpyDeviceToHost, c->stream));
+        HIPJOB(hipStreamSynchronize(c->stream));
+        if (int rc = job.finish_write()) { job.join(); return rc; }
+        job.start_write(hout, len);
+        size_t next = 0;
+        if (n == S) { if (int rc = job.finish_read(&next)) { job.join(); return rc; } }
+        n = next;
+    }
+    return job.finish_write();
+}
 
 }  // namespace zwz

@@ -26,8 +26,6 @@
 namespace fs = std::filesystem;
 using namespace zwz;
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
-
 namespace {
 
 bool read_lines(const std::string& path, std::vector<std::string>& lines) {

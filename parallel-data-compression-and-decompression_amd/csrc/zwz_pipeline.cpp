@@ -45,8 +45,6 @@
 namespace fs = std::filesystem;
 using namespace zwz;
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
-
 namespace {
 
 bool verbose() { static int v = getenv("ZWZ_VERBOSE") ? 1 : 0; return v != 0; }
@@ -162,17 +160,10 @@ int make_slices(zwz_ctx* c, uint32_t cap, Slices& s) {
     int rc = ensure_staging(c, 2 * cap);
     if (rc) return rc;
     s.cap = cap;
-    auto carve = [&](uint8_t* base, int i, uint8_t*& in, uint8_t*& out, uint64_t*& off, uint32_t*& len, uint32_t*& olen, uint32_t*& st) {
-        const size_t total = c->stage_chunks;           // layout of stage_view(): [in | out | off | len | olen | st]
-        uint8_t* in0 = base; uint8_t* out0 = in0 + total * ZWZ_DEV_STRIDE;
-        uint64_t* off0 = reinterpret_cast<uint64_t*>(out0 + total * ZWZ_DEV_STRIDE);
-        uint32_t* len0 = reinterpret_cast<uint32_t*>(off0 + total); uint32_t* olen0 = len0 + total; uint32_t* st0 = olen0 + total;
-        const size_t o = (size_t)i * cap;
-        in = in0 + o * ZWZ_DEV_STRIDE; out = out0 + o * ZWZ_DEV_STRIDE; off = off0 + o; len = len0 + o; olen = olen0 + o; st = st0 + o;
-    };
     for (int i = 0; i < 2; i++) {
-        carve(static_cast<uint8_t*>(c->h_stage), i, s.h_in[i], s.h_out[i], s.h_off[i], s.h_len[i], s.h_olen[i], s.h_st[i]);
-        carve(static_cast<uint8_t*>(c->d_stage), i, s.d_in[i], s.d_out[i], s.d_off[i], s.d_len[i], s.d_olen[i], s.d_st[i]);
+        const StageView v = stage_view(c, (uint32_t)i * cap);
+        s.h_in[i] = v.h_in; s.h_out[i] = v.h_out; s.h_off[i] = v.h_off; s.h_len[i] = v.h_len; s.h_olen[i] = v.h_olen; s.h_st[i] = v.h_status;
+        s.d_in[i] = v.d_in; s.d_out[i] = v.d_out; s.d_off[i] = v.d_off; s.d_len[i] = v.d_len; s.d_olen[i] = v.d_olen; s.d_st[i] = v.d_status;
         hipError_t e = hipEventCreateWithFlags(&s.done[i], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_in[i], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_k[i], hipEventDisableTiming);

@@ -14,24 +14,53 @@
 
 using namespace zwz;
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_fail(e_, #x); } while (0)
-
 namespace {
 
 constexpr uint64_t kSplitMaxKept = 8u << 20;        // kept candidates of one call: the workspace is (levels + 20) words each
 
-struct Carver {
-    uint8_t* p;
-    template <class T> T* take(size_t count) { T* r = reinterpret_cast<T*>(p); p += (count * sizeof(T) + 255) & ~(size_t)255; return r; }
-};
-inline size_t padded(size_t count, size_t size) { return (count * size + 255) & ~(size_t)255; }
+// The three device workspaces of a call, each carved for that call's sizes: which is known only once the step before has run.
+// Per stream (body, tile_first, cfirst, kbase, dbase, pbase, res, bad, the lengths handed to the fallback) and per scan tile (count, offset)
+struct StreamArrays { uint32_t *tile_first, *kbase, *dbase, *pbase, *bad, *chk; uint64_t* fb_len; uint4 *res, *res2; };
+StreamArrays streams_layout(Carver& w, size_t n, size_t tiles, SplitStreams& S) {
+    StreamArrays A;
+    S.body = w.take<uint32_t>(n + 1);
+    S.tile_first = A.tile_first = w.take<uint32_t>(n + 1);
+    S.kbase = A.kbase = w.take<uint32_t>(n + 1);
+    A.dbase = w.take<uint32_t>(n + 1);
+    A.pbase = w.take<uint32_t>(n + 1);
+    A.bad = w.take<uint32_t>(n + 1);
+    S.cfirst = w.take<uint64_t>(n + 1);
+    A.fb_len = w.take<uint64_t>(n + 1);
+    A.res = w.take<uint4>(n);
+    A.res2 = w.take<uint4>(n);
+    A.chk = w.take<uint32_t>(n + 1);
+    S.tile_cnt = w.take<uint32_t>(tiles);
+    S.tile_off = w.take<uint64_t>(tiles);
+    S.base = w.take<uint64_t>(2);
+    return A;
+}
 
-int ensure_ws(zwz_ctx* c, int which, size_t bytes) {
-    if (bytes <= c->split_ws_cap[which]) return ZWZ_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->split_ws[which]) { (void)hipFree(c->split_ws[which]); c->split_ws[which] = nullptr; c->split_ws_cap[which] = 0; }
-    HIPCHK(hipMalloc(&c->split_ws[which], bytes));
-    c->split_ws_cap[which] = bytes;
+// Per kept candidate; returns the launch order's scratch
+uint4* cands_layout(Carver& w, size_t m, uint32_t levels, SplitCands& C) {
+    C.pos = w.take<uint32_t>(m); C.mark = w.take<uint32_t>(m); C.ostart = w.take<uint32_t>(m); C.rank = w.take<uint32_t>(m);
+    C.jump = w.take<uint32_t>((size_t)levels * m);
+    C.in_off = w.take<uint64_t>(m); C.in_len = w.take<uint64_t>(m);
+    C.seg = w.take<uint4>(m); C.meas = w.take<uint4>(m);
+    return w.take<uint4>(m);
+}
+
+// Per chain segment to decode (nd) and per checksum piece (np)
+void decode_layout(Carver& w, size_t nd, size_t np, SplitDecode& D, SplitPieces& P) {
+    D.in_off = w.take<uint64_t>(nd); D.in_len = w.take<uint64_t>(nd); D.seg = w.take<uint4>(nd);
+    P.off = w.take<uint64_t>(np); P.len = w.take<uint32_t>(np); P.val = w.take<uint32_t>(np);
+}
+
+// Reserves workspace `id` for what `layout` takes and carves it
+template <class F>
+int carve_ws(zwz_ctx* c, BufId id, F&& layout) {
+    if (int rc = c->buf[id].reserve(c, 0, layout_bytes(layout))) return rc;
+    Carver w(c->buf[id].p);
+    layout(w);
     return ZWZ_OK;
 }
 
@@ -58,12 +87,8 @@ int split_call(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_o
     HIPCHK(hipMemcpyAsync(h_cap.data(), d_out_cap, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (d_segments) HIPCHK(hipMemsetAsync(d_segments, 0, n * sizeof(uint32_t), st));
-    if ((size_t)(n + 1) * 24 > c->split_host_cap) {
-        if (c->split_host) { (void)hipHostFree(c->split_host); c->split_host = nullptr; c->split_host_cap = 0; }
-        HIPCHK(hipHostMalloc(&c->split_host, (size_t)(n + 1) * 24, hipHostMallocDefault));
-        c->split_host_cap = (size_t)(n + 1) * 24;
-    }
-    uint64_t* fb_len = static_cast<uint64_t*>(c->split_host);
+    if (int rc = c->buf[kBufSplitHost].reserve(c, n, (size_t)(n + 1) * 24)) return rc;
+    uint64_t* fb_len = c->buf[kBufSplitHost].as<uint64_t>();
     uint32_t* tile_first = reinterpret_cast<uint32_t*>(fb_len + n + 1);
     uint32_t *kbase = tile_first + n + 1, *dbase = kbase + n + 1, *pbase = dbase + n + 1;
     uint64_t tiles = 0;
@@ -75,32 +100,12 @@ int split_call(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_o
     tile_first[n] = (uint32_t)tiles;
     if (!tiles) return fall_back(d_in_len);
 
-    // per stream: body, tile_first, cfirst, kbase, dbase, pbase, res, bad, the lengths handed to the fallback; per tile: count, offset
-    {
-        const size_t bytes = 7 * padded(n + 1, 4) + 2 * padded(n + 1, 8) + 2 * padded(n, 16) + padded(tiles, 4) + padded(tiles, 8) + 256;
-        const int rc = ensure_ws(c, 0, bytes);
-        if (rc) return rc;
-    }
-    Carver w0{static_cast<uint8_t*>(c->split_ws[0])};
     SplitStreams S{};
-    S.in = d_in; S.in_off = d_in_off; S.in_len = d_in_len; S.out_cap = d_out_cap; S.n = n; S.wrap = (uint32_t)wrap;
-    S.body = w0.take<uint32_t>(n + 1);
-    uint32_t* d_tile_first = w0.take<uint32_t>(n + 1);
-    uint32_t* d_kbase = w0.take<uint32_t>(n + 1);
-    uint32_t* d_dbase = w0.take<uint32_t>(n + 1);
-    uint32_t* d_pbase = w0.take<uint32_t>(n + 1);
-    uint32_t* d_bad = w0.take<uint32_t>(n + 1);
-    S.cfirst = w0.take<uint64_t>(n + 1);
-    uint64_t* d_fb_len = w0.take<uint64_t>(n + 1);
-    uint4* d_res = w0.take<uint4>(n);
-    uint4* d_res2 = w0.take<uint4>(n);
-    uint32_t* d_chk = w0.take<uint32_t>(n + 1);
-    S.tile_cnt = w0.take<uint32_t>(tiles);
-    S.tile_off = w0.take<uint64_t>(tiles);
-    S.base = w0.take<uint64_t>(2);
-    S.tile_first = d_tile_first; S.kbase = d_kbase; S.n_tiles = (uint32_t)tiles;
-    HIPCHK(hipMemcpyAsync(d_tile_first, tile_first, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), st));
+    S.in = d_in; S.in_off = d_in_off; S.in_len = d_in_len; S.out_cap = d_out_cap; S.n = n; S.wrap = (uint32_t)wrap; S.n_tiles = (uint32_t)tiles;
+    StreamArrays A{};
+    if (int rc = carve_ws(c, kBufSplit0, [&](Carver& w) { A = streams_layout(w, n, tiles, S); })) return rc;
+    HIPCHK(hipMemcpyAsync(A.tile_first, tile_first, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(A.bad, 0, n * sizeof(uint32_t), st));
     if (part) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(S.body), (int)part->p0, 1, st));      // (the body starts where the last slice's chain ended)
     else HIPCHK(launch_split_head(S, min_bytes, st));
     HIPCHK(launch_split_count(S, st));
@@ -119,32 +124,23 @@ int split_call(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_o
     kbase[n] = (uint32_t)kept;
     if (!kept) return fall_back(d_in_len);
     const uint32_t m = (uint32_t)kept, levels = split_levels(longest);
-    {
-        const size_t bytes = (5 + levels) * padded(m, 4) + 2 * padded(m, 8) + 3 * padded(m, 16) + 256;
-        const int rc = ensure_ws(c, 1, bytes);
-        if (rc) return rc;
-    }
-    Carver w1{static_cast<uint8_t*>(c->split_ws[1])};
     SplitCands C{};
     C.m = m;
-    C.pos = w1.take<uint32_t>(m); C.mark = w1.take<uint32_t>(m); C.ostart = w1.take<uint32_t>(m); C.rank = w1.take<uint32_t>(m);
-    C.jump = w1.take<uint32_t>((size_t)levels * m);
-    C.in_off = w1.take<uint64_t>(m); C.in_len = w1.take<uint64_t>(m);
-    C.seg = w1.take<uint4>(m); C.meas = w1.take<uint4>(m);
-    uint4* d_order = w1.take<uint4>(m);
-    HIPCHK(hipMemcpyAsync(d_kbase, kbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    uint4* d_order = nullptr;
+    if (int rc = carve_ws(c, kBufSplit1, [&](Carver& w) { d_order = cands_layout(w, m, levels, C); })) return rc;
+    HIPCHK(hipMemcpyAsync(A.kbase, kbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(launch_split_write(S, C, c->split_budget, st));
     {
         InflateSplitArgs a{d_in, C.in_off, C.in_len, m, nullptr, nullptr, d_order, C.seg, C.meas, nullptr, 1u, c->inflate_serial_header};
         HIPCHK(launch_inflate_split(a, st));
     }
-    HIPCHK(launch_split_resolve(S, C, levels, d_res, part ? 1u : 0u, part ? h_cap[0] : 0, d_res2, st));
+    HIPCHK(launch_split_resolve(S, C, levels, A.res, part ? 1u : 0u, part ? h_cap[0] : 0, A.res2, st));
 
     // 3. the chains' verdicts: the segments to decode, the checksum pieces, and who falls back
     std::vector<uint4> res(n);
-    HIPCHK(hipMemcpyAsync(res.data(), d_res, n * sizeof(uint4), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(res.data(), A.res, n * sizeof(uint4), hipMemcpyDeviceToHost, st));
     uint4 res2{};
-    if (part) HIPCHK(hipMemcpyAsync(&res2, d_res2, sizeof(uint4), hipMemcpyDeviceToHost, st));
+    if (part) HIPCHK(hipMemcpyAsync(&res2, A.res2, sizeof(uint4), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (uint32_t i = 0; i < n; i++) fb_len[i] = h_len[i];
     uint64_t nd = 0, np = 0;
@@ -160,39 +156,29 @@ int split_call(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_o
     // writes status 1 and length 0 for them.  Their real results are written by split_finish_kernel further down.  Both are queued on
     // the context's stream in this order, and the call's correctness depends on that: the later write wins.
     if (n_fall && !part) {
-        HIPCHK(hipMemcpyAsync(d_fb_len, fb_len, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        const int rc = fall_back(d_fb_len);
+        HIPCHK(hipMemcpyAsync(A.fb_len, fb_len, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        const int rc = fall_back(A.fb_len);
         if (rc) return rc;
     }
-    if (wrap == ZWZ_WRAP_GZIP && !c->crc_tables) {
-        HIPCHK(hipMalloc(&c->crc_tables, sizeof(CrcTables)));
-        HIPCHK(launch_crc_tables(static_cast<CrcTables*>(c->crc_tables), st));
-    }
-    {
-        const size_t bytes = 3 * padded(nd, 8) + padded(nd, 16) + padded(np, 8) + 2 * padded(np, 4) + 256;
-        const int rc = ensure_ws(c, 2, bytes);
-        if (rc) return rc;
-    }
-    Carver w2{static_cast<uint8_t*>(c->split_ws[2])};
+    if (wrap == ZWZ_WRAP_GZIP) if (int rc = ensure_crc_tables(c)) return rc;
     SplitDecode D{};
-    D.res = d_res; D.dbase = d_dbase;
-    D.in_off = w2.take<uint64_t>(nd); D.in_len = w2.take<uint64_t>(nd); D.seg = w2.take<uint4>(nd);
+    D.res = A.res; D.dbase = A.dbase;
     SplitPieces P{};
-    P.pbase = d_pbase; P.p = (uint32_t)np;
-    P.off = w2.take<uint64_t>(np); P.len = w2.take<uint32_t>(np); P.val = w2.take<uint32_t>(np);
-    HIPCHK(hipMemcpyAsync(d_dbase, dbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_pbase, pbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    P.pbase = A.pbase; P.p = (uint32_t)np;
+    if (int rc = carve_ws(c, kBufSplit2, [&](Carver& w) { decode_layout(w, nd, np, D, P); })) return rc;
+    HIPCHK(hipMemcpyAsync(A.dbase, dbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(A.pbase, pbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(launch_split_emit(S, C, D, st));
     {
-        InflateSplitArgs a{d_in, D.in_off, D.in_len, (uint32_t)nd, d_out, d_out_off, d_order, D.seg, nullptr, d_bad, 0u, c->inflate_serial_header};
+        InflateSplitArgs a{d_in, D.in_off, D.in_len, (uint32_t)nd, d_out, d_out_off, d_order, D.seg, nullptr, A.bad, 0u, c->inflate_serial_header};
         HIPCHK(launch_inflate_split(a, st));
     }
-    HIPCHK(launch_split_finish(S, D, P, static_cast<const CrcTables*>(c->crc_tables), d_out, d_out_off, d_bad, d_out_len, d_status, d_segments,
-                               part ? d_chk : nullptr, c->cu_count, st));
+    HIPCHK(launch_split_finish(S, D, P, c->buf[kBufCrcTables].as<const CrcTables>(), d_out, d_out_off, A.bad, d_out_len, d_status, d_segments,
+                               part ? A.chk : nullptr, c->cu_count, st));
     if (part) {
-        HIPCHK(hipMemcpyAsync(&part->chk, d_chk, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&part->chk, A.chk, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         uint32_t bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&bad, A.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (bad) { set_error("split inflate: a segment did not decode as it was measured"); return ZWZ_E_FORMAT; }
         part->nseg = res[0].y; part->total = res[0].z; part->end = res2.x; part->kind = res2.y;
@@ -225,12 +211,7 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
     FileJob job;
     if (int rc = job.open(src, dst)) return rc;
     const size_t S = c->split_slice_bytes, O = std::max<size_t>(4 * S, 4u << 20);
-    HIPCHK(hipHostMalloc(&job.h[0], S + 32, hipHostMallocDefault));
-    for (int i = 2; i < 4; i++) HIPCHK(hipHostMalloc(&job.h[i], O, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&job.h[4], 64, hipHostMallocDefault));
-    HIPCHK(hipMalloc(&job.d[0], S + 32));
-    HIPCHK(hipMalloc(&job.d[1], O + 16));
-    HIPCHK(hipMalloc(&job.d[2], 64));
+    if (int rc = job.alloc({S + 32, 0, O, O, 64}, {S + 32, O + 16, 64})) return rc;      // (one input buffer: the next slice depends on this one's end)
     uint8_t* hin = static_cast<uint8_t*>(job.h[0]);
     uint8_t* d_in = static_cast<uint8_t*>(job.d[0]); uint8_t* d_out = static_cast<uint8_t*>(job.d[1]);
     uint64_t* d_par = static_cast<uint64_t*>(job.d[2]);           // in_off, in_len, out_off, out_cap, out_len, (status, segments)
@@ -254,7 +235,7 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
     while (chain_ok) {
         memset(hin + have, 0, 32);
         h_par[0] = 0; h_par[1] = have; h_par[2] = 0; h_par[3] = O;
-        HIPJOB(hipMemcpyAsync(d_in, hin, (have + 31) & ~(size_t)15, hipMemcpyHostToDevice, c->stream));
+        HIPJOB(hipMemcpyAsync(d_in, hin, round_up(have + 16, 16), hipMemcpyHostToDevice, c->stream));
         HIPJOB(hipMemcpyAsync(d_par, h_par, 32, hipMemcpyHostToDevice, c->stream));
         SlicePart part{};
         part.p0 = (uint32_t)(at - base);
@@ -296,8 +277,8 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
         std::vector<uint8_t> whole((size_t)size + 16, 0);
         fseeko(job.in, 0, SEEK_SET);
         if (read_full(job.in, whole.data(), (size_t)size, &io_err) != size || io_err) { set_error("read error on %s", src); return ZWZ_E_IO; }
-        HIPCHK(hipMalloc(&job.d[0], ((size_t)size + 31) & ~(size_t)15));
-        HIPCHK(hipMemcpy(job.d[0], whole.data(), ((size_t)size + 15) & ~(size_t)15, hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&job.d[0], round_up((size_t)size + 16, 16)));
+        HIPCHK(hipMemcpy(job.d[0], whole.data(), round_up((size_t)size, 16), hipMemcpyHostToDevice));
         uint64_t cap = std::max<uint64_t>(8 * size, 1u << 20);
         for (;;) {
             cap = std::min<uint64_t>(cap, kStreamMaxOut - 16);
