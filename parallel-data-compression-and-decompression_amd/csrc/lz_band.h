@@ -176,4 +176,55 @@ ZWZ_HD void band_deep(const uint8_t* data, SFn S, LinkFn link, EFn E, uint32_t f
     if (k1 <= kShortChain) e32 = snap != 0xffffffffu ? snap : e128;
 }
 
+// band_deep in the order lz_match_band's second pass takes it (and its specification): H sharers a batch.
+//   chase    the next H sharers, by their links alone -- the only step that hangs on the one before it;
+//   compare  the batch's H lengths, each on its own;
+//   fold     the lengths into best / snapshot / nice stop IN SHARER ORDER: the first of the greatest length wins, the walk
+//            ends behind the first sharer whose length reaches `nice` (sharers chased beyond it are ignored), the short
+//            chain's snapshot is taken at the first sharer with k > 32.
+// Same arguments, same records as band_deep for every H >= 1 (tests/test_band_pass2_cpu.py).  `visited`, if given, receives
+// the number of sharers the walk looked at.
+template <uint32_t H, class SFn, class LinkFn, class EFn>
+ZWZ_HD void band_deep_batched(const uint8_t* data, SFn S, LinkFn link, EFn E, uint32_t first_own, uint32_t u, uint32_t cnt, uint32_t k1,
+                              uint32_t deep, uint32_t L, uint64_t own, uint32_t& e128, uint32_t& e32, uint32_t* visited = nullptr) {
+    static_assert(H >= 1, "a batch holds a sharer");
+    const uint32_t p = band_pos(S(u)), lookahead = L - p;
+    const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch, nice = lookahead < kNiceLen ? lookahead : kNiceLen;
+    auto next = [&](uint32_t j) -> uint32_t {                  // the sharer behind entry j, kBandNoLink where the band ends
+        if (j >= first_own) {
+            const uint32_t j2 = link(j);
+            return j2 == kBandNoLink || u - j2 > cnt ? kBandNoLink : j2;
+        }
+        uint32_t k2 = u - j + 1u;
+        while (k2 <= cnt && E(u - k2) != own) k2++;
+        return k2 > cnt ? kBandNoLink : u - k2;
+    };
+    uint32_t best = 0, best_pos = 0, snap = 0xffffffffu, seen = 0;
+    uint32_t j = u - k1;
+    bool walking = true;
+    while (walking) {
+        uint32_t jv[H], len[H], nv = 1;
+        jv[0] = j;
+        for (uint32_t h = 1; h < H; h++) {                      // chase
+            const uint32_t j2 = next(jv[h - 1u]);
+            if (j2 == kBandNoLink) break;
+            jv[h] = j2; nv++;
+        }
+        for (uint32_t h = 0; h < nv; h++) len[h] = match_len_from(data, band_pos(S(jv[h])), p, deep, max_len);   // compare
+        bool alive = true;
+        for (uint32_t h = 0; h < nv; h++) {                     // fold
+            if (!alive) break;
+            if (u - jv[h] > kShortChain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
+            if (len[h] > best) { best = len[h]; best_pos = band_pos(S(jv[h])); }
+            seen++;
+            alive = best < nice;
+        }
+        j = alive && nv == H ? next(jv[H - 1u]) : kBandNoLink;
+        walking = j != kBandNoLink;
+    }
+    if (visited) *visited = seen;
+    e128 = entry_pack(best, p - best_pos);
+    if (k1 <= kShortChain) e32 = snap != 0xffffffffu ? snap : e128;
+}
+
 }  // namespace zwz

@@ -322,6 +322,13 @@ constexpr uint32_t kBandRuns = kBandTile / 8;
 #ifndef ZWZ_BAND_WAVES
 #define ZWZ_BAND_WAVES 4
 #endif
+// sharers a batch of the second pass -- the pass in cycle units per 10 000 text chunks: one at a time 6.87 M, 2: 5.97 M, 4: 6.01 M, 8: 6.41 M, 16: 7.32 M (DESIGN.md section 4
+// round 6; 8 and 16 do not fit the 128 registers of a 1 024-thread workgroup without scratch)
+#ifndef ZWZ_BAND_P2_BATCH
+#define ZWZ_BAND_P2_BATCH 4
+#endif
+constexpr uint32_t kP2Batch = ZWZ_BAND_P2_BATCH;
+static_assert(kP2Batch >= 1 && kP2Batch <= 32, "lz_match_band: sharers a batch");
 __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                     const uint32_t* __restrict__ in_len, const uint32_t* __restrict__ list,
                                                                     uint32_t* __restrict__ tickets, const uint32_t* __restrict__ sorted,
@@ -337,6 +344,9 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
     __shared__ uint16_t s_halo_link[kBand];                              // the links of a tile's last 128 entries, for the next tile's halo
     __shared__ uint32_t s_bin[132];
     __shared__ uint16_t s_order[kBandRuns];
+#if ZWZ_BAND_EXP & 16
+    __shared__ uint64_t s_p2_start;                                      // second pass: when it began (thread 0's clock)
+#endif
     const uint32_t tid = threadIdx.x, lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t n_list = tickets[kTicketDenseCount];
     for (uint32_t i = tid; i < 2048u; i += kBandThreads) hasb[i] = 0;
@@ -581,9 +591,9 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
             for (uint32_t i = kBand + tid; i < m; i += kBandThreads) if ((uint32_t)ck[i - kBand] == 0u) reinterpret_cast<uint16_t*>(S)[2u * i + 1u] = (uint16_t)kBandNoLink;
             __syncthreads();
             ZWZ_STAMP(4);
-            // ---- second pass: the flagged entries, gathered into full waves, walk their sharers (csrc/lz_band.h, band_deep).  A hop is
-            // ONE LDS round trip: an entry's word holds its position and its link, so the next entry's word and this one's
-            // eight bytes behind the compared ones are asked for together, and those eight bytes settle all but the longest matches.
+            // ---- second pass: the flagged entries, gathered into full waves, walk their sharers (csrc/lz_band.h, band_deep_batched).  An
+            // entry's word holds its position and its link, so following a chain is one LDS read a hop; the sixteen bytes behind the
+            // compared ones, which settle all but the longest matches, are read a batch of sharers at a time.
             for (uint32_t i = kBand + tid; i - tid < m; i += kBandThreads) {
                 const bool f = i < m && ((uint32_t)ck[i - kBand] >> 8) != 0u;
                 const uint64_t fm = __builtin_amdgcn_ballot_w64(f);
@@ -594,6 +604,9 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                     if (f) flist[base + rank_in(fm)] = (uint16_t)i;
                 }
             }
+#if ZWZ_BAND_EXP & 16
+            if (tid == 0) s_p2_start = __builtin_amdgcn_s_memtime();
+#endif
             __syncthreads();
             ZWZ_STAMP(9);
             // (Round 4, measured and dropped: the walks measured first -- the same chase through the links, nothing compared -- and then taken
@@ -607,6 +620,10 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                 if (lane == 0) g = atomicAdd(&s_grp[1], 1u);
                 g = __builtin_amdgcn_readfirstlane(g);
                 if (64u * g >= n_flag) break;
+#if ZWZ_BAND_EXP & 16
+                // (tickets[16 + 10]: from the pass's start to the moment the middle group is handed out -- "half of the groups done")
+                if (lane == 0 && g == ((n_flag + 63u) >> 6) / 2u) atomicAdd(&tickets[16 + 10], (uint32_t)((__builtin_amdgcn_s_memtime() - s_p2_start) >> 8));
+#endif
                 const bool on = 64u * g + lane < n_flag;
                 const uint32_t i = on ? (uint32_t)flist[64u * g + lane] : kBand;
                 const uint32_t c = ck[i - kBand], cnt = c & 0xffu, k1 = c >> 8;
@@ -621,21 +638,53 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                 uint32_t j = on ? i - k1 : kBand;
                 uint32_t w = S[j];
                 bool walking = on, slow = false;
+                // kP2Batch sharers a trip (csrc/lz_band.h, band_deep_batched, is the specification).  Only the links hang on one another:
+                //   chase    the batch's entry words, a ds_read_b32 and the `more` test a hop -- no data, no ballot; a lane whose walk
+                //            has ended goes on reading the dummy entry kBand;
+                //   compare  a sharer's sixteen bytes against the entry's, the length without a branch;
+                //   fold     best / snapshot / nice stop in sharer order, by selects: what zlib's walk would have kept.
                 while (__builtin_amdgcn_ballot_w64(walking) != 0) {
-                    if (walking && j < kBand && !halo_links) { slow = true; walking = false; }   // into a halo of another format: the plain walk, from the start
-                    const uint32_t q = band_pos(w), link = w >> 16, k = i - j;
-                    const bool more = link != kBandNoLink && i - link <= cnt;
-                    const uint32_t wn = S[more ? link : kBand];
-                    const uint32_t x0 = load_u32(sdata, q + deep) ^ own2_lo, x1 = load_u32(sdata, q + deep + 4u) ^ own2_hi;
-                    const uint32_t x2 = load_u32(sdata, q + deep + 8u) ^ own3_lo, x3 = load_u32(sdata, q + deep + 12u) ^ own3_hi;
-                    if (walking) {
-                        if (k > kShortChain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
-                        uint32_t len = (x0 | x1) ? deep + (band_ctz64(x0, x1) >> 3) : (x2 | x3) ? deep + 8u + (band_ctz64(x2, x3) >> 3) : match_len_from(sdata, q, p, deep + 16u, max_len);
-                        len = len < max_len ? len : max_len;
-                        if (len > best) { best = len; best_pos = q; }
-                        walking = more && best < nice;
-                        j = link; w = wn;
+                    uint32_t wv[kP2Batch], nv = walking ? 1u : 0u;
+                    wv[0] = w;
+                    bool more = walking;
+#pragma unroll
+                    for (uint32_t h = 1; h < kP2Batch; h++) {
+                        const uint32_t link = wv[h - 1u] >> 16;
+                        more = more && i - link <= cnt;                             // (kBandNoLink: i - link wraps far beyond any count)
+                        wv[h] = S[more ? link : kBand];
+                        nv += more ? 1u : 0u;
                     }
+                    const uint32_t link_n = wv[kP2Batch - 1u] >> 16;
+                    const bool more_n = more && i - link_n <= cnt;
+                    const uint32_t wn = S[more_n ? link_n : kBand];             // the next batch's first
+                    // compare + fold, sharer by sharer: the five dwords that hold its sixteen bytes, the length by minimum over the four words'
+                    // first differing bits -- no branch (with one, the compiler reads the upper eight bytes only where the lower eight agree,
+                    // behind a wait of their own)
+                    bool alive = walking;
+                    uint32_t jh = j;
+#pragma unroll
+                    for (uint32_t h = 0; h < kP2Batch; h++) {
+                        const uint32_t q = band_pos(wv[h]), sh = (q + deep) & 3u;
+                        const uint32_t* d = reinterpret_cast<const uint32_t*>(sdata) + ((q + deep) >> 2);
+                        const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4];
+                        uint32_t t0, t1, t2, t3;
+                        asm("v_ffbl_b32 %0, %1" : "=v"(t0) : "v"(__builtin_amdgcn_alignbyte(d1, d0, sh) ^ own2_lo));   // 0xffffffff for 0
+                        asm("v_ffbl_b32 %0, %1" : "=v"(t1) : "v"(__builtin_amdgcn_alignbyte(d2, d1, sh) ^ own2_hi));
+                        asm("v_ffbl_b32 %0, %1" : "=v"(t2) : "v"(__builtin_amdgcn_alignbyte(d3, d2, sh) ^ own3_lo));
+                        asm("v_ffbl_b32 %0, %1" : "=v"(t3) : "v"(__builtin_amdgcn_alignbyte(d4, d3, sh) ^ own3_hi));
+                        const uint32_t tm = min(min(t0, t1 | 32u), min(t2 | 64u, t3 | 96u));       // first differing bit of the 128
+                        bool v = alive && h < nv;
+                        if (!halo_links) { slow = slow || (v && jh < kBand); v = v && jh >= kBand; }   // into a halo of another format: the plain walk, from the start
+                        uint32_t l = deep + (tm >> 3);
+                        if (v && tm == 0xffffffffu) l = match_len_from(sdata, q, p, deep + 16u, max_len);   // (~1 in 2 000 visits)
+                        l = l < max_len ? l : max_len;
+                        if (v && i - jh > kShortChain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
+                        if (v && l > best) { best = l; best_pos = q; }
+                        alive = v && best < nice;
+                        jh = wv[h] >> 16;
+                    }
+                    walking = alive && more_n;
+                    j = link_n; w = wn;
                 }
                 uint32_t e128 = entry_pack(best, p - best_pos), e32 = snap != 0xffffffffu ? snap : e128;
                 if (slow) {

@@ -2731,7 +2731,7 @@ hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /*
             uint32_t h[64];
             ZWZ_TRY(hipStreamSynchronize(s));
             ZWZ_TRY(hipMemcpy(h, a.tickets, sizeof h, hipMemcpyDeviceToHost));
-            fprintf(stderr, "ZWZ_BAND_TIMES n=%u copy=%u scan=%u build=%u count=%u order=%u pass1=%u compact=%u pass2=%u flush=%u ticket=%u\n", a.n, h[16], h[17], h[18], h[19], h[24], h[20], h[25], h[21], h[22], h[23]);
+            fprintf(stderr, "ZWZ_BAND_TIMES n=%u copy=%u scan=%u build=%u count=%u order=%u pass1=%u compact=%u pass2=%u pass2_half=%u flush=%u ticket=%u\n", a.n, h[16], h[17], h[18], h[19], h[24], h[20], h[25], h[21], h[26], h[22], h[23]);
         }
     }
     if (ev) ZWZ_TRY(hipEventRecord(ev[2], s));
