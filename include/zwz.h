@@ -337,6 +337,74 @@ int zwz_deflate_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const u
  * position carry from slice to slice).  dst is written as <dst>.part and renamed only on success; on failure no dst is left. */
 int zwz_deflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst);
 
+/* ---- ZIP archives ---------------------------------------------------------------------------------------------------------------
+ * One raw DEFLATE stream per entry, a CRC-32 per entry and a directory at the end: what unzip, Python's zipfile and every file manager
+ * open.  Written here: method 8 always; the data of entry i is, byte for byte, zwz_deflate_streams_dev's ZWZ_WRAP_RAW stream of buffer i
+ * (an empty buffer is 03 00); the header fields are fixed (csrc/zip_core.h has the table), so an archive's bytes are a function of its
+ * entries alone; ZIP64 records appear where a size, an offset or the count needs them (>= 0xFFFFFFFF, >= 0xFFFF entries), or everywhere
+ * with the context option "zip_force_zip64" = "1" (default "0"; "" restores it).  Read here: methods 0 (stored) and 8, ZIP64, data
+ * descriptors (sizes and CRC come from the central directory), archive comments.  Not supported: data prepended to the archive,
+ * multi-disk archives, encryption, other methods, appending; on the writing side symlinks, empty directories and storing what deflate
+ * does not shrink. */
+typedef struct zwz_zip_entry {        /* one central-directory record, as zwz_zip_index reads it */
+    uint64_t header_off, data_off;    /* local header; first byte of the entry's data (from the LOCAL header's name and extra lengths) */
+    uint64_t csize, usize;            /* ZIP64 extra field applied */
+    uint64_t name_off;                /* the name's bytes inside the archive (the central directory's copy) */
+    uint32_t crc32, external_attr;
+    uint16_t name_len, method, flags, dos_time, dos_date, made_by;
+} zwz_zip_entry;
+typedef struct zwz_zip_meta { uint16_t dos_time, dos_date; uint32_t external_attr; } zwz_zip_meta;
+typedef enum zwz_zip_entry_status {   /* beyond 0..3 (zwz_inflate_status) */
+    ZWZ_ZIP_UNSUPPORTED = 48,    /* method other than 0 / 8, or encrypted (flag bit 0): nothing read or written */
+    ZWZ_ZIP_BAD_ENTRY = 49,      /* data range outside the archive, or stored with csize != usize */
+    ZWZ_ZIP_SIZE_MISMATCH = 50,  /* decodes to fewer or more bytes than usize */
+    ZWZ_ZIP_CRC_MISMATCH = 51
+} zwz_zip_entry_status;
+/* Host only (no GPU), with zwz_bgzf_index's convention: e == NULL counts; fewer than *n_entries entries of cap is ZWZ_E_INVALID
+ * (*n_entries still set).  Finds the end record behind an archive comment of up to 65535 bytes, follows the ZIP64 locator and record,
+ * reads every central record (ZIP64 extra field 0x0001 applied, other extra fields skipped) and every local header (signature; data_off).
+ * ZWZ_E_FORMAT, zwz_last_error() naming the entry and the byte offset: no end record, a disk number other than 0, a record or name
+ * past the archive, a wrong signature, a count that disagrees with the records present, a local header or data range outside
+ * [0, directory start), a stated directory offset that is not where the directory is (prepended data).  An unsupported method or
+ * encryption is not an index error: it is that entry's status in zwz_unzip_dev. */
+int zwz_zip_index(const uint8_t *zip, uint64_t n, zwz_zip_entry *e, uint32_t cap, uint32_t *n_entries);
+/* Worst-case archive bytes for n buffers of these lengths under these names; needs no GPU. */
+uint64_t zwz_zip_bound(const uint64_t *in_len, const char *const *names, uint32_t n);
+/* n buffers in device memory -> one complete archive at d_out: local header and data of entry 0 .. n-1 tightly packed, the central
+ * directory, the end records.  in_off, in_len, names (NUL-terminated, 1..65535 bytes, stored as they are; flag 0x0800 iff a byte is
+ * >= 0x80) and meta are HOST arrays and may be reused when the call returns; meta == NULL: time 0, date 0x0021 (1980-01-01), attribute
+ * 0100644 << 16.  d_in, d_out and every in_off[i] are multiples of 16; buffer i is readable up to its length rounded up to 16.
+ * *d_out_len (device) receives the length the archive needs, whether it fitted or not, and *d_status (device) 0, or 3 when that is
+ * more than out_cap: the contents are then undefined and nothing outside [0, out_cap) is written.  out_cap >= zwz_zip_bound(...) never
+ * overflows.  Asynchronous on the context's stream.  The entries are compressed as gzip streams into staging the context keeps (about
+ * the input's size again) and copied to their places from there.  ZWZ_E_INVALID for a name of length 0 or above 65535, a misaligned
+ * pointer or offset, a null pointer. */
+int zwz_zip_dev(zwz_ctx *ctx, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len, const char *const *names,
+                const zwz_zip_meta *meta, uint32_t n, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_len, uint32_t *d_status);
+/* The archive in device memory (d_zip 16-byte aligned, readable up to zip_len rounded up to 16, never read past that) and n entries
+ * of zwz_zip_index, or any others, in HOST memory.  Entry i decodes to d_out + out_off[i] (host array, multiples of 16): the range
+ * holds exactly entries[i].usize bytes and no byte outside it is ever written.  d_out_len[i] (device u64): the bytes decoded.
+ * d_status[i] (device): 0 or the first of ZWZ_ZIP_UNSUPPORTED, ZWZ_ZIP_BAD_ENTRY, ZWZ_STREAM_TOO_LARGE (a DEFLATED entry with csize >=
+ * 2^29 or usize >= 2^32: zwz_inflate_split_streams_dev's limits; stored entries have none), inflate's 1 / 2, ZWZ_ZIP_SIZE_MISMATCH
+ * (inflate's overflow status 3 included), ZWZ_ZIP_CRC_MISMATCH.  d_segments (device, may be NULL): as zwz_inflate_split_streams_dev
+ * reports it -- an entry this library wrote has a flush point every 65280 bytes and is decoded a wave per piece --, 0 for stored
+ * entries.  Data moves and the CRC-32 are dealt by tiles of 65280 bytes, never by entry.  NOT asynchronous, exactly as
+ * zwz_inflate_split_streams_dev (zwz_ctx_sync before reading results). */
+int zwz_unzip_dev(zwz_ctx *ctx, const uint8_t *d_zip, uint64_t zip_len, const zwz_zip_entry *entries, uint32_t n, uint8_t *d_out,
+                  const uint64_t *out_off, uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_segments);
+/* The regular files under src_dir (no symlinks, no empty directories) as one archive: names relative to src_dir with '/', in bytewise
+ * name order; time and date from st_mtime in local time (year clamped to 1980..2107, seconds halved), attribute st_mode << 16.  Files
+ * pass through pinned staging in slices of whole files of "zip_slice_bytes" (context option, default 268435456; a larger file is a
+ * slice of its own); reading, the GPU and writing overlap; the central directory is kept on the host and written at the end.  An
+ * empty directory gives the valid 22-byte archive.  Written as <dst_zip>.part and renamed on success only. */
+int zwz_zip_dir(zwz_ctx *ctx, const char *src_dir, const char *dst_zip);
+/* Extracts an archive below dst_dir (created if missing), in slices of consecutive entries by the same option.  Before anything is
+ * created every name is checked: an empty or absolute name, a `..` component, a backslash, a NUL or a duplicate is ZWZ_E_FORMAT naming
+ * the entry; so is a deflated entry above zwz_unzip_dev's limits.  A name ending in '/' with size 0 is a directory.  Files get mode
+ * (external_attr >> 16) & 0777 when made_by's high byte is 3 and that is not zero, and the entry's time.  An entry whose status is not
+ * 0 ends the call after its slice: ZWZ_E_CHECKSUM for a CRC or size mismatch, ZWZ_E_FORMAT otherwise; its file is not left behind. */
+int zwz_unzip_file(zwz_ctx *ctx, const char *src_zip, const char *dst_dir);
+
 #ifdef __cplusplus
 }
 #endif

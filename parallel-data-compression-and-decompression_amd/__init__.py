@@ -21,6 +21,10 @@ and ordinary DEFLATE data of any size, a batch of independent streams in one lau
     Codec.inflate_stream_file                                  (one file of any size, in slices; `main gunzip`)
     Codec.deflate_streams / Codec.deflate_streams_dev          (the way there: libz's level-6 full-flush streams, any size)
     Codec.deflate_stream_file, deflate_stream_bound            (one file as one .gz / zlib / raw stream)
+and ZIP archives, a batch of entries per launch (what unzip, zipfile and file managers open; no reference counterpart):
+    Codec.zip / Codec.unzip                                    ([(name, bytes)] -> archive bytes and back)
+    Codec.zip_dev / Codec.unzip_dev                            (device tensors)
+    Codec.zip_dir / Codec.unzip_file, zip_index, zip_bound     (a directory as one .zip and back; the host-only index)
 
 There is no CPU fallback: importing works anywhere (so the build can be checked), but every codec
 call needs the HIP library and a GPU and raises ZwzError otherwise.
@@ -104,6 +108,13 @@ def lib():
         L.zwz_deflate_stream_bound.argtypes = [u64, c.c_int]
         L.zwz_deflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         L.zwz_deflate_stream_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
+        L.zwz_zip_index.argtypes = [vp, u64, vp, u32, c.POINTER(u32)]
+        L.zwz_zip_bound.restype = u64
+        L.zwz_zip_bound.argtypes = [vp, vp, u32]
+        L.zwz_zip_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, u64, vp, vp]
+        L.zwz_unzip_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, vp, vp]
+        L.zwz_zip_dir.argtypes = [vp, c.c_char_p, c.c_char_p]
+        L.zwz_unzip_file.argtypes = [vp, c.c_char_p, c.c_char_p]
         _lib = L
     return _lib
 
@@ -120,6 +131,21 @@ WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP}
 STREAM_END, STREAM_NEED_INPUT, STREAM_DATA_ERROR, STREAM_OVERFLOW = 0, 1, 2, 3
 STREAM_BAD_HEADER, STREAM_CHECKSUM, STREAM_LENGTH, STREAM_TRAILING, STREAM_TOO_LARGE = 32, 33, 34, 35, 36
 STREAM_MAX_IN, STREAM_MAX_OUT = 1 << 29, 1 << 32
+# per-entry status of zwz_unzip_dev beyond the inflate codes and STREAM_TOO_LARGE (include/zwz.h)
+ZIP_UNSUPPORTED, ZIP_BAD_ENTRY, ZIP_SIZE_MISMATCH, ZIP_CRC_MISMATCH = 48, 49, 50, 51
+
+
+class ZipEntry(ctypes.Structure):
+    """zwz_zip_entry: one central-directory record as zip_index reads it."""
+    _fields_ = [("header_off", ctypes.c_uint64), ("data_off", ctypes.c_uint64), ("csize", ctypes.c_uint64), ("usize", ctypes.c_uint64),
+                ("name_off", ctypes.c_uint64), ("crc32", ctypes.c_uint32), ("external_attr", ctypes.c_uint32), ("name_len", ctypes.c_uint16),
+                ("method", ctypes.c_uint16), ("flags", ctypes.c_uint16), ("dos_time", ctypes.c_uint16), ("dos_date", ctypes.c_uint16),
+                ("made_by", ctypes.c_uint16)]
+
+
+class ZipMeta(ctypes.Structure):
+    """zwz_zip_meta: what an entry's headers say beyond name, sizes and CRC."""
+    _fields_ = [("dos_time", ctypes.c_uint16), ("dos_date", ctypes.c_uint16), ("external_attr", ctypes.c_uint32)]
 
 
 def _check(rc, what, **extra):
@@ -377,6 +403,103 @@ class Codec:
         """One file of any size as one gzip (.gz), zlib or raw DEFLATE stream, streamed through the GPU in slices."""
         _check(lib().zwz_deflate_stream_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst)), "zwz_deflate_stream_file")
 
+    # ---- ZIP archives (include/zwz.h: zwz_zip_*) ------------------------------------------------
+    def zip_dev(self, d_in, in_off, in_len, names, d_out, d_out_len, d_status, meta=None, out_cap=None):
+        """zwz_zip_dev: d_in / d_out uint8 device tensors, d_out_len an int64 and d_status an int32 device tensor of one element;
+        in_off, in_len HOST sequences; names a list of bytes (or str, stored as UTF-8); meta None or a list of (dos_time, dos_date,
+        external_attr).  Asynchronous; an archive that does not fit out_cap (default: d_out's size) is status 3, never an exception."""
+        import numpy as np
+        off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        ln = np.ascontiguousarray(in_len, dtype=np.uint64)
+        n = len(names)
+        if off.size != n or ln.size != n or (meta is not None and len(meta) != n):
+            raise ValueError("in_off, in_len, names and meta must have one entry per buffer")
+        c_names = _c_names(names)
+        c_meta = (ZipMeta * max(n, 1))(*[ZipMeta(*m) for m in meta]) if meta is not None else None
+        _check(lib().zwz_zip_dev(self._h, d_in.data_ptr() if n else None, off.ctypes.data, ln.ctypes.data, c_names, c_meta, n, d_out.data_ptr(),
+                                 d_out.numel() if out_cap is None else out_cap, d_out_len.data_ptr(), d_status.data_ptr()), "zwz_zip_dev")
+
+    def zip(self, entries, meta=None):
+        """[(name, bytes)] -> the bytes of one ZIP archive, every entry deflated on the GPU in one pass."""
+        import numpy as np
+        import torch
+        entries = [(n, bytes(b)) for n, b in entries]
+        n = len(entries)
+        dev = torch.device("cuda", self.device)
+        up = lambda a: (a + 15) // 16 * 16
+        lens = np.array([len(b) for _, b in entries], dtype=np.int64)
+        offs = np.zeros(n, dtype=np.int64)
+        if n:
+            offs[1:] = np.cumsum(up(lens[:-1]))
+        blob = np.zeros(max(int(offs[-1] + up(lens[-1])) if n else 0, 16), dtype=np.uint8)
+        for i, (_, b) in enumerate(entries):
+            blob[offs[i]:offs[i] + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        names = [e[0] for e in entries]
+        cap = zip_bound(lens, names)
+        d_in = torch.from_numpy(blob).to(dev)
+        d_out = torch.empty(up(cap), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.zip_dev(d_in, offs, lens, names, d_out, d_len, d_st, meta, cap)
+        self.sync()
+        if int(d_st.item()) != 0:
+            raise ZwzError("zwz_zip_dev: status %d, %d bytes needed above the bound of %d" % (int(d_st.item()), int(d_len.item()), cap))
+        return d_out[:int(d_len.item())].cpu().numpy().tobytes()
+
+    def unzip_dev(self, d_zip, zip_len, entries, d_out, out_off, d_out_len, d_status, d_segments=None):
+        """zwz_unzip_dev: d_zip / d_out uint8 device tensors; entries a ctypes array of ZipEntry (zip_index's) and out_off a HOST
+        sequence; d_out_len int64, d_status and d_segments int32 device tensors.  Waits for the context's stream while it runs; the
+        results are complete after sync().  Never raises for an entry's status."""
+        import numpy as np
+        n = len(entries)
+        off = np.ascontiguousarray(out_off, dtype=np.uint64)
+        if off.size != n:
+            raise ValueError("out_off must have one entry per entry")
+        _check(lib().zwz_unzip_dev(self._h, d_zip.data_ptr(), zip_len, ctypes.addressof(entries) if n else None, n, d_out.data_ptr(), off.ctypes.data,
+                                   d_out_len.data_ptr(), d_status.data_ptr(), d_segments.data_ptr() if d_segments is not None else None),
+               "zwz_unzip_dev")
+
+    def unzip(self, data, with_segments=False):
+        """ZIP archive bytes -> [(name bytes, decoded bytes, status)] in directory order; status 0 or a verdict (ZIP_*, STREAM_*, 1, 2)
+        with whatever was decoded.  with_segments: a fourth item, the pieces decoded in parallel."""
+        import numpy as np
+        import torch
+        data = bytes(data)
+        ents = zip_index(data)
+        n = len(ents)
+        if n == 0:
+            return []
+        dev = torch.device("cuda", self.device)
+        up = lambda a: (a + 15) // 16 * 16
+        ooff, total = [], 0
+        for e in ents:
+            ooff.append(total)
+            total += up(e.usize)
+        d_zip = _device_input(torch, data, self.device)
+        d_out = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_seg = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.unzip_dev(d_zip, len(data), ents, d_out, ooff, d_len, d_st, d_seg)
+        self.sync()
+        host, olen, st, seg = d_out.cpu().numpy(), d_len.cpu().numpy(), d_st.cpu().numpy(), d_seg.cpu().numpy()
+        out = []
+        for i, e in enumerate(ents):
+            item = (data[e.name_off:e.name_off + e.name_len], host[ooff[i]:ooff[i] + int(olen[i])].tobytes(), int(st[i]))
+            out.append(item + (int(seg[i]),) if with_segments else item)
+        return out
+
+    def zip_dir(self, src_dir, dst_zip):
+        """The regular files under src_dir as one ZIP archive (zwz_zip_dir; `main zip`); dst_zip appears only on success."""
+        _check(lib().zwz_zip_dir(self._h, os.fsencode(src_dir), os.fsencode(dst_zip)), "zwz_zip_dir")
+
+    def unzip_file(self, src_zip, dst_dir):
+        """Extracts src_zip below dst_dir (zwz_unzip_file; `main unzip`).  ZwzError with status E_FORMAT / E_CHECKSUM on a damaged archive
+        or a name that would leave dst_dir."""
+        _check(lib().zwz_unzip_file(self._h, os.fsencode(src_zip), os.fsencode(dst_dir)), "zwz_unzip_file")
+
     # ---- directory level -----------------------------------------------------------------------
     def do_compression(self, input_dir, output_dir, file_record, world_rank, world_size=1):
         _check(lib().zwz_compress_dir(self._h, os.fsencode(input_dir), os.fsencode(output_dir), os.fsencode(file_record),
@@ -532,6 +655,12 @@ def _device_input(torch, data, device):
     return buf.to(torch.device("cuda", device))
 
 
+def _c_names(names):
+    """[bytes or str] -> a char*[] for the C ABI (the array keeps the byte strings alive)."""
+    raw = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in names]
+    return (ctypes.c_char_p * max(len(raw), 1))(*raw)
+
+
 def _ranges(np, ranges):
     """[(offset, length), ...] -> a C-contiguous (k, 2) uint64 array (ZwzError for a negative value)."""
     rows = [(int(a), int(b)) for a, b in ranges]
@@ -595,6 +724,35 @@ def inflate_stream_file(src, dst, wrap="gzip"):
 def deflate_stream_bound(n, wrap="gzip"):
     """Worst-case size of one stream of n input bytes from Codec.deflate_streams (about 1.0009 n); needs no GPU."""
     return lib().zwz_deflate_stream_bound(n, WRAPS.get(wrap, wrap))
+
+
+def zip_index(data):
+    """The entries of a ZIP archive in memory, walked on the host (no GPU): a ctypes array of ZipEntry in directory order.  ZwzError
+    with status E_FORMAT names the entry and the byte offset."""
+    data = bytes(data)
+    count = ctypes.c_uint32(0)
+    _check(lib().zwz_zip_index(data, len(data), None, 0, ctypes.byref(count)), "zwz_zip_index")
+    ents = (ZipEntry * count.value)()
+    if count.value:
+        _check(lib().zwz_zip_index(data, len(data), ctypes.addressof(ents), count.value, ctypes.byref(count)), "zwz_zip_index")
+    return ents
+
+
+def zip_bound(lengths, names):
+    """Worst-case archive size for buffers of these lengths under these names; needs no GPU."""
+    import numpy as np
+    ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+    if ln.size != len(names):
+        raise ValueError("one length per name")
+    return lib().zwz_zip_bound(ln.ctypes.data, _c_names(names), len(names))
+
+
+def zip_dir(src_dir, dst_zip):
+    _codec().zip_dir(src_dir, dst_zip)
+
+
+def unzip_file(src_zip, dst_dir):
+    _codec().unzip_file(src_zip, dst_dir)
 
 
 def bgzf_bound(n):

@@ -339,9 +339,27 @@ int bgzf_main(const std::string& op, const char* src, const char* dst, int world
     return 0;
 }
 
+// `main zip <src dir> <dst.zip>` / `main unzip <src.zip> <dst dir>`: a directory as one ZIP archive and back, one process, one GPU.
+// Exit codes as bgzf_main's.
+int zip_main(const std::string& op, const char* src, const char* dst, int world_size, int device) {
+    if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", op.c_str(), world_size); return 1; }
+    const auto t0 = std::chrono::steady_clock::now();
+    zwz_ctx* ctx = nullptr;
+    int rc = zwz_ctx_create(device, 0, &ctx);
+    if (rc == ZWZ_OK) rc = op == "zip" ? zwz_zip_dir(ctx, src, dst) : zwz_unzip_file(ctx, src, dst);
+    zwz_ctx_destroy(ctx);
+    if (rc != ZWZ_OK) {
+        fprintf(stderr, "%s %s: %s (%s)\n", op.c_str(), src, zwz_strerror(rc), zwz_last_error());
+        return rc == ZWZ_E_CHECKSUM ? 2 : 1;
+    }
+    printf("%s %s -> %s in %.3f s\n", op.c_str(), src, dst, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}
+
 void bgzf_usage(const char* argv0) {
     fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n"
-            "       %s gzip <src> <dst> [--zlib|--raw]\n       %s gunzip <src> <dst> [--zlib|--raw]\n", argv0, argv0, argv0, argv0, argv0);
+            "       %s gzip <src> <dst> [--zlib|--raw]\n       %s gunzip <src> <dst> [--zlib|--raw]\n       %s zip <src dir> <dst.zip>\n       %s unzip <src.zip> <dst dir>\n",
+            argv0, argv0, argv0, argv0, argv0, argv0, argv0);
 }
 
 // `main gzip <src file> <dst file> [--zlib|--raw]`: one file as one ordinary gzip (zlib, raw DEFLATE) stream, one process, one GPU.
@@ -516,6 +534,11 @@ int main(int argc, char* argv[]) {
     if (operation == "gzip" || operation == "gunzip") {
         int n = 0;
         return gzip_main(argc, argv, world_size, zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0);
+    }
+    if (operation == "zip" || operation == "unzip") {
+        int n = 0;
+        if (argc != 4) { bgzf_usage(argv[0]); return 1; }
+        return zip_main(operation, argv[2], argv[3], world_size, zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0);
     }
     if (operation == "bgzip" || operation == "bgunzip") {
         int n = 0;

@@ -245,6 +245,7 @@ int zwz_ctx_create(int device, uint32_t max_batch, zwz_ctx** out) {
         if (const char* v = getenv(var)) if (zwz_ctx_set_option(c, option, v) != ZWZ_OK) fprintf(stderr, "zwz: %s=%s is not a value of option \"%s\": ignored\n", var, v, option);
     };
     from_env("ZWZ_MATCH", "match"); from_env("ZWZ_PLAN", "plan"); from_env("ZWZ_INFLATE_HEADER", "inflate_header");
+    from_env("ZWZ_ZIP_SLICE_BYTES", "zip_slice_bytes"); from_env("ZWZ_ZIP_FORCE_ZIP64", "zip_force_zip64");       // (for `main zip` / `main unzip`)
     from_env("ZWZ_SPLIT_SLICE_BYTES", "split_slice_bytes");      // (for `main gunzip`: the slice of zwz_inflate_stream_file)
     const bool tl = getenv("ZWZ_TIMELINE") != nullptr || getenv("ZWZ_VERBOSE") != nullptr;
     const auto t_create = std::chrono::steady_clock::now();
@@ -323,6 +324,13 @@ int zwz_ctx_set_option(zwz_ctx* c, const char* name, const char* value) {
         if (n == "split_min_bytes") c->split_min_bytes = v.empty() ? kSplitMinBytes : (uint32_t)x;
         else if (n == "split_budget") { if (!v.empty() && x < 16) return ZWZ_E_INVALID; c->split_budget = v.empty() ? kSplitBudget : (uint32_t)x; }
         else { if (!v.empty() && x < 2) return ZWZ_E_INVALID; c->split_max_candidates = v.empty() ? kSplitMaxCandidates : (uint32_t)x; }
+    } else if (n == "zip_force_zip64") {
+        if (v == "0" || v.empty()) c->zip_force_zip64 = 0; else if (v == "1") c->zip_force_zip64 = 1; else return ZWZ_E_INVALID;
+    } else if (n == "zip_slice_bytes") {
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v.c_str(), &end, 10);
+        if (!v.empty() && (*end || end == v.c_str() || x < 4096 || x > (1ull << 40))) return ZWZ_E_INVALID;
+        c->zip_slice_bytes = v.empty() ? 268435456ull : x;
     } else return ZWZ_E_INVALID;
     return ZWZ_OK;
 }
@@ -333,6 +341,7 @@ void zwz_ctx_destroy(zwz_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (Buffer& b : c->buf) b.release();
     if (c->ds_copied) (void)hipEventDestroy(c->ds_copied);
+    if (c->zip_copied) (void)hipEventDestroy(c->zip_copied);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_inf) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -32,9 +32,12 @@ enum BufId {
     kBufPieces,          // stream deflate (zwz_dstream.cpp): slots and per-piece arrays
     kBufStreamsDev,      // stream deflate: the per-stream arrays of one call, and their pinned twin
     kBufSplit0, kBufSplit1, kBufSplit2,      // split inflate (zwz_split.cpp): per stream and scan tile / per candidate / per chain segment and checksum piece
+    kBufZipStage,        // ZIP (zwz_zip.cpp): the entries' gzip streams on the way in, their gathered data on the way out
+    kBufZipDev,          // ZIP: the per-entry and per-tile arrays of one call, and their pinned twin
     kNumDeviceBufs,
     kBufStageHost = kNumDeviceBufs, kBufRangeHost, kBufStreamsHost,
     kBufSplitHost,       // split inflate: the per-stream arrays a call uploads (read by copies that may still be queued when it returns)
+    kBufZipHost,
     kNumBufs
 };
 
@@ -61,6 +64,10 @@ struct zwz_ctx {
     // split inflate (zwz_split.cpp): options "split_min_bytes", "split_budget", "split_max_candidates" (split_core.h's defaults)
     uint32_t split_min_bytes = zwz::kSplitMinBytes, split_budget = zwz::kSplitBudget, split_max_candidates = zwz::kSplitMaxCandidates;
     uint32_t split_slice_bytes = zwz::kSplitSliceBytes;      // zwz_inflate_stream_file: "split_slice_bytes"
+    // ZIP (zwz_zip.cpp): options "zip_force_zip64" and "zip_slice_bytes"; the last call's copy out of kBufZipHost has run
+    uint32_t zip_force_zip64 = 0;
+    uint64_t zip_slice_bytes = 268435456ull;
+    hipEvent_t zip_copied = nullptr;
     // Every allocation that outlives a call: grown lazily to the largest call seen (Buffer::reserve), released by zwz_ctx_destroy
     zwz::Buffer buf[zwz::kNumBufs];
     zwz_ctx() { for (int i = zwz::kNumDeviceBufs; i < zwz::kNumBufs; i++) buf[i].pinned = true; }
