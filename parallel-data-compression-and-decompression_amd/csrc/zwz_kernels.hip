@@ -1980,7 +1980,7 @@ static __device__ __forceinline__ uint32_t wave_dyn_lengths(const uint8_t* ring,
         const uint32_t e = cl_fast[bits & 127u], l = e & 15u, sym = e >> 4;
         const uint32_t xb = sym < 16u ? 0u : sym == 16u ? 2u : sym == 17u ? 3u : 7u, nb = l + xb;
         const uint32_t xv = (bits >> l) & ((1u << xb) - 1u);
-        const bool bad = e == 0u || a + nb > total_bits;
+        const bool bad = e == 0u || (uint64_t)bp + lane + nb > total_bits;     // (64 bits: total_bits reaches 2^32 - 8, and bp + lane + nb then wraps)
         // the real symbols: the orbit of offset 0 under "offset + bits of the symbol decoded there"
         const uint32_t jr = lane + (nb ? nb : 1u);               // (strictly forward whatever the table holds: the hop below must end)
         uint64_t M = 0; uint32_t at = 0;
@@ -2265,7 +2265,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                 // (a lane's four slots are 64 bits apart: the same byte alignment and bit shift, eight bytes on -- ONE address and nine
                 // consecutive dwords serve all four, where four separate fetches were twelve reads and four address computations)
                 uint32_t inf[kWinSlots];
-                const uint32_t near_end_s = __builtin_amdgcn_readfirstlane((uint32_t)(bp + wb + 64u * kWinSlots + 64u > total_bits));   // can a symbol of this window reach past the payload?  (a symbol is < 64 bits)
+                const uint32_t near_end_s = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)bp + wb + 64u * kWinSlots + 64u > total_bits));   // can a symbol of this window reach past the payload?  (a symbol is < 64 bits)
                 const uint32_t a0 = bp + wb + lane;
                 const uint32_t byte0 = (a0 >> 3) & (kInfRing - 1u);
                 uint32_t wd[2u * kWinSlots + 1u];

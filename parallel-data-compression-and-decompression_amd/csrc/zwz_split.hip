@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(kResolveThreads) split_resolve_kernel(SplitStr
         const uint64_t before = carry + sh_sum[t] - cnt;
         if (on) {
             C.rank[k] = ncarry + sh_cnt[t] - 1u;
-            C.ostart[k] = before < kSplitMeasureCap ? (uint32_t)before : kSplitMeasureCap;
+            C.ostart[k] = (uint32_t)min<uint64_t>(before, 0xffffffffull);      // (saturates only in a chain whose counts pass the capacity: not decoded)
             atomicMax(&sh_last, k - k0);
             if (partial && C.meas[k].x != kSegBad && before + cnt <= pcap) {     // (a prefix: only a chain's last segment is kSegBad, the sums ascend)
                 atomicAdd(&sh_nok, 1u); atomicAdd(&sh_sumok, (unsigned long long)cnt); atomicMax(&sh_lastok, k - k0);
@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(kResolveThreads) split_resolve_kernel(SplitStr
     }
     const uint4 end = C.meas[k0 + sh_last];
     const uint32_t nin = (uint32_t)S.in_len[s];
-    bool ok = end.x == kSegFinal && ncarry >= 2u && carry <= S.out_cap[s] && carry < kSplitMeasureCap - 16u;
+    bool ok = end.x == kSegFinal && ncarry >= 2u && carry <= S.out_cap[s] && carry <= 0xffffffffull;      // (every capacity the call accepts, 2^32 - 1 included: kSplitMeasureCap bounds one segment, not the stream)
     uint32_t expect = 0;
     if (ok) ok = split_trailer_ok(S.wrap, S.in + S.in_off[s], nin, end.y, (uint32_t)carry, &expect);
     res[s] = ok ? make_uint4(1u, ncarry, (uint32_t)carry, expect) : make_uint4(0, 0, 0, 0);

@@ -14,6 +14,8 @@ and drops the bytes decoded before it, which the acceptance compares, and which 
 """
 import ctypes
 
+import numpy as np
+
 import libz_ref
 
 RAW, ZLIB, GZIP = 0, 1, 2
@@ -36,16 +38,27 @@ def _status_of(msg):
     return DATA_ERROR
 
 
-def _decode_one(wbits, data, room):
-    """One inflate stream over data with at most room + 1 bytes of output -> (status, bytes, unused input).  libz's own z_stream (the
-    library Python's zlib module maps, through libz_ref): on an error the module hides what was decoded before it, and whether the
-    output had passed the cap by then decides between status 3 and the error."""
+def _first_nonzero(data, start):
+    """index of the first byte at or after start that is not zero, or len(data) (bytes.lstrip takes seconds over half a GiB)"""
+    v = np.frombuffer(data, dtype=np.uint8)
+    for o in range(start, len(data), 1 << 24):
+        c = v[o:o + (1 << 24)]
+        if c.any():
+            return o + int((c != 0).argmax())
+    return len(data)
+
+
+def _decode_one(wbits, data, room, start=0):
+    """One inflate stream over data[start:] with at most room + 1 bytes of output -> (status, bytes, where the unused input starts).
+    libz's own z_stream (the library Python's zlib module maps, through libz_ref): on an error the module hides what was decoded
+    before it, and whether the output had passed the cap by then decides between status 3 and the error.  libz reads the bytes
+    object in place (no copy: the streams at the 2^29 limit are half a GiB)."""
     z = libz_ref.lib()
     s = libz_ref.ZStream()
     assert z.inflateInit2_(ctypes.byref(s), wbits, z.zlibVersion(), ctypes.sizeof(s)) == libz_ref.Z_OK
-    inbuf = ctypes.create_string_buffer(data, len(data) or 1)
-    s.next_in = ctypes.cast(inbuf, ctypes.c_void_p)
-    s.avail_in = len(data)
+    inbuf = ctypes.c_char_p(data)                       # (kept alive, as `data` is, until the return)
+    s.next_in = ctypes.cast(inbuf, ctypes.c_void_p).value + start
+    s.avail_in = len(data) - start
     step = 1 << 20
     obuf = ctypes.create_string_buffer(step)
     out = bytearray()
@@ -58,15 +71,15 @@ def _decode_one(wbits, data, room):
             got = want - s.avail_out
             out += obuf.raw[:got]
             if len(out) > room:
-                return OVERFLOW, bytes(out[:room]), b""
+                return OVERFLOW, bytes(out[:room]), len(data)
             if rc == libz_ref.Z_STREAM_END:
-                return END, bytes(out), data[len(data) - s.avail_in:]
+                return END, bytes(out), len(data) - s.avail_in
             if rc == libz_ref.Z_NEED_DICT:
-                return BAD_HEADER, bytes(out), b""
+                return BAD_HEADER, bytes(out), len(data)
             if rc == libz_ref.Z_DATA_ERROR:
-                return _status_of((s.msg or b"").decode()), bytes(out), b""
+                return _status_of((s.msg or b"").decode()), bytes(out), len(data)
             if rc == libz_ref.Z_BUF_ERROR or s.avail_in == 0 and got < want:
-                return NEED_INPUT, bytes(out), b""
+                return NEED_INPUT, bytes(out), len(data)
     finally:
         z.inflateEnd(ctypes.byref(s))
 
@@ -81,28 +94,29 @@ def reference(wrap, data, cap):
     if wrap == ZLIB:
         st, out, _ = _decode_one(15, data, cap)
         return st, out
-    if not data.strip(b"\x00"):
+    if _first_nonzero(data, 0) == len(data):
         return NEED_INPUT, b""
     out = b""
-    rest = data
+    pos = 0
     first = True
     while True:
         if not first:
-            rest = rest.lstrip(b"\x00")
-            if not rest:
+            pos = _first_nonzero(data, pos)
+            if pos == len(data):
                 return END, out
-            if rest[:2] != b"\x1f\x8b":
+            if data[pos:pos + 2] != b"\x1f\x8b":
                 return TRAILING, out
-        st, got, rest = _decode_one(31, rest, cap - len(out))
+        st, got, pos = _decode_one(31, data, cap - len(out), pos)
         out += got
         if st != END:
             return st, out
         first = False
 
 
-def accept(wrap, data, cap, status, got):
-    """None if (status, got) meet the acceptance for this stream, else a string saying why not."""
-    want_st, want = reference(wrap, data, cap)
+def accept(wrap, data, cap, status, got, ref=None):
+    """None if (status, got) meet the acceptance for this stream, else a string saying why not.  ref: reference(wrap, data, cap) where
+    the caller has it already."""
+    want_st, want = ref or reference(wrap, data, cap)
     if status != want_st:
         return "status %d, reference %d" % (status, want_st)
     if status == END and got != want:
