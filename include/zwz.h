@@ -90,7 +90,9 @@ int zwz_ctx_sync(zwz_ctx *ctx);
  * of 16, and the slot readable up to its length rounded up to 16 (the kernels stream whole 16-byte
  * vectors; the extra bytes never influence a result).  Chunk i's result goes to
  * d_out + i * out_stride (out_stride % 16 == 0, >= 65536) with its length in d_out_len[i].
- * All pointers are device memory on the context's GPU. */
+ * All pointers are device memory on the context's GPU.
+ * Level (zwz_ctx_set_level): a chunk's deflate output is the first min(len, 65535) bytes of libz 1.2.11's level-N zlib stream of the
+ * chunk, N = the context's level (6 unless set; the header is 78 9c at 6, 78 5e at 4 and 5).  Inflate reads every level. */
 int zwz_deflate_batch_dev(zwz_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
                           uint32_t n, uint8_t *d_out, uint64_t out_stride, uint32_t *d_out_len);
 int zwz_inflate_batch_dev(zwz_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
@@ -174,6 +176,24 @@ int zwz_gather_shards(int rank, int nranks, const char *my_shard_path, const cha
  * decoder reads such shards.  The environment variables ZWZ_LOSSLESS=1 / ZWZ_CHUNK_SIZE=<n> do the same for the CLI. */
 int zwz_ctx_set_chunk_size(zwz_ctx *ctx, uint32_t bytes);
 
+/* The compression level of EVERY writer of this context -- zwz_deflate_batch(_dev), zwz_compress_dir, zwz_bgzf_compress_dev / _file,
+ * zwz_deflate_streams_dev / zwz_deflate_stream_file, zwz_zip_dev / zwz_zip_dir -- and of no reader.  4, 5 and 6 select libz 1.2.11's level of that
+ * number: the output is byte for byte what libz writes at it (deflateInit(level); gzip -N, bgzip -l N, zip -N).  0 restores the default, 6.
+ * Any other value is ZWZ_E_INVALID, zwz_last_error() says why, and the level stays what it was:
+ *   1-3  libz's deflate_fast skips hash insertions inside matches, so the chains depend on the parse and the position-parallel search does not hold;
+ *   7-9  need chains of 256-4096 candidates and max_lazy up to 258: past the 128-wide band, its key field and the 13-position parse step;
+ *   0    is a different encoder (stored blocks only).
+ * Levels 4 and 5 run level 6's algorithm (deflate_slow + longest_match) with smaller numbers -- good_length / max_lazy / nice_length / max_chain
+ * 4 / 4 / 16 / 16 and 8 / 16 / 32 / 32 against 8 / 16 / 128 / 128 -- about 3 % of ratio on text for less search; DESIGN.md section 20 has the
+ * measured table.  The default comes from the environment variable ZWZ_LEVEL, read once in zwz_ctx_create (a value that is not understood is
+ * reported on stderr and ignored).  Calls on a context are serialised by the caller, so the level may change between any two calls.
+ * Wrappers as libz writes them: the zlib header is 78 5e at 4 and 5 (FLEVEL 1) and 78 9c at 6; gzip, BGZF and ZIP headers do not depend on the
+ * level, nor do zwz_bgzf_bound, zwz_deflate_stream_bound and zwz_zip_bound (their worst case is stored blocks).
+ * For zwz_compress_dir a level other than 6 is opt-in and NOT bit-exact with the reference's shards, exactly like the chunk size: the container is
+ * unchanged, and the reference's decoder and `main decompress` read such shards.  zwz_ctx_level returns the current level. */
+int zwz_ctx_set_level(zwz_ctx *ctx, int level);
+int zwz_ctx_level(zwz_ctx *ctx);
+
 /* Test and diagnosis switches of one context; no reference counterpart (the reference's zlib has one code path,
  * compression.cpp:119-134 / decompression.cpp:16-36) and no effect on any byte produced -- they choose between kernels that compute
  * the same thing, so that tests can drive each of them and a device that fails a self-test at zwz_ctx_create still gets a codec:
@@ -193,7 +213,7 @@ int zwz_ctx_set_option(zwz_ctx *ctx, const char *name, const char *value);
  * Compression cuts the input into blocks of 65280 bytes (htslib's BGZF_BLOCK_SIZE; the last one shorter, none for an empty input)
  * and writes each as one gzip member: 1f 8b 08 04 | 00000000 | 00 ff | 06 00 | 'B' 'C' 02 00 | BSIZE-1 (u16 LE) | raw deflate |
  * CRC-32 (LE) | ISIZE (LE), the raw deflate being bytes [2, len - 4) of the block's zlib 1.2.11 level-6 stream (the bytes of
- * zwz_deflate_batch_dev), then the standard 28-byte EOF member.  Decompression accepts any BGZF: other extra subfields around BC,
+ * zwz_deflate_batch_dev; level-N under zwz_ctx_set_level(N) -- headers, block size and zwz_bgzf_bound do not change), then the standard 28-byte EOF member.  Decompression accepts any BGZF: other extra subfields around BC,
  * any deflate level, empty members anywhere (two BGZF files one after the other), a missing EOF member; it rejects (ZWZ_E_FORMAT,
  * zwz_last_error() naming the member and its byte offset) a member without BC, a BSIZE past the end, trailing bytes that are not
  * a member and ISIZE > 65535.  A CRC-32 or ISIZE mismatch is ZWZ_E_CHECKSUM.  All of it runs on the GPU but the header walk. */
@@ -319,6 +339,8 @@ int zwz_inflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char 
  * zwz_deflate_batch_dev), its last block made non-final and followed by an empty stored block (00 00 ff ff on a byte boundary), and
  * the stream ends with 03 00 and the trailer.  zlib: 78 9c ... Adler-32; gzip: 1f 8b 08 00 00 00 00 00 00 03 ... CRC-32, ISIZE; an
  * empty input is header, 03 00, trailer.  The pieces of one long stream are as parallel as a batch of short ones.
+ * Under zwz_ctx_set_level(N), N = 4 or 5, read "level N" for "level 6": the same full-flush structure of 65280-byte pieces, the zlib header 78 5e,
+ * the gzip header unchanged (XFL 0), the same bound.
  * Input i is in_len[i] bytes at d_in + in_off[i]; output i goes to d_out + out_off[i], at most out_cap[i] bytes.  d_out_len[i]
  * receives the length the stream needs, whether it fitted or not, and d_status[i] 0 or ZWZ_INF_OVERFLOW (3) when that is more than
  * out_cap[i]; what then lies in the range is undefined, and no byte outside [out_off[i], out_off[i] + out_cap[i]) is ever written.
@@ -340,7 +362,7 @@ int zwz_deflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char 
 /* ---- ZIP archives ---------------------------------------------------------------------------------------------------------------
  * One raw DEFLATE stream per entry, a CRC-32 per entry and a directory at the end: what unzip, Python's zipfile and every file manager
  * open.  Written here: method 8 always; the data of entry i is, byte for byte, zwz_deflate_streams_dev's ZWZ_WRAP_RAW stream of buffer i
- * (an empty buffer is 03 00); the header fields are fixed (csrc/zip_core.h has the table), so an archive's bytes are a function of its
+ * (an empty buffer is 03 00), at the context's level (zwz_ctx_set_level; flags, versions and zwz_zip_bound do not depend on it); the header fields are fixed (csrc/zip_core.h has the table), so an archive's bytes are a function of its
  * entries alone; ZIP64 records appear where a size, an offset or the count needs them (>= 0xFFFFFFFF, >= 0xFFFF entries), or everywhere
  * with the context option "zip_force_zip64" = "1" (default "0"; "" restores it).  Read here: methods 0 (stored) and 8, ZIP64, data
  * descriptors (sizes and CRC come from the central directory), archive comments.  Not supported: data prepended to the archive,

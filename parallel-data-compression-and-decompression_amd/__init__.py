@@ -26,6 +26,9 @@ and ZIP archives, a batch of entries per launch (what unzip, zipfile and file ma
     Codec.zip_dev / Codec.unzip_dev                            (device tensors)
     Codec.zip_dir / Codec.unzip_file, zip_index, zip_bound     (a directory as one .zip and back; the host-only index)
 
+and libz's compression level of every writer above (4, 5 or 6, byte for byte libz's output at that level; default 6):
+    Codec.set_level / Codec.level                              (ZWZ_LEVEL sets a codec's default)
+
 There is no CPU fallback: importing works anywhere (so the build can be checked), but every codec
 call needs the HIP library and a GPU and raises ZwzError otherwise.
 """
@@ -89,6 +92,8 @@ def lib():
         L.zwz_decompress_dir.argtypes = [vp, c.c_char_p, c.c_char_p, c.POINTER(c.c_int)]
         L.zwz_decompress_dir_ranked.argtypes = [vp, c.c_char_p, c.c_char_p, c.c_int, c.c_int, ALLGATHER_FN, vp, c.POINTER(c.c_int)]
         L.zwz_ctx_set_chunk_size.argtypes = [vp, u32]
+        L.zwz_ctx_set_level.argtypes = [vp, c.c_int]
+        L.zwz_ctx_level.argtypes = [vp]
         L.zwz_ctx_set_option.argtypes = [vp, c.c_char_p, c.c_char_p]
         L.zwz_bgzf_bound.restype = u64
         L.zwz_bgzf_bound.argtypes = [u64]
@@ -366,7 +371,8 @@ class Codec:
 
     def deflate_streams(self, buffers, wrap="gzip"):
         """[bytes] -> [bytes]: every buffer as one raw / zlib / gzip stream of its own, all in one pass on the GPU.  Each is what libz
-        writes at level 6 with a full flush after every 65 280 bytes, so zlib.decompress / gzip.decompress read it."""
+        writes at level 6 (or at this codec's level: set_level) with a full flush after every 65 280 bytes, so zlib.decompress /
+        gzip.decompress read it."""
         import numpy as np
         import torch
         w = WRAPS.get(wrap, wrap)
@@ -633,6 +639,16 @@ class Codec:
         """Raw bytes per Chunk for do_compression (0 = the reference's 65535).  Opt-in, not bit-exact with the reference's
         shards; LOSSLESS_CHUNK_SIZE never truncates."""
         _check(lib().zwz_ctx_set_chunk_size(self._h, nbytes), "zwz_ctx_set_chunk_size")
+
+    def set_level(self, level):
+        """libz's compression level of every writer of this codec (include/zwz.h: zwz_ctx_set_level): 4, 5 or 6, byte for byte what
+        libz 1.2.11 writes at that level; 0 restores the default (6, or ZWZ_LEVEL).  Any other level raises ZwzError (status E_INVALID)
+        and leaves the level as it was.  Readers are not affected."""
+        _check(lib().zwz_ctx_set_level(self._h, int(level)), "zwz_ctx_set_level")
+
+    @property
+    def level(self):
+        return lib().zwz_ctx_level(self._h)
 
 
 def _device_input(torch, data, device):

@@ -15,6 +15,9 @@ over xGMI when GPUs are present, "gloo" otherwise):
         directory; the reference has no gather (every rank writes compressed_<rank>.zwz itself).  The protocol is
         the library's zwz_gather_shards -- the code csrc/main.cpp drives over RCCL -- with torch.distributed as its transport
 
+    (addition) ZWZ_LEVEL=4|5|6 in the environment selects libz's compression level of every rank's Codec (include/zwz.h:
+        zwz_ctx_set_level); the argv stays the reference's
+
     (addition) decompression is a single-rank job in the reference (main.cpp:61-68); here shard j goes to rank j mod N,
         and fewer shards than ranks are split by record ranges with an all_gather of decoded byte counts
 """

@@ -1,4 +1,4 @@
-// dstream_core.h -- the portable half of zwz_deflate_streams_dev: how the level-6 streams of independent pieces become one raw, zlib
+// dstream_core.h -- the portable half of zwz_deflate_streams_dev: how the streams of independent pieces (level 6, or the context's level) become one raw, zlib
 // or gzip stream of any size.  Host + device, so that a CPU build (tests/emu_dstream) pins every formula here against libz.
 //
 // The output is what libz 1.2.11 writes when every kPieceBytes of input are followed by deflate(Z_FULL_FLUSH) and the last by
@@ -22,8 +22,9 @@ constexpr uint32_t kGzipHeaderBytes = 10;     // 1f 8b 08 00 | mtime 0 | 00 | 03
 
 ZWZ_HD uint32_t dstream_header_bytes(uint32_t wrap) { return wrap == kWrapZlib ? 2u : wrap == kWrapGzip ? kGzipHeaderBytes : 0u; }
 ZWZ_HD uint32_t dstream_trailer_bytes(uint32_t wrap) { return wrap == kWrapZlib ? 4u : wrap == kWrapGzip ? 8u : 0u; }
-ZWZ_HD uint32_t dstream_header_byte(uint32_t wrap, uint32_t i) {
-    if (wrap == kWrapZlib) return i == 0 ? 0x78u : 0x9cu;
+// flg: the zlib header's second byte, zlib_flg(level) -- 9c at level 6, 5e at 4 and 5.  The gzip header does not depend on the level: libz's XFL is 0 but at 1 and 9.
+ZWZ_HD uint32_t dstream_header_byte(uint32_t wrap, uint32_t i, uint32_t flg = 0x9cu) {
+    if (wrap == kWrapZlib) return i == 0 ? 0x78u : flg;
     return i == 0 ? 0x1fu : i == 1 ? 0x8bu : i == 2 ? 0x08u : i == 9 ? 0x03u : 0u;
 }
 // Byte i of what follows the last marker: 03 00, then Adler-32 big-endian (zlib) or CRC-32 and ISIZE little-endian (gzip).

@@ -11,10 +11,16 @@
 //     0..7 -- which settles every length below kDeep (11 / 8);
 //   * a position whose best candidate agrees on all eight bytes is finished by a second pass that visits only the
 //     candidates agreeing on all eight (its "sharers", chained nearest-first through link[]), comparing real bytes;
-//   * zlib's short chain (32 candidates once the previous match is "good") is the key after the 32nd candidate.
+//   * zlib's short chain (32 candidates once the previous match is "good") is the key after the 32nd candidate (at level 6; the level's snap_chain-th in general).
 // The last positions of a chunk (lookahead < kDeep): their eight bytes reach past the data, so their XORs are masked
 // down to the bytes that exist (band_tail_mask) -- "all of them agree" then means "agrees to the end of the data", which
 // is as long as a match can get there (and zlib stops at the first such candidate: the nearest).
+//
+// The compression level (zwz_common.h: LzLevel<N>, template argument Lv, level 6 where none is named) enters in three places: band_count
+// stops at the level's max_chain (16 or 32 candidates, not the band's 128: the halo may stay 128 wide), the short chain's key is the one
+// after snap_chain candidates, and the second pass stops at the level's nice length.  Every level's nice length is above kDeep, so the
+// first pass still settles only lengths below `nice` and the nice stop stays the second pass's business (static_assert in LzLevelOf);
+// tail positions (lookahead < nice) take nice = lookahead from band_generic / the masked keys as before.
 //
 // Portable (host + device): tests/emu builds band_records() on the CPU and diffs it against lz_search().
 #pragma once
@@ -64,7 +70,7 @@ ZWZ_HD bool band_first_at_max_dist(uint32_t own, uint32_t c) {
 
 // Number of candidates of entry u: binary search over the monotone band_valid.  S(i) -> word of array index i (the
 // caller's array starts kBand entries before its first own entry, filled with kBandHaloWord where nothing exists).
-template <class SFn>
+template <class Lv = LzDefaultLevel, class SFn>
 ZWZ_HD uint32_t band_count(SFn S, uint32_t u) {
     const uint32_t own = S(u);
     uint32_t k = 0;
@@ -76,7 +82,7 @@ ZWZ_HD uint32_t band_count(SFn S, uint32_t u) {
         if (t <= kBand && band_valid(own, S(u - t))) k = t;
     }
     if (k == 0u && band_first_at_max_dist(own, S(u - 1u))) k = 1u;
-    return k;
+    return k < Lv::max_chain ? k : Lv::max_chain;             // the level's chain, not the band's width (the halo stays 128 entries)
 }
 
 // Packed comparison key of the k-th candidate: (equal leading bytes of the two 8-byte words) << 8 | (129 - k); 15 in the
@@ -125,16 +131,16 @@ ZWZ_HD uint32_t band_record(uint32_t key, bool pure, uint32_t p, uint32_t cand_p
 }
 
 // The chunk's last positions (and the specification of the whole scheme): candidates u - 1 .. u - cnt, real bytes.
-template <class SFn>
+template <class Lv = LzDefaultLevel, class SFn>
 ZWZ_HD void band_generic(const uint8_t* data, SFn S, uint32_t u, uint32_t cnt, uint32_t L, uint32_t& e128, uint32_t& e32) {
     const uint32_t p = band_pos(S(u)), lookahead = L - p;
-    const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch, nice = lookahead < kNiceLen ? lookahead : kNiceLen;
+    const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch, nice = lookahead < Lv::nice ? lookahead : Lv::nice;
     uint32_t best = kMinMatch - 1u, best_pos = 0, snap = 0xffffffffu;
     for (uint32_t k = 1; k <= cnt; k++) {
         const uint32_t c = band_pos(S(u - k));
         const uint32_t len = match_len_from(data, c, p, 0u, max_len);
         if (len > best) { best = len; best_pos = c; }
-        if (k == kShortChain) snap = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;
+        if (k == Lv::snap_chain) snap = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;
         if (best >= nice) break;
     }
     e128 = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;
@@ -147,17 +153,17 @@ ZWZ_HD void band_generic(const uint8_t* data, SFn S, uint32_t u, uint32_t cnt, u
 // byte from kDeep on.  link(j) -> array index of the nearest sharer of entry j, kBandNoLink if none in ITS band; valid
 // for the tile's own entries (j >= first_own) -- through the halo in front of them the sharers are found by their
 // eight bytes (E(j) -> the 8-byte word as lo | hi << 32, asked for halo entries only).
-template <class SFn, class LinkFn, class EFn>
+template <class Lv = LzDefaultLevel, class SFn, class LinkFn, class EFn>
 ZWZ_HD void band_deep(const uint8_t* data, SFn S, LinkFn link, EFn E, uint32_t first_own, uint32_t u, uint32_t cnt, uint32_t k1,
                       uint32_t deep, uint32_t L, uint64_t own /* entry u's 8-byte word */, uint32_t& e128,
-                      uint32_t& e32 /* in: the first pass's, kept if k1 > 32 */) {
+                      uint32_t& e32 /* in: the first pass's, kept if k1 > snap_chain */) {
     const uint32_t p = band_pos(S(u)), lookahead = L - p;
-    const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch, nice = lookahead < kNiceLen ? lookahead : kNiceLen;
+    const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch, nice = lookahead < Lv::nice ? lookahead : Lv::nice;
     uint32_t best = 0, best_pos = 0, snap = 0xffffffffu;
     uint32_t j = u - k1;
     for (;;) {
         const uint32_t k = u - j;
-        if (k > kShortChain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;   // (0 only if k1 > 32: then unused)
+        if (k > Lv::snap_chain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;   // (0 only if k1 > snap_chain: then unused)
         const uint32_t c = band_pos(S(j));
         const uint32_t len = match_len_from(data, c, p, deep, max_len);
         if (len > best) { best = len; best_pos = c; if (len >= nice) break; }
@@ -173,7 +179,7 @@ ZWZ_HD void band_deep(const uint8_t* data, SFn S, LinkFn link, EFn E, uint32_t f
         }
     }
     e128 = entry_pack(best, p - best_pos);
-    if (k1 <= kShortChain) e32 = snap != 0xffffffffu ? snap : e128;
+    if (k1 <= Lv::snap_chain) e32 = snap != 0xffffffffu ? snap : e128;
 }
 
 // band_deep in the order lz_match_band's second pass takes it (and its specification): H sharers a batch.
@@ -181,15 +187,15 @@ ZWZ_HD void band_deep(const uint8_t* data, SFn S, LinkFn link, EFn E, uint32_t f
 //   compare  the batch's H lengths, each on its own;
 //   fold     the lengths into best / snapshot / nice stop IN SHARER ORDER: the first of the greatest length wins, the walk
 //            ends behind the first sharer whose length reaches `nice` (sharers chased beyond it are ignored), the short
-//            chain's snapshot is taken at the first sharer with k > 32.
+//            chain's snapshot is taken at the first sharer with k > snap_chain (32 at level 6).
 // Same arguments, same records as band_deep for every H >= 1 (tests/test_band_pass2_cpu.py).  `visited`, if given, receives
 // the number of sharers the walk looked at.
-template <uint32_t H, class SFn, class LinkFn, class EFn>
+template <uint32_t H, class Lv = LzDefaultLevel, class SFn, class LinkFn, class EFn>
 ZWZ_HD void band_deep_batched(const uint8_t* data, SFn S, LinkFn link, EFn E, uint32_t first_own, uint32_t u, uint32_t cnt, uint32_t k1,
                               uint32_t deep, uint32_t L, uint64_t own, uint32_t& e128, uint32_t& e32, uint32_t* visited = nullptr) {
     static_assert(H >= 1, "a batch holds a sharer");
     const uint32_t p = band_pos(S(u)), lookahead = L - p;
-    const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch, nice = lookahead < kNiceLen ? lookahead : kNiceLen;
+    const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch, nice = lookahead < Lv::nice ? lookahead : Lv::nice;
     auto next = [&](uint32_t j) -> uint32_t {                  // the sharer behind entry j, kBandNoLink where the band ends
         if (j >= first_own) {
             const uint32_t j2 = link(j);
@@ -214,7 +220,7 @@ ZWZ_HD void band_deep_batched(const uint8_t* data, SFn S, LinkFn link, EFn E, ui
         bool alive = true;
         for (uint32_t h = 0; h < nv; h++) {                     // fold
             if (!alive) break;
-            if (u - jv[h] > kShortChain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
+            if (u - jv[h] > Lv::snap_chain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
             if (len[h] > best) { best = len[h]; best_pos = band_pos(S(jv[h])); }
             seen++;
             alive = best < nice;
@@ -224,7 +230,7 @@ ZWZ_HD void band_deep_batched(const uint8_t* data, SFn S, LinkFn link, EFn E, ui
     }
     if (visited) *visited = seen;
     e128 = entry_pack(best, p - best_pos);
-    if (k1 <= kShortChain) e32 = snap != 0xffffffffu ? snap : e128;
+    if (k1 <= Lv::snap_chain) e32 = snap != 0xffffffffu ? snap : e128;
 }
 
 }  // namespace zwz

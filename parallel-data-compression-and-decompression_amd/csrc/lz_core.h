@@ -9,6 +9,12 @@
 // an early stop at the first length >= min(128, lookahead).  So two (len, dist) records per
 // position -- after 32 and after 128 candidates -- determine the whole lazy parse.
 //
+// The numbers in this text (32, 128, good 8, lazy 16) are level 6's.  Every function below takes the compression level as a template
+// argument Lv (zwz_common.h: LzLevel<4>, <5>, <6>; a caller that names none gets level 6): max_chain for 128, snap_chain for 32,
+// nice, good and max_lazy.  e128 / e32 stay the names of the long and the short record whatever the level.  At level 4 the short
+// record is never consulted (good >= max_lazy: the parse only searches while the pending length is below max_lazy), so it is
+// DEFINED as the long one there -- snap_chain = max_chain -- and the three searches stay comparable record by record.
+//
 // Portable (host + device): the CPU build of this header is exercised against the oracle by
 // tests/ so that the GPU kernels only add the parallel glue.
 #pragma once
@@ -50,6 +56,7 @@ ZWZ_HD uint32_t match_len_from(const uint8_t* data, uint32_t a, uint32_t b, uint
 // next candidate is read together with the filter word, so a rejected candidate costs one LDS
 // round trip, and every stop condition is folded into the loop predicate (a version with early
 // exits spent ~35 exec-mask SALU instructions per candidate).
+template <class Lv = LzDefaultLevel>
 ZWZ_HD void lz_search(const uint8_t* data, const uint16_t* link, uint32_t org, uint32_t p, uint32_t L,
                       uint32_t& e128, uint32_t& e32) {
     e128 = 0; e32 = 0;
@@ -59,7 +66,7 @@ ZWZ_HD void lz_search(const uint8_t* data, const uint16_t* link, uint32_t org, u
     if (p >= kSlidePos && cur <= kWSize) return;         // zlib's window has slid: <= 32768 reads as NIL
     const uint32_t lookahead = L - p;
     const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch;
-    const uint32_t nice = lookahead < kNiceLen ? lookahead : kNiceLen;
+    const uint32_t nice = lookahead < Lv::nice ? lookahead : Lv::nice;
     const uint32_t limit = p > kMaxDist ? p - kMaxDist : 0;
     const uint32_t pp = p - org;
     uint32_t best = kMinMatch - 1, best_pos = 0, n = 0, snap = 0xffffffffu;
@@ -88,10 +95,10 @@ ZWZ_HD void lz_search(const uint8_t* data, const uint16_t* link, uint32_t org, u
         n++;
         cur = next;
     };
-    do examine(); while (cur > limit && n < kShortChain);
-    if (n == kShortChain) {
+    do examine(); while (cur > limit && n < Lv::snap_chain);
+    if (n == Lv::snap_chain) {
         snap = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;
-        while (cur > limit && n < kMaxChain) examine();
+        while (cur > limit && n < Lv::max_chain) examine();
     }
     e128 = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0;
     e32 = snap != 0xffffffffu ? snap : e128;
@@ -115,7 +122,7 @@ struct MaskWriter {
 
 struct ParseResult { uint32_t n_sym; uint32_t n_match; uint32_t last_is_match; };
 
-template <class EntryFn, class HasFn>
+template <class Lv = LzDefaultLevel, class EntryFn, class HasFn>
 ZWZ_HD ParseResult lz_parse(EntryFn entries /* (p, which32) -> packed entry */, HasFn has128 /* word index -> mask */, uint32_t L,
                             uint64_t* sym, uint64_t* mst, uint64_t* m32) {
     const uint32_t nwords = (L + 63) >> 6;
@@ -171,8 +178,8 @@ ZWZ_HD ParseResult lz_parse(EntryFn entries /* (p, which32) -> packed entry */, 
         }
         // a match of length b found at p-1 is pending
         uint32_t cur = 0, sel = 0;
-        if (b < kMaxLazy && p < L) {
-            sel = b >= kGoodLen ? 1u : 0u;
+        if (b < Lv::max_lazy && p < L) {
+            sel = b >= Lv::good ? 1u : 0u;           // (a level with good >= max_lazy never gets here with b >= good)
             cur = entries(p, sel);
             if (entry_len(cur) <= b) cur = 0;     // no improvement
         }
@@ -219,14 +226,14 @@ struct FreshStep {
     uint32_t is_lit;
 };
 
-template <class EntryFn>
+template <class Lv = LzDefaultLevel, class EntryFn>
 ZWZ_HD FreshStep fresh_step(EntryFn entries /* (p, sel) -> record, 0 beyond the chunk */, uint32_t q, uint32_t L) {
     FreshStep r;
     uint32_t e = entries(q, 0u);
     if (e == 0) { r.next = q + 1; r.mpos = q; r.sel = 0; r.is_lit = 1; return r; }
     uint32_t b = entry_len(e), m = q, sel = 0;
-    while (b < kMaxLazy && m + 1 < L) {
-        const uint32_t s2 = b >= kGoodLen ? 1u : 0u;
+    while (b < Lv::max_lazy && m + 1 < L) {
+        const uint32_t s2 = b >= Lv::good ? 1u : 0u;
         const uint32_t c = entries(m + 1, s2);
         if (entry_len(c) <= b) break;
         b = entry_len(c); sel = s2; m++;

@@ -23,6 +23,8 @@
 // position 0 = NIL, the slid window at 65 274); lz_core.h's lz_search + lz_parse remain the specification:
 // tests/emu runs this decomposition, lanes in random order, against them.
 //
+// (The numbers above are level 6's; Lv -- zwz_common.h: LzLevel<N> -- carries good, max_lazy, nice and the two chain lengths of the level.)
+//
 // Portable (host + device).
 #pragma once
 #include "lz_core.h"
@@ -46,7 +48,7 @@ ZWZ_HD uint32_t lazy_avail(uint32_t u, uint32_t h, uint32_t bucket_start /* h ? 
 // longest_match(p) with prev_length = prev_len (2 = nothing pending).  spos(i) -> position of sorted index i.
 // Returns the best length: > prev_len = a longer match at best_pos, else nothing (prev_len).  deflate_slow's TOO_FAR rule
 // (a length-3 match further than 4096 back is dropped) is applied here: it can only strike when prev_len == 2.
-template <class SposFn>
+template <class Lv = LzDefaultLevel, class SposFn>
 ZWZ_HD uint32_t lazy_search(const uint8_t* data, SposFn spos, uint32_t u, uint32_t avail, uint32_t p, uint32_t L, uint32_t prev_len, uint32_t& best_pos) {
     if (avail == 0u || p + kMinMatch > L) return prev_len;
     uint32_t c = spos(u - 1u);
@@ -54,9 +56,9 @@ ZWZ_HD uint32_t lazy_search(const uint8_t* data, SposFn spos, uint32_t u, uint32
     if (p >= kSlidePos && c <= kWSize) return prev_len;       // zlib's window has slid: reads as NIL
     const uint32_t lookahead = L - p;
     const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch;
-    const uint32_t nice = lookahead < kNiceLen ? lookahead : kNiceLen;
+    const uint32_t nice = lookahead < Lv::nice ? lookahead : Lv::nice;
     const uint32_t limit = p > kMaxDist ? p - kMaxDist : 0u;
-    const uint32_t chain = prev_len >= kGoodLen ? kShortChain : kMaxChain;
+    const uint32_t chain = prev_len >= Lv::good ? Lv::short_chain : Lv::max_chain;
     const uint32_t n = avail < chain ? avail : chain;
     uint32_t best = prev_len;
     // filter: a candidate beats `best` only if it agrees with p on bytes best-3 .. best (the trigram itself while best == 2)
@@ -81,14 +83,14 @@ ZWZ_HD uint32_t lazy_search(const uint8_t* data, SposFn spos, uint32_t u, uint32
 
 // What "fresh at q" leads to (lz_core.h fresh_step, searches on demand).  search(p, prev_len, best_pos&) -> best length.
 struct LazyChain { uint32_t step, next; };
-template <class SearchFn>
+template <class Lv = LzDefaultLevel, class SearchFn>
 ZWZ_HD LazyChain lazy_chain(SearchFn search, uint32_t q, uint32_t L) {
     uint32_t bp = 0;
     uint32_t b = search(q, kMinMatch - 1u, bp);
     LazyChain r;
     if (b < kMinMatch) { r.step = 0u; r.next = q + 1u; return r; }
     uint32_t m = q;
-    while (b < kMaxLazy && m + 1u < L) {
+    while (b < Lv::max_lazy && m + 1u < L) {
         uint32_t bp2 = 0;
         const uint32_t b2 = search(m + 1u, b, bp2);
         if (b2 <= b) break;

@@ -339,13 +339,23 @@ int bgzf_main(const std::string& op, const char* src, const char* dst, int world
     return 0;
 }
 
-// `main zip <src dir> <dst.zip>` / `main unzip <src.zip> <dst dir>`: a directory as one ZIP archive and back, one process, one GPU.
+// A level flag of the writers (`gzip`, `bgzip`, `zip`): -4, -5 or -6, libz's level of that number (include/zwz.h: zwz_ctx_set_level).
+// Returns 1 and sets *level for one of those, -1 for any other -N (the caller prints the usage and exits 1), 0 for anything else.
+int level_flag(const std::string& a, int* level) {
+    if (a.size() < 2 || a[0] != '-') return 0;
+    for (size_t i = 1; i < a.size(); i++) if (a[i] < '0' || a[i] > '9') return 0;
+    if (a == "-4" || a == "-5" || a == "-6") { *level = a[1] - '0'; return 1; }
+    return -1;
+}
+
+// `main zip <src dir> <dst.zip> [-4|-5|-6]` / `main unzip <src.zip> <dst dir>`: a directory as one ZIP archive and back, one process, one GPU.
 // Exit codes as bgzf_main's.
-int zip_main(const std::string& op, const char* src, const char* dst, int world_size, int device) {
+int zip_main(const std::string& op, const char* src, const char* dst, int world_size, int device, int level) {
     if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", op.c_str(), world_size); return 1; }
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
+    if (rc == ZWZ_OK && level) rc = zwz_ctx_set_level(ctx, level);
     if (rc == ZWZ_OK) rc = op == "zip" ? zwz_zip_dir(ctx, src, dst) : zwz_unzip_file(ctx, src, dst);
     zwz_ctx_destroy(ctx);
     if (rc != ZWZ_OK) {
@@ -357,26 +367,29 @@ int zip_main(const std::string& op, const char* src, const char* dst, int world_
 }
 
 void bgzf_usage(const char* argv0) {
-    fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n"
-            "       %s gzip <src> <dst> [--zlib|--raw]\n       %s gunzip <src> <dst> [--zlib|--raw]\n       %s zip <src dir> <dst.zip>\n       %s unzip <src.zip> <dst dir>\n",
+    fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index] [-4|-5|-6]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n"
+            "       %s gzip <src> <dst> [--zlib|--raw] [-4|-5|-6]\n       %s gunzip <src> <dst> [--zlib|--raw]\n       %s zip <src dir> <dst.zip> [-4|-5|-6]\n       %s unzip <src.zip> <dst dir>\n"
+            "  -4 -5 -6 (behind the operands or, as gzip takes it, in front of them): libz's compression level of that number (default 6, or ZWZ_LEVEL); no other level exists here\n",
             argv0, argv0, argv0, argv0, argv0, argv0, argv0);
 }
 
-// `main gzip <src file> <dst file> [--zlib|--raw]`: one file as one ordinary gzip (zlib, raw DEFLATE) stream, one process, one GPU.
+// `main gzip <src file> <dst file> [--zlib|--raw] [-4|-5|-6]`: one file as one ordinary gzip (zlib, raw DEFLATE) stream, one process, one GPU.
 // `main gunzip <src file> <dst file> [--zlib|--raw]`: the way back (zwz_inflate_stream_file), for any stream other encoders wrote too.
 int gzip_main(int argc, char** argv, int world_size, int device) {
     const bool back = std::string(argv[1]) == "gunzip";
     if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", argv[1], world_size); return 1; }
-    int wrap = ZWZ_WRAP_GZIP;
+    int wrap = ZWZ_WRAP_GZIP, level = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--zlib") wrap = ZWZ_WRAP_ZLIB;
         else if (a == "--raw") wrap = ZWZ_WRAP_RAW;
+        else if (!back && level_flag(a, &level) == 1) {}
         else { bgzf_usage(argv[0]); return 1; }
     }
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
+    if (rc == ZWZ_OK && level) rc = zwz_ctx_set_level(ctx, level);
     if (rc == ZWZ_OK) rc = back ? zwz_inflate_stream_file(ctx, wrap, argv[2], argv[3]) : zwz_deflate_stream_file(ctx, wrap, argv[2], argv[3]);
     zwz_ctx_destroy(ctx);
     if (rc != ZWZ_OK) { fprintf(stderr, "%s %s: %s (%s)\n", argv[1], argv[2], zwz_strerror(rc), zwz_last_error()); return 1; }
@@ -477,9 +490,11 @@ int bgzf_ext_main(int argc, char* argv[], int world_size, int device) {
     }
     bool index = false, have_off = false, have_size = false;
     uint64_t off = 0, size = 0;
+    int level = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (op == "bgzip" && a == "--index") index = true;
+        else if (op == "bgzip" && level_flag(a, &level) == 1) {}
         else if (op == "bgunzip" && a == "--offset" && i + 1 < argc && parse_u64(argv[i + 1], &off)) { have_off = true; i++; }
         else if (op == "bgunzip" && a == "--size" && i + 1 < argc && parse_u64(argv[i + 1], &size)) { have_size = true; i++; }
         else { bgzf_usage(argv[0]); return 1; }
@@ -489,10 +504,11 @@ int bgzf_ext_main(int argc, char* argv[], int world_size, int device) {
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
+    if (rc == ZWZ_OK && level) rc = zwz_ctx_set_level(ctx, level);
     if (rc == ZWZ_OK) {
         if (op == "bgzip") {
             rc = zwz_bgzf_compress_file(ctx, argv[2], argv[3]);
-            if (rc == ZWZ_OK) rc = zwz_bgzf_gzi_file(argv[3], (std::string(argv[3]) + ".gzi").c_str());
+            if (rc == ZWZ_OK && index) rc = zwz_bgzf_gzi_file(argv[3], (std::string(argv[3]) + ".gzi").c_str());
         } else {
             rc = bgzf_range_to_file(ctx, argv[2], argv[3], off, size, !have_size);
         }
@@ -530,6 +546,11 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "Usage: %s <compress/decompress> <source directory path> <output directory path>\n", argv[0]);
         return 1;
     }
+    // gzip -4 <src> <dst>, as the tools this stands in for take it: a level flag in front of the operands moves behind them
+    if (std::string(argv[1]) == "gzip" || std::string(argv[1]) == "bgzip" || std::string(argv[1]) == "zip") {
+        int lv = 0;
+        if (argc >= 5 && level_flag(argv[2], &lv) != 0) { char* f = argv[2];   /* with two operands behind it only: `gzip -4 src` stays src = -4, dst = src, as before */ for (int i = 2; i + 1 < argc; i++) argv[i] = argv[i + 1]; argv[argc - 1] = f; }
+    }
     std::string operation = argv[1], source_path = argv[2], output_path = argv[3];
     if (operation == "gzip" || operation == "gunzip") {
         int n = 0;
@@ -537,8 +558,9 @@ int main(int argc, char* argv[]) {
     }
     if (operation == "zip" || operation == "unzip") {
         int n = 0;
-        if (argc != 4) { bgzf_usage(argv[0]); return 1; }
-        return zip_main(operation, argv[2], argv[3], world_size, zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0);
+        int level = 0;
+        for (int i = 4; i < argc; i++) if (operation != "zip" || level_flag(argv[i], &level) != 1) { bgzf_usage(argv[0]); return 1; }
+        return zip_main(operation, argv[2], argv[3], world_size, zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0, level);
     }
     if (operation == "bgzip" || operation == "bgunzip") {
         int n = 0;

@@ -3,6 +3,8 @@
 #include "zwz_api_internal.h"
 #include "zwz_bgzf.h"
 
+#include <cerrno>
+#include <climits>
 #include <cstdarg>
 #include <chrono>
 #include <cstdio>
@@ -285,9 +287,32 @@ int zwz_ctx_create(int device, uint32_t max_batch, zwz_ctx** out) {
     }
     { const int rc = codec_self_test(c); if (rc != ZWZ_OK) { zwz_ctx_destroy(c); return rc; } }
     mark("codec known-answer test done");
+    // The default level, read once like ZWZ_MATCH -- but taken up only here: the self-tests above ran at level 6.
+    if (const char* v = getenv("ZWZ_LEVEL")) {
+        char* end = nullptr;
+        errno = 0;
+        const long x = strtol(v, &end, 10);
+        if (!*v || *end || errno || x < INT_MIN || x > INT_MAX || zwz_ctx_set_level(c, (int)x) != ZWZ_OK) fprintf(stderr, "zwz: ZWZ_LEVEL=%s is not a level this library writes (4, 5, 6; 0 = default): ignored\n", v);
+    }
     *out = c;
     return ZWZ_OK;
 }
+
+int zwz_ctx_set_level(zwz_ctx* c, int level) {
+    if (!c) return ZWZ_E_INVALID;
+    if (level == 0) level = kLevelDefault;
+    if (level < kLevelMin || level > kLevelMax) {
+        set_error("zwz_ctx_set_level: no level %d; levels 4, 5 and 6 exist (0 = the default, 6)\n"
+                  "  1-3: libz's deflate_fast skips hash insertions inside matches, so the chains depend on the parse: the position-parallel search does not hold\n"
+                  "  7-9: chains of 256-4096 and max_lazy up to 258: past the 128-wide band and the 13-position parse step\n"
+                  "  0: a different encoder (stored blocks only)", level);
+        return ZWZ_E_INVALID;
+    }
+    c->level = (uint32_t)level;
+    return ZWZ_OK;
+}
+
+int zwz_ctx_level(zwz_ctx* c) { return c ? (int)c->level : ZWZ_E_INVALID; }
 
 int zwz_ctx_set_option(zwz_ctx* c, const char* name, const char* value) {
     if (!c || !name || !value) return ZWZ_E_INVALID;
@@ -385,7 +410,7 @@ int zwz_deflate_batch_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_
         a.in = d_in; a.in_off = d_in_off + done; a.in_len = d_in_len + done; a.n = m;
         a.out = d_out + (size_t)done * out_stride; a.out_stride = out_stride; a.out_len = d_out_len + done;
         carve_workspace(c, a);
-        a.match_mode = c->match_mode; a.plan_serial = c->plan_serial;
+        a.match_mode = c->match_mode; a.plan_serial = c->plan_serial; a.level = c->level;
         HIPCHK(launch_deflate(a, c->stream, c->profiling ? c->ev : nullptr));
         if (c->profiling) {   // profiling serialises slices: stage times are read back per slice
             HIPCHK(hipEventSynchronize(c->ev[kNumDeflateStages]));

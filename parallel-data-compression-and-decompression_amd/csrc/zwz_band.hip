@@ -329,6 +329,10 @@ constexpr uint32_t kBandRuns = kBandTile / 8;
 #endif
 constexpr uint32_t kP2Batch = ZWZ_BAND_P2_BATCH;
 static_assert(kP2Batch >= 1 && kP2Batch <= 32, "lz_match_band: sharers a batch");
+// Lv (zwz_common.h: LzLevel<N>) = the compression level, a template argument and not a value: the unrolling and the register budget below were tuned
+// with the constants in place, and LzLevel<6> gives the kernel it always was.  What a level changes: the count stops at its max_chain (the halo stays 128
+// entries wide), the short chain's snapshot is taken behind snap_chain candidates, the second pass stops at its nice length.
+template <class Lv>
 __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                     const uint32_t* __restrict__ in_len, const uint32_t* __restrict__ list,
                                                                     uint32_t* __restrict__ tickets, const uint32_t* __restrict__ sorted,
@@ -441,23 +445,27 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
             // ---- count (thread <-> entries kBand + tid + 1024 j: the searches of a thread's entries advance together)
             {
                 constexpr uint32_t kOwnPer = (kBandTile + kBandThreads - 1) / kBandThreads;
+                // the greatest count looked for is the level's max_chain, not the band's width: a count beyond it would let pass 1 fold candidates
+                // zlib's chain never reaches (lz_band.h band_count caps the same way)
+                constexpr uint32_t kCap = Lv::max_chain;
+                static_assert(kCap <= kBand && (kCap & (kCap - 1u)) == 0u, "the count is a binary search over [0, max_chain] inside the halo");
                 uint32_t own[kOwnPer], k[kOwnPer];
 #pragma unroll
                 for (uint32_t j = 0; j < kOwnPer; j++) { const uint32_t i = kBand + tid + kBandThreads * j; own[j] = i < m ? S[i] : kBandHaloWord; k[j] = 0; }
                 auto search_step = [&](uint32_t step) {
                     uint32_t c[kOwnPer];
 #pragma unroll
-                    for (uint32_t j = 0; j < kOwnPer; j++) { const uint32_t t = k[j] + step; c[j] = S[kBand + tid + kBandThreads * j - (t <= kBand ? t : 0u)]; }
+                    for (uint32_t j = 0; j < kOwnPer; j++) { const uint32_t t = k[j] + step; c[j] = S[kBand + tid + kBandThreads * j - (t <= kCap ? t : 0u)]; }
 #pragma unroll
-                    for (uint32_t j = 0; j < kOwnPer; j++) { const uint32_t t = k[j] + step; if (t <= kBand && band_valid(own[j], c[j])) k[j] = t; }
+                    for (uint32_t j = 0; j < kOwnPer; j++) { const uint32_t t = k[j] + step; if (t <= kCap && band_valid(own[j], c[j])) k[j] = t; }
                 };
-                search_step(kBand);
-                bool open = false;                                              // inside a long bucket every entry has all 128: nothing to search
+                search_step(kCap);
+                bool open = false;                                              // inside a long bucket every entry has all max_chain candidates: nothing to search
 #pragma unroll
-                for (uint32_t j = 0; j < kOwnPer; j++) open |= kBand + tid + kBandThreads * j < m && k[j] != kBand;
+                for (uint32_t j = 0; j < kOwnPer; j++) open |= kBand + tid + kBandThreads * j < m && k[j] != kCap;
                 if (__builtin_amdgcn_ballot_w64(open) != 0) {
 #pragma unroll
-                    for (uint32_t step = kBand / 2u; step >= 1u; step >>= 1) search_step(step);
+                    for (uint32_t step = kCap / 2u; step >= 1u; step >>= 1) search_step(step);
                 }
 #pragma unroll
                 for (uint32_t j = 0; j < kOwnPer; j++) {
@@ -542,7 +550,7 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                             const uint32_t ka = key_of(c[j], 128u - k0 - j), kb = key_of(c[j + 1], 127u - k0 - j);
                             asm("v_max3_u32 %0, %0, %1, %2" : "+v"(best) : "v"(ka), "v"(kb));
                         }
-                        if (k0 + 8u == kShortChain) snap = best;
+                        if (k0 + 8u == Lv::snap_chain) snap = best;
                     }
                     for (; k0 < kmax; k0 += 8u) {
                         uint2 c[8];
@@ -553,7 +561,7 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                             const uint32_t key = key_of(c[j], 128u - k0 - j);
                             best = max(best, k0 + j + 1u <= cntb ? key : 0u);
                         }
-                        if (k0 + 8u == kShortChain) snap = best;
+                        if (k0 + 8u == Lv::snap_chain) snap = best;
                     }
                 } else {                                                        // a handful of groups per chunk: the plain loop, XORs masked to the bytes that exist
                     const uint32_t nb = tail ? band_tail_bytes(pure, la) : 8u, m_lo = band_tail_mask(nb, 0), m_hi = band_tail_mask(nb, 1);
@@ -561,11 +569,11 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                         const uint2 c = Ei[-(int)k];
                         const uint32_t key = band_key_masked(own.x, own.y, c.x, c.y, m_lo, m_hi, k);
                         best = max(best, k <= cntb ? key : 0u);
-                        if (k == kShortChain) snap = best;
+                        if (k == Lv::snap_chain) snap = best;
                     }
                 }
                 if (cntb == 0u) best = none;
-                const uint32_t key32 = cntb > kShortChain ? snap : best;
+                const uint32_t key32 = cntb > Lv::snap_chain ? snap : best;
                 uint32_t e128 = 0, e32 = 0, k1 = 0;
                 if (best != none) {
                     if (band_key_len(best) == 15u && !tail && !(ZWZ_BAND_EXP & 1)) k1 = band_key_k(best);
@@ -576,7 +584,7 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                     if (k1) {
                         ck[i - kBand] = (uint16_t)(cntb | k1 << 8);
                         reinterpret_cast<uint16_t*>(S)[2u * i + 1u] = (uint16_t)(i - k1);   // the bucket field has done its work: now the link
-                        if (k1 > kShortChain && !(ZWZ_BAND_EXP & 4)) reinterpret_cast<uint32_t*>(ent + p)[1] = e32;   // final; the second pass writes the rest
+                        if (k1 > Lv::snap_chain && !(ZWZ_BAND_EXP & 4)) reinterpret_cast<uint32_t*>(ent + p)[1] = e32;   // final; the second pass writes the rest
                         atomicOr(&hasb[p >> 5], 1u << (p & 31u));
                     } else {
                         reinterpret_cast<uint16_t*>(S)[2u * i + 1u] = (uint16_t)kBandNoLink;
@@ -628,7 +636,7 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                 const uint32_t i = on ? (uint32_t)flist[64u * g + lane] : kBand;
                 const uint32_t c = ck[i - kBand], cnt = c & 0xffu, k1 = c >> 8;
                 const uint32_t p = band_pos(S[i]), la = L - p;
-                const uint32_t max_len = la < kMaxMatch ? la : kMaxMatch, nice = la < kNiceLen ? la : kNiceLen;
+                const uint32_t max_len = la < kMaxMatch ? la : kMaxMatch, nice = la < Lv::nice ? la : Lv::nice;
                 // (sixteen bytes behind the compared ones, not eight: with eight, some lane of the wave fell out into match_len_from's serial loop
                 // at nearly every hop -- a third identical word in a row is a 2-3 % event per lane, i.e. an 85 % event per wave --
                 // and a hop cost ~1 500 cycles; sixteen settle all but ~1 in 2 000 visits)
@@ -678,7 +686,7 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                         uint32_t l = deep + (tm >> 3);
                         if (v && tm == 0xffffffffu) l = match_len_from(sdata, q, p, deep + 16u, max_len);   // (~1 in 2 000 visits)
                         l = l < max_len ? l : max_len;
-                        if (v && i - jh > kShortChain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
+                        if (v && i - jh > Lv::snap_chain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
                         if (v && l > best) { best = l; best_pos = q; }
                         alive = v && best < nice;
                         jh = wv[h] >> 16;
@@ -689,7 +697,7 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                 uint32_t e128 = entry_pack(best, p - best_pos), e32 = snap != 0xffffffffu ? snap : e128;
                 if (slow) {
                     const uint64_t own = (uint64_t)load_u32(sdata, p + off) | (uint64_t)load_u32(sdata, p + off + 4u) << 32;
-                    band_deep(sdata, Sf, [&](uint32_t jj) { return S[jj] >> 16; },
+                    band_deep<Lv>(sdata, Sf, [&](uint32_t jj) { return S[jj] >> 16; },
                               [&](uint32_t jj) { const uint2 e = E[jj]; return (uint64_t)e.x | (uint64_t)e.y << 32; },   // (halo entries only)
                               kBand, i, cnt, k1, deep, L, own, e128, e32);
                 }
@@ -697,7 +705,7 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                     if (ZWZ_BAND_EXP & 4) asm volatile("" :: "v"(e128), "v"(e32), "v"(p));
                     if (!(ZWZ_BAND_EXP & 4)) {
                         reinterpret_cast<uint32_t*>(ent + p)[0] = e128;
-                        if (k1 <= kShortChain) reinterpret_cast<uint32_t*>(ent + p)[1] = e32;
+                        if (k1 <= Lv::snap_chain) reinterpret_cast<uint32_t*>(ent + p)[1] = e32;
                     }
                 }
             }
@@ -724,7 +732,12 @@ uint32_t exp_flags_band() { return (uint32_t)(ZWZ_BAND_EXP); }
 hipError_t configure_band_kernels() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_place_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPlaceLdsBytes);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_band_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLdsBytes);
+    // more than 64 KB of dynamic LDS: EVERY instantiation needs the attribute, or its first launch fails
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_band_kernel<LzLevel<4>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLdsBytes);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_band_kernel<LzLevel<5>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_band_kernel<LzLevel<6>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLdsBytes);
 }
 
 // which: 0 = by a sample of each chunk (production), 2 = every chunk is chain-heavy (tests).
@@ -753,8 +766,13 @@ hipError_t launch_place(const DeflateArgs& a, hipStream_t s) {
 hipError_t launch_match_band(const DeflateArgs& a, hipStream_t s) {
     const uint32_t cus = a.cu_count ? a.cu_count : 256u;
     const uint32_t G = a.n < cus ? a.n : cus;
-    hipLaunchKernelGGL(lz_match_band_kernel, dim3(G), dim3(kBandThreads), kBandLdsBytes, s, a.in, a.in_off, a.in_len, a.dense_list, a.tickets, a.sorted,
-                       a.entries, a.has128);
+    switch (a.level) {
+#define ZWZ_BAND_LAUNCH(N) case N: hipLaunchKernelGGL(lz_match_band_kernel<LzLevel<N>>, dim3(G), dim3(kBandThreads), kBandLdsBytes, s, a.in, a.in_off, a.in_len, a.dense_list, \
+                                                 a.tickets, a.sorted, a.entries, a.has128); break;
+        ZWZ_BAND_LAUNCH(4) ZWZ_BAND_LAUNCH(5) ZWZ_BAND_LAUNCH(6)
+#undef ZWZ_BAND_LAUNCH
+        default: return hipErrorInvalidValue;        // a level without a kernel is an error, never another level's kernel
+    }
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@ constexpr uint32_t kBgzfThreads = 256;        // lanes of the CRC workgroup (crc
 // Worst case of a level-6 zlib stream of kBgzfBlock bytes: at most kMaxBlocks stored blocks (5 header bytes each), the 2 + 4 bytes of
 // zlib framing, and a few bytes of bit padding where stored and coded blocks meet.  Far below the 65535-byte deflate slot, so no
 // member body is ever cut; bgzf_scan still flags a stream that reaches the slot's length (the output length then reads ~0).
+// The same at levels 4 and 5 (zwz_ctx_set_level): the worst case is stored blocks, and the block cuts (16 383 symbols) do not depend on the level.
 static_assert(kBgzfBlock + 5u * 5u + 6u + 16u < 65535u, "a BGZF block's level-6 stream always fits the deflate slot");
 
 // Range reads: one piece is len bytes at offset off of a touched member's decoded block, bound for out + dst

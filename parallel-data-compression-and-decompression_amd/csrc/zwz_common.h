@@ -27,6 +27,35 @@ constexpr uint32_t kMaxLazy = 16;
 constexpr uint32_t kNiceLen = 128;
 constexpr uint32_t kMaxChain = 128;
 constexpr uint32_t kShortChain = 32;
+// The compression level: libz's deflate_slow levels whose numbers fit the kernels.  The names above stay level 6 -- the
+// default, and what the reference writes.  Search and parse code is templated on one of these; a caller that names no level gets LzLevel<6>.
+//   good      prev_length >= good: longest_match walks short_chain = max_chain >> 2 candidates
+//   max_lazy  a pending match of max_lazy bytes or more is not searched behind
+//   nice      a candidate of nice bytes (or the whole lookahead) ends a search
+//   snap_chain  where the searches that keep BOTH records of a position take the short chain's: behind short_chain candidates -- or, at a level
+//             whose parse never asks for that record (good >= max_lazy: a search only runs while prev_length < max_lazy), behind max_chain,
+//             i.e. the short record is the long one.  Every search (walk, band, lazy) states the record that way, so they stay comparable.
+constexpr int kLevelMin = 4, kLevelMax = 6, kLevelDefault = 6;
+template <int N> struct LzLevel;
+template <uint32_t Good, uint32_t Lazy, uint32_t Nice, uint32_t Chain> struct LzLevelOf {
+    static constexpr uint32_t good = Good, max_lazy = Lazy, nice = Nice, max_chain = Chain, short_chain = Chain >> 2;
+    static constexpr bool short_used = Good < Lazy;
+    static constexpr uint32_t snap_chain = short_used ? short_chain : max_chain;
+    static_assert(Chain <= 128, "a chain is at most the band's width (lz_band.h: kBand, the 129 - k key field)");
+    static_assert(Lazy <= 16, "fresh_step looks at no more than 13 positions (lz_core.h; lz_lazy.h: four bits of match offset)");
+    static_assert(Nice > 11 && Nice <= kMaxMatch, "the band's first pass settles lengths below kDeep = 11: the nice stop must stay the second pass's");
+    // good >= max_lazy (level 4): the parse never asks for the short record (a search only runs while prev_length < max_lazy <= good), so it is
+    // defined as the long one rather than special-cased anywhere
+    static_assert(short_used || snap_chain == max_chain, "a short record nobody consults is the long record");
+    static_assert(snap_chain % 8 == 0, "the band's first pass takes the short chain's snapshot at a batch boundary (k0 + 8 == snap_chain)");
+};
+template <> struct LzLevel<4> : LzLevelOf<4, 4, 16, 16> { static constexpr int level = 4; };
+template <> struct LzLevel<5> : LzLevelOf<8, 16, 32, 32> { static constexpr int level = 5; };
+template <> struct LzLevel<6> : LzLevelOf<kGoodLen, kMaxLazy, kNiceLen, kMaxChain> { static constexpr int level = 6; };
+static_assert(LzLevel<6>::short_chain == kShortChain && LzLevel<6>::snap_chain == kShortChain, "level 6 = the constants above");
+using LzDefaultLevel = LzLevel<kLevelDefault>;
+// Second byte of the zlib header libz writes at a level (CMF 0x78): FLEVEL 1 below level 6, 2 at 6; FCHECK makes the pair a multiple of 31.
+ZWZ_HD constexpr uint32_t zlib_flg(uint32_t level) { return level < 6u ? 0x5eu : 0x9cu; }
 constexpr uint32_t kSlidePos = 65274;     // w_size + MAX_DIST: zlib slides its window here
 constexpr uint32_t kWSize = 32768;
 constexpr uint32_t kSymsPerBlock = 16383; // lit_bufsize - 1

@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(256) dstream_begin_kernel(DstreamStreams S, Ds
     const bool fits = hdr + tail <= S.out_cap[i];
     if (fits) {
         uint8_t* dst = O.out + S.out_off[i];
-        for (uint32_t b = 0; b < hdr; b++) dst[b] = (uint8_t)dstream_header_byte(O.wrap, b);
+        for (uint32_t b = 0; b < hdr; b++) dst[b] = (uint8_t)dstream_header_byte(O.wrap, b, O.zflg);
         for (uint32_t b = 0; b < tail; b++) dst[hdr + b] = (uint8_t)dstream_tail_byte(O.wrap, b, init, 0);
     }
     O.out_len[i] = hdr + tail;
@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(256) dstream_pack_kernel(DstreamStreams S, Dst
     uint8_t* dst = O.out + S.out_off[s];
     if (first) {
         if (t == 0) S.xs[s] = P.x[p];              // (read by this stream's pieces in later slices only)
-        if (t < hdr && hdr <= cap) dst[t] = (uint8_t)dstream_header_byte(O.wrap, t);
+        if (t < hdr && hdr <= cap) dst[t] = (uint8_t)dstream_header_byte(O.wrap, t, O.zflg);
     }
     if (last) {
         const uint64_t total = end + tail;

@@ -124,6 +124,8 @@ struct DeflateArgs {
     uint32_t cu_count;         // sizes the persistent grids (0: 256)
     uint32_t match_mode;       // kMatchAuto (production: lz_dense_list decides per chunk) | kMatchWalk | kMatchBand -- the context's option, same records either way
     uint32_t plan_serial;      // 1: the lane-serial block flush (plan_serial_kernel) instead of heap + wave
+    uint32_t level;            // 4, 5 or 6 (zwz_common.h: LzLevel<N>): which instantiation of lz_match / lz_match_band / lz_lazy / lz_parse runs, and the zlib header's FLEVEL.
+                               // Anything else makes launch_deflate fail: a level without kernels is an error
     ChunkInfo* info; BlockInfo* blocks; BlockOut* plans;
     BlockProbe* probes;        // = links (dead once lz_match has run): chunk c's kMaxBlocks probes open ITS link space
     // The chosen record of every match symbol, compact and in stream order (lz_parse -> blockify, encode): a chunk's

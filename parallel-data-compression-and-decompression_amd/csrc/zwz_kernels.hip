@@ -498,6 +498,7 @@ __global__ __launch_bounds__(kLinksThreads) void lz_links_kernel(const uint8_t* 
 // v_alignbyte_b32 looks at the low two bits of its shift operand only, so the byte address itself is the shift.)
 // (data / link: lz_match's rings, csrc/zwz_kernels.h; position x sits at index match_ring(x))
 static __device__ __forceinline__ uint32_t match_ring(uint32_t x) { return min(x, x - kMatchRing); }   // x < 2 * kMatchRing: x - ring wraps to a huge value below the ring's size
+template <class Lv>
 static __device__ __forceinline__ void lz_search_wave(const uint8_t* data, const uint16_t* link, uint32_t p, uint32_t L,
                                                       bool active, uint32_t& e128, uint32_t& e32) {
     typedef __attribute__((address_space(3))) uint8_t* lds_ptr;
@@ -513,7 +514,7 @@ static __device__ __forceinline__ void lz_search_wave(const uint8_t* data, const
     if (!start) cur = p;                                           // a readable stand-in
     const uint32_t lookahead = L - p;
     const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch;
-    const uint32_t nice = lookahead < kNiceLen ? lookahead : kNiceLen;
+    const uint32_t nice = lookahead < Lv::nice ? lookahead : Lv::nice;
     const uint32_t limit = p > kMaxDist ? p - kMaxDist : 0;
     constexpr uint32_t kNone = 0xffffffffu;
     uint32_t best = kMinMatch - 1, best_pos = 0, snap = kNone;
@@ -530,8 +531,8 @@ static __device__ __forceinline__ void lz_search_wave(const uint8_t* data, const
     // candidate count that is what exactness seemed to ask for -- the divergent comparison ran once per 3.7 wave-steps on text for
     // one or two lanes, ~1100 cycles each time: more than half of the walk.)  The loop runs with EXEC = the walking lanes,
     // so parked and finished lanes cost the LDS nothing.  Per lane the sequence of candidates, the counts and every
-    // decision are lz_search's: 128 candidates at most, and zlib's short-chain answer (the best after 32, if a 33rd is
-    // in range) is taken lazily -- `best` only changes in the comparison, so the first comparison behind the 32nd candidate
+    // decision are lz_search's: max_chain candidates at most (128 at level 6), and zlib's short-chain answer (the best after snap_chain -- 32 --,
+    // if one more is in range) is taken lazily -- `best` only changes in the comparison, so the first comparison behind the snap_chain-th candidate
     // (or the end) still sees it.
     constexpr uint32_t kParkLanes = 12;
     uint32_t n_l = 0, nxt = cur;                                   // candidates examined by this lane; the link of `cur`
@@ -572,13 +573,13 @@ static __device__ __forceinline__ void lz_search_wave(const uint8_t* data, const
             "s_mov_b64 exec, %[sv]"
             : [cur] "+v"(cur), [nxt] "+v"(nxt), [nl] "+v"(n_l), [walk] "+s"(walk), [park] "+s"(park), [sv] "=&s"(sv), [cont] "=&s"(cont),
               [cnt] "=&s"(cnt), [a] "=&v"(ta), [b] "=&v"(tb), [w0] "=&v"(w0), [l] "=&v"(tl)
-            : [dbias] "v"(dbias), [lbias] "s"(lbias), [fmask] "v"(f_mask), [scan] "v"(scan_w), [limit] "v"(limit), [bound] "s"(kMaxChain),
+            : [dbias] "v"(dbias), [lbias] "s"(lbias), [fmask] "v"(f_mask), [scan] "v"(scan_w), [limit] "v"(limit), [bound] "s"(Lv::max_chain),
               [npark] "s"(kParkLanes), [ring] "s"(kMatchRing)
             : "vcc", "scc", "memory", "v90", "v91");
         if (park == 0) break;                                      // nobody hit, nobody walks
         bool resume = false;
         if ((park >> lane) & 1ull) {                               // cur = the candidate whose filter word matched, nxt = its link, n_l counts it
-            if (n_l > kShortChain && snap == kNone) snap = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;   // what zlib's short chain returned
+            if (n_l > Lv::snap_chain && snap == kNone) snap = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;   // what zlib's short chain returned
             const uint32_t c_ = match_ring(cur);
             uint32_t x0 = load_u32(data, c_) ^ scan0, x1 = load_u32(data, c_ + 4u) ^ scan1;
             asm volatile("" : "+v"(x0), "+v"(x1));   /* both words now: left alone, the second read is sunk behind a branch on the first */
@@ -586,7 +587,7 @@ static __device__ __forceinline__ void lz_search_wave(const uint8_t* data, const
             uint32_t len = x0 ? l0 : x1 ? l1 : 8u;
             if (len == 8u) len = match_len_from(data, c_, pp, 8u, max_len);
             len = len < max_len ? len : max_len;
-            resume = nxt > limit && n_l < kMaxChain;
+            resume = nxt > limit && n_l < Lv::max_chain;
             if (len > best) {
                 best = len; best_pos = cur;
                 if (len >= nice) resume = false;
@@ -597,7 +598,7 @@ static __device__ __forceinline__ void lz_search_wave(const uint8_t* data, const
         walk |= __builtin_amdgcn_ballot_w64(resume);
         park = 0;
     }
-    if (n_l > kShortChain && snap == kNone) snap = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;   // a 33rd candidate was examined: the short chain's answer
+    if (n_l > Lv::snap_chain && snap == kNone) snap = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;   // a candidate behind the snap_chain-th was examined: the short chain's answer
     e128 = best >= kMinMatch ? entry_pack(best, p - best_pos) : 0u;
     e32 = snap != kNone ? snap : e128;
     // TOO_FAR: a minimum-length match further than 4096 back is dropped (deflate_slow)
@@ -613,6 +614,7 @@ static __device__ __forceinline__ void lz_search_wave(const uint8_t* data, const
 // searched, and they go where the oldest tile's were (a tile-per-workgroup version re-read the whole
 // 147 KB window per tile and spent 58% of its wave-cycles waiting on it; rounds 1-3 slid a linear
 // window down after every tile).
+template <class Lv>      // the compression level (zwz_common.h): the walk's bound, the snapshot and the nice stop of lz_search_wave
 __global__ __launch_bounds__(kMatchThreads) void lz_match_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                  const uint32_t* __restrict__ in_len, const uint16_t* __restrict__ links,
                                                                  uint2* __restrict__ entries, uint64_t* __restrict__ has128,
@@ -725,7 +727,7 @@ __global__ __launch_bounds__(kMatchThreads) void lz_match_kernel(const uint8_t* 
                     float est = (float)cnt[j];
                     if (cnt[j] == kKeyDepth) {
                         const uint32_t win = p[j] < kMaxDist ? p[j] : kMaxDist;
-                        est = fminf(128.0f, (float)(win * kKeyDepth) * __frcp_rn((float)(p[j] - cur[j])));
+                        est = fminf((float)Lv::max_chain, (float)(win * kKeyDepth) * __frcp_rn((float)(p[j] - cur[j])));
                         est = fmaxf(est, (float)kKeyDepth);
                     }
                     const uint32_t k = 1u + (uint32_t)(__log2f(fmaxf(est, 1.0f)) * 2.0f);
@@ -790,7 +792,7 @@ __global__ __launch_bounds__(kMatchThreads) void lz_match_kernel(const uint8_t* 
         }
         auto search_and_store = [&](uint32_t p, bool active) {
             uint32_t e128 = 0, e32 = 0;
-            lz_search_wave(sdata, slink, p, L, active, e128, e32);
+            lz_search_wave<Lv>(sdata, slink, p, L, active, e128, e32);
             if (e128) {
                 ent[p] = make_uint2(e128, e32);   // e128 == 0 implies e32 == 0; readers gate on has128
                 atomicOr(&s_has[(p - ts) >> 5], 1u << (p & 31u));
@@ -949,6 +951,7 @@ struct ParseWaveMem {
     uint8_t flag[64];
 };
 
+template <class Lv>      // the compression level: fresh_step's max_lazy and good_length
 __global__ __launch_bounds__(kParseThreads) void lz_parse_kernel(const uint32_t* __restrict__ in_len, uint32_t n,
                                                                 const uint2* __restrict__ entries, const uint64_t* __restrict__ has128,
                                                                 uint64_t* __restrict__ sym, uint64_t* __restrict__ mst,
@@ -1059,7 +1062,7 @@ __global__ __launch_bounds__(kParseThreads) void lz_parse_kernel(const uint32_t*
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         ZWZ_PSTAMP(0);                                   // quiet-block tests, the window's next records (fetch issued, previous written to LDS)
         FreshStep st{q + 1, q, 0u, 1u};
-        if (valid) st = fresh_step(lookup, q, L);
+        if (valid) st = fresh_step<Lv>(lookup, q, L);
         ZWZ_PSTAMP(1);                                   // every lane's step
         uint32_t succ = st.next >= base + 64u ? 64u : st.next - base;      // 64 = leaves the block
         const uint64_t entry = ((uint64_t)m.ring_r[2 * (blk & 7u)] | ((uint64_t)m.ring_r[2 * (blk & 7u) + 1] << 32));
@@ -1320,7 +1323,7 @@ static __device__ __forceinline__ uint32_t enc_slot_bits(uint32_t wpw, uint32_t 
 template <uint32_t T>                                   // threads of the workgroup; 16 384 / T output vectors a thread
 static __device__ __forceinline__ void encode_stored_chunk(const uint8_t* __restrict__ data, uint32_t L, uint32_t n_blocks,
                                                            uint32_t lane_start, uint32_t lane_end, uint32_t* __restrict__ gout,
-                                                           uint32_t* __restrict__ out_len_slot) {
+                                                           uint32_t* __restrict__ out_len_slot, uint32_t zflg /* the zlib header's second byte: zlib_flg(level) */) {
     __shared__ uint32_t s_hb[kMaxBlocks + 1], s_st[kMaxBlocks + 1];   // stream offset of each block header; its first input byte
     __shared__ uint32_t s_a[T / 64], s_adler_be;
     __shared__ unsigned long long s_b[T / 64];
@@ -1381,7 +1384,7 @@ static __device__ __forceinline__ void encode_stored_chunk(const uint8_t* __rest
     const uint32_t h1 = s_hb[1], h2 = s_hb[2], h3 = s_hb[3], h4 = s_hb[4], h_end = s_hb[n_blocks], adler_be = h_end < kChunk ? s_adler_be : 0u;
     auto block_at = [&](uint32_t x) { return (uint32_t)(x >= h1) + (uint32_t)(x >= h2) + (uint32_t)(x >= h3) + (uint32_t)(x >= h4); };   // unused slots hold h_end
     auto byte_at = [&](uint32_t x) -> uint32_t {
-        if (x < 2u) return x ? 0x9cu : 0x78u;
+        if (x < 2u) return x ? zflg : 0x78u;
         if (x >= h_end) return x - h_end < 4u ? (adler_be >> (8u * (x - h_end))) & 0xffu : 0u;
         uint32_t b = block_at(x);
         if (b >= n_blocks) b = n_blocks - 1u;
@@ -1442,7 +1445,7 @@ __global__ __launch_bounds__(kEncStoredThreads) void encode_stored_kernel(const 
                                                                           const uint32_t* __restrict__ in_len, const ChunkInfo* __restrict__ info,
                                                                           const BlockInfo* __restrict__ blocks, const BlockOut* __restrict__ plans,
                                                                           uint8_t* __restrict__ out, uint64_t out_stride, uint32_t* __restrict__ out_len,
-                                                                          uint32_t* __restrict__ huff_list, uint32_t* __restrict__ small_list, uint32_t* __restrict__ tickets) {
+                                                                          uint32_t* __restrict__ huff_list, uint32_t* __restrict__ small_list, uint32_t* __restrict__ tickets, uint32_t zflg) {
     const uint32_t chunk = blockIdx.x;
     const uint32_t L = in_len[chunk], n_blocks = info[chunk].n_blocks;
     const BlockInfo* bi = blocks + (size_t)chunk * kMaxBlocks;
@@ -1459,7 +1462,7 @@ __global__ __launch_bounds__(kEncStoredThreads) void encode_stored_kernel(const 
         return;
     }
     encode_stored_chunk<kEncStoredThreads>(in + in_off[chunk], L, n_blocks, my_start, my_end,
-                                           reinterpret_cast<uint32_t*>(out + (size_t)chunk * out_stride), out_len + chunk);
+                                           reinterpret_cast<uint32_t*>(out + (size_t)chunk * out_stride), out_len + chunk, zflg);
 }
 
 // (ZWZ_ENC_EXP & 16, experiment builds only -- tools/encode_times.sh: wave 0 of every workgroup sums the cycles per phase in registers,
@@ -1479,7 +1482,9 @@ __device__ unsigned long long g_enc_times[8];
 // kThreads / kOutW: 1 024 threads and a 64 KB staging buffer for every chunk (two workgroups a CU), or -- round 5 -- 256 threads and 16 KB for the
 // chunks of one block and at most kSmallEncBytes bytes (encode_stored_kernel sorts them onto their own list): six workgroups a CU.  A 7 KB file is
 // little work behind a chain of a dozen dependent round trips and barriers, and a CU with two of them in flight mostly waits.
-template <uint32_t kThreads, uint32_t kOutW, uint32_t kMinWaves>
+// kZflg: the zlib header's second byte (zlib_flg(level): 9c at level 6, 5e below) -- a template argument, so that the level-6 kernel is the one it was:
+// as a kernel argument the byte cost both forms scratch (76 -> 80 and 40 -> 52 bytes a lane).
+template <uint32_t kThreads, uint32_t kOutW, uint32_t kMinWaves, uint32_t kZflg>
 __global__ __launch_bounds__(kThreads, kMinWaves) void encode_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                 const uint32_t* __restrict__ in_len, const uint2* __restrict__ entries,
                                                                 const uint64_t* __restrict__ sym, const uint64_t* __restrict__ mst,
@@ -1586,7 +1591,7 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void encode_kernel(const uint8
     // (round 5; see the symbols' block below): the stream's fixed parts then go in behind the symbols, whose waves use the buffer as scratch first.
     const bool one_pass = ci.n_blocks == 1u && s_blk[0].type != kStored && (ZWZ_ENC_EXP & 1) == 0;       // workgroup-uniform
     auto write_headers = [&](bool with_eob) {
-        if (tid == 0) lds_or_bits<kOutW>(s_out, 0, 0x9c78u, 16);
+        if (tid == 0) lds_or_bits<kOutW>(s_out, 0, 0x78u | kZflg << 8, 16);
         for (uint32_t b = 0; b < ci.n_blocks; b++) {
             const EncBlock e = s_blk[b];
             const uint32_t hw = (bo[b].hdr_bits + 31) >> 5;
@@ -2687,15 +2692,21 @@ uint32_t exp_flags_kernels() { return (uint32_t)(ZWZ_MATCH_EXP) | (uint32_t)(ZWZ
 hipError_t configure_kernels() {
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_links_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLinksLdsBytes));
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(exchange_order_probe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLinksLdsBytes));
-    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
-    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kEncodeThreads, kOutWords, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEncodeLdsBytes));
-    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallEncLdsBytes));
+    // more than 64 KB of dynamic LDS: every instantiation needs the attribute, or its first launch fails
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<4>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<5>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<6>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kEncodeThreads, kOutWords, 8, 0x9cu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEncodeLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kEncodeThreads, kOutWords, 8, 0x5eu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEncodeLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs, 0x9cu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallEncLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs, 0x5eu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallEncLdsBytes));
     ZWZ_TRY(configure_lazy_kernels());
     return configure_band_kernels();
 }
 
 hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /* kNumDeflateStages + 1 or null */) {
     if (a.n == 0) return hipSuccess;
+    if (a.level < (uint32_t)kLevelMin || a.level > (uint32_t)kLevelMax) return hipErrorInvalidValue;     // a level without kernels is an error, never another level's kernels
     ZWZ_TRY(hipMemsetAsync(a.tickets, 0, kTicketBytes, s));
     if (ev) ZWZ_TRY(hipEventRecord(ev[0], s));
     // Chain-heavy chunks (lz_dense_list: a sample of each chunk's trigrams): positions sorted by (bucket, position), then the banded
@@ -2714,8 +2725,12 @@ hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /*
         ZWZ_TRY(launch_place(a, s));
     }
     if (ev) ZWZ_TRY(hipEventRecord(ev[1], s));
-    hipLaunchKernelGGL(lz_match_kernel, dim3(a.n), dim3(kMatchThreads), kMatchLdsBytes, s, a.in, a.in_off, a.in_len,
-                       a.links, a.entries, a.has128, a.perm, a.link_stat, which == 1u ? 0u : force == 2u ? 2u : 1u, a.tickets + 40);
+    switch (a.level) {
+#define ZWZ_MATCH_LAUNCH(N) case N: hipLaunchKernelGGL(lz_match_kernel<LzLevel<N>>, dim3(a.n), dim3(kMatchThreads), kMatchLdsBytes, s, a.in, a.in_off, a.in_len, \
+                                                  a.links, a.entries, a.has128, a.perm, a.link_stat, which == 1u ? 0u : force == 2u ? 2u : 1u, a.tickets + 40); break;
+        ZWZ_MATCH_LAUNCH(4) ZWZ_MATCH_LAUNCH(5) ZWZ_MATCH_LAUNCH(6)
+#undef ZWZ_MATCH_LAUNCH
+    }
 #if ZWZ_MATCH_EXP & 16
     if (getenv("ZWZ_MATCH_TIMES")) {
         uint32_t h[64];
@@ -2735,8 +2750,12 @@ hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /*
         }
     }
     if (ev) ZWZ_TRY(hipEventRecord(ev[2], s));
-    hipLaunchKernelGGL(lz_parse_kernel, dim3((a.n + kParseThreads / 64 - 1) / (kParseThreads / 64)), dim3(kParseThreads), 0, s, a.in_len, a.n, a.entries, a.has128, a.sym, a.mst, a.info, a.links,
-                       (which != 1u && lazy) ? a.link_stat : (const uint32_t*)nullptr);
+    switch (a.level) {
+#define ZWZ_PARSE_LAUNCH(N) case N: hipLaunchKernelGGL(lz_parse_kernel<LzLevel<N>>, dim3((a.n + kParseThreads / 64 - 1) / (kParseThreads / 64)), dim3(kParseThreads), 0, s, a.in_len, a.n, \
+                                                  a.entries, a.has128, a.sym, a.mst, a.info, a.links, (which != 1u && lazy) ? a.link_stat : (const uint32_t*)nullptr); break;
+        ZWZ_PARSE_LAUNCH(4) ZWZ_PARSE_LAUNCH(5) ZWZ_PARSE_LAUNCH(6)
+#undef ZWZ_PARSE_LAUNCH
+    }
 #if ZWZ_PARSE_EXP & 16
     if (getenv("ZWZ_PARSE_TIMES")) {
         unsigned long long h[8], z[8] = {0};
@@ -2756,12 +2775,16 @@ hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /*
         uint32_t* huff_list = reinterpret_cast<uint32_t*>(a.perm);          // lz_match's work-order array is dead by now
         uint32_t* small_list = huff_list + a.n;                             // (plan's list of open blocks is dead too)
         hipLaunchKernelGGL(encode_stored_kernel, dim3(a.n), dim3(kEncStoredThreads), 0, s, a.in, a.in_off, a.in_len, a.info, a.blocks, a.plans,
-                           a.out, a.out_stride, a.out_len, huff_list, small_list, a.tickets);
+                           a.out, a.out_stride, a.out_len, huff_list, small_list, a.tickets, zlib_flg(a.level));
         const uint32_t cus = a.cu_count ? a.cu_count : 256u;
-        hipLaunchKernelGGL((encode_kernel<kEncodeThreads, kOutWords, 8>), dim3(a.n < 2u * cus ? a.n : 2u * cus), dim3(kEncodeThreads), kEncodeLdsBytes, s, a.in, a.in_off, a.in_len, a.entries, a.sym,
-                           a.mst, a.info, a.blocks, a.plans, a.out, a.out_stride, a.out_len, a.links, huff_list, a.tickets, (uint32_t)kTicketHuffCount, (uint32_t)kTicketHuffNext);
-        hipLaunchKernelGGL((encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs>), dim3(a.n < kSmallEncWgs * cus ? a.n : kSmallEncWgs * cus), dim3(kSmallEncThreads), kSmallEncLdsBytes, s, a.in, a.in_off, a.in_len, a.entries, a.sym,
+        static_assert(zlib_flg(4) == 0x5eu && zlib_flg(5) == 0x5eu && zlib_flg(6) == 0x9cu, "encode_kernel is instantiated for these two header bytes");
+#define ZWZ_ENCODE_LAUNCH(FLG)                                                                                                                                   \
+        hipLaunchKernelGGL((encode_kernel<kEncodeThreads, kOutWords, 8, FLG>), dim3(a.n < 2u * cus ? a.n : 2u * cus), dim3(kEncodeThreads), kEncodeLdsBytes, s, a.in, a.in_off, a.in_len, a.entries, a.sym, \
+                           a.mst, a.info, a.blocks, a.plans, a.out, a.out_stride, a.out_len, a.links, huff_list, a.tickets, (uint32_t)kTicketHuffCount, (uint32_t)kTicketHuffNext);                 \
+        hipLaunchKernelGGL((encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs, FLG>), dim3(a.n < kSmallEncWgs * cus ? a.n : kSmallEncWgs * cus), dim3(kSmallEncThreads), kSmallEncLdsBytes, s, a.in, a.in_off, a.in_len, a.entries, a.sym, \
                            a.mst, a.info, a.blocks, a.plans, a.out, a.out_stride, a.out_len, a.links, small_list, a.tickets, (uint32_t)kTicketSmallCount, (uint32_t)kTicketSmallNext);
+        if (a.level == 6u) { ZWZ_ENCODE_LAUNCH(0x9cu) } else { ZWZ_ENCODE_LAUNCH(0x5eu) }
+#undef ZWZ_ENCODE_LAUNCH
     }
 #if ZWZ_ENC_EXP & 16
     if (getenv("ZWZ_ENC_TIMES")) {

@@ -64,6 +64,7 @@ struct __attribute__((packed, aligned(2))) LazyVec { uint32_t x, y, z, w; };    
 // (u = sorted index, bs = how many) and the first eight on their way, 3 those are in, 4 it has no candidates.
 struct LazySlot { uint32_t pos, stage, u, bs, first0; LazyVec vec; };
 
+template <class Lv>      // the compression level (zwz_common.h): longest_match's and deflate_slow's five numbers
 __global__ __launch_bounds__(kLazyThreads, 2) void lz_lazy_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                   const uint32_t* __restrict__ in_len, const uint32_t* __restrict__ list,
                                                                   uint32_t* __restrict__ tickets, const uint32_t* __restrict__ sorted,
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(kLazyThreads, 2) void lz_lazy_kernel(const uint8_t*
                 const bool selB = !have && stB != 0u && posB == p;
                 if (selB) { posA = posB; stA = stB; uA = uB; nA = nB; vecA = vecB; wantA = wantB; }
                 const bool hasA = !have && stA != 0u && posA == p;
-                const bool t1 = !have && pend0 && (b >= kMaxLazy || p >= L);
+                const bool t1 = !have && pend0 && (b >= Lv::max_lazy || p >= L);
                 const bool fin = !have && !t1 && p >= L;
                 const bool t3 = !have && !t1 && !fin && (p + kMinMatch > L || (hasA && stA == 4u));
                 const bool out2 = t1 || t3;
@@ -175,8 +176,8 @@ __global__ __launch_bounds__(kLazyThreads, 2) void lz_lazy_kernel(const uint8_t*
                 if (go) {
                     const uint32_t lookahead = L - p;
                     max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch;
-                    nice = lookahead < kNiceLen ? lookahead : kNiceLen;
-                    const uint32_t chain = b >= kGoodLen ? kShortChain : kMaxChain;
+                    nice = lookahead < Lv::nice ? lookahead : Lv::nice;
+                    const uint32_t chain = b >= Lv::good ? Lv::short_chain : Lv::max_chain;    // (good >= max_lazy, level 4: a search never starts with b >= good)
                     nleft = nA < chain ? nA : chain;
                     ui = uA; best = b; best_pos = 0; kfirst = 1u;
                     f_off = b >= kMinMatch ? b - 3u : 0u; f_mask = b >= kMinMatch ? 0xffffffffu : 0xffffffu;
@@ -374,14 +375,24 @@ __global__ __launch_bounds__(kLazyThreads, 2) void lz_lazy_kernel(const uint8_t*
 uint32_t exp_flags_lazy() { return (uint32_t)(ZWZ_LAZY_EXP); }
 
 hipError_t configure_lazy_kernels() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
+    // more than 64 KB of dynamic LDS: every instantiation needs the attribute
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<4>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<5>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<6>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
 }
 
 hipError_t launch_lazy(const DeflateArgs& a, hipStream_t s) {
     const uint32_t cus = a.cu_count ? a.cu_count : 256u;
     const uint32_t G = a.n < 2u * cus ? a.n : 2u * cus;
-    hipLaunchKernelGGL(lz_lazy_kernel, dim3(G), dim3(kLazyThreads), kLazyLdsBytes, s, a.in, a.in_off, a.in_len, a.dense_list, a.tickets, a.sorted,
-                       reinterpret_cast<uint32_t*>(a.entries), a.sym, a.mst, a.info, a.links);
+    switch (a.level) {
+#define ZWZ_LAZY_LAUNCH(N) case N: hipLaunchKernelGGL(lz_lazy_kernel<LzLevel<N>>, dim3(G), dim3(kLazyThreads), kLazyLdsBytes, s, a.in, a.in_off, a.in_len, a.dense_list, a.tickets, \
+                                                 a.sorted, reinterpret_cast<uint32_t*>(a.entries), a.sym, a.mst, a.info, a.links); break;
+        ZWZ_LAZY_LAUNCH(4) ZWZ_LAZY_LAUNCH(5) ZWZ_LAZY_LAUNCH(6)
+#undef ZWZ_LAZY_LAUNCH
+        default: return hipErrorInvalidValue;
+    }
 #if ZWZ_LAZY_EXP & 16
     if (getenv("ZWZ_LAZY_TIMES")) {
         uint32_t h[64];
