@@ -452,14 +452,22 @@ extern "C" int emu_parse_blocks_check(const uint8_t* in, uint32_t L) {
     return 0;
 }
 
-// Batch copy the way the inflate kernel does it: one output byte per lane, owner by binary search
-// over the batch's start offsets, references into the same batch chased down to a literal or to
-// output of an earlier batch.
-extern "C" uint32_t emu_inflate_bytewise(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint32_t* status, uint32_t batch_syms) {
+// Batch copy the way the inflate kernel does it: one output byte per lane; the owner of a byte from a per-byte map (every symbol marks
+// its first byte with 1 + its index, a forward max-scan carries the marks on: the kernel's `mapped` branch) where the batch has at most
+// own_cap bytes, else by binary search over the batch's start offsets; references into the same batch chased down to a literal or to
+// output of an earlier batch.  A batch ends at batch_syms symbols, at the end of the block, and in front of a symbol whose code the
+// packed fast tables do not hold: that symbol goes through the one-symbol path with its own copy (from + i % dist), as in the kernel.
+// Counters over all calls since the last emu_copy_counters(.., 1): the deepest chase (owner lookups behind a byte), batches above
+// own_cap, batches of at most own_cap, matches that overlap themselves with their source in the batch, matches of the one-symbol path.
+namespace {
+uint64_t g_copy_deepest = 0, g_copy_above = 0, g_copy_mapped = 0, g_copy_self_in_batch = 0, g_copy_slow = 0;
+uint32_t inflate_bytewise(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint32_t* status, uint32_t batch_syms, uint32_t own_cap) {
+    enum : uint32_t { kSlow = 3 };
     InflateState st;
-    static InflateTables t;
+    static InflateTables t, tp;
     uint8_t lens[320];
     uint32_t batch[kBatch], pos[kBatch];
+    if (batch_syms > kBatch) batch_syms = kBatch;
     if (inflate_begin(st, in, n)) {
         for (;;) {
             uint32_t src = 0, len = 0;
@@ -472,30 +480,66 @@ extern "C" uint32_t emu_inflate_bytewise(const uint8_t* in, uint32_t n, uint8_t*
                 if (cp < len) st.status = kInfOverflow;
                 if (st.status != kInfRunning) break;
             } else {
+                tp = t;
+                for (uint32_t x = 0; x < (1u << kLitFastBits); x++) tp.lit_fast[x] = pack_lit_entry(t.lit_fast[x]);
+                for (uint32_t x = 0; x < (1u << kDistFastBits); x++) tp.dist_fast[x] = pack_dist_entry(t.dist_fast[x]);
                 bool done = false;
                 while (!done) {
-                    uint32_t k = inflate_decode_batch(st, t, cap, batch, pos, done, batch_syms);
-                    if (!k) continue;
-                    const uint32_t bstart = pos[0], bend = st.out_pos;
-                    uint32_t sp[64], sv[64];
-                    for (uint32_t i = 0; i < 64; i++) { sp[i] = i < k ? pos[i] : 0xffffffffu; sv[i] = i < k ? batch[i] : 0; }
-                    auto owner = [&](uint32_t p, uint32_t& ov, uint32_t& op) {
-                        uint32_t lo = 0;
-                        for (uint32_t stp = 32; stp >= 1; stp >>= 1) if (sp[(lo + stp) & 63] <= p) lo += stp;
-                        ov = sv[lo]; op = sp[lo];
-                    };
-                    std::vector<uint8_t> res(bend - bstart);
-                    for (uint32_t p = bstart; p < bend; p++) {
-                        uint32_t ov, op; owner(p, ov, op);
-                        bool lit = ov < 256; uint32_t s = 0;
-                        if (!lit) { uint32_t d = ov & 0xffff; s = op - d + ((p - op) % d); }
-                        while (!lit && s >= bstart) {
-                            uint32_t ov2, op2; owner(s, ov2, op2);
-                            if (ov2 < 256) { lit = true; ov = ov2; } else { uint32_t d = ov2 & 0xffff; s = op2 - d + ((s - op2) % d); }
-                        }
-                        res[p - bstart] = lit ? (uint8_t)ov : out[s];
+                    uint32_t k = 0;
+                    bool slow = false;
+                    while (k < batch_syms && !done) {
+                        if (packed_slot(in, n, tp, st.br.bit_pos()).kind == kSlow) { slow = true; break; }
+                        k += inflate_decode_batch(st, t, cap, batch + k, pos + k, done, 1u);
                     }
-                    memcpy(out + bstart, res.data(), res.size());
+                    if (k) {
+                        const uint32_t bstart = pos[0], bend = st.out_pos, bbytes = bend - bstart;
+                        const bool mapped = bbytes <= own_cap;
+                        (mapped ? g_copy_mapped : g_copy_above)++;
+                        uint32_t sp[64], sv[64];
+                        for (uint32_t i = 0; i < 64; i++) { sp[i] = i < k ? pos[i] : 0xffffffffu; sv[i] = i < k ? batch[i] : 0; }
+                        std::vector<uint8_t> ownb(mapped ? bbytes : 0u, 0);
+                        if (mapped) {
+                            for (uint32_t i = 0; i < k; i++) ownb[sp[i] - bstart] = (uint8_t)(i + 1u);
+                            uint8_t carry = 0;
+                            for (uint32_t j = 0; j < bbytes; j++) { carry = std::max(carry, ownb[j]); ownb[j] = carry; }
+                        }
+                        for (uint32_t i = 0; i < k; i++) if (sv[i] >= 256u && (sv[i] >> 16) > (sv[i] & 0xffffu) && sp[i] - (sv[i] & 0xffffu) >= bstart) g_copy_self_in_batch++;
+                        auto owner = [&](uint32_t p, uint32_t& ov, uint32_t& op) {
+                            uint32_t lo = 0;
+                            if (mapped) lo = (uint32_t)ownb[p - bstart] - 1u;
+                            else for (uint32_t stp = 32; stp >= 1; stp >>= 1) if (sp[(lo + stp) & 63] <= p) lo += stp;
+                            ov = sv[lo]; op = sp[lo];
+                        };
+                        std::vector<uint8_t> res(bbytes);
+                        for (uint32_t p = bstart; p < bend; p++) {
+                            uint32_t ov, op; owner(p, ov, op);
+                            bool lit = ov < 256; uint32_t s = 0;
+                            uint64_t hops = 0;
+                            if (!lit) { uint32_t d = ov & 0xffff; s = op - d + ((p - op) % d); }
+                            while (!lit && s >= bstart) {
+                                uint32_t ov2, op2; owner(s, ov2, op2);
+                                hops++;
+                                if (ov2 < 256) { lit = true; ov = ov2; } else { uint32_t d = ov2 & 0xffff; s = op2 - d + ((s - op2) % d); }
+                            }
+                            if (hops > g_copy_deepest) g_copy_deepest = hops;
+                            res[p - bstart] = lit ? (uint8_t)ov : out[s];
+                        }
+                        memcpy(out + bstart, res.data(), res.size());
+                    }
+                    if (slow) {
+                        const uint32_t k1 = inflate_decode_batch(st, t, cap, batch, pos, done, 1u);
+                        if (k1) {
+                            const uint32_t mv = batch[0], mp = pos[0];
+                            if (mv < 256u) out[mp] = (uint8_t)mv;
+                            else {
+                                const uint32_t l = mv >> 16, d = mv & 0xffffu, from = mp - d;
+                                std::vector<uint8_t> res(l);
+                                for (uint32_t i = 0; i < l; i++) res[i] = out[from + (i % d)];     // (every lane loads, then stores)
+                                memcpy(out + mp, res.data(), l);
+                                g_copy_slow++;
+                            }
+                        }
+                    }
                 }
                 if (st.status != kInfRunning) break;
             }
@@ -504,6 +548,18 @@ extern "C" uint32_t emu_inflate_bytewise(const uint8_t* in, uint32_t n, uint8_t*
     }
     *status = st.status;
     return st.out_pos;
+}
+}  // namespace
+
+extern "C" uint32_t emu_inflate_bytewise(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint32_t* status, uint32_t batch_syms) {
+    return inflate_bytewise(in, n, out, cap, status, batch_syms, 0u);             // owners by binary search
+}
+extern "C" uint32_t emu_inflate_bytewise_mapped(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint32_t* status, uint32_t batch_syms, uint32_t own_cap) {
+    return inflate_bytewise(in, n, out, cap, status, batch_syms, own_cap);
+}
+extern "C" void emu_copy_counters(uint64_t* out5, int reset) {
+    out5[0] = g_copy_deepest; out5[1] = g_copy_above; out5[2] = g_copy_mapped; out5[3] = g_copy_self_in_batch; out5[4] = g_copy_slow;
+    if (reset) g_copy_deepest = g_copy_above = g_copy_mapped = g_copy_self_in_batch = g_copy_slow = 0;
 }
 
 // statistics for tuning the inflate fast tables: how many symbols miss the lit/len or distance table

@@ -24,6 +24,10 @@ def load():
     lib.emu_inflate_bytewise.restype = ctypes.c_uint32
     lib.emu_inflate_bytewise.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32,
                                          ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]
+    lib.emu_inflate_bytewise_mapped.restype = ctypes.c_uint32
+    lib.emu_inflate_bytewise_mapped.argtypes = lib.emu_inflate_bytewise.argtypes + [ctypes.c_uint32]
+    lib.emu_copy_counters.restype = None
+    lib.emu_copy_counters.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     lib.emu_band_records.restype = ctypes.c_uint32
     lib.emu_band_records.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.emu_plan_split_check.restype = ctypes.c_uint32
@@ -62,3 +66,21 @@ def inflate_bytewise(lib, payload: bytes, cap: int = 65535, batch_syms: int = 64
     st = ctypes.c_uint32()
     n = lib.emu_inflate_bytewise(payload, len(payload), out, cap, ctypes.byref(st), batch_syms)
     return out.raw[:n], st.value
+
+
+def inflate_bytewise_mapped(lib, payload: bytes, cap: int = 65535, batch_syms: int = 64, own_cap: int = 1024):
+    """The same with the kernel's per-byte owner map for batches of at most own_cap bytes (0: every batch searches)."""
+    out = ctypes.create_string_buffer(cap + 8)
+    st = ctypes.c_uint32()
+    n = lib.emu_inflate_bytewise_mapped(payload, len(payload), out, cap, ctypes.byref(st), batch_syms, own_cap)
+    return out.raw[:n], st.value
+
+
+COPY_COUNTERS = ("deepest_chase", "batches_above_cap", "batches_mapped", "self_overlap_in_batch", "slow_matches")
+
+
+def copy_counters(lib, reset=True):
+    """What the byte-wise copies since the last reset went through -> {name: count} (COPY_COUNTERS)."""
+    v = (ctypes.c_uint64 * 5)()
+    lib.emu_copy_counters(v, int(reset))
+    return dict(zip(COPY_COUNTERS, [int(x) for x in v]))
