@@ -6,7 +6,8 @@
 //   * entry u of the sorted array = (h << 16 | p); entry u - k is p's k-th candidate, newest first, as long as it is in
 //     the same bucket, is not position 0 (zlib's NIL), and lies within MAX_DIST (band_count);
 //   * zlib keeps the FIRST candidate of the greatest length, so the answer is max over k of (length, -k): one
-//     v_max_u32 per candidate on a packed key (band_key).  Lengths are compared on eight bytes kept beside each
+//     v_max_u32 per candidate on a packed key (band_key; the kernel takes two candidates' keys in the 16-bit halves of a word,
+//     band_key_pair / band_first_pass).  Lengths are compared on eight bytes kept beside each
 //     entry -- bytes 3..10 behind the trigram where every bucket of the tile holds one trigram only ("pure"), else bytes
 //     0..7 -- which settles every length below kDeep (11 / 8);
 //   * a position whose best candidate agrees on all eight bytes is finished by a second pass that visits only the
@@ -109,7 +110,55 @@ ZWZ_HD uint32_t band_key_masked(uint32_t own_lo, uint32_t own_hi, uint32_t c_lo,
     const uint32_t t = band_ctz64((own_lo ^ c_lo) & m_lo, (own_hi ^ c_hi) & m_hi);
     return ((t & 0x78u) << 5) | (129u - k);
 }
-ZWZ_HD uint32_t band_tail_bytes(bool pure, uint32_t lookahead) {       // bytes of the word inside the data (lookahead >= 3)
+// Two candidates an instruction (lz_match_band's first pass): a key is 12 bits, so the keys of candidates k and k + 1 live in the low and
+// the high 16 bits of one word, and so do the running maximum (a maximum per half; the two meet behind the loop) and the values `none`.
+// `mask` holds, per half, the mask of the first differing bit's byte field: kBandPairLenMask's 0x78 for a candidate the position has, 0
+// for one beyond its count -- that one's key is then of length 0, 129 - k alone.  Such a key (k >= 2: it lies beyond a count >= 1) is
+// below the key of the position's first candidate (>= 128), which is always among the keys the maximum is taken over, and below
+// kBandKeyNoneImpure: it never wins, so nothing has to keep it out of the maximum (band_first_pass below is the whole argument, run).
+constexpr uint32_t kBandPairLenMask = 0x00780078u;
+ZWZ_HD uint32_t band_key_pair(uint32_t own_lo, uint32_t own_hi, uint32_t a_lo, uint32_t a_hi, uint32_t b_lo, uint32_t b_hi, uint32_t k, uint32_t mask) {
+    // (the halves of a first differing bit: 0 .. 63, or 0xffff for "none" -- what the kernel's 16-bit find-first-bit results and minimum give)
+    const uint32_t ta = band_ctz64(own_lo ^ a_lo, own_hi ^ a_hi) & 0xffffu, tb = band_ctz64(own_lo ^ b_lo, own_hi ^ b_hi) & 0xffffu;
+    return (((ta | tb << 16) & mask) << 5) | (129u - k) | (128u - k) << 16;
+}
+// The masks of a trip of eight candidates k0 + 1 .. k0 + 8 for a position of `cnt` candidates, a byte a candidate (0x78 or 0), and
+// the mask of the pair j, j + 1 (j even) out of them.
+ZWZ_HD uint64_t band_trip_mask(uint32_t k0, uint32_t cnt) {
+    const int32_t over = (int32_t)(k0 + 8u) - (int32_t)cnt;                   // the trip's candidates beyond the count
+    const uint32_t d = over < 0 ? 0u : over > 8 ? 8u : (uint32_t)over;
+    return 0x7878787878787878ull >> (8u * d < 63u ? 8u * d : 63u);            // (all eight beyond: 63 bits leave nothing of 0x78...)
+}
+ZWZ_HD uint32_t band_pair_mask(uint64_t trip_mask, uint32_t j) {
+    return ((uint32_t)(trip_mask >> (8u * j)) & 0xffu) | ((uint32_t)(trip_mask >> (8u * j + 8u)) & 0xffu) << 16;
+}
+ZWZ_HD uint32_t band_pair_max(uint32_t pair) { return (pair & 0xffffu) > (pair >> 16) ? pair & 0xffffu : pair >> 16; }
+// The first pass of a position that is no tail, in the order lz_match_band takes it (and its specification): trips of eight candidates,
+// unmasked up to `kmin` (the smallest count among the wave's lanes that have candidates: any value from 0 to cnt here), masked by
+// band_trip_mask up to `kmax` (the wave's greatest count: any value >= cnt), the short chain's snapshot behind the trip that ends at
+// snap_chain.  E(k) -> the k-th candidate's 8-byte word as lo | hi << 32; candidates beyond cnt may hold anything.  Same best and
+// snapshot as the maximum of band_key over the candidates 1 .. cnt (tests/test_band_pass1_cpu.py).
+template <class Lv = LzDefaultLevel, class EFn>
+ZWZ_HD void band_first_pass(uint64_t own, EFn E, uint32_t cnt, uint32_t kmin, uint32_t kmax, uint32_t none, uint32_t& best, uint32_t& snap) {
+    const uint32_t own_lo = (uint32_t)own, own_hi = (uint32_t)(own >> 32);
+    uint32_t best2 = cnt ? none | none << 16 : 0xffffffffu;
+    snap = none;
+    for (uint32_t k0 = 0; k0 < kmax; k0 += 8u) {
+        const bool masked = k0 + 8u > kmin;
+        const uint64_t have = band_trip_mask(k0, cnt);
+        for (uint32_t j = 0; j < 8u; j += 2u) {
+            const uint64_t a = E(k0 + j + 1u), b = E(k0 + j + 2u);
+            const uint32_t key = band_key_pair(own_lo, own_hi, (uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32), k0 + j + 1u,
+                                               masked ? band_pair_mask(have, j) : kBandPairLenMask);
+            const uint32_t lo = (key & 0xffffu) > (best2 & 0xffffu) ? key & 0xffffu : best2 & 0xffffu, hi = (key >> 16) > (best2 >> 16) ? key >> 16 : best2 >> 16;
+            best2 = lo | hi << 16;
+        }
+        if (k0 + 8u == Lv::snap_chain) snap = band_pair_max(best2);
+    }
+    best = cnt ? band_pair_max(best2) : none;
+}
+
+ZWZ_HD uint32_t band_tail_bytes(bool pure, uint32_t lookahead) {      // bytes of the word inside the data (lookahead >= 3)
     const uint32_t nb = pure ? lookahead - 3u : lookahead;
     return nb < 8u ? nb : 8u;
 }

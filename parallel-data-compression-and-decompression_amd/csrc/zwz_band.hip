@@ -309,7 +309,7 @@ __global__ __launch_bounds__(kPlaceThreads) void lz_place_kernel(const uint32_t*
 //   order     runs of eight consecutive entries, sorted by their greatest count: a wave's 64 lanes are eight runs of similar
 //             length (a trip lasts as long as its longest band: 0.66 of the lanes busy in array order, 0.89 this way), and
 //             each run still reads 64 consecutive LDS bytes per step
-//   pass 1    the banded keys (see the loop)
+//   pass 1    the banded keys, two candidates a register (see the loop)
 //   pass 2    the flagged entries, compacted into full waves, walk their sharers (csrc/lz_band.h band_deep)
 constexpr uint32_t kBandArr = kBandTile + kBand;                    // a tile's arrays: 128 halo entries, then the tile's own
 constexpr uint32_t kBandDataBytes = 65536 + 64;                     // the chunk + slack for comparisons that run past its end
@@ -317,7 +317,18 @@ constexpr uint32_t kBandOffS = kBandDataBytes, kBandOffE = kBandOffS + kBandArr 
                    kBandOffHas = kBandOffCk + kBandTile * 2;
 static_assert(kBandOffHas + 8192 == kBandLdsBytes, "lz_match_band LDS layout");
 static_assert(kBandTile % 64 == 0 && kBandOffE % 8 == 0 && kBandOffS % 16 == 0 && kBandOffCk % 16 == 0, "lz_match_band LDS alignment");
-constexpr uint32_t kBandRuns = kBandTile / 8;
+// entries a run of the order phase -- the first pass in cycle units per 10 000 text chunks: 8: 13 604 k, order phase 562 k;
+// 4: 13 583 k, order 935 k (1 504 runs a tile are two a thread, and twice the atomics) and 12 bytes of scratch in the plain build -- the lanes are busier
+// (0.87 against 0.85, tools/exp/band_pass1_replay.py) but a run's 32 consecutive bytes a step cost in LDS conflicts what that gives; 2: s_order does not fit
+#ifndef ZWZ_BAND_RUN
+#define ZWZ_BAND_RUN 8
+#endif
+constexpr uint32_t kBandRun = ZWZ_BAND_RUN;                         // consecutive entries a run of the order phase
+static_assert(kBandRun == 8 || kBandRun == 4 || kBandRun == 2, "lz_match_band: a run is 8, 4 or 2 entries");
+constexpr uint32_t kBandRuns = kBandTile / kBandRun, kBandRunsPer = (kBandRuns + kBandThreads - 1) / kBandThreads;
+// s_order holds a run's index in 16 bits beside 1 072 bytes of other static arrays: runs of 2 (6 016 bytes) do not fit the CU's 160 KB with a tile
+// of 6 016 entries, and nothing of the tile's arrays is dead during the first pass
+static_assert(kBandLdsBytes + 1072u + 2u * kBandRuns <= 160u * 1024u, "lz_match_band: s_order does not fit beside the tile");
 
 #ifndef ZWZ_BAND_WAVES
 #define ZWZ_BAND_WAVES 4
@@ -484,14 +495,21 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
             if (tid < kBand) reinterpret_cast<uint16_t*>(S)[2u * tid + 1u] = a != 0u && halo_links ? s_halo_link[tid] : (uint16_t)kBandNoLink;
             prev_pure = pure;
             // ---- order: counting sort of the runs by their greatest count, longest first (runs without candidates drop out)
-            const uint32_t n_run = (b - a + 7u) >> 3;
-            uint32_t run_key = 0;
-            if (tid < n_run) {
-                const uint4 c8 = *reinterpret_cast<const uint4*>(ck + 8u * tid);   // (counts behind the tile's end are stale: masked below)
-                const uint32_t cw[4] = {c8.x, c8.y, c8.z, c8.w};
+            const uint32_t n_run = (b - a + kBandRun - 1u) / kBandRun;
+            uint32_t run_key[kBandRunsPer];
 #pragma unroll
-                for (uint32_t j = 0; j < 8; j++) if (8u * tid + j < b - a) run_key = max(run_key, (cw[j >> 1] >> (16u * (j & 1u))) & 0xffu);
-                if (run_key) atomicAdd(&s_bin[128u - run_key], 1u);
+            for (uint32_t t = 0; t < kBandRunsPer; t++) {
+                const uint32_t r = tid + kBandThreads * t;
+                run_key[t] = 0;
+                if (r < n_run) {
+                    uint32_t cw[4] = {0, 0, 0, 0};                              // (counts behind the tile's end are stale: masked below)
+                    if constexpr (kBandRun == 8) { const uint4 c8 = *reinterpret_cast<const uint4*>(ck + 8u * r); cw[0] = c8.x; cw[1] = c8.y; cw[2] = c8.z; cw[3] = c8.w; }
+                    else if constexpr (kBandRun == 4) { const uint2 c4 = *reinterpret_cast<const uint2*>(ck + 4u * r); cw[0] = c4.x; cw[1] = c4.y; }
+                    else cw[0] = *reinterpret_cast<const uint32_t*>(ck + 2u * r);
+#pragma unroll
+                    for (uint32_t j = 0; j < kBandRun; j++) if (kBandRun * r + j < b - a) run_key[t] = max(run_key[t], (cw[j >> 1] >> (16u * (j & 1u))) & 0xffu);
+                    if (run_key[t]) atomicAdd(&s_bin[128u - run_key[t]], 1u);
+                }
             }
             __syncthreads();
             if (wave == 0) {                                                    // exclusive scan of the 128 bins
@@ -502,10 +520,12 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                 if (lane == 63) s_nrun = t0 + i1;
             }
             __syncthreads();
-            if (tid < n_run && run_key) s_order[atomicAdd(&s_bin[128u - run_key], 1u)] = (uint16_t)tid;
+#pragma unroll
+            for (uint32_t t = 0; t < kBandRunsPer; t++) if (run_key[t]) s_order[atomicAdd(&s_bin[128u - run_key[t]], 1u)] = (uint16_t)(tid + kBandThreads * t);
             __syncthreads();
             ZWZ_STAMP(8);
-            const uint32_t n_act = s_nrun, n_grp = (n_act + 7u) >> 3;
+            constexpr uint32_t kRunsWave = 64u / kBandRun;                      // runs a wave takes at a time
+            const uint32_t n_act = s_nrun, n_grp = (n_act + kRunsWave - 1u) / kRunsWave;
             const uint32_t none = pure ? kBandKeyNonePure : kBandKeyNoneImpure;
             // ---- first pass
             for (;;) {
@@ -513,58 +533,81 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                 if (lane == 0) g = atomicAdd(&s_grp[0], 1u);
                 g = __builtin_amdgcn_readfirstlane(g);
                 if (g >= n_grp) break;
-                const uint32_t ri = 8u * g + (lane >> 3);
-                const uint32_t i = kBand + 8u * (ri < n_act ? (uint32_t)s_order[ri] : 0u) + (lane & 7u);
+                const uint32_t ri = kRunsWave * g + lane / kBandRun;
+                const uint32_t i = kBand + kBandRun * (ri < n_act ? (uint32_t)s_order[ri] : 0u) + (lane & (kBandRun - 1u));
                 const bool active = ri < n_act && i < m;
                 const uint32_t w = S[i], p = band_pos(w);                       // (i < kBandArr whatever the lane)
                 const uint32_t cntb = active ? (uint32_t)ck[i - kBand] : 0u;
                 const uint2 own = E[i];
-                // The band, eight candidates a trip, nearest first.  A key costs eight vector instructions (two XORs, two find-first-bits,
-                // mask / mask-and-offset, minimum, shift-or with the trip's 129 - k from a scalar register) and two keys join the
-                // running maximum by one v_max3 -- picked by hand: the compiler's own choice was twelve a candidate.  Up to the
-                // smallest count among the lanes that have candidates nothing needs masking; lanes without any are kept out of
-                // it by a running maximum nothing can beat.
+                // The band, eight candidates a trip, nearest first, two candidates an instruction: the keys are 12 bits, so a pair's live in the
+                // 16-bit halves of one register (csrc/lz_band.h band_key_pair is the specification).  A pair costs thirteen vector instructions --
+                // four XORs, four find-first-bits that write their halves themselves (SDWA: 0xffffffff of an all-equal word leaves as 0xffff and
+                // stays in its half; no v_perm to join them), | 32 on the upper words' halves, packed minimum, mask, shift-or with the pair's two
+                // 129 - k from a scalar register, packed running maximum -- 6.5 a candidate where the 32-bit form paid 8.5.  The two halves' maxima
+                // meet once behind the loops; the short chain's snapshot stays packed until then as well (a select a trip).
+                // Up to the smallest count among the lanes that have candidates nothing needs masking.  Beyond it a lane's mask of the length
+                // field (0x78) comes from a register whose bytes say which of the trip's eight candidates the lane still has
+                // (band_trip_mask: seven instructions a trip, a v_perm a pair -- 8.25 a candidate with the trip's address and snapshot select, where
+                // compare + select + max made it 10.5; the unmasked trip is 55 instructions, 6.9 a candidate; with the pair's masks from two compares
+                // and two selects instead, the pass was 13 840 k cycle units per 10 000 text chunks against 13 614 k, the 32-bit keys 16 374 k):
+                // a candidate beyond the count leaves as the key of length 0, 129 - k alone.  No such key wins.  A lane that has a
+                // beyond-count candidate k has cntb >= 1 and k >= 2 (lanes without candidates: below), so the key is <= 127, and the
+                // lane's nearest candidate, k = 1, always valid, has a key >= 128 in the trip's or an earlier trip's maximum.  The maximum
+                // is taken per half, and a half may be won by such a key, but the two halves' maximum is not: the k = 1 key is in the low
+                // half from the first trip on, so behind every trip -- the snapshot's trip included -- the halves' maximum is the maximum
+                // over the valid keys and the start value (pure: 0, below every key; impure: 0x2ff, which the length-0 keys are below as
+                // well).  Lanes without any candidate start from a maximum nothing can beat and get `none` behind the loop.
                 const uint32_t kmax = (ZWZ_BAND_EXP & 2) ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_max_incl(cntb), 63);
                 const uint32_t kmin = 128u - (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_max_incl(cntb ? 128u - cntb : 0u), 63);   // (128 if nobody has any)
-                uint32_t best = cntb ? none : 0xffffffffu, snap = none;
+                uint32_t best, snap = none;
                 const uint2* Ei = E + i;                                        // (i - k >= 0 for every lane: k <= 128 <= i)
-                auto key_of = [&](const uint2 c, uint32_t kc) {
-                    uint32_t t0, t1, a1, key;
-                    asm("v_ffbl_b32 %0, %1" : "=v"(t0) : "v"(own.x ^ c.x));   // 0xffffffff for 0
-                    asm("v_ffbl_b32 %0, %1" : "=v"(t1) : "v"(own.y ^ c.y));
-                    asm("v_and_or_b32 %0, %1, %2, 32" : "=v"(a1) : "v"(t1), "s"(0x78u));   // 32 + 8 * equal bytes of the upper word; 0x78 for all four
-                    const uint32_t m8 = min(t0 & 0x78u, a1);
-                    asm("v_lshl_or_b32 %0, %1, 5, %2" : "=v"(key) : "v"(m8), "s"(kc));
+                auto key2_of = [&](const uint2 ca, const uint2 cb, uint32_t tags, uint32_t mask) {
+                    uint32_t t0, t1, m, key;
+                    asm("v_ffbl_b32_sdwa %0, %1 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD" : "=v"(t0) : "v"(own.x ^ ca.x));   // 0xffff for 0
+                    asm("v_ffbl_b32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(t0) : "v"(own.x ^ cb.x));
+                    asm("v_ffbl_b32_sdwa %0, %1 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD" : "=v"(t1) : "v"(own.y ^ ca.y));
+                    asm("v_ffbl_b32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(t1) : "v"(own.y ^ cb.y));
+                    asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(t0), "v"(t1 | 0x00200020u));   // first differing bit of the 64, a half each
+                    asm("v_lshl_or_b32 %0, %1, 5, %2" : "=v"(key) : "v"(m & mask), "s"(tags));
                     return key;
                 };
                 const uint32_t la = L - p;
                 const bool tail = active && la < deep;                          // the word reaches past the data
                 if (__builtin_amdgcn_ballot_w64(tail) == 0) {
+                    uint32_t best2 = cntb ? none | none << 16 : 0xffffffffu, snap2 = none | none << 16;
+                    auto both = [](uint32_t x) { return max(x & 0xffffu, x >> 16); };
                     uint32_t k0 = 0;
                     for (; k0 + 8u <= kmin; k0 += 8u) {
                         uint2 c[8];
 #pragma unroll
                         for (uint32_t j = 0; j < 8; j++) c[j] = Ei[-(int)(k0 + j + 1u)];
+                        const uint32_t tg = (128u - k0) * 0x10001u;             // candidate k0 + j + 1 in the low half, k0 + j + 2 in the high one
 #pragma unroll
                         for (uint32_t j = 0; j < 8; j += 2) {
-                            const uint32_t ka = key_of(c[j], 128u - k0 - j), kb = key_of(c[j + 1], 127u - k0 - j);
-                            asm("v_max3_u32 %0, %0, %1, %2" : "+v"(best) : "v"(ka), "v"(kb));
+                            const uint32_t key = key2_of(c[j], c[j + 1], tg - (j * 0x10001u + 0x10000u), kBandPairLenMask);
+                            asm("v_pk_max_u16 %0, %0, %1" : "+v"(best2) : "v"(key));
                         }
-                        if (k0 + 8u == Lv::snap_chain) snap = best;
+                        if (k0 + 8u == Lv::snap_chain) snap2 = best2;
                     }
                     for (; k0 < kmax; k0 += 8u) {
                         uint2 c[8];
 #pragma unroll
                         for (uint32_t j = 0; j < 8; j++) c[j] = Ei[-(int)(k0 + j + 1u)];
+                        const uint32_t tg = (128u - k0) * 0x10001u;
+                        const uint64_t have = band_trip_mask(k0, cntb);
 #pragma unroll
-                        for (uint32_t j = 0; j < 8; j++) {
-                            const uint32_t key = key_of(c[j], 128u - k0 - j);
-                            best = max(best, k0 + j + 1u <= cntb ? key : 0u);
+                        for (uint32_t j = 0; j < 8; j += 2) {
+                            const uint32_t hw = (uint32_t)(have >> (j & 4u ? 32 : 0));
+                            const uint32_t mask = __builtin_amdgcn_perm(hw, hw, j & 2u ? 0x0c030c02u : 0x0c010c00u);   // = band_pair_mask(have, j)
+                            const uint32_t key = key2_of(c[j], c[j + 1], tg - (j * 0x10001u + 0x10000u), mask);
+                            asm("v_pk_max_u16 %0, %0, %1" : "+v"(best2) : "v"(key));
                         }
-                        if (k0 + 8u == Lv::snap_chain) snap = best;
+                        if (k0 + 8u == Lv::snap_chain) snap2 = best2;
                     }
+                    best = both(best2); snap = both(snap2);
                 } else {                                                        // a handful of groups per chunk: the plain loop, XORs masked to the bytes that exist
                     const uint32_t nb = tail ? band_tail_bytes(pure, la) : 8u, m_lo = band_tail_mask(nb, 0), m_hi = band_tail_mask(nb, 1);
+                    best = none;
                     for (uint32_t k = 1; k <= kmax; k++) {
                         const uint2 c = Ei[-(int)k];
                         const uint32_t key = band_key_masked(own.x, own.y, c.x, c.y, m_lo, m_hi, k);
