@@ -194,6 +194,27 @@ int zwz_ctx_set_chunk_size(zwz_ctx *ctx, uint32_t bytes);
 int zwz_ctx_set_level(zwz_ctx *ctx, int level);
 int zwz_ctx_level(zwz_ctx *ctx);
 
+/* libz's compression STRATEGY of every writer of this context (the same writers as the level's), and of no reader.  The numbers are libz's:
+ *   ZWZ_STRATEGY_DEFAULT (0)  deflate_slow at the context's level, as above;
+ *   ZWZ_STRATEGY_HUFFMAN (2)  Z_HUFFMAN_ONLY: every byte a literal, entropy coding only (pigz -H, PNG writers);
+ *   ZWZ_STRATEGY_RLE     (3)  Z_RLE: matches at distance 1 only -- runs of a byte (pigz -U).
+ * Under 2 and 3 the output is byte for byte what libz 1.2.11 writes after deflateInit2(level, Z_DEFLATED, wbits, 8, strategy) for ANY level
+ * 1-9: the level stays settable and readable and changes no byte until the strategy is 0 again, and the "match" option chooses nothing.  No
+ * chain is built and nothing is searched: one memory-bound kernel stands in for the search and the parse (DESIGN.md section 21 has the measured
+ * table).  Wrappers as libz writes them: the zlib header is 78 01 (FLEVEL 0), the gzip header's XFL byte is 04 (1f 8b 08 00 00 00 00 00 04 03);
+ * BGZF and ZIP headers do not change, nor do the .gzi index, zwz_bgzf_bound, zwz_deflate_stream_bound and zwz_zip_bound (their worst case is
+ * stored blocks, and a chunk still has at most five).  Ordinary DEFLATE: every reader here and elsewhere decodes it.
+ * 1 (Z_FILTERED) and 4 (Z_FIXED) -- and any other value -- are ZWZ_E_INVALID, zwz_last_error() says why, and the strategy stays what it was:
+ * Z_FILTERED changes which short matches the lazy parse accepts (three parse forms at three levels), Z_FIXED the plan's choice of block type (its
+ * three forms); each is its own piece of work.  The default comes from the environment variable ZWZ_STRATEGY=huffman|rle|default, read once in
+ * zwz_ctx_create (a value that is not understood is reported on stderr and ignored).  For zwz_compress_dir a strategy is opt-in and NOT bit-exact
+ * with the reference's shards, exactly like the level.  zwz_ctx_strategy returns the current strategy. */
+#define ZWZ_STRATEGY_DEFAULT 0
+#define ZWZ_STRATEGY_HUFFMAN 2
+#define ZWZ_STRATEGY_RLE 3
+int zwz_ctx_set_strategy(zwz_ctx *ctx, int strategy);
+int zwz_ctx_strategy(zwz_ctx *ctx);
+
 /* Test and diagnosis switches of one context; no reference counterpart (the reference's zlib has one code path,
  * compression.cpp:119-134 / decompression.cpp:16-36) and no effect on any byte produced -- they choose between kernels that compute
  * the same thing, so that tests can drive each of them and a device that fails a self-test at zwz_ctx_create still gets a codec:

@@ -29,6 +29,9 @@ and ZIP archives, a batch of entries per launch (what unzip, zipfile and file ma
 and libz's compression level of every writer above (4, 5 or 6, byte for byte libz's output at that level; default 6):
     Codec.set_level / Codec.level                              (ZWZ_LEVEL sets a codec's default)
 
+and libz's two search-free strategies for every writer, byte for byte libz's output whatever the level (entropy coding only; runs of a byte only):
+    Codec.set_strategy("huffman" | "rle" | "default") / Codec.strategy      (ZWZ_STRATEGY sets a codec's default)
+
 There is no CPU fallback: importing works anywhere (so the build can be checked), but every codec
 call needs the HIP library and a GPU and raises ZwzError otherwise.
 """
@@ -94,6 +97,8 @@ def lib():
         L.zwz_ctx_set_chunk_size.argtypes = [vp, u32]
         L.zwz_ctx_set_level.argtypes = [vp, c.c_int]
         L.zwz_ctx_level.argtypes = [vp]
+        L.zwz_ctx_set_strategy.argtypes = [vp, c.c_int]
+        L.zwz_ctx_strategy.argtypes = [vp]
         L.zwz_ctx_set_option.argtypes = [vp, c.c_char_p, c.c_char_p]
         L.zwz_bgzf_bound.restype = u64
         L.zwz_bgzf_bound.argtypes = [u64]
@@ -133,6 +138,8 @@ BGZF_BAD_MEMBER, BGZF_ISIZE_MISMATCH, BGZF_CRC_MISMATCH = 16, 17, 18
 # zwz_inflate_streams_dev (include/zwz.h): wrappers, and per-stream statuses beyond the inflate codes 0..3
 WRAP_RAW, WRAP_ZLIB, WRAP_GZIP = 0, 1, 2
 WRAPS = {"raw": WRAP_RAW, "zlib": WRAP_ZLIB, "gzip": WRAP_GZIP}
+STRATEGY_DEFAULT, STRATEGY_HUFFMAN, STRATEGY_RLE = 0, 2, 3      # libz's numbers (include/zwz.h: zwz_ctx_set_strategy)
+STRATEGIES = {"default": STRATEGY_DEFAULT, "huffman": STRATEGY_HUFFMAN, "rle": STRATEGY_RLE}
 STREAM_END, STREAM_NEED_INPUT, STREAM_DATA_ERROR, STREAM_OVERFLOW = 0, 1, 2, 3
 STREAM_BAD_HEADER, STREAM_CHECKSUM, STREAM_LENGTH, STREAM_TRAILING, STREAM_TOO_LARGE = 32, 33, 34, 35, 36
 STREAM_MAX_IN, STREAM_MAX_OUT = 1 << 29, 1 << 32
@@ -649,6 +656,22 @@ class Codec:
     @property
     def level(self):
         return lib().zwz_ctx_level(self._h)
+
+    def set_strategy(self, strategy):
+        """libz's strategy of every writer of this codec (include/zwz.h: zwz_ctx_set_strategy): "default" / 0, "huffman" / 2 (Z_HUFFMAN_ONLY:
+        entropy coding only) or "rle" / 3 (Z_RLE: runs of a byte only), byte for byte what libz 1.2.11 writes under it at any level.  While
+        one is set the level and the match option change no byte.  Anything else (1 = Z_FILTERED and 4 = Z_FIXED included) raises ZwzError
+        (status E_INVALID) and leaves the strategy as it was.  Readers are not affected."""
+        if isinstance(strategy, str):
+            if strategy not in STRATEGIES:
+                raise ValueError("strategy %r: one of %s" % (strategy, ", ".join(sorted(STRATEGIES))))
+            strategy = STRATEGIES[strategy]
+        _check(lib().zwz_ctx_set_strategy(self._h, int(strategy)), "zwz_ctx_set_strategy")
+
+    @property
+    def strategy(self):
+        """The strategy as libz's number: 0 (default), 2 (huffman) or 3 (rle)."""
+        return lib().zwz_ctx_strategy(self._h)
 
 
 def _device_input(torch, data, device):

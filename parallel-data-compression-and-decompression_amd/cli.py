@@ -18,6 +18,8 @@ over xGMI when GPUs are present, "gloo" otherwise):
     (addition) ZWZ_LEVEL=4|5|6 in the environment selects libz's compression level of every rank's Codec (include/zwz.h:
         zwz_ctx_set_level); the argv stays the reference's
 
+    (addition) ZWZ_STRATEGY=huffman|rle likewise selects libz's Z_HUFFMAN_ONLY or Z_RLE for every rank's Codec (zwz_ctx_set_strategy)
+
     (addition) decompression is a single-rank job in the reference (main.cpp:61-68); here shard j goes to rank j mod N,
         and fewer shards than ranks are split by record ranges with an all_gather of decoded byte counts
 """

@@ -22,10 +22,11 @@ constexpr uint32_t kGzipHeaderBytes = 10;     // 1f 8b 08 00 | mtime 0 | 00 | 03
 
 ZWZ_HD uint32_t dstream_header_bytes(uint32_t wrap) { return wrap == kWrapZlib ? 2u : wrap == kWrapGzip ? kGzipHeaderBytes : 0u; }
 ZWZ_HD uint32_t dstream_trailer_bytes(uint32_t wrap) { return wrap == kWrapZlib ? 4u : wrap == kWrapGzip ? 8u : 0u; }
-// flg: the zlib header's second byte, zlib_flg(level) -- 9c at level 6, 5e at 4 and 5.  The gzip header does not depend on the level: libz's XFL is 0 but at 1 and 9.
-ZWZ_HD uint32_t dstream_header_byte(uint32_t wrap, uint32_t i, uint32_t flg = 0x9cu) {
+// flg: the zlib header's second byte, zlib_flg(level) -- 9c at level 6, 5e at 4 and 5, 01 under a strategy (rle_core.h: zlib_flg_of).  The gzip header does
+// not depend on the level: libz's XFL is 0 but at 1 and 9 -- and under Z_HUFFMAN_ONLY and Z_RLE, where it is 4 (xfl: gzip_xfl_of).
+ZWZ_HD uint32_t dstream_header_byte(uint32_t wrap, uint32_t i, uint32_t flg = 0x9cu, uint32_t xfl = 0u) {
     if (wrap == kWrapZlib) return i == 0 ? 0x78u : flg;
-    return i == 0 ? 0x1fu : i == 1 ? 0x8bu : i == 2 ? 0x08u : i == 9 ? 0x03u : 0u;
+    return i == 0 ? 0x1fu : i == 1 ? 0x8bu : i == 2 ? 0x08u : i == 8 ? xfl : i == 9 ? 0x03u : 0u;
 }
 // Byte i of what follows the last marker: 03 00, then Adler-32 big-endian (zlib) or CRC-32 and ISIZE little-endian (gzip).
 ZWZ_HD uint32_t dstream_tail_byte(uint32_t wrap, uint32_t i, uint32_t check, uint64_t total_in) {

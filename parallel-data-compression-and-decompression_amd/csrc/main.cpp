@@ -348,14 +348,25 @@ int level_flag(const std::string& a, int* level) {
     return -1;
 }
 
-// `main zip <src dir> <dst.zip> [-4|-5|-6]` / `main unzip <src.zip> <dst dir>`: a directory as one ZIP archive and back, one process, one GPU.
+// A strategy flag of the writers: --huffman (Z_HUFFMAN_ONLY, pigz -H) or --rle (Z_RLE, pigz -U); include/zwz.h: zwz_ctx_set_strategy.
+// Returns 1 and sets *strategy for one of those, -1 if the other one was given before (a usage error), 0 for anything else.
+int strategy_flag(const std::string& a, int* strategy) {
+    const int st = a == "--huffman" ? ZWZ_STRATEGY_HUFFMAN : a == "--rle" ? ZWZ_STRATEGY_RLE : 0;
+    if (!st) return 0;
+    if (*strategy && *strategy != st) return -1;
+    *strategy = st;
+    return 1;
+}
+
+// `main zip <src dir> <dst.zip> [-4|-5|-6] [--huffman|--rle]` / `main unzip <src.zip> <dst dir>`: a directory as one ZIP archive and back, one process, one GPU.
 // Exit codes as bgzf_main's.
-int zip_main(const std::string& op, const char* src, const char* dst, int world_size, int device, int level) {
+int zip_main(const std::string& op, const char* src, const char* dst, int world_size, int device, int level, int strategy) {
     if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", op.c_str(), world_size); return 1; }
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
     if (rc == ZWZ_OK && level) rc = zwz_ctx_set_level(ctx, level);
+    if (rc == ZWZ_OK && strategy) rc = zwz_ctx_set_strategy(ctx, strategy);
     if (rc == ZWZ_OK) rc = op == "zip" ? zwz_zip_dir(ctx, src, dst) : zwz_unzip_file(ctx, src, dst);
     zwz_ctx_destroy(ctx);
     if (rc != ZWZ_OK) {
@@ -367,29 +378,32 @@ int zip_main(const std::string& op, const char* src, const char* dst, int world_
 }
 
 void bgzf_usage(const char* argv0) {
-    fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index] [-4|-5|-6]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n"
-            "       %s gzip <src> <dst> [--zlib|--raw] [-4|-5|-6]\n       %s gunzip <src> <dst> [--zlib|--raw]\n       %s zip <src dir> <dst.zip> [-4|-5|-6]\n       %s unzip <src.zip> <dst dir>\n"
-            "  -4 -5 -6 (behind the operands or, as gzip takes it, in front of them): libz's compression level of that number (default 6, or ZWZ_LEVEL); no other level exists here\n",
+    fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index] [-4|-5|-6] [--huffman|--rle]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n"
+            "       %s gzip <src> <dst> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle]\n       %s gunzip <src> <dst> [--zlib|--raw]\n       %s zip <src dir> <dst.zip> [-4|-5|-6] [--huffman|--rle]\n       %s unzip <src.zip> <dst dir>\n"
+            "  -4 -5 -6 (behind the operands or, as gzip takes it, in front of them): libz's compression level of that number (default 6, or ZWZ_LEVEL); no other level exists here\n"
+            "  --huffman | --rle (before or behind the operands; not both): libz's strategy Z_HUFFMAN_ONLY (entropy coding only) or Z_RLE (runs of a byte only); default: neither, or ZWZ_STRATEGY\n",
             argv0, argv0, argv0, argv0, argv0, argv0, argv0);
 }
 
-// `main gzip <src file> <dst file> [--zlib|--raw] [-4|-5|-6]`: one file as one ordinary gzip (zlib, raw DEFLATE) stream, one process, one GPU.
+// `main gzip <src file> <dst file> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle]`: one file as one ordinary gzip (zlib, raw DEFLATE) stream, one process, one GPU.
 // `main gunzip <src file> <dst file> [--zlib|--raw]`: the way back (zwz_inflate_stream_file), for any stream other encoders wrote too.
 int gzip_main(int argc, char** argv, int world_size, int device) {
     const bool back = std::string(argv[1]) == "gunzip";
     if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", argv[1], world_size); return 1; }
-    int wrap = ZWZ_WRAP_GZIP, level = 0;
+    int wrap = ZWZ_WRAP_GZIP, level = 0, strategy = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--zlib") wrap = ZWZ_WRAP_ZLIB;
         else if (a == "--raw") wrap = ZWZ_WRAP_RAW;
         else if (!back && level_flag(a, &level) == 1) {}
+        else if (!back && strategy_flag(a, &strategy) == 1) {}
         else { bgzf_usage(argv[0]); return 1; }
     }
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
     if (rc == ZWZ_OK && level) rc = zwz_ctx_set_level(ctx, level);
+    if (rc == ZWZ_OK && strategy) rc = zwz_ctx_set_strategy(ctx, strategy);
     if (rc == ZWZ_OK) rc = back ? zwz_inflate_stream_file(ctx, wrap, argv[2], argv[3]) : zwz_deflate_stream_file(ctx, wrap, argv[2], argv[3]);
     zwz_ctx_destroy(ctx);
     if (rc != ZWZ_OK) { fprintf(stderr, "%s %s: %s (%s)\n", argv[1], argv[2], zwz_strerror(rc), zwz_last_error()); return 1; }
@@ -490,11 +504,12 @@ int bgzf_ext_main(int argc, char* argv[], int world_size, int device) {
     }
     bool index = false, have_off = false, have_size = false;
     uint64_t off = 0, size = 0;
-    int level = 0;
+    int level = 0, strategy = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (op == "bgzip" && a == "--index") index = true;
         else if (op == "bgzip" && level_flag(a, &level) == 1) {}
+        else if (op == "bgzip" && strategy_flag(a, &strategy) == 1) {}
         else if (op == "bgunzip" && a == "--offset" && i + 1 < argc && parse_u64(argv[i + 1], &off)) { have_off = true; i++; }
         else if (op == "bgunzip" && a == "--size" && i + 1 < argc && parse_u64(argv[i + 1], &size)) { have_size = true; i++; }
         else { bgzf_usage(argv[0]); return 1; }
@@ -505,6 +520,7 @@ int bgzf_ext_main(int argc, char* argv[], int world_size, int device) {
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
     if (rc == ZWZ_OK && level) rc = zwz_ctx_set_level(ctx, level);
+    if (rc == ZWZ_OK && strategy) rc = zwz_ctx_set_strategy(ctx, strategy);
     if (rc == ZWZ_OK) {
         if (op == "bgzip") {
             rc = zwz_bgzf_compress_file(ctx, argv[2], argv[3]);
@@ -546,10 +562,15 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "Usage: %s <compress/decompress> <source directory path> <output directory path>\n", argv[0]);
         return 1;
     }
-    // gzip -4 <src> <dst>, as the tools this stands in for take it: a level flag in front of the operands moves behind them
+    // gzip -4 <src> <dst>, gzip --rle -4 <src> <dst>, as the tools this stands in for take them: level and strategy flags in front of the operands move behind them
     if (std::string(argv[1]) == "gzip" || std::string(argv[1]) == "bgzip" || std::string(argv[1]) == "zip") {
-        int lv = 0;
-        if (argc >= 5 && level_flag(argv[2], &lv) != 0) { char* f = argv[2];   /* with two operands behind it only: `gzip -4 src` stays src = -4, dst = src, as before */ for (int i = 2; i + 1 < argc; i++) argv[i] = argv[i + 1]; argv[argc - 1] = f; }
+        for (int moved = 0; argc >= 5 + moved; moved++) {   /* with two operands behind it only: `gzip -4 src` stays src = -4, dst = src, as before */
+            int lv = 0, st = 0;
+            if (level_flag(argv[2], &lv) == 0 && strategy_flag(argv[2], &st) == 0) break;
+            char* f = argv[2];
+            for (int i = 2; i + 1 < argc; i++) argv[i] = argv[i + 1];
+            argv[argc - 1] = f;
+        }
     }
     std::string operation = argv[1], source_path = argv[2], output_path = argv[3];
     if (operation == "gzip" || operation == "gunzip") {
@@ -558,9 +579,9 @@ int main(int argc, char* argv[]) {
     }
     if (operation == "zip" || operation == "unzip") {
         int n = 0;
-        int level = 0;
-        for (int i = 4; i < argc; i++) if (operation != "zip" || level_flag(argv[i], &level) != 1) { bgzf_usage(argv[0]); return 1; }
-        return zip_main(operation, argv[2], argv[3], world_size, zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0, level);
+        int level = 0, strategy = 0;
+        for (int i = 4; i < argc; i++) if (operation != "zip" || (level_flag(argv[i], &level) != 1 && strategy_flag(argv[i], &strategy) != 1)) { bgzf_usage(argv[0]); return 1; }
+        return zip_main(operation, argv[2], argv[3], world_size, zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0, level, strategy);
     }
     if (operation == "bgzip" || operation == "bgunzip") {
         int n = 0;

@@ -294,9 +294,30 @@ int zwz_ctx_create(int device, uint32_t max_batch, zwz_ctx** out) {
         const long x = strtol(v, &end, 10);
         if (!*v || *end || errno || x < INT_MIN || x > INT_MAX || zwz_ctx_set_level(c, (int)x) != ZWZ_OK) fprintf(stderr, "zwz: ZWZ_LEVEL=%s is not a level this library writes (4, 5, 6; 0 = default): ignored\n", v);
     }
+    if (const char* v = getenv("ZWZ_STRATEGY")) {     // the default strategy, as ZWZ_LEVEL: by name, as the CLI's flags spell them
+        const std::string x = v;
+        const int st = x == "huffman" ? ZWZ_STRATEGY_HUFFMAN : x == "rle" ? ZWZ_STRATEGY_RLE : x == "default" ? ZWZ_STRATEGY_DEFAULT : -1;
+        if (st < 0 || zwz_ctx_set_strategy(c, st) != ZWZ_OK) fprintf(stderr, "zwz: ZWZ_STRATEGY=%s is not a strategy this library writes (huffman, rle; default): ignored\n", v);
+    }
     *out = c;
     return ZWZ_OK;
 }
+
+int zwz_ctx_set_strategy(zwz_ctx* c, int strategy) {
+    if (!c) return ZWZ_E_INVALID;
+    if (!strategy_exists(strategy)) {
+        set_error("zwz_ctx_set_strategy: no strategy %d; 0 (default), 2 (Z_HUFFMAN_ONLY) and 3 (Z_RLE) exist\n"
+                  "  2, 3: libz's deflate_huff and deflate_rle look at no hash chain, and what becomes of a position has a closed form: one kernel in place of the search and the parse\n"
+                  "  1 (Z_FILTERED): changes the lazy parse's acceptance of short matches, in three parse forms at three levels\n"
+                  "  4 (Z_FIXED): changes the plan's choice of block type in its three forms\n"
+                  "  each of those two is its own piece of work", strategy);
+        return ZWZ_E_INVALID;
+    }
+    c->strategy = (uint32_t)strategy;
+    return ZWZ_OK;
+}
+
+int zwz_ctx_strategy(zwz_ctx* c) { return c ? (int)c->strategy : ZWZ_E_INVALID; }
 
 int zwz_ctx_set_level(zwz_ctx* c, int level) {
     if (!c) return ZWZ_E_INVALID;
@@ -410,7 +431,7 @@ int zwz_deflate_batch_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_
         a.in = d_in; a.in_off = d_in_off + done; a.in_len = d_in_len + done; a.n = m;
         a.out = d_out + (size_t)done * out_stride; a.out_stride = out_stride; a.out_len = d_out_len + done;
         carve_workspace(c, a);
-        a.match_mode = c->match_mode; a.plan_serial = c->plan_serial; a.level = c->level;
+        a.match_mode = c->match_mode; a.plan_serial = c->plan_serial; a.level = c->level; a.strategy = c->strategy;
         HIPCHK(launch_deflate(a, c->stream, c->profiling ? c->ev : nullptr));
         if (c->profiling) {   // profiling serialises slices: stage times are read back per slice
             HIPCHK(hipEventSynchronize(c->ev[kNumDeflateStages]));

@@ -50,6 +50,8 @@ struct zwz_ctx {
     uint32_t cu_count = 0;
     uint32_t chunk_bytes = 0;        // raw bytes per Chunk for zwz_compress_dir; 0 = default (see chunk_bytes_for)
     uint32_t level = 6;              // libz's compression level of every writer: 4, 5 or 6 (zwz_ctx_set_level; default from ZWZ_LEVEL at zwz_ctx_create)
+    uint32_t strategy = 0;           // libz's strategy of every writer: 0 (default), 2 (Z_HUFFMAN_ONLY) or 3 (Z_RLE) (zwz_ctx_set_strategy; default from ZWZ_STRATEGY);
+                                     // while it is 2 or 3 the level is kept and changes no byte
     // Switches (zwz_ctx_set_option; defaults from ZWZ_MATCH / ZWZ_PLAN / ZWZ_INFLATE_HEADER read ONCE at zwz_ctx_create, or forced by a
     // failed self-test there).  Every setting produces the same bytes; they differ in which kernels run.
     uint32_t match_mode = 0;             // zwz::kMatchAuto | kMatchWalk | kMatchBand

@@ -76,7 +76,7 @@ int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_
     S.in_off = d; S.in_len = d + n; S.out_off = d + 2 * (size_t)n; S.out_cap = d + 3 * (size_t)n; S.pfirst = d + 4 * (size_t)n;
     S.xs = d + 5 * (size_t)n + 1; S.chk = reinterpret_cast<uint32_t*>(S.xs + n); S.n = n;
     if (d_chk) *d_chk = S.chk;
-    const DstreamOut O{d_out, d_out_len, d_status, wrap, partial ? 1u : 0u, zlib_flg(c->level)};
+    const DstreamOut O{d_out, d_out_len, d_status, wrap, partial ? 1u : 0u, zlib_flg_of(c->level, c->strategy), gzip_xfl_of(c->strategy)};
     const PiecesView v = pieces_view(c);
     const CrcTables* tab = c->buf[kBufCrcTables].as<const CrcTables>();
     HIPCHK(hipMemsetAsync(v.base, 0, 16, c->stream));
@@ -130,7 +130,7 @@ int zwz_deflate_stream_file(zwz_ctx* c, int wrap_, const char* src, const char* 
     if (int rc = job.alloc({S + 16, S + 16, O, O, 64}, {S + 16, O, 64})) return rc;
     uint8_t frame[kGzipHeaderBytes + 2 + 8];
     const uint32_t hdr = dstream_header_bytes(wrap);
-    for (uint32_t i = 0; i < hdr; i++) frame[i] = (uint8_t)dstream_header_byte(wrap, i, zlib_flg(c->level));
+    for (uint32_t i = 0; i < hdr; i++) frame[i] = (uint8_t)dstream_header_byte(wrap, i, zlib_flg_of(c->level, c->strategy), gzip_xfl_of(c->strategy));
     if (hdr && fwrite(frame, 1, hdr, job.out) != hdr) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
     uint32_t check = dstream_check_init(wrap);
     uint64_t total_in = 0;

@@ -21,7 +21,7 @@ struct DstreamPieces {
     uint64_t *off, *x;         // its input; bytes of spliced output in front of it (over the whole call)
     uint32_t *len, *olen, *crc, *sidx, *slen, *hbit, *ebit;   // input, slot and spliced lengths; CRC-32 (gzip); stream; dstream_core.h's SplicePoints
 };
-struct DstreamOut { uint8_t* out; uint64_t* out_len; uint32_t* status; uint32_t wrap; uint32_t partial; uint32_t zflg; };   // partial: pieces only (no header, no 03 00, no trailer); zflg: zlib_flg(level)
+struct DstreamOut { uint8_t* out; uint64_t* out_len; uint32_t* status; uint32_t wrap; uint32_t partial; uint32_t zflg; uint32_t xfl; };   // partial: pieces only (no header, no 03 00, no trailer); zflg: zlib_flg_of(level, strategy); xfl: gzip_xfl_of(strategy)
 
 hipError_t launch_dstream_begin(const DstreamStreams& S, const DstreamOut& O, hipStream_t s);
 hipError_t launch_dstream_layout(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, hipStream_t s);

@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(256) dstream_begin_kernel(DstreamStreams S, Ds
     const bool fits = hdr + tail <= S.out_cap[i];
     if (fits) {
         uint8_t* dst = O.out + S.out_off[i];
-        for (uint32_t b = 0; b < hdr; b++) dst[b] = (uint8_t)dstream_header_byte(O.wrap, b, O.zflg);
+        for (uint32_t b = 0; b < hdr; b++) dst[b] = (uint8_t)dstream_header_byte(O.wrap, b, O.zflg, O.xfl);
         for (uint32_t b = 0; b < tail; b++) dst[hdr + b] = (uint8_t)dstream_tail_byte(O.wrap, b, init, 0);
     }
     O.out_len[i] = hdr + tail;
@@ -56,11 +56,17 @@ __global__ void __launch_bounds__(256) dstream_size_kernel(const ChunkInfo* info
     if (p >= m) return;
     const BlockInfo* bi = blocks + (size_t)p * kMaxBlocks;
     const BlockOut* bo = plans + (size_t)p * kMaxBlocks;
-    const SplicePoints sp_ = splice_points(min(info[p].n_blocks, kMaxBlocks), [&](uint32_t b, uint32_t& type, uint32_t& hdr_bits, uint32_t& body_bits, uint32_t& stored) {
+    const uint32_t nb = min(info[p].n_blocks, kMaxBlocks);
+    auto block = [&](uint32_t b, uint32_t& type, uint32_t& hdr_bits, uint32_t& body_bits, uint32_t& stored) {
         type = bo[b].type; hdr_bits = bo[b].hdr_bits; body_bits = bo[b].body_bits; stored = bi[b].end - bi[b].start;
-    });
+    };
+    const SplicePoints sp_ = splice_points(nb, block);
     SplicePoints sp = sp_;
-    if (2u + spliced_source_bytes(sp.end_bit) + 4u != P.olen[p] || sp.hdr_bit >= sp.end_bit) { *err = 1; sp.hdr_bit = 16; sp.end_bit = 16; }
+    // A piece whose symbols fill its blocks exactly ends, in the slot's Z_FINISH stream, with an empty block: the finishing flush writes one
+    // whatever it holds.  A full flush writes a block only if it holds a symbol, so the piece's share of the stream ends with the block before
+    // (dstream_pack_kernel clears what the slot has behind it).  Every piece under Z_HUFFMAN_ONLY of 16 383 k bytes is one.
+    if (nb > 1u && bi[nb - 1u].end == bi[nb - 1u].start && bo[nb - 1u].type != kStored) sp = splice_points(nb - 1u, block);
+    if (2u + spliced_source_bytes(sp_.end_bit) + 4u != P.olen[p] || sp.hdr_bit >= sp.end_bit) { *err = 1; sp.hdr_bit = 16; sp.end_bit = 16; }
     P.hbit[p] = sp.hdr_bit;
     P.ebit[p] = sp.end_bit;
     P.slen[p] = spliced_bytes(sp.end_bit);
@@ -119,6 +125,7 @@ __global__ void __launch_bounds__(256) dstream_pack_kernel(DstreamStreams S, Dst
     if (t == 0) {
         const uint32_t hbit = P.hbit[p], src = spliced_source_bytes(P.ebit[p]);
         slot[hbit >> 3] &= (uint8_t)~(1u << (hbit & 7u));
+        if (P.ebit[p] & 7u) slot[P.ebit[p] >> 3] &= (uint8_t)((1u << (P.ebit[p] & 7u)) - 1u);      // (zero already, unless an empty last block was left out)
         if (slen - 4u > src) slot[2u + src] = 0;
         uint8_t* mk = slot + 2u + slen - 4u;
         mk[0] = 0; mk[1] = 0; mk[2] = 0xff; mk[3] = 0xff;
@@ -130,7 +137,7 @@ __global__ void __launch_bounds__(256) dstream_pack_kernel(DstreamStreams S, Dst
     uint8_t* dst = O.out + S.out_off[s];
     if (first) {
         if (t == 0) S.xs[s] = P.x[p];              // (read by this stream's pieces in later slices only)
-        if (t < hdr && hdr <= cap) dst[t] = (uint8_t)dstream_header_byte(O.wrap, t, O.zflg);
+        if (t < hdr && hdr <= cap) dst[t] = (uint8_t)dstream_header_byte(O.wrap, t, O.zflg, O.xfl);
     }
     if (last) {
         const uint64_t total = end + tail;

@@ -6,6 +6,7 @@
 #include "huff_core.h"
 #include "zwz_common.h"
 #include "lz_band.h"
+#include "rle_core.h"
 
 namespace zwz {
 
@@ -126,6 +127,9 @@ struct DeflateArgs {
     uint32_t plan_serial;      // 1: the lane-serial block flush (plan_serial_kernel) instead of heap + wave
     uint32_t level;            // 4, 5 or 6 (zwz_common.h: LzLevel<N>): which instantiation of lz_match / lz_match_band / lz_lazy / lz_parse runs, and the zlib header's FLEVEL.
                                // Anything else makes launch_deflate fail: a level without kernels is an error
+    uint32_t strategy;         // rle_core.h: kStrategyDefault (deflate_slow at `level`) | kStrategyHuffman | kStrategyRle -- under the last two no search
+                               // kernel and no lz_parse runs (strategy_parse_kernel, zwz_rle.hip, in their place), match_mode and level choose nothing,
+                               // and the zlib header is 78 01.  Anything else makes launch_deflate fail
     ChunkInfo* info; BlockInfo* blocks; BlockOut* plans;
     BlockProbe* probes;        // = links (dead once lz_match has run): chunk c's kMaxBlocks probes open ITS link space
     // The chosen record of every match symbol, compact and in stream order (lz_parse -> blockify, encode): a chunk's
@@ -199,6 +203,7 @@ hipError_t configure_lazy_kernels();                                            
 hipError_t launch_lazy(const DeflateArgs& a, hipStream_t s);
 uint32_t exp_flags_lazy();
 hipError_t launch_plan(const DeflateArgs& a, hipStream_t s);                             // zwz_plan.hip
+hipError_t launch_strategy_parse(const DeflateArgs& a, hipStream_t s);                   // zwz_rle.hip: a.strategy = kStrategyHuffman | kStrategyRle
 hipError_t launch_inflate(const InflateArgs& a, hipStream_t s);
 hipError_t launch_inflate_streams(const InflateStreamArgs& a, hipStream_t s);      // order + inflate_kernel's stream form (statuses provisional)
 hipError_t launch_inflate_split(const InflateSplitArgs& a, hipStream_t s);         // order + inflate_kernel's measuring or segment form

@@ -1152,6 +1152,8 @@ static __device__ __forceinline__ uint32_t select_bit(uint64_t w, uint32_t k) { 
     return (uint32_t)__builtin_ctzll(w);
 }
 
+// kStrategy (rle_core.h) chooses the flush_pos rule, nothing else: a template argument, so that the default form is the kernel it was.
+template <uint32_t kStrategy>
 __global__ __launch_bounds__(kBlockifyThreads) void blockify_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                    const uint32_t* __restrict__ in_len, const uint2* __restrict__ entries,
                                                                    const uint64_t* __restrict__ sym, const uint64_t* __restrict__ mst,
@@ -1279,7 +1281,8 @@ __global__ __launch_bounds__(kBlockifyThreads) void blockify_kernel(const uint8_
         if (tid < kDCodes) bi[b].dfreq[tid] = (uint16_t)s_hist[b][kLCodes + tid];
         if (tid == 0) {
             bi[b].start = s_start[b]; bi[b].end = b + 1 < ci.n_blocks ? s_start[b + 1] : L;
-            bi[b].flush_pos = b + 1 < ci.n_blocks ? s_flush[b] : L;
+            if constexpr (kStrategy == kStrategyDefault) bi[b].flush_pos = b + 1 < ci.n_blocks ? s_flush[b] : L;
+            else bi[b].flush_pos = strategy_flush_pos(kStrategy, b + 1 >= ci.n_blocks, s_flush[b] - 1u, L);      // (s_flush: one behind the last symbol's first position)
             bi[b].first_sym = b * kSymsPerBlock;
         }
     }
@@ -2700,15 +2703,14 @@ hipError_t configure_kernels() {
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kEncodeThreads, kOutWords, 8, 0x5eu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEncodeLdsBytes));
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs, 0x9cu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallEncLdsBytes));
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs, 0x5eu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallEncLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kEncodeThreads, kOutWords, 8, 0x01u>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEncodeLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs, 0x01u>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallEncLdsBytes));
     ZWZ_TRY(configure_lazy_kernels());
     return configure_band_kernels();
 }
 
-hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /* kNumDeflateStages + 1 or null */) {
-    if (a.n == 0) return hipSuccess;
-    if (a.level < (uint32_t)kLevelMin || a.level > (uint32_t)kLevelMax) return hipErrorInvalidValue;     // a level without kernels is an error, never another level's kernels
-    ZWZ_TRY(hipMemsetAsync(a.tickets, 0, kTicketBytes, s));
-    if (ev) ZWZ_TRY(hipEventRecord(ev[0], s));
+// The search and the lazy parse of deflate_slow (a.strategy == kStrategyDefault): stages 0 to 2 of the profile.
+static hipError_t launch_search_parse(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev) {
     // Chain-heavy chunks (lz_dense_list: a sample of each chunk's trigrams): positions sorted by (bucket, position), then the banded
     // search (zwz_band.hip).  The rest: chain links, then lz_match's screening pass over them.  ZWZ_MATCH=walk sends every chunk
     // through links + lz_match (its sorted walk included), =band every chunk through the band.
@@ -2765,9 +2767,28 @@ hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /*
         fprintf(stderr, "ZWZ_PARSE_TIMES n=%u fetch=%llu steps=%llu orbit=%llu events=%llu cover=%llu out=%llu\n", a.n, h[0], h[1], h[2], h[3], h[4], h[5]);
     }
 #endif
+    return hipSuccess;
+}
+
+hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /* kNumDeflateStages + 1 or null */) {
+    if (a.n == 0) return hipSuccess;
+    if (a.level < (uint32_t)kLevelMin || a.level > (uint32_t)kLevelMax) return hipErrorInvalidValue;     // a level without kernels is an error, never another level's kernels
+    ZWZ_TRY(hipMemsetAsync(a.tickets, 0, kTicketBytes, s));
+    if (ev) ZWZ_TRY(hipEventRecord(ev[0], s));
+    const bool searched = a.strategy == kStrategyDefault;
+    if (searched) ZWZ_TRY(launch_search_parse(a, s, ev));
+    else {
+        // Z_HUFFMAN_ONLY / Z_RLE (rle_core.h): no chain, no search, no lazy parse -- one kernel writes what lz_parse would.  The profile's
+        // stages 0 and 1 are empty; the kernel reports under the parse stage.
+        if (a.strategy != kStrategyHuffman && a.strategy != kStrategyRle) return hipErrorInvalidValue;     // a strategy without a kernel is an error
+        if (ev) { ZWZ_TRY(hipEventRecord(ev[1], s)); ZWZ_TRY(hipEventRecord(ev[2], s)); }
+        ZWZ_TRY(launch_strategy_parse(a, s));
+    }
     if (ev) ZWZ_TRY(hipEventRecord(ev[3], s));
-    hipLaunchKernelGGL(blockify_kernel, dim3(a.n), dim3(kBlockifyThreads), 0, s, a.in, a.in_off, a.in_len, a.entries, a.sym, a.mst,
-                       a.info, a.blocks, a.links);
+#define ZWZ_BLOCKIFY_LAUNCH(S) hipLaunchKernelGGL(blockify_kernel<S>, dim3(a.n), dim3(kBlockifyThreads), 0, s, a.in, a.in_off, a.in_len, a.entries, a.sym, a.mst, \
+                                                 a.info, a.blocks, a.links)
+    if (searched) ZWZ_BLOCKIFY_LAUNCH(kStrategyDefault); else if (a.strategy == kStrategyHuffman) ZWZ_BLOCKIFY_LAUNCH(kStrategyHuffman); else ZWZ_BLOCKIFY_LAUNCH(kStrategyRle);
+#undef ZWZ_BLOCKIFY_LAUNCH
     if (ev) ZWZ_TRY(hipEventRecord(ev[4], s));
     ZWZ_TRY(launch_plan(a, s));
     if (ev) ZWZ_TRY(hipEventRecord(ev[5], s));
@@ -2775,15 +2796,16 @@ hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /*
         uint32_t* huff_list = reinterpret_cast<uint32_t*>(a.perm);          // lz_match's work-order array is dead by now
         uint32_t* small_list = huff_list + a.n;                             // (plan's list of open blocks is dead too)
         hipLaunchKernelGGL(encode_stored_kernel, dim3(a.n), dim3(kEncStoredThreads), 0, s, a.in, a.in_off, a.in_len, a.info, a.blocks, a.plans,
-                           a.out, a.out_stride, a.out_len, huff_list, small_list, a.tickets, zlib_flg(a.level));
+                           a.out, a.out_stride, a.out_len, huff_list, small_list, a.tickets, zlib_flg_of(a.level, a.strategy));
         const uint32_t cus = a.cu_count ? a.cu_count : 256u;
-        static_assert(zlib_flg(4) == 0x5eu && zlib_flg(5) == 0x5eu && zlib_flg(6) == 0x9cu, "encode_kernel is instantiated for these two header bytes");
+        static_assert(zlib_flg(4) == 0x5eu && zlib_flg(5) == 0x5eu && zlib_flg(6) == 0x9cu && zlib_flg_of(6, kStrategyHuffman) == 0x01u && zlib_flg_of(4, kStrategyRle) == 0x01u,
+                      "encode_kernel is instantiated for these three header bytes");
 #define ZWZ_ENCODE_LAUNCH(FLG)                                                                                                                                   \
         hipLaunchKernelGGL((encode_kernel<kEncodeThreads, kOutWords, 8, FLG>), dim3(a.n < 2u * cus ? a.n : 2u * cus), dim3(kEncodeThreads), kEncodeLdsBytes, s, a.in, a.in_off, a.in_len, a.entries, a.sym, \
                            a.mst, a.info, a.blocks, a.plans, a.out, a.out_stride, a.out_len, a.links, huff_list, a.tickets, (uint32_t)kTicketHuffCount, (uint32_t)kTicketHuffNext);                 \
         hipLaunchKernelGGL((encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs, FLG>), dim3(a.n < kSmallEncWgs * cus ? a.n : kSmallEncWgs * cus), dim3(kSmallEncThreads), kSmallEncLdsBytes, s, a.in, a.in_off, a.in_len, a.entries, a.sym, \
                            a.mst, a.info, a.blocks, a.plans, a.out, a.out_stride, a.out_len, a.links, small_list, a.tickets, (uint32_t)kTicketSmallCount, (uint32_t)kTicketSmallNext);
-        if (a.level == 6u) { ZWZ_ENCODE_LAUNCH(0x9cu) } else { ZWZ_ENCODE_LAUNCH(0x5eu) }
+        if (!searched) { ZWZ_ENCODE_LAUNCH(0x01u) } else if (a.level == 6u) { ZWZ_ENCODE_LAUNCH(0x9cu) } else { ZWZ_ENCODE_LAUNCH(0x5eu) }
 #undef ZWZ_ENCODE_LAUNCH
     }
 #if ZWZ_ENC_EXP & 16
