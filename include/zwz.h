@@ -307,7 +307,9 @@ typedef enum zwz_stream_status {      /* 0..3 mean what zwz_inflate_status means
     ZWZ_STREAM_CHECKSUM   = 33,   /* Adler-32 / CRC-32 mismatch */
     ZWZ_STREAM_LENGTH     = 34,   /* gzip ISIZE mismatch */
     ZWZ_STREAM_TRAILING   = 35,   /* gzip: bytes after a member that are neither zero padding nor another member */
-    ZWZ_STREAM_TOO_LARGE  = 36    /* d_in_len[i] >= 2^29 or d_out_cap[i] >= 2^32: nothing read or written */
+    ZWZ_STREAM_TOO_LARGE  = 36,   /* d_in_len[i] >= 2^29 or d_out_cap[i] >= 2^32: nothing read or written */
+    ZWZ_STREAM_INDEX      = 37    /* zwz_inflate_indexed_dev: the stream did not decode as its index says (a bit offset, decoded offset, hist or
+                                     end bit that is not the stream's, or a stream of another length) */
 } zwz_stream_status;
 int zwz_inflate_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
                             uint32_t n, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
@@ -352,6 +354,83 @@ int zwz_inflate_split_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, c
  * that splits, a file shorter than 2^29 bytes is decoded again by that one-stream path (which reads further members and names
  * garbage); a longer one is ZWZ_E_FORMAT, its further members are not read.  dst is written as dst.part and renamed on success only.  Synchronous. */
 int zwz_inflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst);
+
+/* ---- A seek index for ordinary streams: parallel and ranged inflate ----------------------------------------------------------------
+ * An ordinary stream -- gzip, zlib.compress, pigz without -i, git, PNG, anything with sync flushes -- offers no cut: every block may
+ * refer 32 KiB back.  It is decoded ONCE at the one-wave rate, and that decode keeps CHECKPOINTS: a block header's first bit, the
+ * decoded offset there and the up to 32 KiB of output in front of it.  From then on the stream decodes with one wave per segment between
+ * two checkpoints, and a batch of byte ranges decodes only the segments it touches.  Building runs at the one-wave rate (about 36 s
+ * per decoded GiB of a single stream): the index pays off from the second access on, or on batches.
+ * The index of one stream, all little-endian: a 64-byte header, `count` entries of 24 bytes, the windows back to back in entry
+ * order, zero padding to a multiple of 16.
+ *   header   0 "ZWZIDX\0\1"   8 u32 wrap   12 u32 span   16 u64 stream length, wrapper included   24 u64 decoded length   32 u32 count
+ *           36 u32 flags, 0   40 u64 end bit: the first bit behind the final block   48 u32 stored CRC-32 / Adler-32, 0 for raw
+ *           52 u32 CRC-32 of the index from byte 64 to its end   56 u64 0
+ *   entry    0 u64 bit offset of a block header's first bit, counted from the stream's first byte   8 u64 decoded offset
+ *           16 u32 hist: bytes of window kept, <= min(32768, decoded offset)   20 u32 0
+ * Entry 0 is the body's first block (decoded offset 0, hist 0); bit offsets rise strictly, decoded offsets do not fall.  A hist below
+ * its bound is a promise that no match of the segment reaches further back, and the decode checks it.  Anyone may write such an
+ * index: after every Z_SYNC_FLUSH of a libz writer the next block starts on a byte boundary at a known decoded offset.  An index
+ * with a wrong magic, length, index CRC or window sum, entries out of order, a hist over its bound, an end bit beyond the stream or a
+ * header field out of range (a decoded length above 1032 times the stream's, which no DEFLATE data reaches, among them) is
+ * ZWZ_E_FORMAT wherever one is read.
+ * Readable extents: the byte copies read whole aligned 4-byte words, so an index on the device and every output range are readable up
+ * to their length rounded up to 16 (an index's length is a multiple of 16 already).
+ * Not in this version: an index for a gzip stream of several members (none is made), an index built in legs for a stream of 2^29
+ * compressed bytes or more, compressed windows, decoding a touched segment only as far as the last byte asked for. */
+/* The most an index of a stream that decodes to decoded_cap bytes takes at this span (0: 1 MiB); 0 for a span that is not allowed. */
+uint64_t zwz_inflate_index_bound(uint64_t decoded_cap, uint32_t span);
+/* zwz_inflate_streams_dev that also writes every stream's index.  The first eleven arguments, the decoded bytes, d_out_len and
+ * d_status are exactly that call's.  span: decoded bytes between checkpoints at least, a power of two in 16 KiB .. 1 GiB; 0 takes
+ * the context option "index_span_bytes" (default 1048576).  The index of stream i goes to d_idx + d_idx_off[i] (device arrays;
+ * d_idx and every offset multiples of 16), at most d_idx_cap[i] bytes, and d_idx_len[i] receives its length: 0 where none was made --
+ * a status other than 0, a second gzip member (zero padding behind the member is fine), or a capacity too small
+ * (zwz_inflate_index_bound(d_out_cap[i], span) always fits).  Asynchronous on the context's stream. */
+int zwz_inflate_streams_index_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
+                                  uint32_t n, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
+                                  uint64_t *d_out_len, uint32_t *d_status, uint32_t span, uint8_t *d_idx,
+                                  const uint64_t *d_idx_off, const uint64_t *d_idx_cap, uint64_t *d_idx_len);
+/* ONE stream of any length (d_in, in_len bytes, 16-byte aligned, readable up to its length rounded up to 16) decoded whole with its
+ * index, one wave per segment: the 2^29 / 2^32 limits hold for a single segment only (else ZWZ_STREAM_TOO_LARGE).  idx (idx_len
+ * bytes) is HOST memory, for planning; d_idx is the same bytes on the device (16-byte aligned), or NULL: the call then uploads them.
+ * The wrapper comes from the index.  d_out may start at ANY byte; no byte outside [d_out, d_out + decoded length) is written.
+ * *d_out_len, *d_status, *d_segments (device; d_segments may be NULL): the decoded length, the verdict, the segments decoded.
+ * Verdicts: 0; 3 with nothing written when out_cap is below the indexed decoded length; ZWZ_STREAM_INDEX when in_len is not the
+ * index's or a segment does not end exactly at its end bit with exactly its indexed count; ZWZ_STREAM_CHECKSUM when the decoded
+ * bytes' CRC-32 / Adler-32 (computed from pieces in parallel) is not BOTH the index's stored value and the stream's own trailer
+ * (gzip: ISIZE too), or when a window of the index is not the bytes that precede its checkpoint.  The windows are put at their final
+ * places in the output before the waves start; the wave of the segment before writes the same bytes there later.
+ * NOT asynchronous (the call waits for the context's stream before it fills its staging); the last kernels are still queued when it
+ * returns: zwz_ctx_sync before reading results -- and, with d_idx NULL, before idx is freed or changed: its upload may still be queued.
+ * ZWZ_E_FORMAT for a malformed index. */
+int zwz_inflate_indexed_dev(zwz_ctx *ctx, const uint8_t *d_in, uint64_t in_len, const uint8_t *idx, uint64_t idx_len,
+                            const uint8_t *d_idx, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_len, uint32_t *d_status,
+                            uint32_t *d_segments);
+/* ranges and the result layout are zwz_bgzf_read_ranges_dev's: k pairs (decoded offset, length) in host memory, their bytes
+ * concatenated in d_out; a range past the decoded length is ZWZ_E_INVALID naming it.  Only the segments holding a requested byte are
+ * decoded, each whole, into scratch the context keeps (its window in front of it; slices of at most 256 MiB of scratch).  With d_idx
+ * NULL only the windows of touched segments are uploaded.  Range reads carry NO checksum verdict: a segment is checked to end at its
+ * end bit with its indexed count (else ZWZ_E_FORMAT naming the segment), the bytes themselves are not; damage inside a segment no
+ * range touches is not seen.  Synchronous. */
+int zwz_inflate_read_ranges_dev(zwz_ctx *ctx, const uint8_t *d_in, uint64_t in_len, const uint8_t *idx, uint64_t idx_len,
+                                const uint8_t *d_idx, const uint64_t *ranges, uint32_t k, uint8_t *d_out);
+/* Host only (no GPU): checks an index as every reader does (ZWZ_E_FORMAT, zwz_last_error() naming the rule) and returns its wrapper,
+ * the stream's length, the decoded length and the number of entries; any of the four pointers may be NULL. */
+int zwz_inflate_index_info(const uint8_t *idx, uint64_t idx_len, int *wrap, uint64_t *stream_len, uint64_t *decoded_len, uint32_t *count);
+/* One file holding one stream -> its index at dst_idx (written as dst_idx.part, renamed on success).  The file goes through
+ * zwz_inflate_streams_index_dev whole, at the context's "index_span_bytes": the one-wave limit of 2^29 compressed bytes applies and is
+ * ZWZ_E_FORMAT naming ZWZ_STREAM_TOO_LARGE; so is a stream that does not decode (ZWZ_E_CHECKSUM for a checksum or ISIZE mismatch) and a
+ * gzip file of several members, for which no index is made.  Synchronous. */
+int zwz_inflate_index_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst_idx);
+/* zwz_inflate_read_ranges_dev from a file into host memory: the index is read from idx_path, and of src only the compressed bytes of
+ * the touched segments (one pread per run of consecutive index entries).  A file of another length than indexed is ZWZ_E_FORMAT. */
+int zwz_inflate_read_ranges_file(zwz_ctx *ctx, const char *src, const char *idx_path, const uint64_t *ranges, uint32_t k, uint8_t *out);
+/* One file of any size decoded whole with its index: the compressed file is read in slices of consecutive index entries (their decoded
+ * bytes at most four times "split_slice_bytes", one entry at least), every segment of a slice by a wave of its own, the bytes written
+ * by a writer thread while the next slice runs.  The CRC-32 / Adler-32 joined from the slices' pieces is checked against the index's
+ * stored value and the file's own trailer (gzip: ISIZE too): ZWZ_E_CHECKSUM; a segment that does not decode as indexed: ZWZ_E_FORMAT.
+ * dst is written as dst.part and renamed on success only.  Synchronous. */
+int zwz_inflate_stream_file_indexed(zwz_ctx *ctx, const char *src, const char *idx_path, const char *dst);
 
 /* ---- DEFLATE streams of any size, written: raw, zlib and gzip ------------------------------------------------------------------
  * Compresses a batch of n independent inputs into n ordinary streams that any inflate reads.  Stream i is, byte for byte, what

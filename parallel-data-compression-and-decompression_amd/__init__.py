@@ -114,6 +114,15 @@ def lib():
         L.zwz_inflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         L.zwz_inflate_split_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
         L.zwz_inflate_stream_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
+        L.zwz_inflate_index_bound.restype = u64
+        L.zwz_inflate_index_bound.argtypes = [u64, u32]
+        L.zwz_inflate_streams_index_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+        L.zwz_inflate_indexed_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp]
+        L.zwz_inflate_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, u32, vp]
+        L.zwz_inflate_index_info.argtypes = [vp, u64, c.POINTER(c.c_int), c.POINTER(u64), c.POINTER(u64), c.POINTER(u32)]
+        L.zwz_inflate_index_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
+        L.zwz_inflate_read_ranges_file.argtypes = [vp, c.c_char_p, c.c_char_p, vp, u32, vp]
+        L.zwz_inflate_stream_file_indexed.argtypes = [vp, c.c_char_p, c.c_char_p, c.c_char_p]
         L.zwz_deflate_stream_bound.restype = u64
         L.zwz_deflate_stream_bound.argtypes = [u64, c.c_int]
         L.zwz_deflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
@@ -142,6 +151,7 @@ STRATEGY_DEFAULT, STRATEGY_HUFFMAN, STRATEGY_RLE = 0, 2, 3      # libz's numbers
 STRATEGIES = {"default": STRATEGY_DEFAULT, "huffman": STRATEGY_HUFFMAN, "rle": STRATEGY_RLE}
 STREAM_END, STREAM_NEED_INPUT, STREAM_DATA_ERROR, STREAM_OVERFLOW = 0, 1, 2, 3
 STREAM_BAD_HEADER, STREAM_CHECKSUM, STREAM_LENGTH, STREAM_TRAILING, STREAM_TOO_LARGE = 32, 33, 34, 35, 36
+STREAM_INDEX = 37           # the stream did not decode as its seek index says (inflate_indexed)
 STREAM_MAX_IN, STREAM_MAX_OUT = 1 << 29, 1 << 32
 # per-entry status of zwz_unzip_dev beyond the inflate codes and STREAM_TOO_LARGE (include/zwz.h)
 ZIP_UNSUPPORTED, ZIP_BAD_ENTRY, ZIP_SIZE_MISMATCH, ZIP_CRC_MISMATCH = 48, 49, 50, 51
@@ -298,6 +308,134 @@ class Codec:
         """One file holding one raw / zlib / gzip stream of any size -> dst (zwz_inflate_stream_file; `main gunzip`).  ZwzError with
         status E_FORMAT / E_CHECKSUM on a damaged file; dst then does not appear."""
         _check(lib().zwz_inflate_stream_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst)), "zwz_inflate_stream_file")
+
+    def inflate_streams_index_dev(self, wrap, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_idx, d_idx_off,
+                                  d_idx_cap, d_idx_len, span=0):
+        """zwz_inflate_streams_index_dev: inflate_streams_dev's arguments and results, and the seek index of stream i at d_idx +
+        d_idx_off[i] (int64 device tensors of offsets, capacities and lengths; a length of 0 where no index was made).  span: decoded
+        bytes between checkpoints, a power of two in 16 KiB .. 1 GiB; 0: the context option "index_span_bytes".  Asynchronous."""
+        n = d_in_len.numel()
+        _check(lib().zwz_inflate_streams_index_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), n,
+                                                   d_out.data_ptr(), d_out_off.data_ptr(), d_out_cap.data_ptr(), d_out_len.data_ptr(),
+                                                   d_status.data_ptr(), int(span), d_idx.data_ptr(), d_idx_off.data_ptr(), d_idx_cap.data_ptr(),
+                                                   d_idx_len.data_ptr()), "zwz_inflate_streams_index_dev")
+
+    def inflate_indexed_dev(self, d_in, in_len, index, d_out, out_cap, d_out_len, d_status, d_segments=None, d_idx=None):
+        """zwz_inflate_indexed_dev: ONE stream (a 16-byte aligned CUDA uint8 tensor, in_len bytes) decoded whole with its index (bytes),
+        a wave per segment, into d_out, which may start at any byte.  d_idx: the index on the device (None: uploaded).  d_out_len
+        (int64), d_status (int32), d_segments (int32, optional): one element each.  The results are complete after sync()."""
+        index = bytes(index)
+        _check(lib().zwz_inflate_indexed_dev(self._h, d_in.data_ptr(), int(in_len), index, len(index), d_idx.data_ptr() if d_idx is not None else None,
+                                             d_out.data_ptr(), int(out_cap), d_out_len.data_ptr(), d_status.data_ptr(),
+                                             d_segments.data_ptr() if d_segments is not None else None), "zwz_inflate_indexed_dev")
+
+    def inflate_index(self, data, wrap="gzip", span=None, out_size=None):
+        """bytes of ONE ordinary raw / zlib / gzip stream -> (decoded bytes, index bytes): the one-wave decode that also keeps a
+        checkpoint every `span` decoded bytes (None: the context's "index_span_bytes", 1 MiB).  The index is b"" where none is made
+        (a gzip stream of several members).  Capacity as inflate_streams guesses and regrows it; raises ZwzError as it does."""
+        import numpy as np
+        import torch
+        w = WRAPS.get(wrap, wrap)
+        data = bytes(data)
+        span = int(span or 0)
+        cap = int(out_size) if out_size is not None else max(4 * len(data), 1 << 16)
+        if out_size is None and w == WRAP_GZIP and len(data) >= 4:
+            cap = max(int.from_bytes(data[-4:], "little"), 1)
+        cap = min(cap, STREAM_MAX_OUT - 1)
+        dev = torch.device("cuda", self.device)
+        d_in = _device_input(torch, data, self.device)
+        while True:
+            bound = lib().zwz_inflate_index_bound(cap, span)
+            if bound == 0:
+                raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
+            d_out = torch.empty((cap + 15) // 16 * 16 or 16, dtype=torch.uint8, device=dev)
+            d_idx = torch.empty(bound, dtype=torch.uint8, device=dev)
+            par = torch.from_numpy(np.array([0, len(data), 0, cap, 0, bound, 0, 0], dtype=np.int64)).to(dev)
+            d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+            self.inflate_streams_index_dev(w, d_in, par[0:1], par[1:2], d_out, par[2:3], par[3:4], par[6:7], d_st, d_idx, par[4:5], par[5:6], par[7:8], span)
+            self.sync()
+            st, olen, ilen = int(d_st.item()), int(par[6].item()), int(par[7].item())
+            if st == STREAM_OVERFLOW and out_size is None and cap < STREAM_MAX_OUT - 1:
+                cap = min(2 * cap, STREAM_MAX_OUT - 1)
+                continue
+            if st != STREAM_END:
+                err = ZwzError("inflate_index: status %d" % st)
+                err.status, err.index, err.stream_status = E_FORMAT, 0, st
+                raise err
+            return d_out[:olen].cpu().numpy().tobytes(), d_idx[:ilen].cpu().numpy().tobytes()
+
+    def inflate_indexed(self, data, index):
+        """bytes of one stream and its index (inflate_index's, or any index of the layout in include/zwz.h) -> decoded bytes, one
+        wave per indexed segment.  Raises ZwzError (.stream_status: STREAM_INDEX when the stream does not decode as the index says,
+        STREAM_CHECKSUM, ...) for a verdict other than 0, and with status E_FORMAT for a malformed index."""
+        import torch
+        index = bytes(index)
+        total = index_info(index)["decoded_len"]                # (validated before anything is sized by it)
+        dev = torch.device("cuda", self.device)
+        d_in = _device_input(torch, data, self.device)
+        d_out = torch.empty((total + 15) // 16 * 16 or 16, dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.inflate_indexed_dev(d_in, len(data), index, d_out, total, d_len, d_st)
+        self.sync()
+        st = int(d_st.item())
+        if st != STREAM_END:
+            err = ZwzError("inflate_indexed: status %d" % st)
+            err.status, err.index, err.stream_status = E_FORMAT, 0, st
+            raise err
+        return d_out[:int(d_len.item())].cpu().numpy().tobytes()
+
+    def read_ranges_dev(self, d_in, in_len, index, ranges, d_out, d_idx=None):
+        """zwz_inflate_read_ranges_dev: the decoded byte ranges (a (k, 2) uint64 array of offset, length) of one stream on the device,
+        concatenated into d_out.  Only the touched segments are decoded; no checksum verdict.  Synchronous."""
+        index = bytes(index)
+        _check(lib().zwz_inflate_read_ranges_dev(self._h, d_in.data_ptr(), int(in_len), index, len(index), d_idx.data_ptr() if d_idx is not None else None,
+                                                 ranges.ctypes.data, len(ranges), d_out.data_ptr()), "zwz_inflate_read_ranges_dev")
+
+    def inflate_index_file(self, src, dst_idx, wrap="gzip", span=None):
+        """One file holding one ordinary stream -> its seek index at dst_idx (zwz_inflate_index_file; `main gzindex`).  span: as
+        inflate_index (sets the context option "index_span_bytes").  Files of 2^29 compressed bytes or more are refused."""
+        if span:
+            self.set_option("index_span_bytes", str(int(span)))
+        _check(lib().zwz_inflate_index_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst_idx)), "zwz_inflate_index_file")
+
+    def inflate_stream_file_indexed(self, src, index_path, dst):
+        """One file of any size decoded whole with its index, a wave per segment (zwz_inflate_stream_file_indexed; `main gunzip
+        --index`).  ZwzError with status E_FORMAT / E_CHECKSUM; dst then does not appear."""
+        _check(lib().zwz_inflate_stream_file_indexed(self._h, os.fsencode(src), os.fsencode(index_path), os.fsencode(dst)),
+               "zwz_inflate_stream_file_indexed")
+
+    def read_ranges_file(self, src, index_path, ranges):
+        """Decoded byte ranges of a file holding one ordinary stream -> a list of bytes; only the compressed bytes of the touched
+        segments are read (zwz_inflate_read_ranges_file)."""
+        import numpy as np
+        rng = _ranges(np, ranges)
+        total = int(rng[:, 1].sum()) if len(rng) else 0
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        _check(lib().zwz_inflate_read_ranges_file(self._h, os.fsencode(src), os.fsencode(index_path), rng.ctypes.data, len(rng), out.ctypes.data),
+               "zwz_inflate_read_ranges_file")
+        return _split(out[:total].tobytes(), rng)
+
+    def read_ranges(self, data, index, ranges):
+        """Decoded byte ranges [(offset, length), ...] of an ordinary stream with its seek index: bytes -> a list of bytes; a CUDA uint8
+        tensor -> one CUDA tensor of the ranges concatenated (as bgzf_read_ranges).  Only the segments holding a requested byte are
+        decoded.  A range past the end raises ZwzError (status E_INVALID)."""
+        import numpy as np
+        import torch
+        as_tensor = isinstance(data, torch.Tensor)
+        rng = _ranges(np, ranges)
+        total = int(rng[:, 1].sum()) if len(rng) else 0
+        dev = torch.device("cuda", self.device)
+        d_in = _device_input(torch, data, self.device)
+        n = data.numel() if as_tensor else len(data)
+        d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.read_ranges_dev(d_in, n, index, rng, d_out)
+        if as_tensor:
+            return d_out[:total]
+        return _split(d_out[:total].cpu().numpy().tobytes(), rng)
 
     def _streams_once(self, torch, np, wrap, streams, caps, split=False):
         """One call over host streams with the given capacities -> (statuses, [bytes])."""
@@ -754,6 +892,15 @@ def do_decompression(input_dir, output_dir, world_rank=0, world_size=1, allgathe
 
 def inflate_stream(data, wrap="gzip", out_size=None):
     return _codec().inflate_stream(data, wrap, out_size)
+
+
+def index_info(index):
+    """A seek index checked as every reader checks it (ZwzError with status E_FORMAT) -> {"wrap", "stream_len", "decoded_len", "count"}.
+    Needs no GPU."""
+    index = bytes(index)
+    w, n, d, k = ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    _check(lib().zwz_inflate_index_info(index, len(index), ctypes.byref(w), ctypes.byref(n), ctypes.byref(d), ctypes.byref(k)), "zwz_inflate_index_info")
+    return {"wrap": w.value, "stream_len": n.value, "decoded_len": d.value, "count": k.value}
 
 
 def inflate_stream_file(src, dst, wrap="gzip"):

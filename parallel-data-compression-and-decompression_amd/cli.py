@@ -216,7 +216,47 @@ def run(operation, source_path, output_path, *, compress_fn=None, decompress_fn=
     return rc
 
 
+def index_main(argv):
+    """`gzindex <src> [<dst.zwi>] [--span N] [--zlib|--raw]` and `gunzip <src> <dst> --index <idx> [--offset B [--size S]]`: the seek
+    index of an ordinary stream and the reads through it, as csrc/main.cpp's commands of the same names.  One process, one GPU."""
+    ap = argparse.ArgumentParser(prog="main " + argv[0])
+    ap.add_argument("source")
+    ap.add_argument("output", nargs="?" if argv[0] == "gzindex" else None)
+    ap.add_argument("--zlib", action="store_true")
+    ap.add_argument("--raw", action="store_true")
+    if argv[0] == "gzindex":
+        ap.add_argument("--span", type=int, default=0)
+    else:
+        ap.add_argument("--index", required=True)
+        ap.add_argument("--offset", type=int)
+        ap.add_argument("--size", type=int)
+    a = ap.parse_args(argv[1:])
+    from . import Codec, index_info
+    codec = Codec(int(os.environ.get("LOCAL_RANK", "0")))
+    try:
+        if argv[0] == "gzindex":
+            codec.inflate_index_file(a.source, a.output or a.source + ".zwi", "zlib" if a.zlib else "raw" if a.raw else "gzip", a.span or None)
+        elif a.offset is None:
+            if a.size is not None:
+                ap.error("--size needs --offset")
+            codec.inflate_stream_file_indexed(a.source, a.index, a.output)
+        else:
+            with open(a.index, "rb") as f:
+                total = index_info(f.read())["decoded_len"]
+            size = a.size if a.size is not None else max(total - a.offset, 0)
+            data = codec.read_ranges_file(a.source, a.index, [(a.offset, size)])[0]
+            with open(a.output + ".part", "wb") as f:
+                f.write(data)
+            os.replace(a.output + ".part", a.output)
+    finally:
+        codec.close()
+    return 0
+
+
 def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if argv and (argv[0] == "gzindex" or (argv[0] == "gunzip" and "--index" in argv)):
+        return index_main(argv)
     ap = argparse.ArgumentParser(prog="main", usage="%(prog)s <compress/decompress> <source directory path> <output directory path>")
     ap.add_argument("operation")
     ap.add_argument("source")

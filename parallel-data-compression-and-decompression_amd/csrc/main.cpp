@@ -379,10 +379,67 @@ int zip_main(const std::string& op, const char* src, const char* dst, int world_
 
 void bgzf_usage(const char* argv0) {
     fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index] [-4|-5|-6] [--huffman|--rle]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n"
-            "       %s gzip <src> <dst> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle]\n       %s gunzip <src> <dst> [--zlib|--raw]\n       %s zip <src dir> <dst.zip> [-4|-5|-6] [--huffman|--rle]\n       %s unzip <src.zip> <dst dir>\n"
+            "       %s gzip <src> <dst> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle]\n       %s gunzip <src> <dst> [--zlib|--raw] [--index <idx> [--offset B [--size S]]]\n       %s gzindex <src> [<dst.zwi>] [--span N] [--zlib|--raw]\n       %s zip <src dir> <dst.zip> [-4|-5|-6] [--huffman|--rle]\n       %s unzip <src.zip> <dst dir>\n"
             "  -4 -5 -6 (behind the operands or, as gzip takes it, in front of them): libz's compression level of that number (default 6, or ZWZ_LEVEL); no other level exists here\n"
             "  --huffman | --rle (before or behind the operands; not both): libz's strategy Z_HUFFMAN_ONLY (entropy coding only) or Z_RLE (runs of a byte only); default: neither, or ZWZ_STRATEGY\n",
-            argv0, argv0, argv0, argv0, argv0, argv0, argv0);
+            argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
+}
+
+bool parse_u64(const char* s, uint64_t* v);
+
+// `main gzindex <src> [<dst.zwi>] [--span N] [--zlib|--raw]`: the seek index of one ordinary stream (zwz_inflate_index_file), by default at <src>.zwi.
+int gzindex_main(int argc, char** argv, int world_size, int device) {
+    if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", argv[1], world_size); return 1; }
+    int wrap = ZWZ_WRAP_GZIP;
+    uint64_t span = 0;
+    std::string src, dst;
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        if (a == "--zlib") wrap = ZWZ_WRAP_ZLIB;
+        else if (a == "--raw") wrap = ZWZ_WRAP_RAW;
+        else if (a == "--span" && i + 1 < argc && parse_u64(argv[i + 1], &span) && span) i++;
+        else if (a[0] != '-' && src.empty()) src = a;
+        else if (a[0] != '-' && dst.empty()) dst = a;
+        else { bgzf_usage(argv[0]); return 1; }
+    }
+    if (src.empty()) { bgzf_usage(argv[0]); return 1; }
+    if (dst.empty()) dst = src + ".zwi";
+    const auto t0 = std::chrono::steady_clock::now();
+    zwz_ctx* ctx = nullptr;
+    int rc = zwz_ctx_create(device, 0, &ctx);
+    if (rc == ZWZ_OK && span) rc = zwz_ctx_set_option(ctx, "index_span_bytes", std::to_string(span).c_str());
+    if (rc == ZWZ_OK) rc = zwz_inflate_index_file(ctx, wrap, src.c_str(), dst.c_str());
+    zwz_ctx_destroy(ctx);
+    if (rc != ZWZ_OK) { fprintf(stderr, "gzindex %s: %s (%s)\n", src.c_str(), zwz_strerror(rc), zwz_last_error()); return 1; }
+    printf("gzindex %s -> %s in %.3f s\n", src.c_str(), dst.c_str(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}
+
+// `main gunzip <src> <dst> --index <idx> [--offset B [--size S]]`: the whole file through its index (zwz_inflate_stream_file_indexed), or the
+// decoded bytes [B, B + S) alone (zwz_inflate_read_ranges_file; S defaults to everything behind B).
+int gunzip_indexed(zwz_ctx* ctx, const char* src, const char* dst, const char* idx_path, bool have_off, uint64_t off, bool have_size, uint64_t size) {
+    if (!have_off) return zwz_inflate_stream_file_indexed(ctx, src, idx_path, dst);
+    std::vector<uint8_t> idx;
+    {
+        FILE* f = fopen(idx_path, "rb");
+        if (!f) { fprintf(stderr, "gunzip: cannot open %s\n", idx_path); return ZWZ_E_IO; }
+        uint8_t tmp[65536];
+        for (size_t k; (k = fread(tmp, 1, sizeof tmp, f)) > 0;) idx.insert(idx.end(), tmp, tmp + k);
+        fclose(f);
+    }
+    uint64_t total = 0;
+    if (int rc = zwz_inflate_index_info(idx.data(), idx.size(), nullptr, nullptr, &total, nullptr)) return rc;
+    if (off > total) { fprintf(stderr, "gunzip: --offset %llu is past the end of the data (%llu bytes)\n", (unsigned long long)off, (unsigned long long)total); return ZWZ_E_INVALID; }
+    if (!have_size) size = total - off;
+    const uint64_t r[2] = {off, size};
+    std::vector<uint8_t> buf((size_t)size + 1);
+    if (int rc = zwz_inflate_read_ranges_file(ctx, src, idx_path, r, 1, buf.data())) return rc;
+    const std::string part = std::string(dst) + ".part";
+    FILE* f = fopen(part.c_str(), "wb");
+    if (!f) { fprintf(stderr, "gunzip: cannot create %s\n", part.c_str()); return ZWZ_E_IO; }
+    const bool ok = fwrite(buf.data(), 1, (size_t)size, f) == (size_t)size;
+    if (fclose(f) != 0 || !ok || rename(part.c_str(), dst) != 0) { unlink(part.c_str()); fprintf(stderr, "gunzip: cannot write %s\n", dst); return ZWZ_E_IO; }
+    return ZWZ_OK;
 }
 
 // `main gzip <src file> <dst file> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle]`: one file as one ordinary gzip (zlib, raw DEFLATE) stream, one process, one GPU.
@@ -391,20 +448,28 @@ int gzip_main(int argc, char** argv, int world_size, int device) {
     const bool back = std::string(argv[1]) == "gunzip";
     if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", argv[1], world_size); return 1; }
     int wrap = ZWZ_WRAP_GZIP, level = 0, strategy = 0;
+    const char* idx_path = nullptr;
+    bool have_off = false, have_size = false;
+    uint64_t off = 0, size = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--zlib") wrap = ZWZ_WRAP_ZLIB;
         else if (a == "--raw") wrap = ZWZ_WRAP_RAW;
+        else if (back && a == "--index" && i + 1 < argc) idx_path = argv[++i];
+        else if (back && a == "--offset" && i + 1 < argc && parse_u64(argv[i + 1], &off)) { have_off = true; i++; }
+        else if (back && a == "--size" && i + 1 < argc && parse_u64(argv[i + 1], &size)) { have_size = true; i++; }
         else if (!back && level_flag(a, &level) == 1) {}
         else if (!back && strategy_flag(a, &strategy) == 1) {}
         else { bgzf_usage(argv[0]); return 1; }
     }
+    if ((have_off && !idx_path) || (have_size && !have_off)) { bgzf_usage(argv[0]); return 1; }
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
     if (rc == ZWZ_OK && level) rc = zwz_ctx_set_level(ctx, level);
     if (rc == ZWZ_OK && strategy) rc = zwz_ctx_set_strategy(ctx, strategy);
-    if (rc == ZWZ_OK) rc = back ? zwz_inflate_stream_file(ctx, wrap, argv[2], argv[3]) : zwz_deflate_stream_file(ctx, wrap, argv[2], argv[3]);
+    if (rc == ZWZ_OK && idx_path) rc = gunzip_indexed(ctx, argv[2], argv[3], idx_path, have_off, off, have_size, size);
+    else if (rc == ZWZ_OK) rc = back ? zwz_inflate_stream_file(ctx, wrap, argv[2], argv[3]) : zwz_deflate_stream_file(ctx, wrap, argv[2], argv[3]);
     zwz_ctx_destroy(ctx);
     if (rc != ZWZ_OK) { fprintf(stderr, "%s %s: %s (%s)\n", argv[1], argv[2], zwz_strerror(rc), zwz_last_error()); return 1; }
     printf("%s %s -> %s in %.3f s\n", argv[1], argv[2], argv[3], std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -557,6 +622,10 @@ int main(int argc, char* argv[]) {
         int n = 0;
         const int dev = zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0;
         return bgzf_ext_main(argc, argv, world_size, dev);
+    }
+    if (argc >= 3 && std::string(argv[1]) == "gzindex") {
+        int n = 0;
+        return gzindex_main(argc, argv, world_size, zwz_device_count(&n) == ZWZ_OK && n > 0 ? env_int(dev_vars, 0) % n : 0);
     }
     if (argc < 4) {   // main.cpp:88-92
         fprintf(stderr, "Usage: %s <compress/decompress> <source directory path> <output directory path>\n", argv[0]);

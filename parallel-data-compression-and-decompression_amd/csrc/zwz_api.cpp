@@ -370,6 +370,12 @@ int zwz_ctx_set_option(zwz_ctx* c, const char* name, const char* value) {
         if (n == "split_min_bytes") c->split_min_bytes = v.empty() ? kSplitMinBytes : (uint32_t)x;
         else if (n == "split_budget") { if (!v.empty() && x < 16) return ZWZ_E_INVALID; c->split_budget = v.empty() ? kSplitBudget : (uint32_t)x; }
         else { if (!v.empty() && x < 2) return ZWZ_E_INVALID; c->split_max_candidates = v.empty() ? kSplitMaxCandidates : (uint32_t)x; }
+    } else if (n == "index_span_bytes") {
+        // zwz_inflate_streams_index_dev (index_core.h): decoded bytes between two checkpoints, a power of two
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v.c_str(), &end, 10);
+        if (!v.empty() && (*end || end == v.c_str() || x > kIdxSpanMax || !index_span_ok((uint32_t)x))) return ZWZ_E_INVALID;
+        c->index_span_bytes = v.empty() ? kIdxSpanDefault : (uint32_t)x;
     } else if (n == "zip_force_zip64") {
         if (v == "0" || v.empty()) c->zip_force_zip64 = 0; else if (v == "1") c->zip_force_zip64 = 1; else return ZWZ_E_INVALID;
     } else if (n == "zip_slice_bytes") {

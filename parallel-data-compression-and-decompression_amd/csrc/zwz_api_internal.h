@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/zwz.h"
+#include "index_core.h"
 #include "split_core.h"
 #include "zwz_kernels.h"
 
@@ -34,10 +35,13 @@ enum BufId {
     kBufSplit0, kBufSplit1, kBufSplit2,      // split inflate (zwz_split.cpp): per stream and scan tile / per candidate / per chain segment and checksum piece
     kBufZipStage,        // ZIP (zwz_zip.cpp): the entries' gzip streams on the way in, their gathered data on the way out
     kBufZipDev,          // ZIP: the per-entry and per-tile arrays of one call, and their pinned twin
+    kBufIndex0,          // seek index (zwz_index.cpp): segment records, window moves, checksum pieces and flags of one call, and its pinned twin
+    kBufIndex1,          // seek index: an index uploaded for a call, or the scratch slots of a range read
     kNumDeviceBufs,
     kBufStageHost = kNumDeviceBufs, kBufRangeHost, kBufStreamsHost,
     kBufSplitHost,       // split inflate: the per-stream arrays a call uploads (read by copies that may still be queued when it returns)
     kBufZipHost,
+    kBufIndexHost,
     kNumBufs
 };
 
@@ -67,6 +71,7 @@ struct zwz_ctx {
     // split inflate (zwz_split.cpp): options "split_min_bytes", "split_budget", "split_max_candidates" (split_core.h's defaults)
     uint32_t split_min_bytes = zwz::kSplitMinBytes, split_budget = zwz::kSplitBudget, split_max_candidates = zwz::kSplitMaxCandidates;
     uint32_t split_slice_bytes = zwz::kSplitSliceBytes;      // zwz_inflate_stream_file: "split_slice_bytes"
+    uint32_t index_span_bytes = zwz::kIdxSpanDefault;        // zwz_inflate_streams_index_dev with span 0: "index_span_bytes"
     // ZIP (zwz_zip.cpp): options "zip_force_zip64" and "zip_slice_bytes"; the last call's copy out of kBufZipHost has run
     uint32_t zip_force_zip64 = 0;
     uint64_t zip_slice_bytes = 268435456ull;

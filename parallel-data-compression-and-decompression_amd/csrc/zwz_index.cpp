@@ -1,0 +1,468 @@
+// zwz_index.cpp -- the seek index for ordinary DEFLATE streams of include/zwz.h: zwz_inflate_streams_index_dev (one decode that also
+// writes the index), zwz_inflate_indexed_dev (one stream decoded whole, a wave per indexed segment) and zwz_inflate_read_ranges_dev
+// (only the segments a batch of ranges touches), and their file forms: zwz_inflate_index_file, zwz_inflate_read_ranges_file (a pread of
+// the touched segments only) and zwz_inflate_stream_file_indexed (slices of consecutive index entries, zwz_filejob.h's writer).
+// index_core.h has the layout, the checks and the planning; the kernels are
+// inflate_kernel's marking and indexed-segment forms (zwz_kernels.hip) and zwz_index.hip.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "dstream_core.h"
+#include "zwz_api_internal.h"
+#include <fcntl.h>
+#include <string>
+
+#include "zwz_bgzf.h"
+#include "zwz_filejob.h"
+#include "zwz_index.h"
+
+using namespace zwz;
+
+namespace {
+
+constexpr uint64_t kIdxWorkspaceBytes = 256ull << 20;     // scratch slots of one slice of a range read (a longer segment is a slice of its own)
+constexpr uint64_t kIdxSegMaxOut = 0xffff0000ull;         // origin + hist + count of one segment stay 32-bit positions
+
+// The arrays of one call.  The first `upload` bytes are filled on the host (the pinned twin has the same layout) and copied.
+struct CallArrays {
+    uint64_t *in_off, *in_len; uint4 *seg, *seg2; IndexMove* mv;
+    uint64_t* slot_off; uint32_t *row, *nlong; RangePiece* pieces;
+    size_t upload;
+    uint4* order; uint32_t *bad, *flag; uint64_t* piece_off; uint32_t *piece_len, *piece_val;
+};
+CallArrays call_layout(Carver& w, size_t ns, size_t np, size_t nc) {
+    CallArrays A;
+    A.in_off = w.take<uint64_t>(ns); A.in_len = w.take<uint64_t>(ns); A.seg = w.take<uint4>(ns); A.seg2 = w.take<uint4>(ns); A.mv = w.take<IndexMove>(ns);
+    A.slot_off = w.take<uint64_t>(ns); A.row = w.take<uint32_t>(ns + 1); A.nlong = w.take<uint32_t>(ns); A.pieces = w.take<RangePiece>(np);
+    A.upload = w.used;
+    A.order = w.take<uint4>(ns); A.bad = w.take<uint32_t>(ns + 1); A.flag = w.take<uint32_t>(1);
+    A.piece_off = w.take<uint64_t>(nc); A.piece_len = w.take<uint32_t>(nc); A.piece_val = w.take<uint32_t>(nc);
+    return A;
+}
+
+struct Parsed { IndexView v; std::vector<uint64_t> woff; };      // woff[k]: where entry k's window starts in the index
+
+int parse_index(const uint8_t* idx, uint64_t idx_len, Parsed* P, const char* who) {
+    const uint32_t f = index_parse(idx, idx_len, &P->v);
+    if (f != kIdxOk) { set_error("%s: the index is malformed: %s", who, index_fault_name(f)); return ZWZ_E_FORMAT; }
+    P->woff.resize(P->v.count);
+    uint64_t at = P->v.win_off;
+    for (uint32_t k = 0; k < P->v.count; k++) { P->woff[k] = at; at += P->v.entry(k).hist; }
+    return ZWZ_OK;
+}
+
+// Segment k's records at slot j of the call's arrays; `a` = the address in the call's output buffer of the byte hist in front of the
+// segment's first.  False if the segment is beyond the kernel's 32-bit positions.
+bool fill_segment(const Parsed& P, uint32_t k, uint64_t a, size_t j, CallArrays& H, uint32_t* n_moves) {
+    const IndexView& v = P.v;
+    const IndexEntry e = v.entry(k);
+    const uint64_t end_bit = v.seg_end_bit(k), count = v.seg_end_off(k) - e.off;
+    const uint64_t base = (e.bit >> 3) & ~15ull, len = ((end_bit + 7u) >> 3) - base;
+    if (len >= kStreamMaxIn || count + e.hist + 16u > kIdxSegMaxOut) return false;
+    H.in_off[j] = base; H.in_len[j] = len;
+    H.seg[j] = make_uint4((uint32_t)((e.bit >> 3) & 15u) | (uint32_t)(e.bit & 7u) << 4 | (k + 1u == v.count ? 128u : 0u), (uint32_t)j, (uint32_t)count, e.hist);
+    H.seg2[j] = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)(end_bit - base * 8u), 0u);
+    if (e.hist) H.mv[(*n_moves)++] = IndexMove{P.woff[k], a, e.hist, 0u};
+    return true;
+}
+
+// Both layouts of a call: the device arrays D and their pinned twin H (waits for the stream: an earlier call's copies may still read H)
+int reserve_call(zwz_ctx* c, size_t ns, size_t np, size_t nc, CallArrays* D, CallArrays* H) {
+    const size_t bytes = layout_bytes([&](Carver& w) { call_layout(w, ns, np, nc); });
+    if (int rc = c->buf[kBufIndex0].reserve(c, 0, bytes)) return rc;
+    if (int rc = c->buf[kBufIndexHost].reserve(c, 0, bytes)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Carver wd(c->buf[kBufIndex0].p), wh(c->buf[kBufIndexHost].p);
+    *D = call_layout(wd, ns, np, nc); *H = call_layout(wh, ns, np, nc);
+    return ZWZ_OK;
+}
+
+// A verdict that needs no GPU work: the three result words of zwz_inflate_indexed_dev
+int write_verdict(zwz_ctx* c, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_segments, uint32_t status) {
+    HIPCHK(hipMemsetAsync(d_out_len, 0, sizeof(uint64_t), c->stream));
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status), (int)status, 1, c->stream));
+    if (d_segments) HIPCHK(hipMemsetAsync(d_segments, 0, sizeof(uint32_t), c->stream));
+    return ZWZ_OK;
+}
+
+}  // namespace
+
+extern "C" uint64_t zwz_inflate_index_bound(uint64_t decoded_cap, uint32_t span) {
+    if (span == 0) span = kIdxSpanDefault;
+    return index_span_ok(span) ? index_bound(decoded_cap, span) : 0u;
+}
+
+extern "C" int zwz_inflate_streams_index_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, uint32_t n,
+                                             uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len, uint32_t* d_status,
+                                             uint32_t span, uint8_t* d_idx, const uint64_t* d_idx_off, const uint64_t* d_idx_cap, uint64_t* d_idx_len) {
+    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    if (span == 0) span = c->index_span_bytes;
+    if (!index_span_ok(span)) return ZWZ_E_INVALID;
+    if (n && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status || !d_idx || !d_idx_off || !d_idx_cap || !d_idx_len))
+        return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
+    if (n == 0) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = ensure_inf_order(c, n)) return rc;
+    if (int rc = c->buf[kBufStreamRec].reserve(c, n, (size_t)n * sizeof(uint4))) return rc;
+    if (int rc = ensure_crc_tables(c)) return rc;                 // (the index CRC, whatever the wrapper)
+    uint4* rec = c->buf[kBufStreamRec].as<uint4>();
+    const CrcTables* tab = c->buf[kBufCrcTables].as<const CrcTables>();
+    InflateMarkArgs a{{d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, c->buf[kBufInfOrder].as<uint4>(), rec, (uint32_t)wrap,
+                       c->inflate_serial_header}, d_idx, d_idx_off, d_idx_cap, d_idx_len, span};
+    HIPCHK(launch_inflate_mark(a, c->stream));
+    HIPCHK(launch_stream_check(tab, d_out, d_out_off, rec, n, (uint32_t)wrap, d_status, c->cu_count, c->stream));
+    HIPCHK(launch_index_windows(tab, IndexBuild{d_out, d_out_off, d_in_len, d_status, n, (uint32_t)wrap, span, d_idx, d_idx_off, d_idx_len}, c->stream));
+    return ZWZ_OK;
+}
+
+extern "C" int zwz_inflate_indexed_dev(zwz_ctx* c, const uint8_t* d_in, uint64_t in_len, const uint8_t* idx, uint64_t idx_len, const uint8_t* d_idx,
+                                       uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_segments) {
+    if (!c || !d_in || !idx || !d_out || !d_out_len || !d_status) return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    Parsed P;
+    if (int rc = parse_index(idx, idx_len, &P, "zwz_inflate_indexed_dev")) return rc;
+    // d_out may start at any byte: the waves' positions count from `al`, the 16-byte boundary at or in front of it, and the checksum's
+    // first piece is the bytes up to the next one
+    const uint32_t shift = (uint32_t)((uintptr_t)d_out & 15u);
+    uint8_t* al = d_out - shift;
+    const IndexView& v = P.v;
+    if (out_cap < v.decoded_len) return write_verdict(c, d_out_len, d_status, d_segments, kInfOverflow);
+    if (in_len != v.stream_len) return write_verdict(c, d_out_len, d_status, d_segments, kStrIndex);
+    const uint32_t ns = v.count;
+    const uint32_t head = (uint32_t)std::min<uint64_t>(v.decoded_len, (16u - shift) & 15u);
+    const uint64_t nc = v.wrap == kWrapRaw ? 0u : 1u + (v.decoded_len - head + kPieceBytes - 1) / kPieceBytes;
+    if (nc > 0xffffffffull) return write_verdict(c, d_out_len, d_status, d_segments, kStrTooLarge);
+    CallArrays D, H;
+    if (int rc = reserve_call(c, ns, 0, (size_t)nc, &D, &H)) return rc;
+    uint32_t n_moves = 0;
+    for (uint32_t k = 0; k < ns; k++) {
+        const IndexEntry e = v.entry(k);
+        if (!fill_segment(P, k, shift + e.off - e.hist, k, H, &n_moves)) return write_verdict(c, d_out_len, d_status, d_segments, kStrTooLarge);
+        H.seg[k].y = 0;                                       // (one stream: one verdict word)
+    }
+    hipStream_t st = c->stream;
+    if (!d_idx) {
+        if (int rc = c->buf[kBufIndex1].reserve(c, 0, (size_t)idx_len + 16)) return rc;
+        HIPCHK(hipMemcpyAsync(c->buf[kBufIndex1].p, idx, (size_t)idx_len, hipMemcpyHostToDevice, st));
+        d_idx = c->buf[kBufIndex1].as<const uint8_t>();
+    }
+    if (v.wrap == kWrapGzip) if (int rc = ensure_crc_tables(c)) return rc;
+    HIPCHK(hipMemcpyAsync(D.in_off, H.in_off, H.upload, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(D.bad, 0, (size_t)(reinterpret_cast<uint8_t*>(D.flag) - reinterpret_cast<uint8_t*>(D.bad)) + 256, st));      // bad and, behind it, flag
+    HIPCHK(launch_index_place(d_idx, al, D.mv, n_moves, st));
+    HIPCHK(launch_inflate_indexed(InflateIndexedArgs{d_in, D.in_off, D.in_len, ns, al, D.order, D.seg, D.seg2, D.bad, c->inflate_serial_header}, st));
+    HIPCHK(launch_index_compare(d_idx, al, D.mv, n_moves, D.flag, st));
+    IndexFinish f{d_in, in_len, (v.end_bit + 7u) >> 3, d_out, v.decoded_len, head, v.wrap, v.check, ns, D.piece_off, D.piece_len, D.piece_val, (uint32_t)nc,
+                  D.bad, D.flag, d_out_len, d_status, d_segments};
+    HIPCHK(launch_index_finish(c->buf[kBufCrcTables].as<const CrcTables>(), f, c->cu_count, st));
+    return ZWZ_OK;
+}
+
+namespace {
+
+int plan_ranges(const IndexView& v, const uint64_t* ranges, uint32_t k, IndexPlan* plan, const char* who) {
+    const int64_t bad_range = index_plan(v, ranges, k, plan);
+    if (bad_range >= 0) {
+        set_error("%s: range %lld (offset %llu, length %llu) lies past the decoded length %llu", who, (long long)bad_range,
+                  (unsigned long long)ranges[2 * bad_range], (unsigned long long)ranges[2 * bad_range + 1], (unsigned long long)v.decoded_len);
+        return ZWZ_E_INVALID;
+    }
+    return ZWZ_OK;
+}
+
+// The touched segments of a plan decoded into scratch slots, slice by slice, and their pieces dealt to d_out.  remap: where touched
+// segment i's input starts in d_in (a multiple of 16) when d_in holds only what was read of a file; null: d_in is the stream.
+// Returns synchronised.
+int ranges_core(zwz_ctx* c, const Parsed& P, const IndexPlan& plan, const uint8_t* d_in, const std::vector<uint64_t>* remap, const uint8_t* idx,
+                const uint8_t* d_idx, uint8_t* d_out, const char* who) {
+    const IndexView& v = P.v;
+    hipStream_t st = c->stream;
+    const size_t nt = plan.segs.size();
+    for (size_t s0 = 0; s0 < nt;) {
+        // a slice of touched segments whose slots fit the workspace bound
+        size_t s1 = s0;
+        uint64_t bytes = 0;
+        std::vector<uint64_t> slot;
+        while (s1 < nt) {
+            const IndexEntry e = v.entry(plan.segs[s1]);
+            const uint64_t need = round_up((size_t)(e.hist + (v.seg_end_off(plan.segs[s1]) - e.off)), 16) + 16;
+            if (s1 > s0 && bytes + need > kIdxWorkspaceBytes) break;
+            slot.push_back(bytes); bytes += need; s1++;
+        }
+        const size_t ns = s1 - s0, np = plan.row[s1] - plan.row[s0];
+        CallArrays D, H;
+        if (int rc = reserve_call(c, ns, np, 0, &D, &H)) return rc;
+        if (int rc = c->buf[kBufIndex1].reserve(c, 0, (size_t)bytes + 16)) return rc;
+        uint8_t* slots = c->buf[kBufIndex1].as<uint8_t>();
+        uint32_t n_moves = 0;
+        for (size_t j = 0; j < ns; j++) {
+            const uint32_t sk = plan.segs[s0 + j];
+            if (!fill_segment(P, sk, slot[j], j, H, &n_moves)) { set_error("%s: segment %u is beyond the limits of one wave", who, sk); return ZWZ_E_FORMAT; }
+            if (remap) H.in_off[j] = (*remap)[s0 + j];
+            const uint32_t hist = v.entry(sk).hist;
+            H.slot_off[j] = slot[j] + hist;
+            // the row's pieces, the long ones first
+            const uint32_t r0 = plan.row[s0 + j], r1 = plan.row[s0 + j + 1], b = r0 - plan.row[s0];
+            uint32_t at = b, nl = 0;
+            for (int pass = 0; pass < 2; pass++)
+                for (uint32_t p = r0; p < r1; p++) {
+                    const IndexPiece& q = plan.pieces[p];
+                    if ((q.len >= kWavePieceMax) == (pass == 0)) { H.pieces[at++] = RangePiece{q.dst, q.off, q.len}; nl += pass == 0; }
+                }
+            H.row[j] = b; H.nlong[j] = nl;
+        }
+        H.row[ns] = (uint32_t)np;
+        HIPCHK(hipMemcpyAsync(D.in_off, H.in_off, H.upload, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(D.bad, 0, round_up((ns + 1) * sizeof(uint32_t), 256), st));
+        if (d_idx) HIPCHK(launch_index_place(d_idx, slots, D.mv, n_moves, st));
+        else for (uint32_t i = 0; i < n_moves; i++) HIPCHK(hipMemcpyAsync(slots + H.mv[i].dst, idx + H.mv[i].src, H.mv[i].len, hipMemcpyHostToDevice, st));   // the windows this slice needs
+        HIPCHK(launch_inflate_indexed(InflateIndexedArgs{d_in, D.in_off, D.in_len, (uint32_t)ns, slots, D.order, D.seg, D.seg2, D.bad, c->inflate_serial_header}, st));
+        HIPCHK(launch_index_extract(slots, D.slot_off, D.row, D.nlong, D.pieces, (uint32_t)ns, D.bad, d_out, c->cu_count, st));
+        std::vector<uint32_t> bad(ns);
+        HIPCHK(hipMemcpyAsync(bad.data(), D.bad, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t j = 0; j < ns; j++)
+            if (bad[j]) {
+                set_error("%s: segment %u (decoded offset %llu) does not decode as indexed", who, plan.segs[s0 + j], (unsigned long long)v.entry(plan.segs[s0 + j]).off);
+                return ZWZ_E_FORMAT;
+            }
+        s0 = s1;
+    }
+    return ZWZ_OK;
+}
+
+// The compressed bytes of the touched segments of a plan out of a file: one pread per run of consecutive index entries, the runs one
+// after the other in `buf` (each from a multiple of 16, zeros behind the last); remap[i] = where touched segment i's input starts.
+int pread_touched(int fd, const char* src, const IndexView& v, const IndexPlan& plan, std::vector<uint8_t>* buf, std::vector<uint64_t>* remap) {
+    buf->clear(); remap->clear();
+    const size_t nt = plan.segs.size();
+    for (size_t i = 0; i < nt;) {
+        size_t j = i;
+        while (j + 1 < nt && plan.segs[j + 1] == plan.segs[j] + 1u) j++;
+        const uint64_t first = (v.entry(plan.segs[i]).bit >> 3) & ~15ull, last = (v.seg_end_bit(plan.segs[j]) + 7u) >> 3;
+        const size_t at = buf->size();
+        buf->resize(at + round_up((size_t)(last - first), 16) + 16, 0);
+        for (uint64_t got = 0; got < last - first;) {
+            const ssize_t r = pread(fd, buf->data() + at + got, (size_t)(last - first - got), (off_t)(first + got));
+            if (r <= 0) { set_error("read error on %s at offset %llu", src, (unsigned long long)(first + got)); return ZWZ_E_IO; }
+            got += (uint64_t)r;
+        }
+        for (size_t t = i; t <= j; t++) remap->push_back(at + (((v.entry(plan.segs[t]).bit >> 3) & ~15ull) - first));
+        i = j + 1;
+    }
+    return ZWZ_OK;
+}
+
+int read_whole_file(const char* path, std::vector<uint8_t>* out, size_t slack) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { set_error("cannot open %s", path); return ZWZ_E_IO; }
+    fseeko(f, 0, SEEK_END);
+    const off_t n = ftello(f);
+    fseeko(f, 0, SEEK_SET);
+    out->assign((size_t)n + slack, 0);
+    bool err = false;
+    const size_t got = read_full(f, out->data(), (size_t)n, &err);
+    fclose(f);
+    if (err || got != (size_t)n) { set_error("read error on %s", path); return ZWZ_E_IO; }
+    out->resize((size_t)n + slack);
+    return ZWZ_OK;
+}
+
+struct DevMem {          // device memory of one file call
+    void* p = nullptr;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    int get(size_t n) { if (p) { (void)hipFree(p); p = nullptr; } HIPCHK(hipMalloc(&p, n ? n : 16)); return ZWZ_OK; }
+    template <class T = uint8_t> T* as() const { return static_cast<T*>(p); }
+};
+
+}  // namespace
+
+extern "C" int zwz_inflate_read_ranges_dev(zwz_ctx* c, const uint8_t* d_in, uint64_t in_len, const uint8_t* idx, uint64_t idx_len, const uint8_t* d_idx,
+                                           const uint64_t* ranges, uint32_t k, uint8_t* d_out) {
+    if (!c || !d_in || !idx || (k && (!ranges || !d_out))) return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    Parsed P;
+    if (int rc = parse_index(idx, idx_len, &P, "zwz_inflate_read_ranges_dev")) return rc;
+    if (in_len != P.v.stream_len) { set_error("zwz_inflate_read_ranges_dev: the stream has %llu bytes, the index was made for %llu", (unsigned long long)in_len, (unsigned long long)P.v.stream_len); return ZWZ_E_FORMAT; }
+    IndexPlan plan;
+    if (int rc = plan_ranges(P.v, ranges, k, &plan, "zwz_inflate_read_ranges_dev")) return rc;
+    return ranges_core(c, P, plan, d_in, nullptr, idx, d_idx, d_out, "zwz_inflate_read_ranges_dev");
+}
+
+extern "C" int zwz_inflate_index_info(const uint8_t* idx, uint64_t idx_len, int* wrap, uint64_t* stream_len, uint64_t* decoded_len, uint32_t* count) {
+    if (!idx) return ZWZ_E_INVALID;
+    IndexView v;
+    const uint32_t f = index_parse(idx, idx_len, &v);
+    if (f != kIdxOk) { set_error("zwz_inflate_index_info: the index is malformed: %s", index_fault_name(f)); return ZWZ_E_FORMAT; }
+    if (wrap) *wrap = (int)v.wrap;
+    if (stream_len) *stream_len = v.stream_len;
+    if (decoded_len) *decoded_len = v.decoded_len;
+    if (count) *count = v.count;
+    return ZWZ_OK;
+}
+
+// The file goes through zwz_inflate_streams_index_dev whole: its limit of 2^29 compressed bytes is the call's.
+extern "C" int zwz_inflate_index_file(zwz_ctx* c, int wrap, const char* src, const char* dst_idx) {
+    if (!c || !src || !dst_idx || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<uint8_t> in;
+    if (int rc = read_whole_file(src, &in, 32)) return rc;
+    const uint64_t n = in.size() - 32;
+    if (n >= kStreamMaxIn) { set_error("zwz_inflate_index_file: %s has %llu bytes: an index is built by one wave, which reads fewer than 2^29 (stream status %u)", src, (unsigned long long)n, (unsigned)kStrTooLarge); return ZWZ_E_FORMAT; }
+    DevMem d_in, d_out, d_idx, d_par;
+    if (int rc = d_in.get(round_up((size_t)n + 16, 16))) return rc;
+    if (int rc = d_par.get(64)) return rc;
+    HIPCHK(hipMemcpy(d_in.p, in.data(), round_up((size_t)n + 16, 16), hipMemcpyHostToDevice));
+    const uint32_t span = c->index_span_bytes;
+    uint64_t cap = std::max<uint64_t>(8 * n, 1u << 20), h_par[8];
+    for (;;) {
+        cap = std::min<uint64_t>(cap, kStreamMaxOut - 16);
+        const uint64_t bound = index_bound(cap, span);
+        if (int rc = d_out.get((size_t)cap + 16)) return rc;
+        if (int rc = d_idx.get((size_t)bound)) return rc;
+        const uint64_t par[8] = {0, n, 0, cap, 0, bound, 0, 0};      // in_off, in_len, out_off, out_cap, idx_off, idx_cap, out_len, idx_len
+        HIPCHK(hipMemcpy(d_par.p, par, sizeof par, hipMemcpyHostToDevice));
+        uint64_t* q = d_par.as<uint64_t>();
+        DevMem st_mem;
+        if (int rc = st_mem.get(16)) return rc;
+        if (int rc = zwz_inflate_streams_index_dev(c, wrap, d_in.as<uint8_t>(), q, q + 1, 1, d_out.as<uint8_t>(), q + 2, q + 3, q + 6, st_mem.as<uint32_t>(), span,
+                                                   d_idx.as<uint8_t>(), q + 4, q + 5, q + 7)) return rc;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        uint32_t status = 0;
+        HIPCHK(hipMemcpy(h_par, d_par.p, sizeof h_par, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&status, st_mem.p, 4, hipMemcpyDeviceToHost));
+        if (status == kInfOverflow && cap < kStreamMaxOut - 16) { cap *= 2; continue; }
+        if (status == kStrChecksum || status == kStrLength) { set_error("zwz_inflate_index_file: %s: %s mismatch", src, status == kStrLength ? "length" : "checksum"); return ZWZ_E_CHECKSUM; }
+        if (status != kInfEnd) { set_error("zwz_inflate_index_file: %s: stream status %u after %llu decoded bytes", src, status, (unsigned long long)h_par[6]); return ZWZ_E_FORMAT; }
+        break;
+    }
+    if (h_par[7] == 0) { set_error("zwz_inflate_index_file: %s decodes, but no index is made for a gzip file of several members", src); return ZWZ_E_FORMAT; }
+    std::vector<uint8_t> idx((size_t)h_par[7]);
+    HIPCHK(hipMemcpy(idx.data(), d_idx.p, idx.size(), hipMemcpyDeviceToHost));
+    const std::string part = std::string(dst_idx) + ".part";
+    FILE* f = fopen(part.c_str(), "wb");
+    if (!f) { set_error("cannot create %s", part.c_str()); return ZWZ_E_IO; }
+    const bool ok = fwrite(idx.data(), 1, idx.size(), f) == idx.size();
+    if (fclose(f) != 0 || !ok || rename(part.c_str(), dst_idx) != 0) { unlink(part.c_str()); set_error("cannot write %s", dst_idx); return ZWZ_E_IO; }
+    return ZWZ_OK;
+}
+
+namespace {
+
+struct SrcFile {         // the compressed file of a range call, by descriptor
+    int fd = -1;
+    ~SrcFile() { if (fd >= 0) close(fd); }
+    int open_checked(const char* src, uint64_t want_len, const char* who) {
+        fd = open(src, O_RDONLY);
+        if (fd < 0) { set_error("cannot open %s", src); return ZWZ_E_IO; }
+        const off_t n = lseek(fd, 0, SEEK_END);
+        if ((uint64_t)n != want_len) { set_error("%s: %s has %llu bytes, the index was made for %llu", who, src, (unsigned long long)n, (unsigned long long)want_len); return ZWZ_E_FORMAT; }
+        return ZWZ_OK;
+    }
+};
+
+// The touched segments of `plan` out of the file and through ranges_core into d_out
+int ranges_from_file(zwz_ctx* c, const SrcFile& f, const char* src, const Parsed& P, const IndexPlan& plan, const uint8_t* idx, DevMem& d_in, uint8_t* d_out,
+                     const char* who) {
+    std::vector<uint8_t> buf;
+    std::vector<uint64_t> remap;
+    if (int rc = pread_touched(f.fd, src, P.v, plan, &buf, &remap)) return rc;
+    if (int rc = d_in.get(buf.size() + 16)) return rc;
+    if (!buf.empty()) HIPCHK(hipMemcpy(d_in.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+    return ranges_core(c, P, plan, d_in.as<uint8_t>(), &remap, idx, nullptr, d_out, who);
+}
+
+}  // namespace
+
+extern "C" int zwz_inflate_read_ranges_file(zwz_ctx* c, const char* src, const char* idx_path, const uint64_t* ranges, uint32_t k, uint8_t* out) {
+    if (!c || !src || !idx_path || (k && (!ranges || !out))) return ZWZ_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<uint8_t> idx;
+    if (int rc = read_whole_file(idx_path, &idx, 0)) return rc;
+    Parsed P;
+    if (int rc = parse_index(idx.data(), idx.size(), &P, "zwz_inflate_read_ranges_file")) return rc;
+    IndexPlan plan;
+    if (int rc = plan_ranges(P.v, ranges, k, &plan, "zwz_inflate_read_ranges_file")) return rc;
+    SrcFile f;
+    if (int rc = f.open_checked(src, P.v.stream_len, "zwz_inflate_read_ranges_file")) return rc;
+    DevMem d_in, d_out;
+    if (int rc = d_out.get((size_t)plan.total + 16)) return rc;
+    if (int rc = ranges_from_file(c, f, src, P, plan, idx.data(), d_in, d_out.as<uint8_t>(), "zwz_inflate_read_ranges_file")) return rc;
+    if (plan.total) HIPCHK(hipMemcpy(out, d_out.p, (size_t)plan.total, hipMemcpyDeviceToHost));
+    return ZWZ_OK;
+}
+
+// Slices of consecutive index entries: each slice's compressed bytes are read (pread), its segments decoded a wave each, its bytes
+// written by the writer thread while the next slice runs; the checksum is joined from the slices' pieces and checked against the index's
+// and the file's own trailer at the end.
+extern "C" int zwz_inflate_stream_file_indexed(zwz_ctx* c, const char* src, const char* idx_path, const char* dst) {
+    if (!c || !src || !idx_path || !dst) return ZWZ_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    const char* who = "zwz_inflate_stream_file_indexed";
+    std::vector<uint8_t> idx;
+    if (int rc = read_whole_file(idx_path, &idx, 0)) return rc;
+    Parsed P;
+    if (int rc = parse_index(idx.data(), idx.size(), &P, who)) return rc;
+    const IndexView& v = P.v;
+    SrcFile f;
+    if (int rc = f.open_checked(src, v.stream_len, who)) return rc;
+    FileJob job;
+    if (int rc = job.open(src, dst)) return rc;
+    // a slice: entries whose decoded bytes fit the output staging (one entry at least)
+    uint64_t O = std::min<uint64_t>(std::max<uint64_t>(4ull * c->split_slice_bytes, 65536), std::max<uint64_t>(v.decoded_len, 16));
+    for (uint32_t k = 0; k < v.count; k++) O = std::max<uint64_t>(O, v.seg_end_off(k) - v.entry(k).off);
+    const size_t np = (size_t)(O / kPieceBytes + 2);
+    if (int rc = job.alloc({0, 0, (size_t)O, (size_t)O, 0}, {0, (size_t)O + 16, 0})) return rc;
+    DevMem d_in, d_pieces;
+    if (int rc = d_pieces.get(np * 16 + 768)) return rc;
+    uint64_t* p_off = d_pieces.as<uint64_t>();
+    uint32_t* p_len = reinterpret_cast<uint32_t*>(d_pieces.as<uint8_t>() + round_up(np * 8, 256));
+    uint32_t* p_val = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(p_len) + round_up(np * 4, 256));
+    if (v.wrap == kWrapGzip) if (int rc = ensure_crc_tables(c)) return rc;
+    std::vector<uint32_t> h_len(np), h_val(np);
+    uint32_t check = dstream_check_init(v.wrap);
+    int b = 0;
+    for (uint32_t k0 = 0; k0 < v.count;) {
+        uint32_t k1 = k0 + 1;
+        while (k1 < v.count && v.seg_end_off(k1) - v.entry(k0).off <= O) k1++;
+        const uint64_t r[2] = {v.entry(k0).off, v.seg_end_off(k1 - 1) - v.entry(k0).off};
+        k0 = k1;
+        if (!r[1]) continue;
+        IndexPlan plan;
+        if (int rc = plan_ranges(v, r, 1, &plan, who)) return rc;
+        if (int rc = ranges_from_file(c, f, src, P, plan, idx.data(), d_in, job.dp(1), who)) { job.join(); return rc; }
+        const uint32_t pieces = v.wrap == kWrapRaw ? 0u : (uint32_t)((r[1] + kPieceBytes - 1) / kPieceBytes);
+        IndexFinish fin{};
+        fin.out = job.dp(1); fin.total = r[1]; fin.wrap = v.wrap; fin.piece_off = p_off; fin.piece_len = p_len; fin.piece_val = p_val;
+        fin.pieces = pieces;
+        fin.head = (uint32_t)std::min<uint64_t>(kPieceBytes, r[1]);        // (an aligned buffer: the first piece is a whole one)
+        HIPJOB(launch_index_piece_sums(c->buf[kBufCrcTables].as<const CrcTables>(), fin, c->cu_count, c->stream));
+        if (int rc = job.finish_write()) return rc;                      // (two writes back: this buffer is free)
+        uint8_t* hout = job.hp(2 + b);
+        HIPJOB(hipMemcpyAsync(hout, job.d[1], (size_t)r[1], hipMemcpyDeviceToHost, c->stream));
+        if (pieces) {
+            HIPJOB(hipMemcpyAsync(h_len.data(), p_len, pieces * 4u, hipMemcpyDeviceToHost, c->stream));
+            HIPJOB(hipMemcpyAsync(h_val.data(), p_val, pieces * 4u, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPJOB(hipStreamSynchronize(c->stream));
+        for (uint32_t j = 0; j < pieces; j++)
+            check = v.wrap == kWrapZlib ? AdlerSum::join(check, h_val[j], AdlerSum::pof(h_len[j])) : CrcSum::join(check, h_val[j], CrcSum::pof(h_len[j]));
+        job.start_write(hout, (size_t)r[1]);
+        b ^= 1;
+    }
+    if (int rc = job.finish_write()) return rc;
+    if (v.wrap != kWrapRaw) {
+        uint8_t tr[8] = {};
+        const size_t want = v.wrap == kWrapZlib ? 4 : 8;
+        if (pread(f.fd, tr, want, (off_t)((v.end_bit + 7u) >> 3)) != (ssize_t)want) { set_error("%s: %s ends inside its trailer", who, src); return ZWZ_E_FORMAT; }
+        const uint32_t stored = v.wrap == kWrapZlib ? be32_at(tr) : le32_at(tr);
+        if (stored != check || v.check != check) { set_error("%s: %s: checksum mismatch", who, src); return ZWZ_E_CHECKSUM; }
+        if (v.wrap == kWrapGzip && le32_at(tr + 4) != (uint32_t)v.decoded_len) { set_error("%s: %s: length mismatch", who, src); return ZWZ_E_CHECKSUM; }
+    }
+    return job.commit(dst);
+}
+

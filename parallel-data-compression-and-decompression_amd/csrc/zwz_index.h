@@ -1,0 +1,44 @@
+// zwz_index.h -- launcher interface of zwz_index.hip: the kernels around inflate_kernel's marking and indexed-segment forms
+// (index_core.h has the layout and the method; the two forms themselves are in zwz_kernels.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "index_core.h"
+#include "zwz_bgzf.h"
+
+namespace zwz {
+
+// After the marking decode and its checksum: per stream, the windows out of the decoded output into the index, the header, the
+// index CRC; idx_len[i] = 0 where the stream's status is not 0.
+struct IndexBuild {
+    const uint8_t* out; const uint64_t* out_off; const uint64_t* in_len; const uint32_t* status; uint32_t n, wrap, span;
+    uint8_t* idx; const uint64_t* idx_off; uint64_t* idx_len;
+};
+hipError_t launch_index_windows(const CrcTables* tab, const IndexBuild& b, hipStream_t s);
+
+// One window to place: `len` bytes at `src` of the index go to `dst` of the output (or of the scratch slots)
+struct IndexMove { uint64_t src, dst; uint32_t len, pad; };
+hipError_t launch_index_place(const uint8_t* idx, uint8_t* out, const IndexMove* mv, uint32_t m, hipStream_t s);
+// flag |= 1 where a window differs from the bytes that now stand at its place
+hipError_t launch_index_compare(const uint8_t* idx, const uint8_t* out, const IndexMove* mv, uint32_t m, uint32_t* flag, hipStream_t s);
+
+// The checksum of out[0, total) from pieces -- the first `head` bytes, up to a 16-byte boundary, then kPieceBytes each -- and the verdict of a whole-stream decode: bad[0] -> kStrIndex; a window
+// that was not the stream's bytes (flag), a checksum other than the index's or other than the stream's own trailer at byte `trailer`
+// of in[0, in_len) -> kStrChecksum; else 0.  Writes out_len, status and segments.
+struct IndexFinish {
+    const uint8_t* in; uint64_t in_len, trailer; const uint8_t* out; uint64_t total; uint32_t head, wrap, expect, nseg;
+    uint64_t* piece_off; uint32_t* piece_len; uint32_t* piece_val; uint32_t pieces;
+    const uint32_t* bad; const uint32_t* flag;
+    uint64_t* out_len; uint32_t* status; uint32_t* segments;
+};
+hipError_t launch_index_finish(const CrcTables* tab, const IndexFinish& f, uint32_t cu_count, hipStream_t s);
+// the first half alone (the file call joins the slices' pieces on the host): piece_off, piece_len and piece_val of out[0, total)
+hipError_t launch_index_piece_sums(const CrcTables* tab, const IndexFinish& f, uint32_t cu_count, hipStream_t s);
+
+// Range reads: touched segment i's decoded bytes start at slots + slot_off[i]; its pieces row[i] .. row[i + 1], the first nlong[i] of
+// them long, go to out (bgzf_verify_extract's dealing).  Pieces of a segment whose bad[i] is set are not copied.
+hipError_t launch_index_extract(const uint8_t* slots, const uint64_t* slot_off, const uint32_t* row, const uint32_t* nlong, const RangePiece* pieces,
+                                uint32_t m, const uint32_t* bad, uint8_t* out, uint32_t cu_count, hipStream_t s);
+
+}  // namespace zwz

@@ -1,0 +1,191 @@
+// zwz_index.hip -- the device half of the seek index around inflate_kernel's marking and indexed-segment forms (index_core.h has the
+// layout and the method): the windows out of a decoded stream into its index with the header and the index CRC (windows), the windows
+// of a call to where its segment waves expect them (place), whether they were the stream's bytes (compare), the checksum of a
+// whole-stream decode from fixed pieces joined with dstream_core.h's sums and its verdict (finish), and the pieces of a batch of
+// ranges out of the decoded segments (extract).
+#include "../../include/zwz.h"
+#include "adler_wg.h"
+#include "copy_wg.h"
+#include "crc_wg.h"
+#include "dstream_core.h"
+#include "zwz_device.h"
+#include "zwz_index.h"
+
+namespace zwz {
+
+namespace {
+
+__device__ __forceinline__ uint64_t ld64(const uint8_t* p) { return *reinterpret_cast<const uint64_t*>(p); }      // (8-byte aligned fields)
+__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); }
+
+// One workgroup per stream.  The marking form has left the entries, and in the header the decoded length, the count, the end bit and
+// the stored checksum; idx_len[i] is the index's padded length, 0 if none can be made.
+__global__ void __launch_bounds__(kBgzfThreads) index_windows_kernel(const CrcTables* tab, IndexBuild b) {
+    __shared__ CrcLds s;
+    crc_load_tables(s, tab);
+    const uint32_t t = threadIdx.x;
+    for (uint32_t i = blockIdx.x; i < b.n; i += gridDim.x) {
+        const uint64_t len = b.idx_len[i];
+        if (len == 0 || len > 0xffffffffull || b.status[i] != 0u) {          // (workgroup-uniform)
+            if (t == 0) b.idx_len[i] = 0;
+            continue;
+        }
+        uint8_t* p = b.idx + b.idx_off[i];
+        const uint32_t count = ld32(p + 32);
+        const uint8_t* ent = p + kIdxHeader;
+        uint8_t* win = p + kIdxHeader + (size_t)count * kIdxEntry;
+        const uint8_t* src = b.out + b.out_off[i];
+        uint64_t at = 0;
+        for (uint32_t k = 0; k < count; k++) {
+            const uint64_t off = ld64(ent + (size_t)k * kIdxEntry + 8);
+            const uint32_t h = ld32(ent + (size_t)k * kIdxEntry + 16);
+            wg_copy(win + at, src + off - h, h);
+            at += h;
+        }
+        for (uint64_t z = kIdxHeader + (uint64_t)count * kIdxEntry + at + t; z < len; z += kBgzfThreads) p[z] = 0;
+        __threadfence();
+        __syncthreads();
+        const uint32_t crc = crc_block_wg(s, p + kIdxHeader, (uint32_t)(len - kIdxHeader));
+        if (t == 0) {
+            uint32_t* h = reinterpret_cast<uint32_t*>(p);
+            h[0] = 0x495a575au; h[1] = 0x01005844u;                           // "ZWZIDX\0\1"
+            h[2] = b.wrap; h[3] = b.span;
+            const uint64_t n = b.in_len[i];
+            h[4] = (uint32_t)n; h[5] = (uint32_t)(n >> 32);
+            h[9] = 0; h[13] = crc; h[14] = 0; h[15] = 0;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) index_place_kernel(const uint8_t* idx, uint8_t* out, const IndexMove* mv, uint32_t m) {
+    for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) { const IndexMove q = mv[i]; wg_copy(out + q.dst, idx + q.src, q.len); }
+}
+
+__global__ void __launch_bounds__(256) index_compare_kernel(const uint8_t* idx, const uint8_t* out, const IndexMove* mv, uint32_t m, uint32_t* flag) {
+    for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) {
+        const IndexMove q = mv[i];
+        uint32_t differs = 0;
+        for (uint32_t j = threadIdx.x; j < q.len; j += 256u) differs |= (uint32_t)(out[q.dst + j] != idx[q.src + j]);
+        if (differs) atomicOr(flag, 1u);
+    }
+}
+
+__global__ void __launch_bounds__(256) index_pieces_kernel(IndexFinish f) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= f.pieces) return;
+    const uint64_t at = j ? f.head + (uint64_t)(j - 1u) * kPieceBytes : 0u;
+    f.piece_off[j] = at;
+    f.piece_len[j] = j ? (uint32_t)min<uint64_t>(kPieceBytes, f.total - at) : f.head;
+}
+
+__global__ void __launch_bounds__(kBgzfThreads) index_adler_kernel(IndexFinish f) {
+    __shared__ uint32_t s_part[2 * kBgzfThreads / 64];
+    for (uint32_t j = blockIdx.x; j < f.pieces; j += gridDim.x) {
+        const uint32_t a = adler_range_wg(s_part, f.out + f.piece_off[j], f.piece_len[j]);
+        if (threadIdx.x == 0) f.piece_val[j] = a;
+    }
+}
+
+// One wave: lane l joins its share of consecutive pieces, lane 0 the 64 shares; then the verdict.
+template <class Sum, bool kCheck>
+__global__ void __launch_bounds__(64) index_finish_kernel(IndexFinish f) {
+    const uint32_t lane = lane_id();
+    uint32_t acc = Sum::identity();
+    if (kCheck) {
+        const uint32_t cnt = f.pieces, K = (cnt + 63u) / 64u, p1 = Sum::pof(kPieceBytes);
+        uint32_t x = Sum::identity();
+        uint64_t bytes = 0;
+        for (uint32_t j = lane * K; j < min(cnt, (lane + 1u) * K); j++) {
+            const uint32_t len = f.piece_len[j];
+            x = Sum::join(x, f.piece_val[j], len == kPieceBytes ? p1 : Sum::pof(len));
+            bytes += len;
+        }
+        const uint32_t pl = Sum::pof(bytes);
+        for (uint32_t l = 0; l < 64u; l++) acc = Sum::join(acc, (uint32_t)__shfl((int)x, (int)l, 64), (uint32_t)__shfl((int)pl, (int)l, 64));
+    }
+    if (lane != 0) return;
+    uint32_t st = 0;
+    if (f.bad[0]) st = kStrIndex;
+    else if (f.flag[0]) st = kStrChecksum;
+    else if (kCheck) {
+        // the stream's own trailer: Adler-32 big-endian (zlib); CRC-32 and ISIZE little-endian (gzip)
+        const uint32_t want = f.wrap == kWrapZlib ? 4u : 8u;
+        bool ok = acc == f.expect && f.trailer + want <= f.in_len;
+        if (ok) {
+            const uint8_t* q = f.in + f.trailer;
+            ok = f.wrap == kWrapZlib ? be32_at(q) == acc : le32_at(q) == acc && le32_at(q + 4) == (uint32_t)f.total;
+        }
+        if (!ok) st = kStrChecksum;
+    }
+    f.out_len[0] = f.total;
+    f.status[0] = st;
+    if (f.segments) f.segments[0] = f.nseg;
+}
+
+// bgzf_verify_extract's dealing of the pieces: long ones by the workgroup, short ones a wave each
+__global__ void __launch_bounds__(kBgzfThreads) index_extract_kernel(const uint8_t* slots, const uint64_t* slot_off, const uint32_t* row, const uint32_t* nlong,
+                                                                     const RangePiece* pieces, uint32_t m, const uint32_t* bad, uint8_t* out) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) {
+        if (bad[i]) continue;
+        const uint8_t* slot = slots + slot_off[i];
+        const uint32_t p0 = row[i], pl = p0 + nlong[i], p1 = row[i + 1];
+        for (uint32_t p = p0; p < pl; p++) { const RangePiece q = pieces[p]; wg_copy(out + q.dst, slot + q.off, q.len); }
+        for (uint32_t p = pl + wave; p < p1; p += kBgzfThreads / 64) { const RangePiece q = pieces[p]; lanes_copy(out + q.dst, slot + q.off, q.len, lane, 64); }
+    }
+}
+
+uint32_t grid_for(uint32_t m, uint32_t cu_count, uint32_t per_cu) {
+    const uint32_t g = (cu_count ? cu_count : 256u) * per_cu;
+    return m < g ? m : g;
+}
+
+}  // namespace
+
+hipError_t launch_index_windows(const CrcTables* tab, const IndexBuild& b, hipStream_t s) {
+    if (!b.n) return hipSuccess;
+    index_windows_kernel<<<b.n, kBgzfThreads, 0, s>>>(tab, b);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_place(const uint8_t* idx, uint8_t* out, const IndexMove* mv, uint32_t m, hipStream_t s) {
+    if (!m) return hipSuccess;
+    index_place_kernel<<<m < 65536u ? m : 65536u, 256, 0, s>>>(idx, out, mv, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_compare(const uint8_t* idx, const uint8_t* out, const IndexMove* mv, uint32_t m, uint32_t* flag, hipStream_t s) {
+    if (!m) return hipSuccess;
+    index_compare_kernel<<<m < 65536u ? m : 65536u, 256, 0, s>>>(idx, out, mv, m, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_piece_sums(const CrcTables* tab, const IndexFinish& f, uint32_t cu_count, hipStream_t s) {
+    if (f.wrap == kWrapRaw || !f.pieces) return hipSuccess;
+    index_pieces_kernel<<<(f.pieces + 255u) / 256u, 256, 0, s>>>(f);
+    if (f.wrap == kWrapGzip) return launch_crc32_blocks(tab, f.out, f.piece_off, f.piece_len, f.pieces, f.piece_val, cu_count, s);
+    index_adler_kernel<<<grid_for(f.pieces, cu_count, 8u), kBgzfThreads, 0, s>>>(f);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_finish(const CrcTables* tab, const IndexFinish& f, uint32_t cu_count, hipStream_t s) {
+    if (f.wrap == kWrapRaw) {
+        index_finish_kernel<AdlerSum, false><<<1, 64, 0, s>>>(f);
+        return hipGetLastError();
+    }
+    const hipError_t e = launch_index_piece_sums(tab, f, cu_count, s);
+    if (e != hipSuccess) return e;
+    if (f.wrap == kWrapGzip) index_finish_kernel<CrcSum, true><<<1, 64, 0, s>>>(f);
+    else index_finish_kernel<AdlerSum, true><<<1, 64, 0, s>>>(f);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_extract(const uint8_t* slots, const uint64_t* slot_off, const uint32_t* row, const uint32_t* nlong, const RangePiece* pieces,
+                                uint32_t m, const uint32_t* bad, uint8_t* out, uint32_t cu_count, hipStream_t s) {
+    if (!m) return hipSuccess;
+    index_extract_kernel<<<grid_for(m, cu_count, 4u), kBgzfThreads, 0, s>>>(slots, slot_off, row, nlong, pieces, m, bad, out);
+    return hipGetLastError();
+}
+
+}  // namespace zwz

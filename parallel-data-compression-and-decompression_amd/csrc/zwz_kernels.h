@@ -151,6 +151,11 @@ struct StreamParams {
     const uint4* seg;          // per segment: (p & 15, stream, first output byte within the stream's range, count); measuring: (p & 15, stream, -, p & ~15)
     uint4* meas;               // measuring form: a SegMeasure per segment
     uint32_t* bad;             // segment form: set for a stream one of whose segments did not end as measured
+    // the index forms (index_core.h), appended likewise
+    const uint4* seg2;         // indexed-segment form, per segment: (address in `out` of the byte `hist` in front of the segment's first, low / high; end bit from the wave's input; -)
+    uint8_t* idx; const uint64_t* idx_off; const uint64_t* idx_cap;   // marking form: stream i's index at idx + idx_off[i], idx_cap[i] bytes
+    uint64_t* idx_len;         // marking form: the index's padded length, 0 where none was made
+    uint32_t span;             // marking form: output bytes between checkpoints, at least
 };
 // zwz_inflate_split_streams_dev: one wave per segment.  seg_in_off[i] = the stream's offset + (p & ~15), seg_in_len[i] = the bytes the wave may read from there
 struct InflateSplitArgs {
@@ -166,6 +171,20 @@ struct InflateStreamArgs {
     uint4* order;              // n entries of scratch, as InflateArgs::order (never null here)
     uint4* rec;                // n entries of scratch
     uint32_t wrap, serial_header;
+};
+// zwz_inflate_streams_index_dev: the stream form that also notes checkpoints (kFormMark)
+struct InflateMarkArgs {
+    InflateStreamArgs s;
+    uint8_t* idx; const uint64_t* idx_off; const uint64_t* idx_cap; uint64_t* idx_len; uint32_t span;
+};
+// zwz_inflate_indexed_dev / zwz_inflate_read_ranges_dev: one wave per segment of an index (kFormIndexed).  seg_in_off[i] = the byte of the
+// segment's first bit rounded down to 16, seg_in_len[i] = from there to the byte that holds the bit in front of the end bit
+struct InflateIndexedArgs {
+    const uint8_t* in; const uint64_t* seg_in_off; const uint64_t* seg_in_len; uint32_t n;
+    uint8_t* out;
+    uint4* order;              // n entries of scratch
+    const uint4* seg; const uint4* seg2; uint32_t* bad;
+    uint32_t serial_header;
 };
 // match_mode: auto = lz_dense_list decides per chunk between links + lz_match (+ lz_parse) and sort + lz_lazy; walk / band / lazy = every chunk through
 // that search; autoband / autolazy = the per-chunk choice with the band + lz_parse / lz_lazy for the chain-heavy ones.  Same bytes whichever runs.
@@ -207,6 +226,8 @@ hipError_t launch_strategy_parse(const DeflateArgs& a, hipStream_t s);          
 hipError_t launch_inflate(const InflateArgs& a, hipStream_t s);
 hipError_t launch_inflate_streams(const InflateStreamArgs& a, hipStream_t s);      // order + inflate_kernel's stream form (statuses provisional)
 hipError_t launch_inflate_split(const InflateSplitArgs& a, hipStream_t s);         // order + inflate_kernel's measuring or segment form
+hipError_t launch_inflate_mark(const InflateMarkArgs& a, hipStream_t s);           // order + inflate_kernel's marking form (statuses provisional)
+hipError_t launch_inflate_indexed(const InflateIndexedArgs& a, hipStream_t s);     // order + inflate_kernel's indexed-segment form
 struct CrcTables;                                                                  // zwz_bgzf.h
 // zwz_stream.hip: the checksum of every stream's checked output (rec) and its final status
 hipError_t launch_stream_check(const CrcTables* tab, const uint8_t* out, const uint64_t* out_off, const uint4* rec, uint32_t n,

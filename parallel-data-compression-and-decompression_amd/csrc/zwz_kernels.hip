@@ -32,6 +32,7 @@
 #include "inflate_core.h"
 #include "stream_core.h"
 #include "split_core.h"
+#include "index_core.h"
 #include "lz_core.h"
 #include "zwz_md5.h"
 #include "zwz_kernels.h"
@@ -2039,6 +2040,11 @@ struct InflateWaveMem {
 // is counted, never written (no stored copy, no owner map, no byte copy), and sp.meas[i] says how the segment ended.  2, the segment
 // form: output goes to its place in the stream's range, which starts at any byte address -- dst is that address rounded down to 16, its
 // low four bits are the first position and the origin -- and is bounded by the measured count.  0 compiles as before the parameter.
+// kFormMark (3; zwz_inflate_streams_index_dev, index_core.h): the stream form, which also notes a checkpoint -- the header's first bit and
+// the output position -- into the stream's index at every block header that lies at least sp.span output bytes behind the last one, the end
+// bit of the first member and whether a second one followed.  kFormIndexed (4): the segment form for a segment of an index: it starts at
+// any BIT, its origin lies `hist` bytes in front of its first output byte (those bytes are in memory already: index_place_kernel), and
+// it ends at the block header whose first bit is the segment's end bit, or behind the final block.  1, 2 and 0 compile as before these two.
 template <bool kSerialHeader, bool kStream, uint32_t kSplit = 0>
 __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                   const uint32_t* __restrict__ in_len, uint32_t n,
@@ -2059,17 +2065,31 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     uint8_t* dst;
     uint32_t cap = kChunk;                             // output bound
     uint32_t seg_body = 0, seg_start = 0, seg_base = 0, seg_stream = 0, seg_fin = kSegBad;   // kSplit
-    if constexpr (kSplit != 0) {
+    constexpr bool kSeg = kSplit == 1 || kSplit == 2 || kSplit == kFormIndexed;              // the wave's unit is a segment
+    constexpr bool kMark = kSplit == kFormMark;
+    uint32_t seg_bit = 0, seg_origin = 0, seg_end = 0, seg_last = 0;                         // kFormIndexed
+    if constexpr (kSeg) {
         static_assert(kStream, "the split forms are stream forms");
         const uint4 sgv = sp.seg[chunk];               // (p & 15, stream, first output byte in the stream's range | -, count | p & ~15)
         const uint4 sg = make_uint4(__builtin_amdgcn_readfirstlane(sgv.x), __builtin_amdgcn_readfirstlane(sgv.y), __builtin_amdgcn_readfirstlane(sgv.z), __builtin_amdgcn_readfirstlane(sgv.w));   // (wave-uniform: scalar registers)
         seg_body = sg.x; seg_stream = sg.y;
         if constexpr (kSplit == 1) { dst = nullptr; cap = kSplitMeasureCap; seg_base = sg.w; }
-        else { dst = out + sp.out_off[seg_stream] + (sg.z & ~15u); seg_start = sg.z & 15u; cap = seg_start + sg.w; }
+        else if constexpr (kSplit == 2) { dst = out + sp.out_off[seg_stream] + (sg.z & ~15u); seg_start = sg.z & 15u; cap = seg_start + sg.w; }
+        else {
+            // indexed: (p & 15 | bit << 4 | last segment << 7, stream, count, hist) and (address in `out` of the byte hist in front of the
+            // segment's first, 64 bits; the end bit counted from the wave's input; -)
+            const uint4 s2v = sp.seg2[chunk];
+            const uint32_t a_lo = __builtin_amdgcn_readfirstlane(s2v.x), a_hi = __builtin_amdgcn_readfirstlane(s2v.y);
+            seg_end = __builtin_amdgcn_readfirstlane(s2v.z);
+            seg_body = sg.x & 15u; seg_bit = (sg.x >> 4) & 7u; seg_last = (sg.x >> 7) & 1u;
+            dst = out + (((uint64_t)a_hi << 32 | a_lo) & ~15ull);
+            seg_origin = a_lo & 15u; seg_start = seg_origin + sg.w; cap = seg_start + sg.z;
+        }
     } else if constexpr (kStream) {
         const uint64_t cap64 = sp.out_cap[chunk];
         if (oe.z >= kStreamMaxIn || cap64 >= kStreamMaxOut) {     // (the order clips a 64-bit length to 32 bits)
             if (lane == 0) { sp.out_len[chunk] = 0; status[chunk] = kStrTooLarge; sp.rec[chunk] = make_uint4(0, 0, 0, kStrTooLarge); }
+            if constexpr (kMark) if (lane == 0) sp.idx_len[chunk] = 0;
             return;
         }
         dst = out + sp.out_off[chunk];
@@ -2105,6 +2125,14 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     uint32_t origin = 0;                               // kStream: the current gzip member's first output byte
     StreamRecord rec{0, 0, 0, kInfRunning};
     if constexpr (kSplit == 2) origin = seg_start;
+    if constexpr (kSplit == kFormIndexed) origin = seg_origin;
+    // kFormMark, lane 0: the stream's index (entries from byte kIdxHeader on), its capacity, the bytes the index takes so far, checkpoints
+    // noted, the output position of the last one; whether no index can be made (capacity), whether the first member's end bit is known
+    // and what it is, whether a second member followed
+    uint8_t* mk_idx = nullptr;
+    uint64_t mk_cap = 0, mk_bytes = kIdxHeader;
+    uint32_t mk_count = 0, mk_last = 0, mk_full = 0, mk_have_end = 0, mk_end = 0, mk_second = 0;
+    if constexpr (kMark) { mk_idx = sp.idx + sp.idx_off[chunk]; mk_cap = sp.idx_cap[chunk]; }
     // kStream: the first byte at or after q that is not zero, or nin (the zeros around gzip members), the wave 1 KiB a step
     auto skip_zeros = [&](uint32_t q) -> uint32_t {
         q = __builtin_amdgcn_readfirstlane(q);
@@ -2126,8 +2154,11 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         }
         return nin;
     };
-    if constexpr (kSplit != 0) {
-        if (lane == 0) { st.br.init(m.ring, nin, kInfRing - 1u); st.out_pos = seg_start; st.last = 0; st.status = kInfRunning; st.br.seek_bit(seg_body * 8u); }
+    if constexpr (kSeg) {
+        if (lane == 0) {
+            st.br.init(m.ring, nin, kInfRing - 1u); st.out_pos = seg_start; st.last = 0; st.status = kInfRunning;
+            if constexpr (kSplit == kFormIndexed) st.br.seek_bit(seg_body * 8u + seg_bit); else st.br.seek_bit(seg_body * 8u);
+        }
         go = 1;                                        // (seg_body < 16: top_up(0) has the bytes)
     } else if constexpr (kStream) {
         const uint32_t nz = sp.wrap == kWrapGzip ? skip_zeros(0) : nin;
@@ -2152,6 +2183,23 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         // from the header's first bit: the reader's byte position runs up to 8 bytes ahead of it, and a ring filled for that position can
         // have let the bytes of a header that starts just before a 1 KiB boundary go (the wave reads the header and the block from the ring)
         top_up(st.br.bit_pos() >> 3);
+        if constexpr (kSplit == kFormIndexed) {        // the segment ends in front of the header at its end bit (one stepped over: the verdict below)
+            uint32_t at_end = 0;
+            if (lane == 0) at_end = st.br.bit_pos() >= seg_end;
+            if (__builtin_amdgcn_readfirstlane(at_end)) break;
+        }
+        if constexpr (kMark) {
+            if (lane == 0 && !mk_full && !mk_second && index_mark_due(mk_count, st.out_pos, mk_last, sp.span)) {
+                const uint32_t hist = index_hist_bound(st.out_pos);
+                const uint64_t need = mk_bytes + kIdxEntry + hist;
+                if (need + 15u > mk_cap) mk_full = 1;      // the index would not fit: none is made, the decode goes on
+                else {
+                    uint32_t* e = reinterpret_cast<uint32_t*>(mk_idx + kIdxHeader + (size_t)mk_count * kIdxEntry);
+                    e[0] = st.br.bit_pos(); e[1] = 0; e[2] = st.out_pos; e[3] = 0; e[4] = hist; e[5] = 0;
+                    mk_count++; mk_last = st.out_pos; mk_bytes = need;
+                }
+            }
+        }
         {   // the block header: lane 0 reads the bits, the wave builds the tables (inflate_core.h: inflate_block_rest, in its pieces)
             uint32_t v = 0, ok = 0;
             if (lane == 0) { opos = st.out_pos; ok = inflate_block_type(st, v) ? 1u : 0u; }
@@ -2533,7 +2581,11 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
             }
             if (__builtin_amdgcn_readfirstlane(halt)) break;
         }
-        if constexpr (kSplit != 0) {
+        if constexpr (kSplit == kFormIndexed) {
+            uint32_t fin = 0;
+            if (lane == 0) fin = st.last;              // behind a final block nothing follows: whether that is where the index says, below
+            if (__builtin_amdgcn_readfirstlane(fin)) break;
+        } else if constexpr (kSeg) {
             uint32_t fin = kSegBad;
             if (lane == 0) fin = split_stop(st.last, kind == kBlkStored && slen == 0u);
             seg_fin = __builtin_amdgcn_readfirstlane(fin);
@@ -2541,6 +2593,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         } else if constexpr (kStream) {
             // the end of a member: its trailer; a gzip stream goes on behind the zeros that may follow with its next member
             uint32_t more = 0, next = 0;
+            if constexpr (kMark) if (lane == 0 && st.last && !mk_have_end) { mk_have_end = 1; mk_end = st.br.bit_pos(); }
             if (lane == 0 && st.last) {
                 const uint32_t q = (st.br.bit_pos() + 7u) >> 3;
                 st.status = stream_trailer(sp.wrap, src, nin, q, st.out_pos, st.out_pos - origin, rec, &next);
@@ -2553,6 +2606,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                 if (lane == 0) { sst = gzip_next_member(src, nin, nz, &body); st.status = sst; st.last = 0; }
                 body = __builtin_amdgcn_readfirstlane(body);
                 if (__builtin_amdgcn_readfirstlane(sst) != kInfRunning) break;
+                if constexpr (kMark) mk_second = 1;
                 origin = __builtin_amdgcn_readfirstlane(st.out_pos);
                 top_up(body);
                 if (lane == 0) st.br.seek_bit(body * 8u);
@@ -2569,10 +2623,22 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         if (lane == 0) sp.meas[chunk] = make_uint4(seg_fin, seg_base + ((st.br.bit_pos() + 7u) >> 3), st.out_pos, st.status);
     } else if constexpr (kSplit == 2) {
         if (lane == 0 && !(seg_fin != kSegBad && st.out_pos == cap)) sp.bad[seg_stream] = 1;      // (cannot happen: the measuring form decoded the same bits)
+    } else if constexpr (kSplit == kFormIndexed) {
+        // (an index that lies -- a wrong bit, offset or hist, an end bit inside a block -- ends here: the decoder stopped, or stands elsewhere)
+        if (lane == 0 && !index_segment_good(st.status, st.br.bit_pos(), seg_end, st.out_pos, cap, st.last, seg_last)) sp.bad[seg_stream] = 1;
     } else if constexpr (kStream) {
         if (lane == 0) {
             sp.out_len[chunk] = st.out_pos; status[chunk] = st.status;
             sp.rec[chunk] = make_uint4(rec.checked, rec.expect, rec.has_check, st.status);
+            if constexpr (kMark) {
+                // provisional: index_windows_kernel fills the windows in and seals the header once the checksum's verdict is there
+                const bool made = !mk_full && !mk_second && mk_have_end && mk_count;
+                sp.idx_len[chunk] = made ? (mk_bytes + 15u) & ~15ull : 0u;
+                if (made) {
+                    uint32_t* h = reinterpret_cast<uint32_t*>(mk_idx);
+                    h[6] = st.out_pos; h[7] = 0; h[8] = mk_count; h[10] = mk_end; h[11] = 0; h[12] = rec.has_check ? rec.expect : 0u;
+                }
+            }
         }
     } else {
         if (lane == 0) { out_len[chunk] = st.out_pos; status[chunk] = st.status; }
@@ -3009,6 +3075,31 @@ hipError_t launch_inflate_split(const InflateSplitArgs& a, hipStream_t s) {
     if (a.measure) { if (a.serial_header) ZWZ_SPLIT_LAUNCH(true, 1); else ZWZ_SPLIT_LAUNCH(false, 1); }
     else { if (a.serial_header) ZWZ_SPLIT_LAUNCH(true, 2); else ZWZ_SPLIT_LAUNCH(false, 2); }
 #undef ZWZ_SPLIT_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_inflate_mark(const InflateMarkArgs& m, hipStream_t s) {
+    const InflateStreamArgs& a = m.s;
+    if (a.n == 0) return hipSuccess;
+    const uint32_t per = kInflateThreads / 64;
+    hipLaunchKernelGGL(inflate_order_kernel<uint64_t>, dim3(1), dim3(1024), 0, s, a.in_off, a.in_len, a.n, a.order);
+    StreamParams sp{a.out_off, a.out_cap, a.out_len, a.rec, a.wrap};
+    sp.idx = m.idx; sp.idx_off = m.idx_off; sp.idx_cap = m.idx_cap; sp.idx_len = m.idx_len; sp.span = m.span;
+    const dim3 grid((a.n + per - 1) / per), block(kInflateThreads);
+    if (a.serial_header) hipLaunchKernelGGL((inflate_kernel<true, true, kFormMark>), grid, block, 0, s, a.in, a.in_off, nullptr, a.n, a.out, 0, nullptr, a.status, (const uint4*)a.order, sp);
+    else hipLaunchKernelGGL((inflate_kernel<false, true, kFormMark>), grid, block, 0, s, a.in, a.in_off, nullptr, a.n, a.out, 0, nullptr, a.status, (const uint4*)a.order, sp);
+    return hipGetLastError();
+}
+
+hipError_t launch_inflate_indexed(const InflateIndexedArgs& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    const uint32_t per = kInflateThreads / 64;
+    hipLaunchKernelGGL(inflate_order_kernel<uint64_t>, dim3(1), dim3(1024), 0, s, a.seg_in_off, a.seg_in_len, a.n, a.order);
+    StreamParams sp{};
+    sp.seg = a.seg; sp.seg2 = a.seg2; sp.bad = a.bad;
+    const dim3 grid((a.n + per - 1) / per), block(kInflateThreads);
+    if (a.serial_header) hipLaunchKernelGGL((inflate_kernel<true, true, kFormIndexed>), grid, block, 0, s, a.in, a.seg_in_off, nullptr, a.n, a.out, 0, nullptr, nullptr, (const uint4*)a.order, sp);
+    else hipLaunchKernelGGL((inflate_kernel<false, true, kFormIndexed>), grid, block, 0, s, a.in, a.seg_in_off, nullptr, a.n, a.out, 0, nullptr, nullptr, (const uint4*)a.order, sp);
     return hipGetLastError();
 }
 
