@@ -414,6 +414,36 @@ int zwz_inflate_indexed_dev(zwz_ctx *ctx, const uint8_t *d_in, uint64_t in_len, 
  * range touches is not seen.  Synchronous. */
 int zwz_inflate_read_ranges_dev(zwz_ctx *ctx, const uint8_t *d_in, uint64_t in_len, const uint8_t *idx, uint64_t idx_len,
                                 const uint8_t *d_idx, const uint64_t *ranges, uint32_t k, uint8_t *d_out);
+/* zwz_inflate_indexed_dev for n streams in ONE call: the segments of all of them are one launch, and so are the placing and the
+ * comparing of their windows, their checksum pieces and their verdicts (zwz_inflate_indexed_dev is this call with n = 1).
+ * in_off, in_len, idx_off, idx_len, out_off and out_cap are HOST arrays of n (zwz_deflate_streams_dev's convention; they may be
+ * reused when the call returns); d_in, d_out, d_out_len, d_status and d_segments (which may be NULL) are device memory, the last three
+ * of n elements.  Stream i is in_len[i] bytes at d_in + in_off[i] (d_in and every in_off[i] multiples of 16, readable up to the
+ * length rounded up to 16).  Index i is idx_len[i] bytes at idx + idx_off[i] in HOST memory and, with d_idx given, the same bytes at
+ * d_idx + idx_off[i] (d_idx and every idx_off[i] multiples of 16): the layout zwz_inflate_streams_index_dev writes, so what it built is
+ * decoded with the same offsets after one copy to the host.  With d_idx NULL the call uploads the indexes.  The wrapper of stream i
+ * comes from its index: one batch may mix raw, zlib and gzip.
+ * Output i goes to d_out + out_off[i], ANY byte address; no byte outside [out_off[i], out_off[i] + decoded length) is written; the
+ * ranges must not overlap.  d_out_len[i], d_status[i] and d_segments[i] are exactly what zwz_inflate_indexed_dev gives for stream i
+ * alone (0; 3 with nothing written; ZWZ_STREAM_INDEX; ZWZ_STREAM_TOO_LARGE; ZWZ_STREAM_CHECKSUM), and the verdicts are independent: a
+ * stream that fails changes no byte and no verdict of another.
+ * A malformed index is ZWZ_E_FORMAT for the whole call, zwz_last_error() naming the stream number and the rule; nothing is launched
+ * or written.  n == 0 is ZWZ_OK.  More than 2^32 - 1 segments or checksum pieces in one call is ZWZ_E_INVALID.  Synchronisation as
+ * zwz_inflate_indexed_dev's. */
+int zwz_inflate_indexed_batch_dev(zwz_ctx *ctx, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
+                                  const uint8_t *idx, const uint64_t *idx_off, const uint64_t *idx_len, const uint8_t *d_idx,
+                                  uint8_t *d_out, const uint64_t *out_off, const uint64_t *out_cap,
+                                  uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_segments);
+/* zwz_inflate_read_ranges_dev across the n streams of a batch laid out as zwz_inflate_indexed_batch_dev's: ranges is k TRIPLES
+ * (stream number, decoded offset, length) in host memory, in any order, overlapping, repeated or empty; d_out receives their bytes
+ * concatenated in the given order.  The touched segments of all streams are decoded together, each whole, in slices of at most
+ * 256 MiB of scratch; with d_idx NULL only their windows are uploaded.  No checksum verdict.  Synchronous.
+ * ZWZ_E_INVALID names the range for a stream number >= n, a range past its stream's decoded length or an overflowing end;
+ * ZWZ_E_FORMAT names the stream for a malformed index or an in_len other than indexed, and the stream and the segment for a segment
+ * that does not decode as indexed.  Only the indexes of streams that a range names are read. */
+int zwz_inflate_read_ranges_batch_dev(zwz_ctx *ctx, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
+                                      const uint8_t *idx, const uint64_t *idx_off, const uint64_t *idx_len, const uint8_t *d_idx,
+                                      const uint64_t *ranges, uint32_t k, uint8_t *d_out);
 /* Host only (no GPU): checks an index as every reader does (ZWZ_E_FORMAT, zwz_last_error() naming the rule) and returns its wrapper,
  * the stream's length, the decoded length and the number of entries; any of the four pointers may be NULL. */
 int zwz_inflate_index_info(const uint8_t *idx, uint64_t idx_len, int *wrap, uint64_t *stream_len, uint64_t *decoded_len, uint32_t *count);

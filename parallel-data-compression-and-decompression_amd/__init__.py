@@ -19,6 +19,8 @@ and ordinary DEFLATE data of any size, a batch of independent streams in one lau
     Codec.inflate_streams / Codec.inflate_streams_dev          (raw, zlib or gzip; bytes or device tensors)
     Codec.inflate_stream / Codec.inflate_split_streams_dev     (one long stream with full-flush points: a wave per piece)
     Codec.inflate_stream_file                                  (one file of any size, in slices; `main gunzip`)
+    Codec.inflate_index / Codec.inflate_indexed / Codec.read_ranges            (the seek index of one ordinary stream: a wave per segment)
+    Codec.inflate_indexed_batch / Codec.read_ranges_batch, pack_indexes        (many indexed streams in one launch; the _dev forms)
     Codec.deflate_streams / Codec.deflate_streams_dev          (the way there: libz's level-6 full-flush streams, any size)
     Codec.deflate_stream_file, deflate_stream_bound            (one file as one .gz / zlib / raw stream)
 and ZIP archives, a batch of entries per launch (what unzip, zipfile and file managers open; no reference counterpart):
@@ -119,6 +121,8 @@ def lib():
         L.zwz_inflate_streams_index_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
         L.zwz_inflate_indexed_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp]
         L.zwz_inflate_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, u32, vp]
+        L.zwz_inflate_indexed_batch_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.zwz_inflate_read_ranges_batch_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp]
         L.zwz_inflate_index_info.argtypes = [vp, u64, c.POINTER(c.c_int), c.POINTER(u64), c.POINTER(u64), c.POINTER(u32)]
         L.zwz_inflate_index_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
         L.zwz_inflate_read_ranges_file.argtypes = [vp, c.c_char_p, c.c_char_p, vp, u32, vp]
@@ -393,6 +397,111 @@ class Codec:
         index = bytes(index)
         _check(lib().zwz_inflate_read_ranges_dev(self._h, d_in.data_ptr(), int(in_len), index, len(index), d_idx.data_ptr() if d_idx is not None else None,
                                                  ranges.ctypes.data, len(ranges), d_out.data_ptr()), "zwz_inflate_read_ranges_dev")
+
+    def inflate_indexed_batch_dev(self, d_in, in_off, in_len, indexes, d_out, out_off, out_cap, d_out_len, d_status, d_segments=None, d_idx=None,
+                                  idx_off=None):
+        """zwz_inflate_indexed_batch_dev: n streams (stream i: in_len[i] bytes at in_off[i], a multiple of 16, of the 16-byte aligned CUDA
+        uint8 tensor d_in) decoded whole with their indexes in ONE call, output i to d_out[out_off[i]:], any byte offset, of capacity
+        out_cap[i].  in_off, in_len, out_off, out_cap: HOST sequences or numpy arrays.  indexes: a list of index bytes, or
+        pack_indexes' result (made once for repeated calls); idx_off: where each index lies in the packed host buffer and in d_idx,
+        multiples of 16 (None: one behind the other).  d_idx: the same buffer on the device (None: uploaded).  d_out_len (int64),
+        d_status (int32), d_segments (int32, optional): n elements each, complete after sync().  ZwzError with status E_FORMAT,
+        naming the stream, for a malformed index."""
+        import numpy as np
+        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
+        pk = indexes if isinstance(indexes, PackedIndexes) else pack_indexes(indexes, idx_off)
+        n = len(arr[0])
+        if any(len(a) != n for a in arr) or pk.n != n:
+            raise ValueError("in_off, in_len, out_off, out_cap and the indexes must have one element per stream")
+        _check(lib().zwz_inflate_indexed_batch_dev(self._h, d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n, pk.blob.ctypes.data, pk.off.ctypes.data,
+                                                   pk.len.ctypes.data, d_idx.data_ptr() if d_idx is not None else None, d_out.data_ptr(),
+                                                   arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(), d_status.data_ptr(),
+                                                   d_segments.data_ptr() if d_segments is not None else None), "zwz_inflate_indexed_batch_dev")
+
+    def read_ranges_batch_dev(self, d_in, in_off, in_len, indexes, ranges, d_out, d_idx=None, idx_off=None):
+        """zwz_inflate_read_ranges_batch_dev: the decoded byte ranges (a (k, 3) uint64 array of stream number, offset, length) of the
+        streams of a batch laid out as inflate_indexed_batch_dev's, concatenated into d_out.  Only the touched segments are decoded;
+        only the indexes of named streams are read; no checksum verdict.  Synchronous."""
+        import numpy as np
+        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len)]
+        pk = indexes if isinstance(indexes, PackedIndexes) else pack_indexes(indexes, idx_off)
+        n = len(arr[0])
+        if len(arr[1]) != n or pk.n != n:
+            raise ValueError("in_off, in_len and the indexes must have one element per stream")
+        _check(lib().zwz_inflate_read_ranges_batch_dev(self._h, d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n, pk.blob.ctypes.data,
+                                                       pk.off.ctypes.data, pk.len.ctypes.data, d_idx.data_ptr() if d_idx is not None else None,
+                                                       ranges.ctypes.data, len(ranges), d_out.data_ptr()), "zwz_inflate_read_ranges_batch_dev")
+
+    def _batch_input(self, torch, np, datas):
+        """[bytes or CUDA uint8 tensor] -> (one 16-byte aligned CUDA tensor holding them at multiples of 16, offsets, lengths)"""
+        dev = torch.device("cuda", self.device)
+        lens = np.array([d.numel() if isinstance(d, torch.Tensor) else len(d) for d in datas], dtype=np.uint64)
+        offs = np.zeros(len(datas), dtype=np.uint64)
+        if len(datas):
+            offs[1:] = np.cumsum((lens[:-1] + 15) // 16 * 16)
+        total = int(offs[-1] + (lens[-1] + 15) // 16 * 16) if len(datas) else 0
+        if any(isinstance(d, torch.Tensor) for d in datas):
+            d_in = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
+            for d, o, n in zip(datas, offs.tolist(), lens.tolist()):
+                d_in[o:o + n].copy_(d.reshape(-1) if isinstance(d, torch.Tensor) else torch.frombuffer(bytearray(d), dtype=torch.uint8))
+            return d_in, offs, lens
+        blob = np.zeros(max(total, 16), dtype=np.uint8)
+        for d, o, n in zip(datas, offs.tolist(), lens.tolist()):
+            blob[o:o + n] = np.frombuffer(d, dtype=np.uint8)
+        return torch.from_numpy(blob).to(dev), offs, lens
+
+    def inflate_indexed_batch(self, datas, indexes):
+        """[bytes of one stream each] and their indexes -> [decoded bytes], every segment of every stream in one launch; the streams
+        may mix raw, zlib and gzip.  Raises ZwzError for the first failing stream, naming it (.index, .stream_status), as
+        inflate_streams does, and with status E_FORMAT for a malformed index."""
+        import numpy as np
+        import torch
+        datas = [bytes(d) for d in datas]
+        indexes = [bytes(x) for x in indexes]
+        if len(datas) != len(indexes):
+            raise ValueError("one index per stream")
+        n = len(datas)
+        if n == 0:
+            return []
+        totals = np.array([index_info(x)["decoded_len"] for x in indexes], dtype=np.uint64)      # (validated before anything is sized by it)
+        ooff = np.zeros(n, dtype=np.uint64)
+        ooff[1:] = np.cumsum((totals[:-1] + 15) // 16 * 16)
+        dev = torch.device("cuda", self.device)
+        d_in, offs, lens = self._batch_input(torch, np, datas)
+        d_out = torch.empty(int(ooff[-1] + (totals[-1] + 15) // 16 * 16) or 16, dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.inflate_indexed_batch_dev(d_in, offs, lens, indexes, d_out, ooff, totals, d_len, d_st)
+        self.sync()
+        st, olen, host = d_st.cpu().numpy(), d_len.cpu().numpy(), d_out.cpu().numpy()
+        for i in range(n):
+            if st[i] != STREAM_END:
+                err = ZwzError("inflate_indexed_batch: stream %d: status %d" % (i, st[i]))
+                err.status, err.index, err.stream_status = E_FORMAT, i, int(st[i])
+                raise err
+        return [host[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes() for i in range(n)]
+
+    def read_ranges_batch(self, datas, indexes, ranges):
+        """Decoded byte ranges [(stream, offset, length), ...] out of a batch of ordinary streams with their seek indexes, in one call:
+        [bytes] -> a list of bytes; CUDA uint8 tensors -> one CUDA tensor of the ranges concatenated.  Only the segments holding a
+        requested byte are decoded.  A stream number past the batch or a range past its stream's end raises ZwzError (status E_INVALID)."""
+        import numpy as np
+        import torch
+        as_tensor = any(isinstance(d, torch.Tensor) for d in datas)
+        indexes = [bytes(x) for x in indexes]
+        if len(datas) != len(indexes):
+            raise ValueError("one index per stream")
+        rng = _ranges(np, ranges, 3)
+        total = int(rng[:, 2].sum()) if len(rng) else 0
+        dev = torch.device("cuda", self.device)
+        d_in, offs, lens = self._batch_input(torch, np, datas)
+        d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        self.read_ranges_batch_dev(d_in, offs, lens, indexes, rng, d_out)
+        if as_tensor:
+            return d_out[:total]
+        return _split(d_out[:total].cpu().numpy().tobytes(), rng)
 
     def inflate_index_file(self, src, dst_idx, wrap="gzip", span=None):
         """One file holding one ordinary stream -> its seek index at dst_idx (zwz_inflate_index_file; `main gzindex`).  span: as
@@ -838,19 +947,21 @@ def _c_names(names):
     return (ctypes.c_char_p * max(len(raw), 1))(*raw)
 
 
-def _ranges(np, ranges):
-    """[(offset, length), ...] -> a C-contiguous (k, 2) uint64 array (ZwzError for a negative value)."""
-    rows = [(int(a), int(b)) for a, b in ranges]
-    if any(a < 0 or b < 0 for a, b in rows):
-        err = ZwzError("bgzf ranges: offsets and lengths are not negative")
+def _ranges(np, ranges, width=2):
+    """[(offset, length), ...] -> a C-contiguous (k, 2) uint64 array (ZwzError for a negative value); width 3: (stream, offset, length)."""
+    rows = [tuple(int(x) for x in r) for r in ranges]
+    if any(len(r) != width for r in rows):
+        raise ValueError("every range has %d elements" % width)
+    if any(x < 0 for r in rows for x in r):
+        err = ZwzError("ranges: stream numbers, offsets and lengths are not negative")
         err.status = E_INVALID
         raise err
-    return np.ascontiguousarray(np.array(rows, dtype=np.uint64).reshape(-1, 2))
+    return np.ascontiguousarray(np.array(rows, dtype=np.uint64).reshape(-1, width))
 
 
 def _split(blob, rng):
     out, o = [], 0
-    for n in rng[:, 1].tolist():
+    for n in rng[:, -1].tolist():
         out.append(blob[o:o + n])
         o += n
     return out
@@ -892,6 +1003,31 @@ def do_decompression(input_dir, output_dir, world_rank=0, world_size=1, allgathe
 
 def inflate_stream(data, wrap="gzip", out_size=None):
     return _codec().inflate_stream(data, wrap, out_size)
+
+
+class PackedIndexes:
+    """The seek indexes of a batch in one host buffer (pack_indexes): .blob (uint8), .off and .len (uint64, one element a stream)."""
+    def __init__(self, blob, off, length):
+        self.blob, self.off, self.len, self.n = blob, off, length, len(off)
+
+
+def pack_indexes(indexes, idx_off=None):
+    """[index bytes] -> PackedIndexes: index i at idx_off[i] of one host buffer (multiples of 16; None: one behind the other), the
+    layout Codec.inflate_indexed_batch_dev and Codec.read_ranges_batch_dev take, and their d_idx on the device."""
+    import numpy as np
+    lens = np.array([len(x) for x in indexes], dtype=np.uint64)
+    if idx_off is None:
+        off = np.zeros(len(lens), dtype=np.uint64)
+        if len(lens):
+            off[1:] = np.cumsum((lens[:-1] + 15) // 16 * 16)
+    else:
+        off = np.ascontiguousarray(idx_off, dtype=np.uint64)
+        if len(off) != len(lens):
+            raise ValueError("one offset per index")
+    blob = np.zeros(int((off + lens).max()) + 16 if len(lens) else 16, dtype=np.uint8)
+    for x, o in zip(indexes, off.tolist()):
+        blob[o:o + len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+    return PackedIndexes(blob, off, lens)
 
 
 def index_info(index):

@@ -18,6 +18,7 @@
 #pragma once
 #include "stream_core.h"
 
+#include <algorithm>
 #include <vector>
 
 namespace zwz {
@@ -32,10 +33,40 @@ ZWZ_HD uint64_t le64_of(const uint8_t* p) { return (uint64_t)le32_at(p) | (uint6
 ZWZ_HD void put_le32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 ZWZ_HD void put_le64(uint8_t* p, uint64_t v) { put_le32(p, (uint32_t)v); put_le32(p + 4, (uint32_t)(v >> 32)); }
 
-// crc_raw_bytes over a length of 64 bits
+// The host's tables for crc_raw_long: slice[k][b] = the register after byte b and k zero bytes (crc_core.h's T_k), built once
+constexpr uint32_t kCrcHostSlices = 16;
+struct CrcHostTables {
+    uint32_t slice[kCrcHostSlices][256];
+    CrcHostTables() {
+        for (uint32_t b = 0; b < 256u; b++) slice[0][b] = crc_shift8(b);
+        for (uint32_t k = 1; k < kCrcHostSlices; k++)
+            for (uint32_t b = 0; b < 256u; b++) slice[k][b] = (slice[k - 1][b] >> 8) ^ slice[0][slice[k - 1][b] & 255u];
+    }
+};
+inline const CrcHostTables& crc_host_tables() { static const CrcHostTables t; return t; }
+
+// crc_raw_bytes over a length of 64 bits, 16 bytes a step: the register goes into the first four, every byte through the table of its
+// distance from the step's end
+inline uint32_t crc_raw_sliced(uint32_t c, const uint8_t* p, uint64_t n) {
+    const CrcHostTables& t = crc_host_tables();
+    for (; n >= kCrcHostSlices; p += kCrcHostSlices, n -= kCrcHostSlices) {
+        const uint32_t w[4] = {le32_at(p) ^ c, le32_at(p + 4), le32_at(p + 8), le32_at(p + 12)};
+        c = 0;
+        for (uint32_t j = 0; j < 4u; j++)
+            c ^= t.slice[15u - 4u * j][w[j] & 255u] ^ t.slice[14u - 4u * j][(w[j] >> 8) & 255u] ^ t.slice[13u - 4u * j][(w[j] >> 16) & 255u] ^ t.slice[12u - 4u * j][w[j] >> 24];
+    }
+    for (; n; p++, n--) c = t.slice[0][(c ^ *p) & 255u] ^ (c >> 8);
+    return c;
+}
+
+// crc_raw_bytes over a length of 64 bits (the host through its tables; a kernel, which has crc_wg.h for anything long, bit by bit)
 ZWZ_HD uint32_t crc_raw_long(uint32_t c, const uint8_t* p, uint64_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
     for (uint64_t at = 0; at < n; at += 1u << 30) c = crc_raw_bytes(c, p + at, (uint32_t)(n - at < (1u << 30) ? n - at : 1u << 30));
     return c;
+#else
+    return crc_raw_sliced(c, p, n);
+#endif
 }
 
 ZWZ_HD bool index_span_ok(uint32_t span) { return span >= kIdxSpanMin && span <= kIdxSpanMax && !(span & (span - 1u)); }
@@ -146,6 +177,67 @@ inline int64_t index_plan(const IndexView& v, const uint64_t* ranges, uint32_t k
     std::vector<uint32_t> fill(plan->row.begin(), plan->row.end());
     for (const Raw& q : raw) plan->pieces[fill[slot[q.seg]]++] = q.p;
     return -1;
+}
+
+// The batch (zwz_inflate_read_ranges_batch_dev): ranges are triples (stream number, decoded offset, length); the touched segments of all
+// streams in one list, ascending by (stream, segment), with their pieces as compressed sparse rows in range order, as IndexPlan's.
+struct IndexBatchPlan { std::vector<uint32_t> stream, segs, row; std::vector<IndexPiece> pieces; uint64_t total = 0; };
+
+// Which streams the triples name: named[s] = 1.  -1: fine; otherwise the first range whose stream number is not below n
+inline int64_t index_batch_named(const uint64_t* triples, uint32_t k, uint32_t n, std::vector<uint8_t>* named) {
+    named->assign(n, 0);
+    for (uint32_t r = 0; r < k; r++) {
+        if (triples[3 * r] >= n) return r;
+        (*named)[(size_t)triples[3 * r]] = 1;
+    }
+    return -1;
+}
+
+// -1: fine; otherwise the first range that lies past its stream's decoded length or whose end overflows.  Only the views of named
+// streams are read (every stream number is below n: index_batch_named).
+inline int64_t index_plan_batch(const IndexView* views, const uint64_t* triples, uint32_t k, IndexBatchPlan* plan) {
+    plan->stream.clear(); plan->segs.clear(); plan->row.clear(); plan->pieces.clear(); plan->total = 0;
+    struct Raw { uint64_t key; IndexPiece p; };                          // key: stream << 32 | segment
+    std::vector<Raw> raw;
+    uint64_t dst = 0;
+    for (uint32_t r = 0; r < k; r++) {
+        const uint64_t s = triples[3 * r], a = triples[3 * r + 1], len = triples[3 * r + 2];
+        const IndexView& v = views[s];
+        if (a + len < a || a + len > v.decoded_len) return r;
+        uint64_t at = a, left = len;
+        while (left) {
+            const uint32_t g = index_segment_of(v, at);
+            const uint64_t s0 = v.entry(g).off, s1 = v.seg_end_off(g);
+            const uint64_t take = left < s1 - at ? left : s1 - at;
+            raw.push_back(Raw{s << 32 | g, IndexPiece{dst, (uint32_t)(at - s0), (uint32_t)take}});
+            at += take; dst += take; left -= take;
+        }
+    }
+    plan->total = dst;
+    // the rows: a stable sort by key keeps a row's pieces in range order
+    std::vector<uint32_t> by(raw.size());
+    for (uint32_t i = 0; i < by.size(); i++) by[i] = i;
+    std::stable_sort(by.begin(), by.end(), [&](uint32_t x, uint32_t y) { return raw[x].key < raw[y].key; });
+    plan->pieces.reserve(raw.size());
+    for (size_t i = 0; i < by.size(); i++) {
+        const Raw& q = raw[by[i]];
+        if (i == 0 || q.key != raw[by[i - 1]].key) { plan->stream.push_back((uint32_t)(q.key >> 32)); plan->segs.push_back((uint32_t)q.key); plan->row.push_back((uint32_t)i); }
+        plan->pieces.push_back(q.p);
+    }
+    plan->row.push_back((uint32_t)raw.size());
+    return -1;
+}
+
+// The checksum pieces of a whole-stream decode whose first byte stands at an address with the low four bits `low4`: piece 0 is the
+// `head` bytes up to the next 16-byte boundary (it may be empty), the others kIdxPieceBytes each, the last one what is left.
+constexpr uint32_t kIdxPieceBytes = 65280;          // dstream_core.h's kPieceBytes
+ZWZ_HD uint32_t index_head_bytes(uint32_t low4, uint64_t total) { const uint32_t h = (16u - low4) & 15u; return total < h ? (uint32_t)total : h; }
+ZWZ_HD uint64_t index_piece_count(uint32_t wrap, uint32_t head, uint64_t total) { return wrap == kWrapRaw ? 0u : 1u + (total - head + kIdxPieceBytes - 1u) / kIdxPieceBytes; }
+ZWZ_HD uint64_t index_piece_start(uint32_t head, uint64_t j) { return j ? head + (j - 1u) * kIdxPieceBytes : 0u; }
+ZWZ_HD uint32_t index_piece_bytes(uint32_t head, uint64_t total, uint64_t j) {
+    if (j == 0) return head;
+    const uint64_t left = total - index_piece_start(head, j);
+    return left < kIdxPieceBytes ? (uint32_t)left : kIdxPieceBytes;
 }
 
 // Header and index CRC of an index whose entries and windows are in place (n: its padded length)

@@ -17,24 +17,39 @@ struct IndexBuild {
 };
 hipError_t launch_index_windows(const CrcTables* tab, const IndexBuild& b, hipStream_t s);
 
-// One window to place: `len` bytes at `src` of the index go to `dst` of the output (or of the scratch slots)
-struct IndexMove { uint64_t src, dst; uint32_t len, pad; };
+// One window to place: `len` bytes at `src` of the index buffer go to `dst` of the output (or of the scratch slots); `stream`: whose
+// flag a difference sets
+struct IndexMove { uint64_t src, dst; uint32_t len, stream; };
 hipError_t launch_index_place(const uint8_t* idx, uint8_t* out, const IndexMove* mv, uint32_t m, hipStream_t s);
-// flag |= 1 where a window differs from the bytes that now stand at its place
+// flag[stream] |= 1 where a window differs from the bytes that now stand at its place
 hipError_t launch_index_compare(const uint8_t* idx, const uint8_t* out, const IndexMove* mv, uint32_t m, uint32_t* flag, hipStream_t s);
 
-// The checksum of out[0, total) from pieces -- the first `head` bytes, up to a 16-byte boundary, then kPieceBytes each -- and the verdict of a whole-stream decode: bad[0] -> kStrIndex; a window
-// that was not the stream's bytes (flag), a checksum other than the index's or other than the stream's own trailer at byte `trailer`
-// of in[0, in_len) -> kStrChecksum; else 0.  Writes out_len, status and segments.
-struct IndexFinish {
-    const uint8_t* in; uint64_t in_len, trailer; const uint8_t* out; uint64_t total; uint32_t head, wrap, expect, nseg;
+// The checksum pieces of out[0, total): the first `head` bytes, then kPieceBytes each -- piece_off, piece_len and piece_val (the file
+// call joins the slices' pieces on the host)
+struct IndexPieces {
+    const uint8_t* out; uint64_t total; uint32_t head, wrap;
     uint64_t* piece_off; uint32_t* piece_len; uint32_t* piece_val; uint32_t pieces;
+};
+hipError_t launch_index_piece_sums(const CrcTables* tab, const IndexPieces& f, uint32_t cu_count, hipStream_t s);
+
+// One stream of a whole decode (zwz_inflate_indexed_batch_dev; the one-stream call is a batch of one).  Its bytes are in[in_off, in_off +
+// in_len) with the trailer at byte `trailer` of them; its output out[out_off, out_off + total) with the checksum pieces piece0 ..
+// piece0 + pieces (index_core.h's layout from `head`).  refused: a verdict the host has reached already (no segment of the stream runs).
+struct IndexStream {
+    uint64_t in_off, in_len, trailer, out_off, total;
+    uint32_t head, wrap, expect, nseg, piece0, pieces, refused, pad;
+};
+// The pieces of all streams, their checksums -- the first `gzip_pieces` of the list are CRC-32's, the others Adler-32's -- and a wave
+// per stream that joins its pieces and gives the verdict: refused, else bad[i] -> kStrIndex; a window that was not the stream's bytes
+// (flag[i]), a checksum other than the index's or other than the stream's own trailer -> kStrChecksum; else 0.  Writes out_len[i],
+// status[i] and, if given, segments[i] of every stream.
+struct IndexBatch {
+    const uint8_t* in; const uint8_t* out; const IndexStream* rec; uint32_t n;
+    uint64_t* piece_off; uint32_t* piece_len; uint32_t* piece_val; uint32_t pieces, gzip_pieces;
     const uint32_t* bad; const uint32_t* flag;
     uint64_t* out_len; uint32_t* status; uint32_t* segments;
 };
-hipError_t launch_index_finish(const CrcTables* tab, const IndexFinish& f, uint32_t cu_count, hipStream_t s);
-// the first half alone (the file call joins the slices' pieces on the host): piece_off, piece_len and piece_val of out[0, total)
-hipError_t launch_index_piece_sums(const CrcTables* tab, const IndexFinish& f, uint32_t cu_count, hipStream_t s);
+hipError_t launch_index_batch_finish(const CrcTables* tab, const IndexBatch& b, uint32_t cu_count, hipStream_t s);
 
 // Range reads: touched segment i's decoded bytes start at slots + slot_off[i]; its pieces row[i] .. row[i + 1], the first nlong[i] of
 // them long, go to out (bgzf_verify_extract's dealing).  Pieces of a segment whose bad[i] is set are not copied.

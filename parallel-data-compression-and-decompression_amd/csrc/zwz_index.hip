@@ -1,8 +1,8 @@
 // zwz_index.hip -- the device half of the seek index around inflate_kernel's marking and indexed-segment forms (index_core.h has the
 // layout and the method): the windows out of a decoded stream into its index with the header and the index CRC (windows), the windows
 // of a call to where its segment waves expect them (place), whether they were the stream's bytes (compare), the checksum of a
-// whole-stream decode from fixed pieces joined with dstream_core.h's sums and its verdict (finish), and the pieces of a batch of
-// ranges out of the decoded segments (extract).
+// batch of whole-stream decodes from fixed pieces joined with dstream_core.h's sums and every stream's verdict (batch finish), and the
+// pieces of a batch of ranges out of the decoded segments (extract).
 #include "../../include/zwz.h"
 #include "adler_wg.h"
 #include "copy_wg.h"
@@ -67,60 +67,83 @@ __global__ void __launch_bounds__(256) index_compare_kernel(const uint8_t* idx, 
         const IndexMove q = mv[i];
         uint32_t differs = 0;
         for (uint32_t j = threadIdx.x; j < q.len; j += 256u) differs |= (uint32_t)(out[q.dst + j] != idx[q.src + j]);
-        if (differs) atomicOr(flag, 1u);
+        if (differs) atomicOr(flag + q.stream, 1u);
     }
 }
 
-__global__ void __launch_bounds__(256) index_pieces_kernel(IndexFinish f) {
+static_assert(kIdxPieceBytes == kPieceBytes, "index_core.h's piece layout is dstream_core.h's piece");
+
+__global__ void __launch_bounds__(256) index_pieces_kernel(IndexPieces f) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= f.pieces) return;
-    const uint64_t at = j ? f.head + (uint64_t)(j - 1u) * kPieceBytes : 0u;
-    f.piece_off[j] = at;
-    f.piece_len[j] = j ? (uint32_t)min<uint64_t>(kPieceBytes, f.total - at) : f.head;
+    f.piece_off[j] = index_piece_start(f.head, j);
+    f.piece_len[j] = index_piece_bytes(f.head, f.total, j);
 }
 
-__global__ void __launch_bounds__(kBgzfThreads) index_adler_kernel(IndexFinish f) {
+// A workgroup per stream, a thread per piece: where in `out` the stream's pieces lie
+__global__ void __launch_bounds__(256) index_batch_pieces_kernel(const IndexStream* rec, uint32_t n, uint64_t* piece_off, uint32_t* piece_len) {
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const IndexStream r = rec[i];                                          // (workgroup-uniform)
+        for (uint32_t j = threadIdx.x; j < r.pieces; j += 256u) {
+            piece_off[r.piece0 + j] = r.out_off + index_piece_start(r.head, j);
+            piece_len[r.piece0 + j] = index_piece_bytes(r.head, r.total, j);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBgzfThreads) index_adler_kernel(const uint8_t* out, const uint64_t* piece_off, const uint32_t* piece_len, uint32_t* piece_val,
+                                                                   uint32_t pieces) {
     __shared__ uint32_t s_part[2 * kBgzfThreads / 64];
-    for (uint32_t j = blockIdx.x; j < f.pieces; j += gridDim.x) {
-        const uint32_t a = adler_range_wg(s_part, f.out + f.piece_off[j], f.piece_len[j]);
-        if (threadIdx.x == 0) f.piece_val[j] = a;
+    for (uint32_t j = blockIdx.x; j < pieces; j += gridDim.x) {
+        const uint32_t a = adler_range_wg(s_part, out + piece_off[j], piece_len[j]);
+        if (threadIdx.x == 0) piece_val[j] = a;
     }
 }
 
-// One wave: lane l joins its share of consecutive pieces, lane 0 the 64 shares; then the verdict.
-template <class Sum, bool kCheck>
-__global__ void __launch_bounds__(64) index_finish_kernel(IndexFinish f) {
+// Lane l joins its share of `cnt` consecutive pieces, then every lane the 64 shares: the checksum of the pieces' bytes (wave-uniform)
+template <class Sum>
+__device__ uint32_t index_join_pieces(const uint32_t* piece_len, const uint32_t* piece_val, uint32_t cnt, uint32_t lane) {
+    const uint32_t K = (cnt + 63u) / 64u, p1 = Sum::pof(kPieceBytes);
+    uint32_t x = Sum::identity(), acc = Sum::identity();
+    uint64_t bytes = 0;
+    for (uint32_t j = lane * K; j < min(cnt, (lane + 1u) * K); j++) {
+        const uint32_t len = piece_len[j];
+        x = Sum::join(x, piece_val[j], len == kPieceBytes ? p1 : Sum::pof(len));
+        bytes += len;
+    }
+    const uint32_t pl = Sum::pof(bytes);
+    for (uint32_t l = 0; l < 64u; l++) acc = Sum::join(acc, (uint32_t)__shfl((int)x, (int)l, 64), (uint32_t)__shfl((int)pl, (int)l, 64));
+    return acc;
+}
+
+// One wave per stream: the join of its pieces, then the verdict and the stream's three result words.
+__global__ void __launch_bounds__(64) index_batch_finish_kernel(IndexBatch b) {
     const uint32_t lane = lane_id();
-    uint32_t acc = Sum::identity();
-    if (kCheck) {
-        const uint32_t cnt = f.pieces, K = (cnt + 63u) / 64u, p1 = Sum::pof(kPieceBytes);
-        uint32_t x = Sum::identity();
-        uint64_t bytes = 0;
-        for (uint32_t j = lane * K; j < min(cnt, (lane + 1u) * K); j++) {
-            const uint32_t len = f.piece_len[j];
-            x = Sum::join(x, f.piece_val[j], len == kPieceBytes ? p1 : Sum::pof(len));
-            bytes += len;
+    for (uint32_t i = blockIdx.x; i < b.n; i += gridDim.x) {
+        const IndexStream r = b.rec[i];                                        // (wave-uniform, as every branch on it below)
+        uint32_t st = r.refused;
+        uint64_t total = r.total;
+        if (st) total = 0;
+        else if (b.bad[i]) st = kStrIndex;
+        else if (b.flag[i]) st = kStrChecksum;
+        else if (r.wrap != kWrapRaw) {
+            const uint32_t acc = r.wrap == kWrapGzip ? index_join_pieces<CrcSum>(b.piece_len + r.piece0, b.piece_val + r.piece0, r.pieces, lane)
+                                                     : index_join_pieces<AdlerSum>(b.piece_len + r.piece0, b.piece_val + r.piece0, r.pieces, lane);
+            // the stream's own trailer: Adler-32 big-endian (zlib); CRC-32 and ISIZE little-endian (gzip)
+            const uint32_t want = r.wrap == kWrapZlib ? 4u : 8u;
+            bool ok = acc == r.expect && r.trailer + want <= r.in_len;
+            if (ok) {
+                const uint8_t* q = b.in + r.in_off + r.trailer;
+                ok = r.wrap == kWrapZlib ? be32_at(q) == acc : le32_at(q) == acc && le32_at(q + 4) == (uint32_t)r.total;
+            }
+            if (!ok) st = kStrChecksum;
         }
-        const uint32_t pl = Sum::pof(bytes);
-        for (uint32_t l = 0; l < 64u; l++) acc = Sum::join(acc, (uint32_t)__shfl((int)x, (int)l, 64), (uint32_t)__shfl((int)pl, (int)l, 64));
-    }
-    if (lane != 0) return;
-    uint32_t st = 0;
-    if (f.bad[0]) st = kStrIndex;
-    else if (f.flag[0]) st = kStrChecksum;
-    else if (kCheck) {
-        // the stream's own trailer: Adler-32 big-endian (zlib); CRC-32 and ISIZE little-endian (gzip)
-        const uint32_t want = f.wrap == kWrapZlib ? 4u : 8u;
-        bool ok = acc == f.expect && f.trailer + want <= f.in_len;
-        if (ok) {
-            const uint8_t* q = f.in + f.trailer;
-            ok = f.wrap == kWrapZlib ? be32_at(q) == acc : le32_at(q) == acc && le32_at(q + 4) == (uint32_t)f.total;
+        if (lane == 0) {
+            b.out_len[i] = total;
+            b.status[i] = st;
+            if (b.segments) b.segments[i] = r.refused ? 0u : r.nseg;
         }
-        if (!ok) st = kStrChecksum;
     }
-    f.out_len[0] = f.total;
-    f.status[0] = st;
-    if (f.segments) f.segments[0] = f.nseg;
 }
 
 // bgzf_verify_extract's dealing of the pieces: long ones by the workgroup, short ones a wave each
@@ -161,23 +184,23 @@ hipError_t launch_index_compare(const uint8_t* idx, const uint8_t* out, const In
     return hipGetLastError();
 }
 
-hipError_t launch_index_piece_sums(const CrcTables* tab, const IndexFinish& f, uint32_t cu_count, hipStream_t s) {
+hipError_t launch_index_piece_sums(const CrcTables* tab, const IndexPieces& f, uint32_t cu_count, hipStream_t s) {
     if (f.wrap == kWrapRaw || !f.pieces) return hipSuccess;
     index_pieces_kernel<<<(f.pieces + 255u) / 256u, 256, 0, s>>>(f);
     if (f.wrap == kWrapGzip) return launch_crc32_blocks(tab, f.out, f.piece_off, f.piece_len, f.pieces, f.piece_val, cu_count, s);
-    index_adler_kernel<<<grid_for(f.pieces, cu_count, 8u), kBgzfThreads, 0, s>>>(f);
+    index_adler_kernel<<<grid_for(f.pieces, cu_count, 8u), kBgzfThreads, 0, s>>>(f.out, f.piece_off, f.piece_len, f.piece_val, f.pieces);
     return hipGetLastError();
 }
 
-hipError_t launch_index_finish(const CrcTables* tab, const IndexFinish& f, uint32_t cu_count, hipStream_t s) {
-    if (f.wrap == kWrapRaw) {
-        index_finish_kernel<AdlerSum, false><<<1, 64, 0, s>>>(f);
-        return hipGetLastError();
+hipError_t launch_index_batch_finish(const CrcTables* tab, const IndexBatch& b, uint32_t cu_count, hipStream_t s) {
+    if (!b.n) return hipSuccess;
+    if (b.pieces) {
+        index_batch_pieces_kernel<<<grid_for(b.n, cu_count, 8u), 256, 0, s>>>(b.rec, b.n, b.piece_off, b.piece_len);
+        const uint32_t g = b.gzip_pieces, a = b.pieces - g;
+        if (g) { const hipError_t e = launch_crc32_blocks(tab, b.out, b.piece_off, b.piece_len, g, b.piece_val, cu_count, s); if (e != hipSuccess) return e; }
+        if (a) index_adler_kernel<<<grid_for(a, cu_count, 8u), kBgzfThreads, 0, s>>>(b.out, b.piece_off + g, b.piece_len + g, b.piece_val + g, a);
     }
-    const hipError_t e = launch_index_piece_sums(tab, f, cu_count, s);
-    if (e != hipSuccess) return e;
-    if (f.wrap == kWrapGzip) index_finish_kernel<CrcSum, true><<<1, 64, 0, s>>>(f);
-    else index_finish_kernel<AdlerSum, true><<<1, 64, 0, s>>>(f);
+    index_batch_finish_kernel<<<grid_for(b.n, cu_count, 16u), 64, 0, s>>>(b);
     return hipGetLastError();
 }
 

@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """The seek index of ordinary streams on the GPU (a standalone tool; bench.py is the project's yardstick and does not run this).
 
-    python tools/inflate_index_bench.py [--scale 1.0] [--steps 5] [--warmup 2] [--span 0] [--out FILE]
+    python tools/inflate_index_bench.py [--scale 1.0] [--steps 5] [--warmup 2] [--span 0] [--only batch] [--out FILE]
 
 The workload is DESIGN.md section 17's S3: 64 x 16 MiB text, each one ordinary gzip stream from Python's zlib (nothing to split).
   floor     zwz_inflate_streams_dev on the batch: one wave a stream
   build     zwz_inflate_streams_index_dev on the batch: the same decode that also writes every stream's index
-  indexed   zwz_inflate_indexed_dev, one call a stream (the call takes ONE stream), the indexes on the device.  The gate: >= 10 x floor
+  indexed   zwz_inflate_indexed_dev, one call a stream, the indexes on the device
+  indexed_batch   the same batch through ONE zwz_inflate_indexed_batch_dev call, the indexes on the device.  The gate: its time is at
+            most a tenth of floor's, both measured in this run
   one       one stream of the batch alone: zwz_inflate_streams_dev against zwz_inflate_indexed_dev
   ranges    4 096 ranges of 4 KiB out of one stream through zwz_inflate_read_ranges_dev
+  ranges_batch    4 096 ranges of 4 KiB spread over all streams in one zwz_inflate_read_ranges_batch_dev call, against the same ranges
+            through one zwz_inflate_read_ranges_dev call a stream
+--only batch runs floor, indexed_batch and ranges_batch alone (what a second span is measured with).
 --scale multiplies the number of streams.  Every figure is decoded bytes over the wall time of synchronised calls, median of --steps
 after --warmup, the variants alternating in one process, with the spread (max - min) / median; every output is compared with the
 input on the device.  One JSON line on stdout (and in --out).
@@ -51,6 +56,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--span", type=int, default=0)
+    ap.add_argument("--only", default="", choices=["", "batch"])
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
@@ -116,37 +122,75 @@ def main():
                                       d_idx[i_off[i]:])
         codec.sync()
 
+    pk = z.pack_indexes(idx_host, i_off)                     # (the host copy of d_idx's layout, made once)
+    caps = np.full(k, n, dtype=np.uint64)
+
+    def indexed_batch():
+        codec.inflate_indexed_batch_dev(d_comp, c_off, c_len, pk, d_out, s_off, caps, d_olen, d_st, d_seg, d_idx)
+        codec.sync()
+
+    d_seg.fill_(-1)
+    indexed_batch()
+    ok = ok and check() and [int(x) for x in d_seg.cpu().numpy()] == segs
+    d_seg.fill_(-1)
     indexed()
     ok = ok and check() and [int(x) for x in d_seg.cpu().numpy()] == segs
     res = {"tool": "inflate_index_bench", "scale": a.scale, "steps": a.steps, "warmup": a.warmup, "span": span, "streams": k, "decoded_bytes": n * k,
            "compressed_bytes": int(c_len.sum()), "segments_per_stream": [min(segs), max(segs)], "index_bytes": int(i_len.sum()),
            "index_share_of_decoded": round(float(i_len.sum()) / (n * k), 4)}
-    times = alternate({"floor": floor, "build": build, "indexed": indexed}, a.steps, a.warmup)
+    variants = {"floor": floor, "indexed_batch": indexed_batch} if a.only else {"floor": floor, "build": build, "indexed": indexed, "indexed_batch": indexed_batch}
+    times = alternate(variants, a.steps, a.warmup)
     for name, (med, spread) in times.items():
         res[name + "_wall_ms"], res[name + "_gbps"], res[name + "_spread"] = round(med * 1e3, 3), round(n * k / med / 1e9, 3), round(spread, 3)
-    indexed()
+    indexed_batch()
     ok = ok and check()
-    res["indexed_over_floor"] = round(res["indexed_gbps"] / res["floor_gbps"], 2)
-    res["gate_10x_floor"] = res["indexed_over_floor"] >= 10.0
-    res["build_over_floor_time"] = round(res["build_wall_ms"] / res["floor_wall_ms"], 3)
-    # one stream alone
-    times = alternate({"one_floor": lambda: floor(1), "one_indexed": lambda: indexed(1)}, a.steps, a.warmup)
-    for name, (med, spread) in times.items():
-        res[name + "_wall_ms"], res[name + "_gbps"], res[name + "_spread"] = round(med * 1e3, 3), round(n / med / 1e9, 3), round(spread, 3)
-    indexed(1)
-    ok = ok and check(1)
-    res["one_indexed_over_floor"] = round(res["one_indexed_gbps"] / res["one_floor_gbps"], 2)
-    # 4 096 ranges of 4 KiB out of stream 0
-    rng = random.Random(5)
-    ranges = z._ranges(np, [(rng.randrange(n - 4096), 4096) for _ in range(4096)])
+    res["indexed_batch_over_floor"] = round(res["floor_wall_ms"] / res["indexed_batch_wall_ms"], 2)
+    res["gate_10x_floor"] = res["indexed_batch_wall_ms"] * 10.0 <= res["floor_wall_ms"]
+    # 4 096 ranges of 4 KiB over all streams: one batched call against one call a stream
+    rng = random.Random(6)
+    trip = z._ranges(np, [(rng.randrange(k), rng.randrange(n - 4096), 4096) for _ in range(4096)], 3)
     d_rng = torch.zeros(4096 * 4096, dtype=torch.uint8, device=dev)
+    d_one = torch.zeros(4096 * 4096, dtype=torch.uint8, device=dev)
+    per = [np.flatnonzero(trip[:, 0] == i) for i in range(k)]
+    starts = np.concatenate([[0], np.cumsum([4096 * len(p) for p in per])]).astype(np.int64)
 
-    def read():
-        codec.read_ranges_dev(d_comp, int(c_len[0]), idx_host[0], ranges, d_rng, d_idx)
-    med, spread = alternate({"ranges": read}, a.steps, a.warmup)["ranges"]
-    want = torch.cat([d_src[int(o):int(o) + 4096] for o in ranges[:, 0]])
+    def ranges_batch():
+        codec.read_ranges_batch_dev(d_comp, c_off, c_len, pk, trip, d_rng, d_idx)
+
+    def ranges_each():
+        for i in range(k):
+            if len(per[i]):
+                codec.read_ranges_dev(d_comp[c_off[i]:], int(c_len[i]), idx_host[i], np.ascontiguousarray(trip[per[i], 1:]), d_one[starts[i]:], d_idx[i_off[i]:])
+
+    times = alternate({"ranges_batch": ranges_batch, "ranges_each": ranges_each}, a.steps, a.warmup)
+    want = torch.cat([d_src[int(s) * n + int(o):int(s) * n + int(o) + 4096] for s, o, _ in trip])
     ok = ok and torch.equal(d_rng, want)
-    res["ranges_wall_ms"], res["ranges_per_s"], res["ranges_spread"] = round(med * 1e3, 3), round(4096 / med), round(spread, 3)
+    order = np.concatenate(per)
+    ok = ok and torch.equal(d_one.view(-1, 4096), want.view(-1, 4096)[torch.from_numpy(order).to(dev)])
+    for name, (med, spread) in times.items():
+        res[name + "_wall_ms"], res[name + "_per_s"], res[name + "_spread"] = round(med * 1e3, 3), round(4096 / med), round(spread, 3)
+    res["ranges_batch_over_each"] = round(res["ranges_each_wall_ms"] / res["ranges_batch_wall_ms"], 2)
+    if not a.only:
+        res["indexed_over_floor"] = round(res["indexed_gbps"] / res["floor_gbps"], 2)
+        res["build_over_floor_time"] = round(res["build_wall_ms"] / res["floor_wall_ms"], 3)
+        # one stream alone
+        times = alternate({"one_floor": lambda: floor(1), "one_indexed": lambda: indexed(1)}, a.steps, a.warmup)
+        for name, (med, spread) in times.items():
+            res[name + "_wall_ms"], res[name + "_gbps"], res[name + "_spread"] = round(med * 1e3, 3), round(n / med / 1e9, 3), round(spread, 3)
+        indexed(1)
+        ok = ok and check(1)
+        res["one_indexed_over_floor"] = round(res["one_indexed_gbps"] / res["one_floor_gbps"], 2)
+        # 4 096 ranges of 4 KiB out of stream 0
+        rng = random.Random(5)
+        ranges = z._ranges(np, [(rng.randrange(n - 4096), 4096) for _ in range(4096)])
+        d_rng = torch.zeros(4096 * 4096, dtype=torch.uint8, device=dev)
+
+        def read():
+            codec.read_ranges_dev(d_comp, int(c_len[0]), idx_host[0], ranges, d_rng, d_idx)
+        med, spread = alternate({"ranges": read}, a.steps, a.warmup)["ranges"]
+        want = torch.cat([d_src[int(o):int(o) + 4096] for o in ranges[:, 0]])
+        ok = ok and torch.equal(d_rng, want)
+        res["ranges_wall_ms"], res["ranges_per_s"], res["ranges_spread"] = round(med * 1e3, 3), round(4096 / med), round(spread, 3)
     codec.close()
     res["ok"] = bool(ok)
     line = json.dumps(res)
