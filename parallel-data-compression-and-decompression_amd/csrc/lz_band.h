@@ -25,6 +25,8 @@
 //
 // Portable (host + device): tests/emu builds band_records() on the CPU and diffs it against lz_search().
 #pragma once
+#include <cassert>
+
 #include "lz_core.h"
 
 namespace zwz {
@@ -278,6 +280,61 @@ ZWZ_HD void band_deep_batched(const uint8_t* data, SFn S, LinkFn link, EFn E, ui
         walking = j != kBandNoLink;
     }
     if (visited) *visited = seen;
+    e128 = entry_pack(best, p - best_pos);
+    if (k1 <= Lv::snap_chain) e32 = snap != 0xffffffffu ? snap : e128;
+}
+
+// band_deep as lz_match_band's second pass takes it since round 8 (and its specification): zlib's own scan_end test (longest_match
+// looks at the byte at offset best_len before it compares anything), which the sharers' walk never had.  The walk's first sharer is
+// always compared; a later sharer at position c is compared only if data[c + best] == data[p + best], else it counts as looked at
+// and changes nothing.
+// Same records as band_deep:
+//   * a length is the number of equal leading bytes, so len > best means the bytes 0 .. best agree, the one at offset `best` among
+//     them: a sharer that fails the probe has len <= best and cannot meet the only condition under which best / best_pos change;
+//   * the snapshot (at the first sharer with k > snap_chain, before it is considered), the count limit and the nice stop hang on k
+//     and best alone, and best is what it would have been;
+//   * the probe reads inside the data: the walk goes on only while best < nice <= max_len = min(258, L - p), and a sharer lies in
+//     front of its position, c < p, so c + best < p + best < L (asserted in host builds).
+// Same arguments as band_deep_batched; `visited` receives the sharers looked at (band_deep_batched's number), `compared` those
+// that went through match_len_from.  tests/test_band_pass2_probe_cpu.py.
+template <class Lv = LzDefaultLevel, class SFn, class LinkFn, class EFn>
+ZWZ_HD void band_deep_probed(const uint8_t* data, SFn S, LinkFn link, EFn E, uint32_t first_own, uint32_t u, uint32_t cnt, uint32_t k1,
+                             uint32_t deep, uint32_t L, uint64_t own, uint32_t& e128, uint32_t& e32, uint32_t* visited = nullptr,
+                             uint32_t* compared = nullptr) {
+    const uint32_t p = band_pos(S(u)), lookahead = L - p;
+    const uint32_t max_len = lookahead < kMaxMatch ? lookahead : kMaxMatch, nice = lookahead < Lv::nice ? lookahead : Lv::nice;
+    uint32_t best = 0, best_pos = 0, snap = 0xffffffffu, seen = 0, full = 0;
+    uint32_t j = u - k1;
+    for (;;) {
+        const uint32_t k = u - j;
+        if (k > Lv::snap_chain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
+        const uint32_t c = band_pos(S(j));
+        bool probe = seen == 0u;
+        if (!probe) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+            assert(c < p && best < nice && p + best < L);
+#endif
+            probe = data[c + best] == data[p + best];
+        }
+        seen++;
+        if (probe) {
+            full++;
+            const uint32_t len = match_len_from(data, c, p, deep, max_len);
+            if (len > best) { best = len; best_pos = c; if (len >= nice) break; }
+        }
+        if (j >= first_own) {
+            const uint32_t j2 = link(j);
+            if (j2 == kBandNoLink || u - j2 > cnt) break;
+            j = j2;
+        } else {
+            uint32_t k2 = k + 1u;
+            while (k2 <= cnt && E(u - k2) != own) k2++;
+            if (k2 > cnt) break;
+            j = u - k2;
+        }
+    }
+    if (visited) *visited = seen;
+    if (compared) *compared = full;
     e128 = entry_pack(best, p - best_pos);
     if (k1 <= Lv::snap_chain) e32 = snap != 0xffffffffu ? snap : e128;
 }

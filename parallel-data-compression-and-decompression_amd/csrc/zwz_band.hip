@@ -333,13 +333,12 @@ static_assert(kBandLdsBytes + 1072u + 2u * kBandRuns <= 160u * 1024u, "lz_match_
 #ifndef ZWZ_BAND_WAVES
 #define ZWZ_BAND_WAVES 4
 #endif
-// sharers a batch of the second pass -- the pass in cycle units per 10 000 text chunks: one at a time 6.87 M, 2: 5.97 M, 4: 6.01 M, 8: 6.41 M, 16: 7.32 M (DESIGN.md section 4
-// round 6; 8 and 16 do not fit the 128 registers of a 1 024-thread workgroup without scratch)
-#ifndef ZWZ_BAND_P2_BATCH
-#define ZWZ_BAND_P2_BATCH 4
+// hops a run-ahead step of the second pass may take before the wave meets for a compare again, 0 = as many as it takes -- the pass in cycle units per
+// 10 000 text chunks: 4: 4.41 M, 6: 4.20 M, 8: 4.29 M, 12: 4.53 M, 16: 4.87 M, unbounded: 8.72 M; the batched walk it replaces: 6.02 M
+#ifndef ZWZ_BAND_P2_RUN
+#define ZWZ_BAND_P2_RUN 6
 #endif
-constexpr uint32_t kP2Batch = ZWZ_BAND_P2_BATCH;
-static_assert(kP2Batch >= 1 && kP2Batch <= 32, "lz_match_band: sharers a batch");
+constexpr uint32_t kP2Run = ZWZ_BAND_P2_RUN;
 // Lv (zwz_common.h: LzLevel<N>) = the compression level, a template argument and not a value: the unrolling and the register budget below were tuned
 // with the constants in place, and LzLevel<6> gives the kernel it always was.  What a level changes: the count stops at its max_chain (the halo stays 128
 // entries wide), the short chain's snapshot is taken behind snap_chain candidates, the second pass stops at its nice length.
@@ -642,9 +641,9 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
             for (uint32_t i = kBand + tid; i < m; i += kBandThreads) if ((uint32_t)ck[i - kBand] == 0u) reinterpret_cast<uint16_t*>(S)[2u * i + 1u] = (uint16_t)kBandNoLink;
             __syncthreads();
             ZWZ_STAMP(4);
-            // ---- second pass: the flagged entries, gathered into full waves, walk their sharers (csrc/lz_band.h, band_deep_batched).  An
+            // ---- second pass: the flagged entries, gathered into full waves, walk their sharers (csrc/lz_band.h, band_deep_probed).  An
             // entry's word holds its position and its link, so following a chain is one LDS read a hop; the sixteen bytes behind the
-            // compared ones, which settle all but the longest matches, are read a batch of sharers at a time.
+            // compared ones, which settle all but the longest matches, are read only of the sharers that pass a one-byte probe.
             for (uint32_t i = kBand + tid; i - tid < m; i += kBandThreads) {
                 const bool f = i < m && ((uint32_t)ck[i - kBand] >> 8) != 0u;
                 const uint64_t fm = __builtin_amdgcn_ballot_w64(f);
@@ -685,58 +684,70 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                 // and a hop cost ~1 500 cycles; sixteen settle all but ~1 in 2 000 visits)
                 const uint32_t own2_lo = load_u32(sdata, p + deep), own2_hi = load_u32(sdata, p + deep + 4u);
                 const uint32_t own3_lo = load_u32(sdata, p + deep + 8u), own3_hi = load_u32(sdata, p + deep + 12u);
-                uint32_t best = 0, best_pos = 0, snap = 0xffffffffu;
-                uint32_t j = on ? i - k1 : kBand;
-                uint32_t w = S[j];
-                bool walking = on, slow = false;
-                // kP2Batch sharers a trip (csrc/lz_band.h, band_deep_batched, is the specification).  Only the links hang on one another:
-                //   chase    the batch's entry words, a ds_read_b32 and the `more` test a hop -- no data, no ballot; a lane whose walk
-                //            has ended goes on reading the dummy entry kBand;
-                //   compare  a sharer's sixteen bytes against the entry's, the length without a branch;
-                //   fold     best / snapshot / nice stop in sharer order, by selects: what zlib's walk would have kept.
-                while (__builtin_amdgcn_ballot_w64(walking) != 0) {
-                    uint32_t wv[kP2Batch], nv = walking ? 1u : 0u;
-                    wv[0] = w;
-                    bool more = walking;
-#pragma unroll
-                    for (uint32_t h = 1; h < kP2Batch; h++) {
-                        const uint32_t link = wv[h - 1u] >> 16;
-                        more = more && i - link <= cnt;                             // (kBandNoLink: i - link wraps far beyond any count)
-                        wv[h] = S[more ? link : kBand];
-                        nv += more ? 1u : 0u;
-                    }
-                    const uint32_t link_n = wv[kP2Batch - 1u] >> 16;
-                    const bool more_n = more && i - link_n <= cnt;
-                    const uint32_t wn = S[more_n ? link_n : kBand];             // the next batch's first
-                    // compare + fold, sharer by sharer: the five dwords that hold its sixteen bytes, the length by minimum over the four words'
-                    // first differing bits -- no branch (with one, the compiler reads the upper eight bytes only where the lower eight agree,
-                    // behind a wait of their own)
-                    bool alive = walking;
-                    uint32_t jh = j;
-#pragma unroll
-                    for (uint32_t h = 0; h < kP2Batch; h++) {
-                        const uint32_t q = band_pos(wv[h]), sh = (q + deep) & 3u;
+                // The walk behind a probe (csrc/lz_band.h, band_deep_probed, is the specification and has the proof): a sharer can change the
+                // result only if it is longer than `best`, and then its byte at offset `best` is the entry's -- zlib's scan_end test.  Four visits
+                // in five fail it (tools/exp/band_pass2_probe.py), and a wave of 64 nearly always holds a lane that passes, so masking the compare
+                // per sharer would skip nothing: the lanes run ahead through rejected sharers on their own and meet only for the compares.
+                //   compare    one sharer, for the lanes that stand on a candidate (at first every lane, on its nearest sharer, unprobed): its
+                //              sixteen bytes against the entry's, the length without a branch, best / snapshot / nice stop by selects, the next
+                //              sharer's word asked for beside the data; a lane that improved reloads its probe byte, sdata[p + best];
+                //   run-ahead  hops: the byte at the sharer's offset `best` and the word behind its link, asked for together, so a rejected
+                //              sharer costs one LDS round trip; a lane stops at a probe hit or at its chain's end, the loop ends when no lane
+                //              hops or after kP2Run hops.
+                // The short chain's snapshot is taken at the compares only: best changes nowhere else, so "best in front of the first sharer
+                // with k > snap_chain" is best at the first COMPARED sharer with such a k -- or, if none follows, the final best, which the
+                // record falls back to anyway.  The probe reads inside the data (c + best < p + best < L while best < nice); the reload behind
+                // an improvement that ends the walk may read the slack behind the chunk, and nothing looks at it.
+                // `reach`: the candidates the links lead to -- all of them, or, in front of a halo of another word format, the tile's own.  A walk
+                // that would go on into such a halo is the plain walk's, from the start (`slow`, found out behind the loop).
+                const uint32_t reach = halo_links ? cnt : min(cnt, i - kBand);
+                uint32_t best = 0, best_pos = 0, snap = 0xffffffffu, pb = 0;
+                // (k > snap_chain, asked of a sharer at position q: a bucket's entries lie in position order, so it is "q lies in front of
+                // candidate snap_chain's position" -- one read a walk instead of a candidate number carried through every hop)
+                const uint32_t q_snap = cnt > Lv::snap_chain ? band_pos(S[i - Lv::snap_chain]) : 0u;
+                uint32_t w = S[on ? i - k1 : kBand];
+                bool slow = on && k1 > reach;
+                bool cand = on && !slow, hop = false;
+                while (__builtin_amdgcn_ballot_w64(cand || hop) != 0) {
+                    if (__builtin_amdgcn_ballot_w64(cand) != 0) {
+                        // the five dwords that hold the sharer's sixteen bytes, the length by minimum over the four words' first differing
+                        // bits -- no branch (with one, the compiler reads the upper eight bytes only where the lower eight agree, behind a
+                        // wait of their own)
+                        const uint32_t q = band_pos(w), sh = (q + deep) & 3u;
                         const uint32_t* d = reinterpret_cast<const uint32_t*>(sdata) + ((q + deep) >> 2);
                         const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4];
+                        const uint32_t kn = i - (w >> 16);                          // (kBandNoLink: wraps far beyond any count)
+                        const bool more = kn <= reach;
+                        const uint32_t wn = S[more ? w >> 16 : kBand];
                         uint32_t t0, t1, t2, t3;
                         asm("v_ffbl_b32 %0, %1" : "=v"(t0) : "v"(__builtin_amdgcn_alignbyte(d1, d0, sh) ^ own2_lo));   // 0xffffffff for 0
                         asm("v_ffbl_b32 %0, %1" : "=v"(t1) : "v"(__builtin_amdgcn_alignbyte(d2, d1, sh) ^ own2_hi));
                         asm("v_ffbl_b32 %0, %1" : "=v"(t2) : "v"(__builtin_amdgcn_alignbyte(d3, d2, sh) ^ own3_lo));
                         asm("v_ffbl_b32 %0, %1" : "=v"(t3) : "v"(__builtin_amdgcn_alignbyte(d4, d3, sh) ^ own3_hi));
                         const uint32_t tm = min(min(t0, t1 | 32u), min(t2 | 64u, t3 | 96u));       // first differing bit of the 128
-                        bool v = alive && h < nv;
-                        if (!halo_links) { slow = slow || (v && jh < kBand); v = v && jh >= kBand; }   // into a halo of another format: the plain walk, from the start
                         uint32_t l = deep + (tm >> 3);
-                        if (v && tm == 0xffffffffu) l = match_len_from(sdata, q, p, deep + 16u, max_len);   // (~1 in 2 000 visits)
+                        if (cand && tm == 0xffffffffu) l = match_len_from(sdata, q, p, deep + 16u, max_len);   // (~1 in 2 000 of the batched walk's visits)
                         l = l < max_len ? l : max_len;
-                        if (v && i - jh > Lv::snap_chain && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
-                        if (v && l > best) { best = l; best_pos = q; }
-                        alive = v && best < nice;
-                        jh = wv[h] >> 16;
+                        if (cand && q < q_snap && snap == 0xffffffffu) snap = best ? entry_pack(best, p - best_pos) : 0u;
+                        if (cand && l > best) { best = l; best_pos = q; pb = sdata[p + l]; }
+                        const bool on_ = cand && best < nice && more;               // the walk goes on
+                        hop = hop || on_;
+                        if (on_) w = wn;
+                        cand = false;
                     }
-                    walking = alive && more_n;
-                    j = link_n; w = wn;
+                    for (uint32_t r = 0; (kP2Run == 0u || r < kP2Run) && __builtin_amdgcn_ballot_w64(hop) != 0; r++) {
+                        const uint32_t cb = sdata[band_pos(w) + best];
+                        const uint32_t kn = i - (w >> 16);
+                        const bool more = kn <= reach;
+                        const uint32_t wn = S[more ? w >> 16 : kBand];
+                        const bool hit = cb == pb;
+                        cand = cand || (hop && hit);
+                        hop = hop && !hit && more;
+                        if (hop) w = wn;
+                    }
                 }
+                // (w is the last sharer the lane stood on: a walk that ended below `nice` because its next link leads into the halo)
+                if (!halo_links) slow = slow || (on && best < nice && i - (w >> 16) <= cnt && i - (w >> 16) > reach);
                 uint32_t e128 = entry_pack(best, p - best_pos), e32 = snap != 0xffffffffu ? snap : e128;
                 if (slow) {
                     const uint64_t own = (uint64_t)load_u32(sdata, p + off) | (uint64_t)load_u32(sdata, p + off + 4u) << 32;
