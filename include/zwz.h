@@ -376,8 +376,9 @@ int zwz_inflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char 
  * ZWZ_E_FORMAT wherever one is read.
  * Readable extents: the byte copies read whole aligned 4-byte words, so an index on the device and every output range are readable up
  * to their length rounded up to 16 (an index's length is a multiple of 16 already).
- * Not in this version: an index for a gzip stream of several members (none is made), an index built in legs for a stream of 2^29
- * compressed bytes or more, compressed windows, decoding a touched segment only as far as the last byte asked for. */
+ * Not in this version: an index for a gzip stream of several members (none is made), compressed windows, decoding a touched segment
+ * only as far as the last byte asked for.  (A stream of 2^29 compressed bytes or more gets its index from zwz_inflate_legs_dev below;
+ * the file calls do not use it yet: zwz_inflate_index_file and zwz_inflate_stream_file keep the one-launch limits they state.) */
 /* The most an index of a stream that decodes to decoded_cap bytes takes at this span (0: 1 MiB); 0 for a span that is not allowed. */
 uint64_t zwz_inflate_index_bound(uint64_t decoded_cap, uint32_t span);
 /* zwz_inflate_streams_dev that also writes every stream's index.  The first eleven arguments, the decoded bytes, d_out_len and
@@ -390,6 +391,35 @@ int zwz_inflate_streams_index_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, c
                                   uint32_t n, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
                                   uint64_t *d_out_len, uint32_t *d_status, uint32_t span, uint8_t *d_idx,
                                   const uint64_t *d_idx_off, const uint64_t *d_idx_cap, uint64_t *d_idx_len);
+/* zwz_inflate_streams_index_dev for streams of ANY length, in LEGS.  A leg is one launch of a stream's wave over a window of its input
+ * and a window of its output that fit the kernel's 32-bit positions; everything 64 bits wide is carried from leg to leg.  While it
+ * decodes, the wave keeps its latest RESTART POINT: the last block header at which a checkpoint was due (by the index's rule and span,
+ * whether or not an index is made) or the last gzip member start.  A leg whose window runs out before the stream does is rewound: the
+ * next leg starts at the restart point, with the up to 32 KiB of output in front of it as its window, and decodes again what lay behind
+ * it.  A leg that is rewound to the very point it started from gets double the window that ran out; past 2^29 - 16 input or 2^32 - 16
+ * output bytes the stream is ZWZ_STREAM_TOO_LARGE with d_out_len[i] = the last restart point's decoded offset, so the limits hold for
+ * one stretch between two restart points, not for the stream.
+ * in_off, in_len, out_off, out_cap, idx_off and idx_cap are HOST arrays of n (zwz_deflate_streams_dev's convention), lengths and
+ * capacities 64-bit and not limited; d_in, d_out, d_idx, d_out_len, d_status and d_idx_len are device memory.  Alignment rules are
+ * zwz_inflate_streams_dev's.  d_idx may be NULL (with idx_off, idx_cap, d_idx_len): decode only; restart points are then still taken at
+ * `span` (0: the context's "index_span_bytes").
+ * For every stream within the one-launch limits, whatever the leg sizes, the decoded bytes, d_out_len[i], d_status[i], d_idx_len[i]
+ * and the index bytes are exactly zwz_inflate_streams_index_dev's -- damaged and cut streams and streams of several members
+ * included -- and no byte outside [out_off[i], out_off[i] + out_cap[i]) is written.  Checkpoints are due by the same rule and the same
+ * running offset as in one launch: nothing is forced at a leg's end.  Entries carry 64-bit bit and decoded offsets, and ISIZE is
+ * checked against the member's length mod 2^32.  The checksum is taken from pieces of the whole output in parallel once every stream
+ * has ended.  An index of 2^32 bytes or more is not made.
+ * legs (HOST, 3 n words, may be NULL): per stream the legs run, the legs rewound and the windows grown.
+ * One launch per round holds one wave per unfinished stream, and the call waits for the context's stream every round: NOT
+ * asynchronous; the last kernels are still queued when it returns (zwz_ctx_sync before reading results).
+ * Context options (zwz_ctx_set_option, decimal, "" restores the default):
+ *   "leg_bytes"      268435456      4096 .. 2^29 - 16, a multiple of 16   compressed bytes a leg may read
+ *   "leg_out_bytes"  2^32 - 65536   65536 .. that value                   decoded bytes a leg may write
+ * A stream runs at the one-wave rate, and a rewind pays for what it decodes twice: this call removes a limit, it makes nothing faster. */
+int zwz_inflate_legs_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
+                         uint8_t *d_out, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *d_out_len, uint32_t *d_status,
+                         uint32_t span, uint8_t *d_idx, const uint64_t *idx_off, const uint64_t *idx_cap, uint64_t *d_idx_len,
+                         uint32_t *legs);
 /* ONE stream of any length (d_in, in_len bytes, 16-byte aligned, readable up to its length rounded up to 16) decoded whole with its
  * index, one wave per segment: the 2^29 / 2^32 limits hold for a single segment only (else ZWZ_STREAM_TOO_LARGE).  idx (idx_len
  * bytes) is HOST memory, for planning; d_idx is the same bytes on the device (16-byte aligned), or NULL: the call then uploads them.

@@ -120,6 +120,7 @@ def lib():
         L.zwz_inflate_index_bound.argtypes = [u64, u32]
         L.zwz_inflate_streams_index_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
         L.zwz_inflate_indexed_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp]
+        L.zwz_inflate_legs_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         L.zwz_inflate_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp, u32, vp]
         L.zwz_inflate_indexed_batch_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.zwz_inflate_read_ranges_batch_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp]
@@ -323,6 +324,80 @@ class Codec:
                                                    d_out.data_ptr(), d_out_off.data_ptr(), d_out_cap.data_ptr(), d_out_len.data_ptr(),
                                                    d_status.data_ptr(), int(span), d_idx.data_ptr(), d_idx_off.data_ptr(), d_idx_cap.data_ptr(),
                                                    d_idx_len.data_ptr()), "zwz_inflate_streams_index_dev")
+
+    def inflate_legs_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status, span=0, d_idx=None, idx_off=None,
+                         idx_cap=None, d_idx_len=None, legs=None):
+        """zwz_inflate_legs_dev: inflate_streams_index_dev for streams of any length, decoded in legs.  in_off, in_len, out_off, out_cap,
+        idx_off, idx_cap: HOST sequences or numpy arrays of one element per stream; d_in, d_out, d_idx: 16-byte aligned CUDA uint8 tensors;
+        d_out_len, d_idx_len (int64), d_status (int32): CUDA tensors of n.  d_idx None: decode only.  legs: a numpy uint32 array of 3 n
+        that receives per stream the legs run, the legs rewound and the windows grown, or None.  The results are complete after sync()."""
+        import numpy as np
+        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
+        n = len(arr[0])
+        if any(len(a) != n for a in arr):
+            raise ValueError("in_off, in_len, out_off and out_cap must have one element per stream")
+        ia = None
+        if d_idx is not None:
+            ia = [np.ascontiguousarray(a, dtype=np.uint64) for a in (idx_off, idx_cap)]
+            if any(len(a) != n for a in ia) or d_idx_len is None:
+                raise ValueError("idx_off, idx_cap and d_idx_len go with d_idx, one element per stream")
+        if legs is not None and (legs.dtype != np.uint32 or legs.size != 3 * n or not legs.flags["C_CONTIGUOUS"]):
+            raise ValueError("legs must be a contiguous uint32 array of 3 n")
+        _check(lib().zwz_inflate_legs_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n, d_out.data_ptr(),
+                                          arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(), d_status.data_ptr(), int(span),
+                                          d_idx.data_ptr() if d_idx is not None else None, ia[0].ctypes.data if ia else None,
+                                          ia[1].ctypes.data if ia else None, d_idx_len.data_ptr() if d_idx is not None else None,
+                                          legs.ctypes.data if legs is not None else None), "zwz_inflate_legs_dev")
+
+    def inflate_legs(self, datas, wrap="gzip", span=None, index=True, out_caps=None, with_legs=False):
+        """[bytes of one stream each] -> [(decoded bytes, index bytes or b"", status)] through the decode in legs: streams of any length,
+        at the context's "leg_bytes" / "leg_out_bytes".  Nothing is raised for a failing stream: its status (STREAM_*) is returned with
+        what was decoded before the stop.  index=False decodes only.  out_caps: the capacity of every stream (None: guessed from the
+        input and regrown while any stream ends with STREAM_OVERFLOW).  with_legs: also return an (n, 3) array of the legs run, the legs
+        rewound and the windows grown per stream."""
+        import numpy as np
+        import torch
+        w = WRAPS.get(wrap, wrap)
+        datas = [bytes(d) for d in datas]
+        n = len(datas)
+        span = int(span or 0)
+        if n == 0:
+            return ([], np.zeros((0, 3), dtype=np.uint32)) if with_legs else []
+        if lib().zwz_inflate_index_bound(1, span) == 0:
+            raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
+        dev = torch.device("cuda", self.device)
+        d_in, offs, lens = self._batch_input(torch, np, datas)
+        caps = np.array([max(4 * len(d), 1 << 16) for d in datas] if out_caps is None else [int(x) for x in out_caps], dtype=np.uint64)
+        while True:
+            slot = (caps + np.uint64(15)) // np.uint64(16) * np.uint64(16) + np.uint64(16)
+            ooff = np.zeros(n, dtype=np.uint64)
+            ooff[1:] = np.cumsum(slot[:-1])
+            d_out = torch.empty(int(ooff[-1] + slot[-1]), dtype=torch.uint8, device=dev)
+            d_len = torch.zeros(n, dtype=torch.int64, device=dev)
+            d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+            d_idx = ioff = icap = d_ilen = None
+            if index:
+                icap = np.array([lib().zwz_inflate_index_bound(int(x), span) for x in caps], dtype=np.uint64)
+                ioff = np.zeros(n, dtype=np.uint64)
+                ioff[1:] = np.cumsum(icap[:-1])
+                d_idx = torch.empty(int(ioff[-1] + icap[-1]), dtype=torch.uint8, device=dev)
+                d_ilen = torch.zeros(n, dtype=torch.int64, device=dev)
+            legs = np.zeros(3 * n, dtype=np.uint32)
+            torch.cuda.synchronize(dev)
+            self.inflate_legs_dev(w, d_in, offs, lens, d_out, ooff, caps, d_len, d_st, span, d_idx, ioff, icap, d_ilen, legs)
+            self.sync()
+            st = d_st.cpu().numpy()
+            if out_caps is None and (st == STREAM_OVERFLOW).any():
+                caps = np.where(st == STREAM_OVERFLOW, caps * np.uint64(2), caps)
+                continue
+            olen = d_len.cpu().numpy()
+            ilen = d_ilen.cpu().numpy() if index else np.zeros(n, dtype=np.int64)
+            res = []
+            for i in range(n):
+                dec = d_out[int(ooff[i]):int(ooff[i]) + int(olen[i])].cpu().numpy().tobytes()
+                idx = d_idx[int(ioff[i]):int(ioff[i]) + int(ilen[i])].cpu().numpy().tobytes() if index and ilen[i] else b""
+                res.append((dec, idx, int(st[i])))
+            return (res, legs.reshape(n, 3)) if with_legs else res
 
     def inflate_indexed_dev(self, d_in, in_len, index, d_out, out_cap, d_out_len, d_status, d_segments=None, d_idx=None):
         """zwz_inflate_indexed_dev: ONE stream (a 16-byte aligned CUDA uint8 tensor, in_len bytes) decoded whole with its index (bytes),

@@ -376,6 +376,14 @@ int zwz_ctx_set_option(zwz_ctx* c, const char* name, const char* value) {
         const unsigned long long x = strtoull(v.c_str(), &end, 10);
         if (!v.empty() && (*end || end == v.c_str() || x > kIdxSpanMax || !index_span_ok((uint32_t)x))) return ZWZ_E_INVALID;
         c->index_span_bytes = v.empty() ? kIdxSpanDefault : (uint32_t)x;
+    } else if (n == "leg_bytes" || n == "leg_out_bytes") {
+        // zwz_inflate_legs_dev (leg_core.h): the compressed bytes a leg may read (a multiple of 16), the decoded bytes it may write
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v.c_str(), &end, 10);
+        const bool in = n == "leg_bytes";
+        if (!v.empty() && (*end || end == v.c_str() || x < (in ? kLegBytesMin : kLegOutBytesMin) || x > (in ? kLegMaxIn : kLegOutBytesDefault) || (in && (x & 15u)))) return ZWZ_E_INVALID;
+        if (in) c->leg_bytes = v.empty() ? kLegBytesDefault : x;
+        else c->leg_out_bytes = v.empty() ? kLegOutBytesDefault : x;
     } else if (n == "zip_force_zip64") {
         if (v == "0" || v.empty()) c->zip_force_zip64 = 0; else if (v == "1") c->zip_force_zip64 = 1; else return ZWZ_E_INVALID;
     } else if (n == "zip_slice_bytes") {

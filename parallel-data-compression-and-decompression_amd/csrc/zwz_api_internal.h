@@ -37,11 +37,14 @@ enum BufId {
     kBufZipDev,          // ZIP: the per-entry and per-tile arrays of one call, and their pinned twin
     kBufIndex0,          // seek index (zwz_index.cpp): segment records, window moves, checksum pieces and flags of one call, and its pinned twin
     kBufIndex1,          // seek index: an index uploaded for a call, or the scratch slots of a range read
+    kBufLegs,            // decode in legs (zwz_legs.cpp): the per-stream arrays of one call, and their pinned twin
+    kBufLegPieces,       // decode in legs: the checksum pieces of one call
     kNumDeviceBufs,
     kBufStageHost = kNumDeviceBufs, kBufRangeHost, kBufStreamsHost,
     kBufSplitHost,       // split inflate: the per-stream arrays a call uploads (read by copies that may still be queued when it returns)
     kBufZipHost,
     kBufIndexHost,
+    kBufLegsHost,
     kNumBufs
 };
 
@@ -72,6 +75,8 @@ struct zwz_ctx {
     uint32_t split_min_bytes = zwz::kSplitMinBytes, split_budget = zwz::kSplitBudget, split_max_candidates = zwz::kSplitMaxCandidates;
     uint32_t split_slice_bytes = zwz::kSplitSliceBytes;      // zwz_inflate_stream_file: "split_slice_bytes"
     uint32_t index_span_bytes = zwz::kIdxSpanDefault;        // zwz_inflate_streams_index_dev with span 0: "index_span_bytes"
+    // decode in legs (zwz_legs.cpp): options "leg_bytes" and "leg_out_bytes" (leg_core.h's defaults)
+    uint64_t leg_bytes = zwz::kLegBytesDefault, leg_out_bytes = zwz::kLegOutBytesDefault;
     // ZIP (zwz_zip.cpp): options "zip_force_zip64" and "zip_slice_bytes"; the last call's copy out of kBufZipHost has run
     uint32_t zip_force_zip64 = 0;
     uint64_t zip_slice_bytes = 268435456ull;

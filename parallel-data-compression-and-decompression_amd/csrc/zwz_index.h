@@ -51,6 +51,16 @@ struct IndexBatch {
 };
 hipError_t launch_index_batch_finish(const CrcTables* tab, const IndexBatch& b, uint32_t cu_count, hipStream_t s);
 
+// The decode in legs (zwz_inflate_legs_dev): the checksum of out[out_off, out_off + total) of every stream from the same pieces, joined
+// and compared with `expect`; status[i] = ZWZ_STREAM_CHECKSUM where they differ.  Of an IndexStream it reads out_off, total (the checked
+// length), head, wrap, expect, piece0, pieces, refused (the stream got its verdict from the host) and nseg (0: no checksum was read).
+struct LegsCheck {
+    const uint8_t* out; const IndexStream* rec; uint32_t n, wrap;
+    uint64_t* piece_off; uint32_t* piece_len; uint32_t* piece_val; uint32_t pieces;
+    uint32_t* status;
+};
+hipError_t launch_legs_check(const CrcTables* tab, const LegsCheck& b, uint32_t cu_count, hipStream_t s);
+
 // Range reads: touched segment i's decoded bytes start at slots + slot_off[i]; its pieces row[i] .. row[i + 1], the first nlong[i] of
 // them long, go to out (bgzf_verify_extract's dealing).  Pieces of a segment whose bad[i] is set are not copied.
 hipError_t launch_index_extract(const uint8_t* slots, const uint64_t* slot_off, const uint32_t* row, const uint32_t* nlong, const RangePiece* pieces,

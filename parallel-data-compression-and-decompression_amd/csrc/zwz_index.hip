@@ -146,6 +146,19 @@ __global__ void __launch_bounds__(64) index_batch_finish_kernel(IndexBatch b) {
     }
 }
 
+// The decode in legs (zwz_legs.cpp), one wave per stream: the join of the pieces of its checked output against the checksum its
+// trailers gave; a mismatch beats the provisional status (stream_core.h: stream_verdict).  nseg: whether any checksum was read.
+__global__ void __launch_bounds__(64) legs_finish_kernel(const IndexStream* rec, uint32_t n, const uint32_t* piece_len, const uint32_t* piece_val, uint32_t* status) {
+    const uint32_t lane = lane_id();
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const IndexStream r = rec[i];                                          // (wave-uniform)
+        if (r.refused || !r.nseg) continue;
+        const uint32_t acc = r.wrap == kWrapGzip ? index_join_pieces<CrcSum>(piece_len + r.piece0, piece_val + r.piece0, r.pieces, lane)
+                                                 : index_join_pieces<AdlerSum>(piece_len + r.piece0, piece_val + r.piece0, r.pieces, lane);
+        if (lane == 0 && acc != r.expect) status[i] = kStrChecksum;
+    }
+}
+
 // bgzf_verify_extract's dealing of the pieces: long ones by the workgroup, short ones a wave each
 __global__ void __launch_bounds__(kBgzfThreads) index_extract_kernel(const uint8_t* slots, const uint64_t* slot_off, const uint32_t* row, const uint32_t* nlong,
                                                                      const RangePiece* pieces, uint32_t m, const uint32_t* bad, uint8_t* out) {
@@ -201,6 +214,17 @@ hipError_t launch_index_batch_finish(const CrcTables* tab, const IndexBatch& b, 
         if (a) index_adler_kernel<<<grid_for(a, cu_count, 8u), kBgzfThreads, 0, s>>>(b.out, b.piece_off + g, b.piece_len + g, b.piece_val + g, a);
     }
     index_batch_finish_kernel<<<grid_for(b.n, cu_count, 16u), 64, 0, s>>>(b);
+    return hipGetLastError();
+}
+
+hipError_t launch_legs_check(const CrcTables* tab, const LegsCheck& b, uint32_t cu_count, hipStream_t s) {
+    if (!b.n || b.wrap == kWrapRaw) return hipSuccess;       // raw: no checksum, the provisional status is final
+    if (b.pieces) {
+        index_batch_pieces_kernel<<<grid_for(b.n, cu_count, 8u), 256, 0, s>>>(b.rec, b.n, b.piece_off, b.piece_len);
+        if (b.wrap == kWrapGzip) { const hipError_t e = launch_crc32_blocks(tab, b.out, b.piece_off, b.piece_len, b.pieces, b.piece_val, cu_count, s); if (e != hipSuccess) return e; }
+        else index_adler_kernel<<<grid_for(b.pieces, cu_count, 8u), kBgzfThreads, 0, s>>>(b.out, b.piece_off, b.piece_len, b.piece_val, b.pieces);
+    }
+    legs_finish_kernel<<<grid_for(b.n, cu_count, 16u), 64, 0, s>>>(b.rec, b.n, b.piece_len, b.piece_val, b.status);
     return hipGetLastError();
 }
 

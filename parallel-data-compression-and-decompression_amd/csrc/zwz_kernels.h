@@ -7,6 +7,7 @@
 #include "zwz_common.h"
 #include "lz_band.h"
 #include "rle_core.h"
+#include "leg_core.h"
 
 namespace zwz {
 
@@ -148,8 +149,16 @@ struct StreamParams {
     uint4* rec;                // per stream (checked length, expected checksum, has a checksum, provisional status): stream_core.h's StreamRecord
     uint32_t wrap;             // stream_core.h: kWrapRaw / kWrapZlib / kWrapGzip
     // the split forms (split_core.h), appended so that the stream form's arguments lie where they lay
-    const uint4* seg;          // per segment: (p & 15, stream, first output byte within the stream's range, count); measuring: (p & 15, stream, -, p & ~15)
-    uint4* meas;               // measuring form: a SegMeasure per segment
+    // (the leg form, leg_core.h, reads out_off, wrap, span and -- null: no index wanted -- idx, idx_off, idx_cap, idx_len; its two arrays share the
+    // split forms' slots, which it does not use, so that the layout every other form reads its arguments from is what it was)
+    union {
+        const uint4* seg;      // per segment: (p & 15, stream, first output byte within the stream's range, count); measuring: (p & 15, stream, -, p & ~15)
+        const LegPlan* legw;   // leg form, per stream: the windows of this leg
+    };
+    union {
+        uint4* meas;           // measuring form: a SegMeasure per segment
+        LegState* leg;         // leg form, per stream: the state the leg starts from, and the one it leaves
+    };
     uint32_t* bad;             // segment form: set for a stream one of whose segments did not end as measured
     // the index forms (index_core.h), appended likewise
     const uint4* seg2;         // indexed-segment form, per segment: (address in `out` of the byte `hist` in front of the segment's first, low / high; end bit from the wave's input; -)
@@ -185,6 +194,15 @@ struct InflateIndexedArgs {
     uint4* order;              // n entries of scratch
     const uint4* seg; const uint4* seg2; uint32_t* bad;
     uint32_t serial_header;
+};
+// zwz_inflate_legs_dev: one wave per unfinished stream (kFormLeg).  order[j] = (offset in `in` of the window of the j-th unfinished stream,
+// low / high; the window's bytes; the stream's number), filled by the host; out_off, idx_off, idx_cap: device copies of the call's arrays
+struct InflateLegArgs {
+    const uint8_t* in; const uint4* order; uint32_t n;
+    uint8_t* out; const uint64_t* out_off; uint64_t* out_len; uint32_t* status;
+    uint8_t* idx; const uint64_t* idx_off; const uint64_t* idx_cap; uint64_t* idx_len; uint32_t span;
+    const LegPlan* legw; LegState* leg;
+    uint32_t wrap, serial_header;
 };
 // match_mode: auto = lz_dense_list decides per chunk between links + lz_match (+ lz_parse) and sort + lz_lazy; walk / band / lazy = every chunk through
 // that search; autoband / autolazy = the per-chunk choice with the band + lz_parse / lz_lazy for the chain-heavy ones.  Same bytes whichever runs.
@@ -228,6 +246,7 @@ hipError_t launch_inflate_streams(const InflateStreamArgs& a, hipStream_t s);   
 hipError_t launch_inflate_split(const InflateSplitArgs& a, hipStream_t s);         // order + inflate_kernel's measuring or segment form
 hipError_t launch_inflate_mark(const InflateMarkArgs& a, hipStream_t s);           // order + inflate_kernel's marking form (statuses provisional)
 hipError_t launch_inflate_indexed(const InflateIndexedArgs& a, hipStream_t s);     // order + inflate_kernel's indexed-segment form
+hipError_t launch_inflate_legs(const InflateLegArgs& a, hipStream_t s);            // inflate_kernel's leg form (statuses provisional)
 struct CrcTables;                                                                  // zwz_bgzf.h
 // zwz_stream.hip: the checksum of every stream's checked output (rec) and its final status
 hipError_t launch_stream_check(const CrcTables* tab, const uint8_t* out, const uint64_t* out_off, const uint4* rec, uint32_t n,

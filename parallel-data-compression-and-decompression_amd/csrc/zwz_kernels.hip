@@ -2019,6 +2019,16 @@ static __device__ __forceinline__ uint32_t wave_dyn_lengths(const uint8_t* ring,
     return bp;
 }
 
+// What inflate_kernel's leg form keeps beyond the other forms' registers (leg_core.h).  Lane 0: the state as it stands and the latest
+// restart point.  Wave-uniform: the first input byte and the first decoded byte of the leg's windows in the stream, whether the windows
+// reach the stream's end / its capacity, and the start -- its kind, its bit and its first output byte in the windows, its hist.
+template <bool kOn> struct LegRegs {
+    LegState cur, snap;
+    uint64_t in, out;
+    uint32_t infin, outfin, start, bit, first, hist;
+};
+template <> struct LegRegs<false> {};
+
 struct InflateWaveMem {
     InflateTables t;
     uint8_t lens[320];
@@ -2045,6 +2055,11 @@ struct InflateWaveMem {
 // bit of the first member and whether a second one followed.  kFormIndexed (4): the segment form for a segment of an index: it starts at
 // any BIT, its origin lies `hist` bytes in front of its first output byte (those bytes are in memory already: index_place_kernel), and
 // it ends at the block header whose first bit is the segment's end bit, or behind the final block.  1, 2 and 0 compile as before these two.
+// kFormLeg (5; zwz_inflate_legs_dev, leg_core.h): the marking form over a WINDOW of a stream's input and output, sp.legw[i], with a start
+// state and a resume record, sp.leg[i]: it starts in front of the wrapper's header, at a block header with its window in memory (as
+// kFormIndexed) or at a member start, carries what is 64 bits wide in a LegState, keeps the latest restart point in lane 0's registers, and
+// leaves either the stream's provisional verdict or -- when a window ran out before the stream did -- the restart point for the next leg.
+// 0 to 4 compile as before it.
 template <bool kSerialHeader, bool kStream, uint32_t kSplit = 0>
 __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                   const uint32_t* __restrict__ in_len, uint32_t n,
@@ -2067,6 +2082,8 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     uint32_t seg_body = 0, seg_start = 0, seg_base = 0, seg_stream = 0, seg_fin = kSegBad;   // kSplit
     constexpr bool kSeg = kSplit == 1 || kSplit == 2 || kSplit == kFormIndexed;              // the wave's unit is a segment
     constexpr bool kMark = kSplit == kFormMark;
+    constexpr bool kLeg = kSplit == kFormLeg;
+    LegRegs<kLeg> lg;                                  // kFormLeg (empty otherwise)
     uint32_t seg_bit = 0, seg_origin = 0, seg_end = 0, seg_last = 0;                         // kFormIndexed
     if constexpr (kSeg) {
         static_assert(kStream, "the split forms are stream forms");
@@ -2085,6 +2102,20 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
             dst = out + (((uint64_t)a_hi << 32 | a_lo) & ~15ull);
             seg_origin = a_lo & 15u; seg_start = seg_origin + sg.w; cap = seg_start + sg.z;
         }
+    } else if constexpr (kLeg) {
+        static_assert(kStream, "the leg form is a stream form");
+        auto uni64 = [](uint64_t v) { return (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32 | __builtin_amdgcn_readfirstlane((uint32_t)v); };
+        const LegPlan w = sp.legw[chunk];
+        lg.cur = sp.leg[chunk]; lg.snap = lg.cur;
+        lg.in = uni64(w.in_base); lg.out = uni64(w.out_base);
+        lg.infin = __builtin_amdgcn_readfirstlane(w.in_final); lg.outfin = __builtin_amdgcn_readfirstlane(w.out_final);
+        lg.start = __builtin_amdgcn_readfirstlane(lg.cur.start);
+        // (positions inside the wave are relative to the windows: leg_next keeps them below 2^32)
+        lg.bit = lg.start == kLegFresh ? 0u : __builtin_amdgcn_readfirstlane((uint32_t)(lg.cur.bit - lg.in * 8u));
+        lg.first = __builtin_amdgcn_readfirstlane((uint32_t)(lg.cur.out - lg.out));
+        lg.hist = __builtin_amdgcn_readfirstlane(leg_hist(lg.cur));
+        dst = out + sp.out_off[chunk] + lg.out;       // 16-byte aligned: the window's base is a multiple of 16
+        cap = __builtin_amdgcn_readfirstlane(w.out_len);
     } else if constexpr (kStream) {
         const uint64_t cap64 = sp.out_cap[chunk];
         if (oe.z >= kStreamMaxIn || cap64 >= kStreamMaxOut) {     // (the order clips a 64-bit length to 32 bits)
@@ -2133,6 +2164,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     uint64_t mk_cap = 0, mk_bytes = kIdxHeader;
     uint32_t mk_count = 0, mk_last = 0, mk_full = 0, mk_have_end = 0, mk_end = 0, mk_second = 0;
     if constexpr (kMark) { mk_idx = sp.idx + sp.idx_off[chunk]; mk_cap = sp.idx_cap[chunk]; }
+    if constexpr (kLeg) if (sp.idx) { mk_idx = sp.idx + sp.idx_off[chunk]; mk_cap = sp.idx_cap[chunk]; }
     // kStream: the first byte at or after q that is not zero, or nin (the zeros around gzip members), the wave 1 KiB a step
     auto skip_zeros = [&](uint32_t q) -> uint32_t {
         q = __builtin_amdgcn_readfirstlane(q);
@@ -2154,12 +2186,56 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         }
         return nin;
     };
+    // kFormLeg: a member start at byte q of the window, behind the trailer of the member before: the zeros, then another member (-> 1, the
+    // reader at its body), the stream's end or its verdict (-> 0).  A window that ends in the zeros, or one byte behind them, says nothing
+    // unless the stream ends there too: more input is needed, and zeros that reach the window's end are behind the restart point.
+    auto leg_member = [&](uint32_t q) -> uint32_t {
+      if constexpr (kLeg) {
+        const uint32_t nz = skip_zeros(q);
+        if (!lg.infin && nin - nz < 2u) {
+            if (lane == 0) {
+                if (nz >= nin) leg_at_member(lg.cur, lg.snap, lg.in + nin, lg.out + st.out_pos);
+                st.status = kInfNeedInput;
+            }
+            return 0u;
+        }
+        uint32_t body = 0, sst = kInfRunning;
+        if (lane == 0) { sst = gzip_next_member(src, nin, nz, &body); st.status = sst; st.last = 0; }
+        body = __builtin_amdgcn_readfirstlane(body);
+        if (__builtin_amdgcn_readfirstlane(sst) != kInfRunning) return 0u;
+        if (lane == 0) { lg.cur.mk_second = 1; lg.cur.origin = lg.out + st.out_pos; }
+        origin = __builtin_amdgcn_readfirstlane(st.out_pos);
+        top_up(body);
+        if (lane == 0) st.br.seek_bit(body * 8u);
+        return 1u;
+      } else return 0u;
+    };
     if constexpr (kSeg) {
         if (lane == 0) {
             st.br.init(m.ring, nin, kInfRing - 1u); st.out_pos = seg_start; st.last = 0; st.status = kInfRunning;
             if constexpr (kSplit == kFormIndexed) st.br.seek_bit(seg_body * 8u + seg_bit); else st.br.seek_bit(seg_body * 8u);
         }
         go = 1;                                        // (seg_body < 16: top_up(0) has the bytes)
+    } else if constexpr (kLeg) {
+        if (lane == 0) { st.br.init(m.ring, nin, kInfRing - 1u); st.out_pos = lg.first; st.last = 0; st.status = kInfRunning; }
+        if (lg.start == kLegBlock) {                  // the window's hist bytes are in memory in front of the first output byte
+            origin = lg.first - lg.hist;
+            top_up(lg.bit >> 3);
+            if (lane == 0) st.br.seek_bit(lg.bit);
+            go = 1;
+        } else if (lg.start == kLegMember) {
+            go = leg_member(lg.bit >> 3);
+        } else {                                       // fresh: as the stream form begins
+            const uint32_t nz = sp.wrap == kWrapGzip ? skip_zeros(0) : nin;
+            uint32_t body = 0, sst = kInfRunning;
+            if (lane == 0) { sst = stream_begin(sp.wrap, src, nin, nz, &body); st.status = sst; }
+            body = __builtin_amdgcn_readfirstlane(body);
+            go = __builtin_amdgcn_readfirstlane(sst) == kInfRunning;
+            if (go) {
+                top_up(body);
+                if (lane == 0) st.br.seek_bit(body * 8u);
+            }
+        }
     } else if constexpr (kStream) {
         const uint32_t nz = sp.wrap == kWrapGzip ? skip_zeros(0) : nin;
         uint32_t body = 0, sst = kInfRunning;
@@ -2199,6 +2275,9 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                     mk_count++; mk_last = st.out_pos; mk_bytes = need;
                 }
             }
+        }
+        if constexpr (kLeg) {
+            if (lane == 0) leg_at_header(lg.cur, lg.snap, lg.in * 8u + st.br.bit_pos(), lg.out + st.out_pos, sp.span, mk_idx, mk_cap);
         }
         {   // the block header: lane 0 reads the bits, the wave builds the tables (inflate_core.h: inflate_block_rest, in its pieces)
             uint32_t v = 0, ok = 0;
@@ -2590,6 +2669,22 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
             if (lane == 0) fin = split_stop(st.last, kind == kBlkStored && slen == 0u);
             seg_fin = __builtin_amdgcn_readfirstlane(fin);
             if (seg_fin != kSegBad) break;
+        } else if constexpr (kLeg) {
+            // the end of a member, as the stream form's below, on 64-bit offsets; the next member's start is a restart point
+            uint32_t more = 0, next = 0;
+            if (lane == 0 && st.last) {
+                if (!lg.cur.mk_have_end) { lg.cur.mk_have_end = 1; lg.cur.mk_end = lg.in * 8u + st.br.bit_pos(); }
+                const uint32_t q = (st.br.bit_pos() + 7u) >> 3;
+                const uint64_t at = lg.out + st.out_pos;
+                st.status = leg_trailer(sp.wrap, src, nin, q, at, at - lg.cur.origin, lg.cur, &next);
+                more = st.status == kInfRunning;
+                if (more) leg_at_member(lg.cur, lg.snap, lg.in + next, at);
+            }
+            if (__builtin_amdgcn_readfirstlane(more)) {
+                if (leg_member(__builtin_amdgcn_readfirstlane(next))) continue;
+                break;
+            }
+            if (__builtin_amdgcn_readfirstlane((uint32_t)(st.status != kInfRunning))) break;
         } else if constexpr (kStream) {
             // the end of a member: its trailer; a gzip stream goes on behind the zeros that may follow with its next member
             uint32_t more = 0, next = 0;
@@ -2626,6 +2721,27 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
     } else if constexpr (kSplit == kFormIndexed) {
         // (an index that lies -- a wrong bit, offset or hist, an end bit inside a block -- ends here: the decoder stopped, or stands elsewhere)
         if (lane == 0 && !index_segment_good(st.status, st.br.bit_pos(), seg_end, st.out_pos, cap, st.last, seg_last)) sp.bad[seg_stream] = 1;
+    } else if constexpr (kLeg) {
+        if (lane == 0) {
+            if (leg_rewound(st.status, lg.infin != 0u, lg.outfin != 0u)) {
+                lg.snap.done = 0; lg.snap.status = st.status;
+                sp.leg[chunk] = lg.snap;
+            } else {
+                lg.cur.done = 1; lg.cur.status = st.status; lg.cur.end_out = lg.out + st.out_pos;
+                sp.leg[chunk] = lg.cur;
+                sp.out_len[chunk] = lg.cur.end_out; status[chunk] = st.status;
+                if (sp.idx) {
+                    // provisional, as the marking form's: index_windows_kernel fills the windows in and seals the header
+                    const bool made = !lg.cur.mk_full && !lg.cur.mk_second && lg.cur.mk_have_end && lg.cur.mk_count;
+                    sp.idx_len[chunk] = made ? (lg.cur.mk_bytes + 15u) & ~15ull : 0u;
+                    if (made) {
+                        uint32_t* h = reinterpret_cast<uint32_t*>(mk_idx);
+                        h[6] = (uint32_t)lg.cur.end_out; h[7] = (uint32_t)(lg.cur.end_out >> 32); h[8] = lg.cur.mk_count;
+                        h[10] = (uint32_t)lg.cur.mk_end; h[11] = (uint32_t)(lg.cur.mk_end >> 32); h[12] = lg.cur.has_check ? lg.cur.expect : 0u;
+                    }
+                }
+            }
+        }
     } else if constexpr (kStream) {
         if (lane == 0) {
             sp.out_len[chunk] = st.out_pos; status[chunk] = st.status;
@@ -3088,6 +3204,19 @@ hipError_t launch_inflate_mark(const InflateMarkArgs& m, hipStream_t s) {
     const dim3 grid((a.n + per - 1) / per), block(kInflateThreads);
     if (a.serial_header) hipLaunchKernelGGL((inflate_kernel<true, true, kFormMark>), grid, block, 0, s, a.in, a.in_off, nullptr, a.n, a.out, 0, nullptr, a.status, (const uint4*)a.order, sp);
     else hipLaunchKernelGGL((inflate_kernel<false, true, kFormMark>), grid, block, 0, s, a.in, a.in_off, nullptr, a.n, a.out, 0, nullptr, a.status, (const uint4*)a.order, sp);
+    return hipGetLastError();
+}
+
+hipError_t launch_inflate_legs(const InflateLegArgs& a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    const uint32_t per = kInflateThreads / 64;
+    StreamParams sp{};
+    sp.out_off = a.out_off; sp.out_len = a.out_len; sp.wrap = a.wrap;
+    sp.idx = a.idx; sp.idx_off = a.idx_off; sp.idx_cap = a.idx_cap; sp.idx_len = a.idx_len; sp.span = a.span;
+    sp.legw = a.legw; sp.leg = a.leg;
+    const dim3 grid((a.n + per - 1) / per), block(kInflateThreads);
+    if (a.serial_header) hipLaunchKernelGGL((inflate_kernel<true, true, kFormLeg>), grid, block, 0, s, a.in, nullptr, nullptr, a.n, a.out, 0, nullptr, a.status, (const uint4*)a.order, sp);
+    else hipLaunchKernelGGL((inflate_kernel<false, true, kFormLeg>), grid, block, 0, s, a.in, nullptr, nullptr, a.n, a.out, 0, nullptr, a.status, (const uint4*)a.order, sp);
     return hipGetLastError();
 }
 
