@@ -348,11 +348,13 @@ int zwz_inflate_split_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, c
  * 4096 .. 2^28); per slice the pieces that end inside it are found and decoded as above and written, and the next slice starts where
  * the chain stands.  Sizes are 64-bit: no 2^29 or 2^32 limit for a file that splits; a piece must fit a slice and its decoded bytes
  * four slices (at least 4 MiB).  A file in which no piece ends cleanly before any byte was written (no flush points, sync flushes,
- * another wrapper) is decoded as one stream by zwz_inflate_streams_dev's path if it is shorter than 2^29 bytes.  Otherwise, and if
- * the chain breaks later (a cut or damaged file), ZWZ_E_FORMAT with zwz_last_error() naming the compressed offset.  A CRC-32,
- * Adler-32 or ISIZE that does not match is ZWZ_E_CHECKSUM.  When bytes other than zeros follow the first gzip member of a file
- * that splits, a file shorter than 2^29 bytes is decoded again by that one-stream path (which reads further members and names
- * garbage); a longer one is ZWZ_E_FORMAT, its further members are not read.  dst is written as dst.part and renamed on success only.  Synchronous. */
+ * another wrapper) is decoded as one stream by zwz_inflate_streams_dev's path if it is shorter than 2^29 bytes, and in legs by
+ * zwz_inflate_legs_file's loop (below) if it is longer or that path ends at its largest capacity: any .gz decodes, a long one that
+ * does not split at the one-wave rate.  If the chain breaks after bytes were written (a cut or damaged file), ZWZ_E_FORMAT with
+ * zwz_last_error() naming the compressed offset.  A CRC-32, Adler-32 or ISIZE that does not match is ZWZ_E_CHECKSUM.  When bytes
+ * other than zeros follow the first gzip member of a file that splits, the file is decoded again from its first byte: by the
+ * one-stream path if it is shorter than 2^29 bytes (which reads further members and names garbage), in legs otherwise.  dst is
+ * written as dst.part and renamed on success only.  Synchronous. */
 int zwz_inflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst);
 
 /* ---- A seek index for ordinary streams: parallel and ranged inflate ----------------------------------------------------------------
@@ -377,8 +379,8 @@ int zwz_inflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char 
  * Readable extents: the byte copies read whole aligned 4-byte words, so an index on the device and every output range are readable up
  * to their length rounded up to 16 (an index's length is a multiple of 16 already).
  * Not in this version: an index for a gzip stream of several members (none is made), compressed windows, decoding a touched segment
- * only as far as the last byte asked for.  (A stream of 2^29 compressed bytes or more gets its index from zwz_inflate_legs_dev below;
- * the file calls do not use it yet: zwz_inflate_index_file and zwz_inflate_stream_file keep the one-launch limits they state.) */
+ * only as far as the last byte asked for.  (A stream of 2^29 compressed bytes or more gets its index from zwz_inflate_legs_dev below,
+ * a file of that size from zwz_inflate_legs_file, which zwz_inflate_index_file and zwz_inflate_stream_file call where one launch ends.) */
 /* The most an index of a stream that decodes to decoded_cap bytes takes at this span (0: 1 MiB); 0 for a span that is not allowed. */
 uint64_t zwz_inflate_index_bound(uint64_t decoded_cap, uint32_t span);
 /* zwz_inflate_streams_dev that also writes every stream's index.  The first eleven arguments, the decoded bytes, d_out_len and
@@ -477,11 +479,36 @@ int zwz_inflate_read_ranges_batch_dev(zwz_ctx *ctx, const uint8_t *d_in, const u
 /* Host only (no GPU): checks an index as every reader does (ZWZ_E_FORMAT, zwz_last_error() naming the rule) and returns its wrapper,
  * the stream's length, the decoded length and the number of entries; any of the four pointers may be NULL. */
 int zwz_inflate_index_info(const uint8_t *idx, uint64_t idx_len, int *wrap, uint64_t *stream_len, uint64_t *decoded_len, uint32_t *count);
-/* One file holding one stream -> its index at dst_idx (written as dst_idx.part, renamed on success).  The file goes through
- * zwz_inflate_streams_index_dev whole, at the context's "index_span_bytes": the one-wave limit of 2^29 compressed bytes applies and is
- * ZWZ_E_FORMAT naming ZWZ_STREAM_TOO_LARGE; so is a stream that does not decode (ZWZ_E_CHECKSUM for a checksum or ISIZE mismatch) and a
- * gzip file of several members, for which no index is made.  Synchronous. */
+/* One file holding one stream -> its index at dst_idx (written as dst_idx.part, renamed on success).  A file shorter than 2^29 bytes
+ * goes through zwz_inflate_streams_index_dev whole, at the context's "index_span_bytes"; a longer one, or one whose decoded bytes end
+ * that launch at its largest capacity, through zwz_inflate_legs_file's loop (below), at the one-wave rate.  A stream that does not decode
+ * is ZWZ_E_FORMAT (ZWZ_E_CHECKSUM for a checksum or ISIZE mismatch); so is a gzip file of several members, for which no index is made.
+ * Synchronous. */
 int zwz_inflate_index_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst_idx);
+/* One file holding one raw, zlib or gzip stream of ANY length (gzip: any number of members with zero padding, as zwz_inflate_legs_dev
+ * reads them) -> its decoded bytes at dst and its seek index, at the context's "index_span_bytes", at dst_idx, from one decode in LEGS.
+ * Either of dst and dst_idx may be NULL, not both (ZWZ_E_INVALID).  The compressed file passes through one pinned buffer and one device
+ * window; the decoded bytes through one device window, with the up to 32 KiB in front of a restart point carried to the head of the next
+ * leg's; what a leg has made final -- the bytes below its restart point, all of them once the stream has ended -- is copied to one of two
+ * pinned buffers and written by a writer thread while the next leg runs, its checksum joined from pieces onto a running value, and the
+ * index entries below the restart point's own leave the device with their windows, which wait in a spool file (dst_idx.part.windows).
+ * Memory is bounded by the windows, not by the file; windows grow as in zwz_inflate_legs_dev, past its limits ZWZ_E_FORMAT naming
+ * ZWZ_STREAM_TOO_LARGE and the last restart point.  It makes no stream faster: ONE wave decodes the stream, about 36 s a decoded GiB, and
+ * what lies behind a restart point is decoded twice.  What it buys is that any .gz can be decoded and indexed; with the index,
+ * zwz_inflate_stream_file_indexed and zwz_inflate_read_ranges_file then work on it at the parallel rate.
+ * Both files are written through .part names and renamed on success only; on any failure no dst, dst_idx, .part or spool file is left.
+ * ZWZ_OK for stream status 0; ZWZ_E_CHECKSUM for a checksum or ISIZE mismatch (a mismatch beats any later stop); ZWZ_E_FORMAT for any
+ * other status, zwz_last_error() naming the status, the decoded bytes and the COMPRESSED BYTE OFFSET at which the decoder stopped;
+ * with dst_idx given also for a gzip file of several members and for an index of 2^32 bytes or more (neither is an obstacle to dst
+ * alone); ZWZ_E_IO as the other file calls.  For every file within the one-launch limits the return code is zwz_inflate_stream_file's /
+ * zwz_inflate_index_file's, and the index bytes are the latter's.
+ * stats (may be NULL), 8 words: legs run; legs rewound; windows grown; commits that wrote bytes; largest input window; largest output
+ * window; index entries; bytes of device plus pinned memory the call allocated (at their peak).
+ * Context options (zwz_ctx_set_option, decimal, "" restores the default; also read from the environment at zwz_ctx_create):
+ *   "leg_file_bytes"      67108864    4096 .. 2^29 - 16, a multiple of 16       ZWZ_LEG_FILE_BYTES      the input window
+ *   "leg_file_out_bytes"  268435456   65536 .. 2^32 - 65536, a multiple of 16   ZWZ_LEG_FILE_OUT_BYTES  the output window
+ * Synchronous: every wait is a join of a thread that only does file I/O, or a stream synchronisation. */
+int zwz_inflate_legs_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst, const char *dst_idx, uint64_t *stats);
 /* zwz_inflate_read_ranges_dev from a file into host memory: the index is read from idx_path, and of src only the compressed bytes of
  * the touched segments (one pread per run of consecutive index entries).  A file of another length than indexed is ZWZ_E_FORMAT. */
 int zwz_inflate_read_ranges_file(zwz_ctx *ctx, const char *src, const char *idx_path, const uint64_t *ranges, uint32_t k, uint8_t *out);

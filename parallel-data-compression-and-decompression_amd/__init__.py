@@ -21,6 +21,7 @@ and ordinary DEFLATE data of any size, a batch of independent streams in one lau
     Codec.inflate_stream_file                                  (one file of any size, in slices; `main gunzip`)
     Codec.inflate_index / Codec.inflate_indexed / Codec.read_ranges            (the seek index of one ordinary stream: a wave per segment)
     Codec.inflate_indexed_batch / Codec.read_ranges_batch, pack_indexes        (many indexed streams in one launch; the _dev forms)
+    Codec.inflate_legs_file                                    (one file of ANY length through leg windows: its bytes and / or its seek index; one wave)
     Codec.deflate_streams / Codec.deflate_streams_dev          (the way there: libz's level-6 full-flush streams, any size)
     Codec.deflate_stream_file, deflate_stream_bound            (one file as one .gz / zlib / raw stream)
 and ZIP archives, a batch of entries per launch (what unzip, zipfile and file managers open; no reference counterpart):
@@ -126,6 +127,7 @@ def lib():
         L.zwz_inflate_read_ranges_batch_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp]
         L.zwz_inflate_index_info.argtypes = [vp, u64, c.POINTER(c.c_int), c.POINTER(u64), c.POINTER(u64), c.POINTER(u32)]
         L.zwz_inflate_index_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
+        L.zwz_inflate_legs_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p, c.c_char_p, vp]
         L.zwz_inflate_read_ranges_file.argtypes = [vp, c.c_char_p, c.c_char_p, vp, u32, vp]
         L.zwz_inflate_stream_file_indexed.argtypes = [vp, c.c_char_p, c.c_char_p, c.c_char_p]
         L.zwz_deflate_stream_bound.restype = u64
@@ -144,6 +146,7 @@ def lib():
 
 
 E_INVALID = -1
+E_IO = -4
 E_FORMAT = -6
 E_CHECKSUM = -7
 BGZF_BLOCK_SIZE = 65280     # raw bytes per BGZF member (htslib's BGZF_BLOCK_SIZE)
@@ -580,10 +583,27 @@ class Codec:
 
     def inflate_index_file(self, src, dst_idx, wrap="gzip", span=None):
         """One file holding one ordinary stream -> its seek index at dst_idx (zwz_inflate_index_file; `main gzindex`).  span: as
-        inflate_index (sets the context option "index_span_bytes").  Files of 2^29 compressed bytes or more are refused."""
+        inflate_index (sets the context option "index_span_bytes").  A file of 2^29 compressed bytes or more goes through
+        inflate_legs_file's loop, at the one-wave rate."""
         if span:
             self.set_option("index_span_bytes", str(int(span)))
         _check(lib().zwz_inflate_index_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst_idx)), "zwz_inflate_index_file")
+
+    LEGS_FILE_STATS = ("legs", "rewound", "grown", "commits", "max_in_window", "max_out_window", "index_entries", "allocated_bytes")
+
+    def inflate_legs_file(self, src, dst=None, idx=None, wrap="gzip"):
+        """One file holding one raw, zlib or gzip stream of ANY length -> its decoded bytes at dst and / or its seek index (at the
+        context's "index_span_bytes") at idx, decoded in legs through staging windows of "leg_file_bytes" compressed and
+        "leg_file_out_bytes" decoded bytes (zwz_inflate_legs_file; `main gunzip --legs`, `main gzindex --legs`).  Memory is bounded by the
+        windows, not by the file.  It makes no stream faster: one wave decodes it, about 36 s a decoded GiB.  Returns the call's stats
+        as a dict (LEGS_FILE_STATS); ZwzError with status E_FORMAT / E_CHECKSUM / E_IO, with .stats, and then neither file appears."""
+        import numpy as np
+        st = np.zeros(8, dtype=np.uint64)
+        rc = lib().zwz_inflate_legs_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), None if dst is None else os.fsencode(dst),
+                                         None if idx is None else os.fsencode(idx), st.ctypes.data)
+        stats = dict(zip(self.LEGS_FILE_STATS, (int(x) for x in st)))
+        _check(rc, "zwz_inflate_legs_file", stats=stats)
+        return stats
 
     def inflate_stream_file_indexed(self, src, index_path, dst):
         """One file of any size decoded whole with its index, a wave per segment (zwz_inflate_stream_file_indexed; `main gunzip
@@ -961,7 +981,9 @@ class Codec:
         """Test / experiment switches of this context (include/zwz.h: zwz_ctx_set_option): "match" = auto | walk | band | lazy |
         autoband | autolazy, "plan" = wave | serial, "inflate_header" = wave | serial.  Every choice produces the same bytes; a form that
         failed its self-test on this device is refused.  "split_min_bytes", "split_budget", "split_max_candidates" (decimal strings):
-        the limits of inflate_split_streams_dev."""
+        the limits of inflate_split_streams_dev.  "leg_bytes", "leg_out_bytes": the windows of inflate_legs_dev; "leg_file_bytes" (default
+        67108864; 4096 .. 2^29 - 16) and "leg_file_out_bytes" (default 268435456; 65536 .. 2^32 - 65536), multiples of 16: the staging
+        windows of inflate_legs_file.  An empty string restores a default."""
         _check(lib().zwz_ctx_set_option(self._h, name.encode(), value.encode()), "zwz_ctx_set_option")
 
     def set_chunk_size(self, nbytes):

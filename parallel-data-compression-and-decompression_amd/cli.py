@@ -218,7 +218,9 @@ def run(operation, source_path, output_path, *, compress_fn=None, decompress_fn=
 
 def index_main(argv):
     """`gzindex <src> [<dst.zwi>] [--span N] [--zlib|--raw]` and `gunzip <src> <dst> --index <idx> [--offset B [--size S]]`: the seek
-    index of an ordinary stream and the reads through it, as csrc/main.cpp's commands of the same names.  One process, one GPU."""
+    index of an ordinary stream and the reads through it, as csrc/main.cpp's commands of the same names.  One process, one GPU.
+    `gzindex ... --legs` and `gunzip <src> <dst> --legs [--write-index <dst.zwi> [--span N]]` decode in legs through staging windows
+    (Codec.inflate_legs_file) whatever the file's size: one wave, about 36 s a decoded GiB."""
     ap = argparse.ArgumentParser(prog="main " + argv[0])
     ap.add_argument("source")
     ap.add_argument("output", nargs="?" if argv[0] == "gzindex" else None)
@@ -226,15 +228,29 @@ def index_main(argv):
     ap.add_argument("--raw", action="store_true")
     if argv[0] == "gzindex":
         ap.add_argument("--span", type=int, default=0)
+        ap.add_argument("--legs", action="store_true", help="decode in legs through staging windows, whatever the file's size")
     else:
-        ap.add_argument("--index", required=True)
+        ap.add_argument("--index")
+        ap.add_argument("--legs", action="store_true", help="decode in legs through staging windows, whatever the file's size")
+        ap.add_argument("--write-index", dest="write_index", help="with --legs: also write the seek index, from the same decode")
+        ap.add_argument("--span", type=int, default=0, help="with --write-index: decoded bytes between checkpoints")
         ap.add_argument("--offset", type=int)
         ap.add_argument("--size", type=int)
     a = ap.parse_args(argv[1:])
+    wrap = "zlib" if a.zlib else "raw" if a.raw else "gzip"
+    if argv[0] == "gunzip" and (bool(a.legs) == bool(a.index) or (a.write_index and not a.legs) or (a.span and not a.write_index)):
+        ap.error("one of --index <idx> and --legs; --write-index needs --legs, --span needs --write-index")
     from . import Codec, index_info
     codec = Codec(int(os.environ.get("LOCAL_RANK", "0")))
     try:
-        if argv[0] == "gzindex":
+        if a.legs:
+            if a.span:
+                codec.set_option("index_span_bytes", str(a.span))
+            if argv[0] == "gzindex":
+                codec.inflate_legs_file(a.source, None, a.output or a.source + ".zwi", wrap)
+            else:
+                codec.inflate_legs_file(a.source, a.output, a.write_index, wrap)
+        elif argv[0] == "gzindex":
             codec.inflate_index_file(a.source, a.output or a.source + ".zwi", "zlib" if a.zlib else "raw" if a.raw else "gzip", a.span or None)
         elif a.offset is None:
             if a.size is not None:
@@ -255,7 +271,7 @@ def index_main(argv):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if argv and (argv[0] == "gzindex" or (argv[0] == "gunzip" and "--index" in argv)):
+    if argv and (argv[0] == "gzindex" or (argv[0] == "gunzip" and ("--index" in argv or "--legs" in argv))):
         return index_main(argv)
     ap = argparse.ArgumentParser(prog="main", usage="%(prog)s <compress/decompress> <source directory path> <output directory path>")
     ap.add_argument("operation")

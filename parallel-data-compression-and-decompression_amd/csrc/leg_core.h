@@ -65,15 +65,18 @@ ZWZ_HD void leg_put_entry(uint32_t* e, uint64_t bit, uint64_t off, uint32_t hist
 // The snapshot rule at a block header whose first bit is `bit`, at decoded offset `out` (lane 0).  Where a mark is due the state as it
 // stands BEFORE the mark becomes the restart point -- a leg that starts there finds the mark due again and notes the same entry -- and
 // the mark is noted: into `idx` (the stream's index, null: none wanted) unless it is full or a second member has begun.
-ZWZ_HD void leg_at_header(LegState& cur, LegState& snap, uint64_t bit, uint64_t out, uint32_t span, uint8_t* idx, uint64_t idx_cap) {
+// ent_first, ent_slots: the index array at `idx` holds `ent_slots` entries of which the first is the stream's entry ent_first (the file
+// loop rebases the array every leg, legfile_core.h; the device call's array is the index itself).
+ZWZ_HD void leg_at_header(LegState& cur, LegState& snap, uint64_t bit, uint64_t out, uint32_t span, uint8_t* idx, uint64_t idx_cap, uint32_t ent_first = 0,
+                          uint32_t ent_slots = 0xffffffffu) {
     if (!leg_mark_due(cur.mk_seen, out, cur.mk_last, span)) return;
     snap = cur; snap.start = kLegBlock; snap.bit = bit; snap.out = out;
     if (idx && !cur.mk_full && !cur.mk_second) {
         const uint32_t hist = index_hist_bound(out);
         const uint64_t need = cur.mk_bytes + kIdxEntry + hist;
-        if (need + 15u > idx_cap) cur.mk_full = 1;         // the index would not fit: none is made, the decode goes on
+        if (need + 15u > idx_cap || cur.mk_count - ent_first >= ent_slots) cur.mk_full = 1;         // the index would not fit: none is made, the decode goes on
         else {
-            leg_put_entry(reinterpret_cast<uint32_t*>(idx + kIdxHeader + (size_t)cur.mk_count * kIdxEntry), bit, out, hist);
+            leg_put_entry(reinterpret_cast<uint32_t*>(idx + kIdxHeader + (size_t)(cur.mk_count - ent_first) * kIdxEntry), bit, out, hist);
             cur.mk_count++; cur.mk_bytes = need;
         }
     }

@@ -249,6 +249,7 @@ int zwz_ctx_create(int device, uint32_t max_batch, zwz_ctx** out) {
     from_env("ZWZ_MATCH", "match"); from_env("ZWZ_PLAN", "plan"); from_env("ZWZ_INFLATE_HEADER", "inflate_header");
     from_env("ZWZ_ZIP_SLICE_BYTES", "zip_slice_bytes"); from_env("ZWZ_ZIP_FORCE_ZIP64", "zip_force_zip64");       // (for `main zip` / `main unzip`)
     from_env("ZWZ_SPLIT_SLICE_BYTES", "split_slice_bytes");      // (for `main gunzip`: the slice of zwz_inflate_stream_file)
+    from_env("ZWZ_LEG_FILE_BYTES", "leg_file_bytes"); from_env("ZWZ_LEG_FILE_OUT_BYTES", "leg_file_out_bytes");      // (for `main gunzip` / `main gzindex`: zwz_inflate_legs_file's windows)
     const bool tl = getenv("ZWZ_TIMELINE") != nullptr || getenv("ZWZ_VERBOSE") != nullptr;
     const auto t_create = std::chrono::steady_clock::now();
     auto mark = [&](const char* what) { if (tl) fprintf(stderr, "zwz: context: %s at +%.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_create).count()); };
@@ -384,6 +385,14 @@ int zwz_ctx_set_option(zwz_ctx* c, const char* name, const char* value) {
         if (!v.empty() && (*end || end == v.c_str() || x < (in ? kLegBytesMin : kLegOutBytesMin) || x > (in ? kLegMaxIn : kLegOutBytesDefault) || (in && (x & 15u)))) return ZWZ_E_INVALID;
         if (in) c->leg_bytes = v.empty() ? kLegBytesDefault : x;
         else c->leg_out_bytes = v.empty() ? kLegOutBytesDefault : x;
+    } else if (n == "leg_file_bytes" || n == "leg_file_out_bytes") {
+        // zwz_inflate_legs_file (legfile_core.h): the staging windows a file passes through, multiples of 16
+        char* end = nullptr;
+        const unsigned long long x = strtoull(v.c_str(), &end, 10);
+        const bool in = n == "leg_file_bytes";
+        if (!v.empty() && (*end || end == v.c_str() || x < (in ? kLegFileBytesMin : kLegFileOutBytesMin) || x > (in ? kLegMaxIn : kLegFileOutBytesMax) || (x & 15u))) return ZWZ_E_INVALID;
+        if (in) c->leg_file_bytes = v.empty() ? kLegFileBytesDefault : x;
+        else c->leg_file_out_bytes = v.empty() ? kLegFileOutBytesDefault : x;
     } else if (n == "zip_force_zip64") {
         if (v == "0" || v.empty()) c->zip_force_zip64 = 0; else if (v == "1") c->zip_force_zip64 = 1; else return ZWZ_E_INVALID;
     } else if (n == "zip_slice_bytes") {

@@ -77,6 +77,8 @@ struct zwz_ctx {
     uint32_t index_span_bytes = zwz::kIdxSpanDefault;        // zwz_inflate_streams_index_dev with span 0: "index_span_bytes"
     // decode in legs (zwz_legs.cpp): options "leg_bytes" and "leg_out_bytes" (leg_core.h's defaults)
     uint64_t leg_bytes = zwz::kLegBytesDefault, leg_out_bytes = zwz::kLegOutBytesDefault;
+    // the file loop (zwz_legs_file.cpp): options "leg_file_bytes" and "leg_file_out_bytes" (legfile_core.h's defaults), the staging windows
+    uint64_t leg_file_bytes = zwz::kLegFileBytesDefault, leg_file_out_bytes = zwz::kLegFileOutBytesDefault;
     // ZIP (zwz_zip.cpp): options "zip_force_zip64" and "zip_slice_bytes"; the last call's copy out of kBufZipHost has run
     uint32_t zip_force_zip64 = 0;
     uint64_t zip_slice_bytes = 268435456ull;

@@ -14,6 +14,7 @@
 #include "dstream_core.h"
 #include "zwz_api_internal.h"
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <string>
 
 #include "zwz_bgzf.h"
@@ -461,14 +462,15 @@ extern "C" int zwz_inflate_index_info(const uint8_t* idx, uint64_t idx_len, int*
     return ZWZ_OK;
 }
 
-// The file goes through zwz_inflate_streams_index_dev whole: its limit of 2^29 compressed bytes is the call's.
-extern "C" int zwz_inflate_index_file(zwz_ctx* c, int wrap, const char* src, const char* dst_idx) {
-    if (!c || !src || !dst_idx || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
-    HIPCHK(hipSetDevice(c->device));
+namespace {
+
+// A file within the one-launch limits through zwz_inflate_streams_index_dev whole.  kGoLegs: its decoded bytes do not fit the launch's
+// largest capacity.
+constexpr int kGoLegs = 1;
+int index_file_one_launch(zwz_ctx* c, int wrap, const char* src, const char* dst_idx) {
     std::vector<uint8_t> in;
     if (int rc = read_whole_file(src, &in, 32)) return rc;
     const uint64_t n = in.size() - 32;
-    if (n >= kStreamMaxIn) { set_error("zwz_inflate_index_file: %s has %llu bytes: an index is built by one wave, which reads fewer than 2^29 (stream status %u)", src, (unsigned long long)n, (unsigned)kStrTooLarge); return ZWZ_E_FORMAT; }
     DevMem d_in, d_out, d_idx, d_par;
     if (int rc = d_in.get(round_up((size_t)n + 16, 16))) return rc;
     if (int rc = d_par.get(64)) return rc;
@@ -492,6 +494,7 @@ extern "C" int zwz_inflate_index_file(zwz_ctx* c, int wrap, const char* src, con
         HIPCHK(hipMemcpy(h_par, d_par.p, sizeof h_par, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(&status, st_mem.p, 4, hipMemcpyDeviceToHost));
         if (status == kInfOverflow && cap < kStreamMaxOut - 16) { cap *= 2; continue; }
+        if (status == kInfOverflow) return kGoLegs;
         if (status == kStrChecksum || status == kStrLength) { set_error("zwz_inflate_index_file: %s: %s mismatch", src, status == kStrLength ? "length" : "checksum"); return ZWZ_E_CHECKSUM; }
         if (status != kInfEnd) { set_error("zwz_inflate_index_file: %s: stream status %u after %llu decoded bytes", src, status, (unsigned long long)h_par[6]); return ZWZ_E_FORMAT; }
         break;
@@ -505,6 +508,19 @@ extern "C" int zwz_inflate_index_file(zwz_ctx* c, int wrap, const char* src, con
     const bool ok = fwrite(idx.data(), 1, idx.size(), f) == idx.size();
     if (fclose(f) != 0 || !ok || rename(part.c_str(), dst_idx) != 0) { unlink(part.c_str()); set_error("cannot write %s", dst_idx); return ZWZ_E_IO; }
     return ZWZ_OK;
+}
+
+}  // namespace
+
+// A file of 2^29 bytes or more, or one whose decoded bytes one launch cannot hold, goes through the file loop in legs (zwz_legs_file.cpp).
+extern "C" int zwz_inflate_index_file(zwz_ctx* c, int wrap, const char* src, const char* dst_idx) {
+    if (!c || !src || !dst_idx || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    struct stat sb;
+    if (stat(src, &sb) != 0) { set_error("cannot open %s", src); return ZWZ_E_IO; }
+    if ((uint64_t)sb.st_size >= kStreamMaxIn) return zwz_inflate_legs_file(c, wrap, src, nullptr, dst_idx, nullptr);
+    const int rc = index_file_one_launch(c, wrap, src, dst_idx);
+    return rc == kGoLegs ? zwz_inflate_legs_file(c, wrap, src, nullptr, dst_idx, nullptr) : rc;
 }
 
 namespace {

@@ -21,6 +21,9 @@ hipError_t launch_index_windows(const CrcTables* tab, const IndexBuild& b, hipSt
 // flag a difference sets
 struct IndexMove { uint64_t src, dst; uint32_t len, stream; };
 hipError_t launch_index_place(const uint8_t* idx, uint8_t* out, const IndexMove* mv, uint32_t m, hipStream_t s);
+// The file loop's commit: window i, mv[i].len bytes at mv[i].src of a leg's output staging (stage_len bytes readable), goes to mv[i].dst
+// of `packed` (packed_cap bytes).  Offsets are 64-bit; a move outside either buffer is skipped.
+hipError_t launch_index_gather(const uint8_t* stage, uint64_t stage_len, uint8_t* packed, uint64_t packed_cap, const IndexMove* mv, uint32_t m, hipStream_t s);
 // flag[stream] |= 1 where a window differs from the bytes that now stand at its place
 hipError_t launch_index_compare(const uint8_t* idx, const uint8_t* out, const IndexMove* mv, uint32_t m, uint32_t* flag, hipStream_t s);
 

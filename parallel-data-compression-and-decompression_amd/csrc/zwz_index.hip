@@ -62,6 +62,16 @@ __global__ void __launch_bounds__(256) index_place_kernel(const uint8_t* idx, ui
     for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) { const IndexMove q = mv[i]; wg_copy(out + q.dst, idx + q.src, q.len); }
 }
 
+// The file loop's commit (zwz_legs_file.cpp): the windows of a leg's committed entries out of its output staging, packed back to back.
+// A workgroup per window; a move that does not lie inside both buffers is not made (the host planned it: cannot happen).
+__global__ void __launch_bounds__(256) index_gather_kernel(const uint8_t* stage, uint64_t stage_len, uint8_t* packed, uint64_t packed_cap, const IndexMove* mv, uint32_t m) {
+    for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) {
+        const IndexMove q = mv[i];                                             // (workgroup-uniform)
+        if (q.src > stage_len || q.len > stage_len - q.src || q.dst > packed_cap || q.len > packed_cap - q.dst) continue;
+        wg_copy(packed + q.dst, stage + q.src, q.len);
+    }
+}
+
 __global__ void __launch_bounds__(256) index_compare_kernel(const uint8_t* idx, const uint8_t* out, const IndexMove* mv, uint32_t m, uint32_t* flag) {
     for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) {
         const IndexMove q = mv[i];
@@ -188,6 +198,12 @@ hipError_t launch_index_windows(const CrcTables* tab, const IndexBuild& b, hipSt
 hipError_t launch_index_place(const uint8_t* idx, uint8_t* out, const IndexMove* mv, uint32_t m, hipStream_t s) {
     if (!m) return hipSuccess;
     index_place_kernel<<<m < 65536u ? m : 65536u, 256, 0, s>>>(idx, out, mv, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_gather(const uint8_t* stage, uint64_t stage_len, uint8_t* packed, uint64_t packed_cap, const IndexMove* mv, uint32_t m, hipStream_t s) {
+    if (!m) return hipSuccess;
+    index_gather_kernel<<<m < 65536u ? m : 65536u, 256, 0, s>>>(stage, stage_len, packed, packed_cap, mv, m);
     return hipGetLastError();
 }
 

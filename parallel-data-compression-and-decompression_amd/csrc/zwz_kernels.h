@@ -7,7 +7,7 @@
 #include "zwz_common.h"
 #include "lz_band.h"
 #include "rle_core.h"
-#include "leg_core.h"
+#include "legfile_core.h"
 
 namespace zwz {
 
@@ -161,7 +161,10 @@ struct StreamParams {
     };
     uint32_t* bad;             // segment form: set for a stream one of whose segments did not end as measured
     // the index forms (index_core.h), appended likewise
-    const uint4* seg2;         // indexed-segment form, per segment: (address in `out` of the byte `hist` in front of the segment's first, low / high; end bit from the wave's input; -)
+    union {
+        const uint4* seg2;     // indexed-segment form, per segment: (address in `out` of the byte `hist` in front of the segment's first, low / high; end bit from the wave's input; -)
+        const LegStage* legf;  // leg form, per stream: where the windows lie in staging (zwz_inflate_legs_file), or null: in the stream's own ranges
+    };
     uint8_t* idx; const uint64_t* idx_off; const uint64_t* idx_cap;   // marking form: stream i's index at idx + idx_off[i], idx_cap[i] bytes
     uint64_t* idx_len;         // marking form: the index's padded length, 0 where none was made
     uint32_t span;             // marking form: output bytes between checkpoints, at least
@@ -203,6 +206,7 @@ struct InflateLegArgs {
     uint8_t* idx; const uint64_t* idx_off; const uint64_t* idx_cap; uint64_t* idx_len; uint32_t span;
     const LegPlan* legw; LegState* leg;
     uint32_t wrap, serial_header;
+    const LegStage* legf = nullptr;      // zwz_inflate_legs_file: the windows lie in staging (legfile_core.h)
 };
 // match_mode: auto = lz_dense_list decides per chunk between links + lz_match (+ lz_parse) and sort + lz_lazy; walk / band / lazy = every chunk through
 // that search; autoband / autolazy = the per-chunk choice with the band + lz_parse / lz_lazy for the chain-heavy ones.  Same bytes whichever runs.

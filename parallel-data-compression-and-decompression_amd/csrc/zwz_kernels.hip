@@ -2026,6 +2026,7 @@ template <bool kOn> struct LegRegs {
     LegState cur, snap;
     uint64_t in, out;
     uint32_t infin, outfin, start, bit, first, hist;
+    uint32_t ent_first, ent_slots;      // lane 0: the stream's entry that stands first in the index array, and the array's slots (legfile_core.h: LegStage)
 };
 template <> struct LegRegs<false> {};
 
@@ -2059,7 +2060,9 @@ struct InflateWaveMem {
 // state and a resume record, sp.leg[i]: it starts in front of the wrapper's header, at a block header with its window in memory (as
 // kFormIndexed) or at a member start, carries what is 64 bits wide in a LegState, keeps the latest restart point in lane 0's registers, and
 // leaves either the stream's provisional verdict or -- when a window ran out before the stream did -- the restart point for the next leg.
-// 0 to 4 compile as before it.
+// With sp.legf (zwz_inflate_legs_file, legfile_core.h) the windows lie in staging: the output window starts at out + legf[i].out_at, the
+// index array holds the entries from the stream's entry ent_first on, ent_slots of them.  A finished leg leaves the bit it stopped at in
+// the state's pad words.  0 to 4 compile as before it.
 template <bool kSerialHeader, bool kStream, uint32_t kSplit = 0>
 __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                   const uint32_t* __restrict__ in_len, uint32_t n,
@@ -2114,7 +2117,12 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         lg.bit = lg.start == kLegFresh ? 0u : __builtin_amdgcn_readfirstlane((uint32_t)(lg.cur.bit - lg.in * 8u));
         lg.first = __builtin_amdgcn_readfirstlane((uint32_t)(lg.cur.out - lg.out));
         lg.hist = __builtin_amdgcn_readfirstlane(leg_hist(lg.cur));
-        dst = out + sp.out_off[chunk] + lg.out;       // 16-byte aligned: the window's base is a multiple of 16
+        lg.ent_first = 0; lg.ent_slots = 0xffffffffu;
+        if (sp.legf) {                                 // the windows lie in staging (zwz_inflate_legs_file): 16-byte aligned there too
+            const LegStage g = sp.legf[chunk];
+            dst = out + uni64(g.out_at);
+            lg.ent_first = g.ent_first; lg.ent_slots = g.ent_slots;
+        } else dst = out + sp.out_off[chunk] + lg.out;       // 16-byte aligned: the window's base is a multiple of 16
         cap = __builtin_amdgcn_readfirstlane(w.out_len);
     } else if constexpr (kStream) {
         const uint64_t cap64 = sp.out_cap[chunk];
@@ -2277,7 +2285,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
             }
         }
         if constexpr (kLeg) {
-            if (lane == 0) leg_at_header(lg.cur, lg.snap, lg.in * 8u + st.br.bit_pos(), lg.out + st.out_pos, sp.span, mk_idx, mk_cap);
+            if (lane == 0) leg_at_header(lg.cur, lg.snap, lg.in * 8u + st.br.bit_pos(), lg.out + st.out_pos, sp.span, mk_idx, mk_cap, lg.ent_first, lg.ent_slots);
         }
         {   // the block header: lane 0 reads the bits, the wave builds the tables (inflate_core.h: inflate_block_rest, in its pieces)
             uint32_t v = 0, ok = 0;
@@ -2728,6 +2736,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
                 sp.leg[chunk] = lg.snap;
             } else {
                 lg.cur.done = 1; lg.cur.status = st.status; lg.cur.end_out = lg.out + st.out_pos;
+                leg_put_stop(lg.cur, lg.in * 8u + st.br.bit_pos());
                 sp.leg[chunk] = lg.cur;
                 sp.out_len[chunk] = lg.cur.end_out; status[chunk] = st.status;
                 if (sp.idx) {
@@ -3213,7 +3222,7 @@ hipError_t launch_inflate_legs(const InflateLegArgs& a, hipStream_t s) {
     StreamParams sp{};
     sp.out_off = a.out_off; sp.out_len = a.out_len; sp.wrap = a.wrap;
     sp.idx = a.idx; sp.idx_off = a.idx_off; sp.idx_cap = a.idx_cap; sp.idx_len = a.idx_len; sp.span = a.span;
-    sp.legw = a.legw; sp.leg = a.leg;
+    sp.legw = a.legw; sp.leg = a.leg; sp.legf = a.legf;
     const dim3 grid((a.n + per - 1) / per), block(kInflateThreads);
     if (a.serial_header) hipLaunchKernelGGL((inflate_kernel<true, true, kFormLeg>), grid, block, 0, s, a.in, nullptr, nullptr, a.n, a.out, 0, nullptr, a.status, (const uint4*)a.order, sp);
     else hipLaunchKernelGGL((inflate_kernel<false, true, kFormLeg>), grid, block, 0, s, a.in, nullptr, nullptr, a.n, a.out, 0, nullptr, a.status, (const uint4*)a.order, sp);

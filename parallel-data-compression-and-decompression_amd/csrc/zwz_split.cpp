@@ -269,7 +269,17 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
     if (int rc = job.finish_write()) return rc;
     fseeko(job.in, 0, SEEK_END);
     const uint64_t size = (uint64_t)ftello(job.in);
-    // the whole file as one stream through zwz_inflate_streams_dev, the capacity doubled until it fits; what was written is dropped
+    // the whole file in legs through staging windows (zwz_legs_file.cpp), where the paths below end: at the one-wave rate; what was written is dropped
+    auto in_legs = [&]() -> int {
+        job.join();
+        for (void*& p : job.h) if (p) { (void)hipHostFree(p); p = nullptr; }
+        for (void*& p : job.d) if (p) { (void)hipFree(p); p = nullptr; }
+        fclose(job.out); job.out = nullptr; unlink(job.part.c_str());
+        return zwz_inflate_legs_file(c, wrap_, src, dst, nullptr, nullptr);
+    };
+    // the whole file as one stream through zwz_inflate_streams_dev, the capacity doubled until it fits; what was written is dropped.
+    // kGoLegs: the decoded bytes do not fit the largest capacity of one launch
+    constexpr int kGoLegs = 1;
     auto one_stream = [&]() -> int {
         job.join();
         if (fflush(job.out) != 0 || ftruncate(fileno(job.out), 0) != 0 || fseeko(job.out, 0, SEEK_SET) != 0) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
@@ -292,6 +302,7 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
             HIPCHK(hipMemcpy(h_par + 4, d_par + 4, 16, hipMemcpyDeviceToHost));
             const uint32_t status = (uint32_t)h_par[5];
             if (status == kInfOverflow && cap < kStreamMaxOut - 16) { cap *= 2; continue; }
+            if (status == kInfOverflow) return kGoLegs;
             if (status == kStrChecksum || status == kStrLength) { set_error("zwz_inflate_stream_file: %s: %s mismatch", src, status == kStrLength ? "length" : "checksum"); return ZWZ_E_CHECKSUM; }
             if (status != kInfEnd) { set_error("zwz_inflate_stream_file: %s: stream status %u after %llu decoded bytes", src, status, (unsigned long long)h_par[4]); return ZWZ_E_FORMAT; }
             break;
@@ -303,12 +314,11 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
     };
     if (!chain_ok || kind != kSegFinal) {
         // the chain broke at `at`
-        if (total || size >= kStreamMaxIn) {
-            set_error("zwz_inflate_stream_file: %s: no block ends cleanly from compressed offset %llu on%s", src, (unsigned long long)at,
-                      total ? "" : " and the file is too large for the one-stream path");
-            return ZWZ_E_FORMAT;
-        }
-        return one_stream();              // nothing written yet
+        if (total) { set_error("zwz_inflate_stream_file: %s: no block ends cleanly from compressed offset %llu on", src, (unsigned long long)at); return ZWZ_E_FORMAT; }
+        // nothing written yet
+        if (size >= kStreamMaxIn) return in_legs();
+        const int rc = one_stream();
+        return rc == kGoLegs ? in_legs() : rc;
     }
     // the trailer behind the final block, and for gzip nothing but zero bytes behind it
     if (wrap != kWrapRaw) {
@@ -321,13 +331,13 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
         if (wrap == kWrapGzip) {
             if (le32_at(tr + 4) != (uint32_t)total) { set_error("zwz_inflate_stream_file: %s: length mismatch", src); return ZWZ_E_CHECKSUM; }
             uint8_t buf[4096];
-            uint64_t q = at + 8;
-            for (size_t k; (k = fread(buf, 1, sizeof buf, job.in)) > 0; q += k)
+            for (size_t k; (k = fread(buf, 1, sizeof buf, job.in)) > 0;)
                 for (size_t i = 0; i < k; i++)
                     if (buf[i]) {
-                        if (size < kStreamMaxIn) return one_stream();      // another member, or garbage: that path reads the one and names the other
-                        set_error("zwz_inflate_stream_file: %s: bytes behind the first member at compressed offset %llu (further members of a file this large are not read)", src, (unsigned long long)(q + i));
-                        return ZWZ_E_FORMAT;
+                        // another member, or garbage: both paths read the one and name the other, from the file's first byte
+                        if (size >= kStreamMaxIn) return in_legs();
+                        const int rc = one_stream();
+                        return rc == kGoLegs ? in_legs() : rc;
                     }
         }
     }
