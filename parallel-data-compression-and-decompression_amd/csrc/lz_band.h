@@ -65,6 +65,22 @@ ZWZ_HD bool band_valid(uint32_t own, uint32_t c) {
     const uint32_t d = own - c;
     return (own ^ c) < 0x10000u && d < kMaxDist && d != band_pos(own);
 }
+// band_valid as a range test, for a search that asks it of many words c with one `own` (band_count, lz_match_band's count phase):
+// band_lo(own) is the lowest word that can be a candidate of `own`, found once, and a probe is one subtraction and one unsigned
+// compare -- band_in_reach(own, lo, c) == band_valid(own, c) for every c != own.
+// Proof.  Let h, p be own's bucket and position, q_lo = max(p - (kMaxDist - 1), 1) for p >= 1 and 0 for p = 0; lo = h << 16 | q_lo.
+// Then q_lo <= p, so lo <= own and span = own - lo = p - q_lo < kMaxDist: c - lo < span (unsigned) says lo <= c < own with nothing
+// wrapping, i.e. c has own's upper half -- bucket h -- and a position q with q_lo <= q < p.  band_valid asks for bucket h, d = p - q
+// in [0, kMaxDist) -- q <= p and q >= p - (kMaxDist - 1) -- and q != 0: bucket h and max(p - (kMaxDist - 1), 1) <= q <= p, which for
+// c != own (q != p) is the same set, and for p = 0 the empty one on both sides (span = 0).  The halo word as `own` is position 0: no
+// candidates; as c it is bucket 0xffff, above every own, and a word of an earlier bucket is below lo.  (c == own: band_valid says yes
+// where p != 0, the range says no -- an entry is never its own predecessor in the array, so no search asks.)
+ZWZ_HD uint32_t band_lo(uint32_t own) {
+    const uint32_t p = band_pos(own), far = p > kMaxDist - 1u ? p - (kMaxDist - 1u) : 0u, one = p < 1u ? p : 1u;
+    return (own & 0xffff0000u) | (far > one ? far : one);
+}
+ZWZ_HD bool band_in_reach(uint32_t own, uint32_t lo, uint32_t c) { return c - lo < own - lo; }
+
 // The first candidate alone may sit at exactly MAX_DIST -- unless zlib's window has slid by then (lz_search's start test).
 ZWZ_HD bool band_first_at_max_dist(uint32_t own, uint32_t c) {
     const uint32_t p = band_pos(own), q = band_pos(c);
@@ -75,14 +91,14 @@ ZWZ_HD bool band_first_at_max_dist(uint32_t own, uint32_t c) {
 // caller's array starts kBand entries before its first own entry, filled with kBandHaloWord where nothing exists).
 template <class Lv = LzDefaultLevel, class SFn>
 ZWZ_HD uint32_t band_count(SFn S, uint32_t u) {
-    const uint32_t own = S(u);
+    const uint32_t own = S(u), lo = band_lo(own);
     uint32_t k = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-    for (uint32_t step = kBand; step >= 1u; step >>= 1) {      // largest k in [0, 128] with band_valid(S(u - k))
+    for (uint32_t step = kBand; step >= 1u; step >>= 1) {      // largest k in [0, 128] with band_valid(S(u - k)), asked as band_in_reach
         const uint32_t t = k + step;
-        if (t <= kBand && band_valid(own, S(u - t))) k = t;
+        if (t <= kBand && band_in_reach(own, lo, S(u - t))) k = t;
     }
     if (k == 0u && band_first_at_max_dist(own, S(u - 1u))) k = 1u;
     return k < Lv::max_chain ? k : Lv::max_chain;             // the level's chain, not the band's width (the halo stays 128 entries)

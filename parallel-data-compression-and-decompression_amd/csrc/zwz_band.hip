@@ -304,7 +304,7 @@ __global__ __launch_bounds__(kPlaceThreads) void lz_place_kernel(const uint32_t*
 //   scatter   every thread looks at its 64 dests; the ones inside the tile drop (bucket << 16 | position) into their slot
 //   build     the 8-byte comparison word of every entry; "pure" (one trigram per bucket, so the word starts behind the trigram)
 //             unless two neighbours of one bucket differ in their trigrams -- then the words are rebuilt from the trigram on
-//   count     candidates per entry (binary search over the monotone band_valid, six entries a thread in flight together);
+//   count     candidates per entry (binary search over the monotone band_valid, asked as a range test, six entries a thread in flight together);
 //             the chunk's last positions are finished here, byte by byte
 //   order     runs of eight consecutive entries, sorted by their greatest count: a wave's 64 lanes are eight runs of similar
 //             length (a trip lasts as long as its longest band: 0.66 of the lanes busy in array order, 0.89 this way), and
@@ -462,20 +462,39 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
                 uint32_t own[kOwnPer], k[kOwnPer];
 #pragma unroll
                 for (uint32_t j = 0; j < kOwnPer; j++) { const uint32_t i = kBand + tid + kBandThreads * j; own[j] = i < m ? S[i] : kBandHaloWord; k[j] = 0; }
-                auto search_step = [&](uint32_t step) {
-                    uint32_t c[kOwnPer];
-#pragma unroll
-                    for (uint32_t j = 0; j < kOwnPer; j++) { const uint32_t t = k[j] + step; c[j] = S[kBand + tid + kBandThreads * j - (t <= kCap ? t : 0u)]; }
-#pragma unroll
-                    for (uint32_t j = 0; j < kOwnPer; j++) { const uint32_t t = k[j] + step; if (t <= kCap && band_valid(own[j], c[j])) k[j] = t; }
-                };
-                search_step(kCap);
+                // A probe is band_in_reach (csrc/lz_band.h, with the proof that it is band_valid): subtract, compare, and the search's place moves
+                // under the mask -- four vector instructions where band_valid and the `t <= kCap` guard took thirteen and a branch.  The place is a
+                // pointer kCap words in front of the entry the search stands on, so a step's word lies at a constant offset behind it.  An entry
+                // that has all kCap candidates (the first step) goes on with an empty range: nothing passes, its place stays.
+                static_assert(kBandOffS >= 4u * kCap, "the running pointer stays inside the LDS block");
+                uint32_t lo[kOwnPer], span[kOwnPer];
+                const uint32_t* at[kOwnPer];
                 bool open = false;                                              // inside a long bucket every entry has all max_chain candidates: nothing to search
 #pragma unroll
-                for (uint32_t j = 0; j < kOwnPer; j++) open |= kBand + tid + kBandThreads * j < m && k[j] != kCap;
+                for (uint32_t j = 0; j < kOwnPer; j++) { lo[j] = band_lo(own[j]); span[j] = own[j] - lo[j]; at[j] = S + (kBand - kCap) + tid + kBandThreads * j; }
+                {
+                    uint32_t c[kOwnPer];
+#pragma unroll
+                    for (uint32_t j = 0; j < kOwnPer; j++) c[j] = at[j][0];
+#pragma unroll
+                    for (uint32_t j = 0; j < kOwnPer; j++) {
+                        const bool all = c[j] - lo[j] < span[j];
+                        k[j] = all ? kCap : 0u;
+                        span[j] = all ? 0u : span[j];
+                        open |= kBand + tid + kBandThreads * j < m && !all;
+                    }
+                }
                 if (__builtin_amdgcn_ballot_w64(open) != 0) {
 #pragma unroll
-                    for (uint32_t step = kCap / 2u; step >= 1u; step >>= 1) search_step(step);
+                    for (uint32_t step = kCap / 2u; step >= 1u; step >>= 1) {
+                        uint32_t c[kOwnPer];
+#pragma unroll
+                        for (uint32_t j = 0; j < kOwnPer; j++) c[j] = at[j][kCap - step];
+#pragma unroll
+                        for (uint32_t j = 0; j < kOwnPer; j++) at[j] -= c[j] - lo[j] < span[j] ? step : 0u;
+                    }
+#pragma unroll
+                    for (uint32_t j = 0; j < kOwnPer; j++) k[j] += (uint32_t)(S + (kBand - kCap) + tid + kBandThreads * j - at[j]);
                 }
 #pragma unroll
                 for (uint32_t j = 0; j < kOwnPer; j++) {
@@ -644,14 +663,25 @@ __global__ __launch_bounds__(kBandThreads, ZWZ_BAND_WAVES) void lz_match_band_ke
             // ---- second pass: the flagged entries, gathered into full waves, walk their sharers (csrc/lz_band.h, band_deep_probed).  An
             // entry's word holds its position and its link, so following a chain is one LDS read a hop; the sixteen bytes behind the
             // compared ones, which settle all but the longest matches, are read only of the sharers that pass a one-byte probe.
-            for (uint32_t i = kBand + tid; i - tid < m; i += kBandThreads) {
-                const bool f = i < m && ((uint32_t)ck[i - kBand] >> 8) != 0u;
-                const uint64_t fm = __builtin_amdgcn_ballot_w64(f);
-                if (fm) {
+            // A thread's entries' words are read together and the wave adds its total to s_nflag ONCE -- an add a trip was six returning
+            // atomics a wave, one behind the other, sixteen waves on the one word.  The list's order is another; every walk is its entry's own.
+            {
+                constexpr uint32_t kOwnPer = (kBandTile + kBandThreads - 1) / kBandThreads;
+                uint32_t fl[kOwnPer], total = 0;
+#pragma unroll
+                for (uint32_t t = 0; t < kOwnPer; t++) { const uint32_t i = kBand + tid + kBandThreads * t; fl[t] = i < m ? (uint32_t)ck[i - kBand] >> 8 : 0u; }
+#pragma unroll
+                for (uint32_t t = 0; t < kOwnPer; t++) total += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(fl[t] != 0u));
+                if (total) {
                     uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(&s_nflag, (uint32_t)__popcll(fm));
+                    if (lane == 0) base = atomicAdd(&s_nflag, total);
                     base = __builtin_amdgcn_readfirstlane(base);
-                    if (f) flist[base + rank_in(fm)] = (uint16_t)i;
+#pragma unroll
+                    for (uint32_t t = 0; t < kOwnPer; t++) {
+                        const uint64_t fm = __builtin_amdgcn_ballot_w64(fl[t] != 0u);
+                        if (fl[t] != 0u) flist[base + rank_in(fm)] = (uint16_t)(kBand + tid + kBandThreads * t);
+                        base += (uint32_t)__popcll(fm);
+                    }
                 }
             }
 #if ZWZ_BAND_EXP & 16
