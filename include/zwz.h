@@ -237,7 +237,8 @@ int zwz_ctx_set_option(zwz_ctx *ctx, const char *name, const char *value);
  * zwz_deflate_batch_dev; level-N under zwz_ctx_set_level(N) -- headers, block size and zwz_bgzf_bound do not change), then the standard 28-byte EOF member.  Decompression accepts any BGZF: other extra subfields around BC,
  * any deflate level, empty members anywhere (two BGZF files one after the other), a missing EOF member; it rejects (ZWZ_E_FORMAT,
  * zwz_last_error() naming the member and its byte offset) a member without BC, a BSIZE past the end, trailing bytes that are not
- * a member and ISIZE > 65535.  A CRC-32 or ISIZE mismatch is ZWZ_E_CHECKSUM.  All of it runs on the GPU but the header walk. */
+ * a member and ISIZE > 65535.  A CRC-32 or ISIZE mismatch is ZWZ_E_CHECKSUM.  All of it runs on the GPU; the header walk has a host
+ * form (zwz_bgzf_index) and a device form (zwz_bgzf_index_dev, below). */
 uint64_t zwz_bgzf_bound(uint64_t n);   /* worst-case compressed bytes for n input bytes, EOF member included */
 /* Asynchronous on the context's stream.  d_in 16-byte aligned and readable up to n rounded up to 16 (as every slot of
  * zwz_deflate_batch_dev); out_cap >= zwz_bgzf_bound(n) (else ZWZ_E_INVALID).  *d_out_len (device u64) receives the total length. */
@@ -278,6 +279,46 @@ int zwz_bgzf_read_ranges_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len,
 /* The same from a file into host memory.  With a .gzi only the touched members are read (one pread per run of consecutive
  * entries); gzi_path == NULL walks the member headers from the start until the last requested byte is covered. */
 int zwz_bgzf_read_ranges_file(zwz_ctx *ctx, const char *src, const char *gzi_path, const uint64_t *ranges, uint32_t k, uint8_t *out);
+
+/* ---- BGZF: the member walk on the device, and chunks by virtual offset -----------------------------------------------------------
+ * The walk of the member headers as a parallel job (candidate scan, parse, pointer jumping over the chain of BSIZE links), so that a
+ * stream in device memory -- the output of zwz_bgzf_compress_dev, say -- is indexed and decoded without a copy to the host.
+ *
+ * A VIRTUAL OFFSET (what .bai / .csi / .tbi indexes and htslib's bgzf_tell speak in) is
+ *     compressed offset of a member << 16 | offset inside its decoded block.
+ * Write U(c) for the decoded offset of the member that starts at compressed offset c; the position of virtual offset v is
+ * P(v) = U(v >> 16) + (v & 0xffff), and the CHUNK (vbeg, vend) is the decoded bytes [P(vbeg), P(vend)).  With cbeg = vbeg >> 16 and
+ * cend = vend >> 16 a chunk is valid when vbeg <= vend, a member parses at cbeg, the chain of members from cbeg hits cend exactly
+ * (or cend == gz_len), each offset inside a block is at most that member's ISIZE (equality is the block's end, which bgzf_tell can
+ * return) and is 0 where cend == gz_len.  vbeg > vend, an offset inside a block above ISIZE, a cend the chain from cbeg steps over
+ * and a cbeg at or past gz_len are ZWZ_E_INVALID, zwz_last_error() naming the chunk and the reason.  A cbeg that is no member, or a
+ * broken member on the way, is ZWZ_E_FORMAT in the words of zwz_bgzf_index (member numbers count from cbeg).  Chunks may overlap,
+ * repeat, be empty and come in any order; the compressed spans [cbeg, cend] of chunks that overlap or touch are walked as one chain
+ * from the lowest cbeg, and a cbeg that is not on that chain is ZWZ_E_FORMAT.  Members holding a requested byte are decoded and fully
+ * checked (inflate, CRC-32, ISIZE) as range reads check them; a member that is only passed over contributes its header and ISIZE
+ * on trust.  No .gzi is needed: the compressed offsets are in the request. */
+/* zwz_bgzf_index for a buffer in device memory: same counts, offsets, raw_len, same ZWZ_E_FORMAT and zwz_last_error() text.
+ * d_member_off (device, may be NULL to count) receives min(cap, *n_members) offsets; fewer than *n_members: ZWZ_E_INVALID with
+ * the counts set.  d_gz 16-byte aligned (else ZWZ_E_INVALID).  Synchronous. */
+int zwz_bgzf_index_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len, uint64_t *d_member_off, uint32_t cap,
+                       uint32_t *n_members, uint64_t *raw_len);
+/* zwz_bgzf_gzi for a buffer in device memory: byte for byte the same .gzi, into HOST memory (what zwz_bgzf_read_ranges_dev takes) */
+int zwz_bgzf_gzi_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len, uint8_t *gzi, uint64_t cap, uint64_t *gzi_len);
+/* Host only (no GPU): decoded offsets -> virtual offsets by a .gzi (the member is the last entry at or below the offset, as range
+ * reads resolve it; an offset whose member starts at or above 2^48, or lies 65536 or more bytes past its entry: ZWZ_E_INVALID) */
+int zwz_bgzf_voffsets(const uint8_t *gzi, uint64_t gzi_len, const uint64_t *offsets, uint32_t k, uint64_t *voffsets);
+/* chunks: k pairs (vbeg, vend) of virtual offsets in host memory.  sizes[k] (host): decoded bytes of each chunk, from the members'
+ * ISIZE fields (on trust until read).  Only headers and trailers between the chunks' compressed offsets are looked at. */
+int zwz_bgzf_chunk_sizes_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len, const uint64_t *chunks, uint32_t k, uint64_t *sizes);
+/* The chunks' bytes concatenated in the given order into d_out (device; sum of sizes > out_cap: ZWZ_E_INVALID, sizes still set).
+ * Needs no index.  Synchronous; damage reported as zwz_bgzf_read_ranges_dev reports it (member numbers count the members walked). */
+int zwz_bgzf_read_chunks_dev(zwz_ctx *ctx, const uint8_t *d_gz, uint64_t gz_len, const uint64_t *chunks, uint32_t k,
+                             uint8_t *d_out, uint64_t out_cap, uint64_t *sizes);
+/* The same for a file.  The headers are walked on the host, from each chunk's cbeg: nothing in front of a chunk's first member or
+ * more than 65 536 bytes behind the start of its last one is read, in bounded memory.  zwz_bgzf_chunk_sizes_file needs no GPU. */
+int zwz_bgzf_chunk_sizes_file(const char *src, const uint64_t *chunks, uint32_t k, uint64_t *sizes);
+int zwz_bgzf_read_chunks_file(zwz_ctx *ctx, const char *src, const uint64_t *chunks, uint32_t k, uint8_t *out, uint64_t out_cap,
+                              uint64_t *sizes);
 
 /* ---- DEFLATE streams of any size: raw, zlib and gzip ---------------------------------------------------------------------------
  * Decodes a batch of n independent streams in one pass on the GPU, one wave per stream (a single stream is not faster than one

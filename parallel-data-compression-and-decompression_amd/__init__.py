@@ -15,6 +15,9 @@ and BGZF (blocked gzip, readable by gzip / zcat / htslib; no reference counterpa
     Codec.bgzf_compress_file / Codec.bgzf_decompress_file      (whole files, streamed)
     bgzf_gzi / bgzf_gzi_file                                   (the .gzi index, host only)
     Codec.bgzf_read_ranges / Codec.bgzf_read_ranges_file       (random access: decoded byte ranges)
+    Codec.bgzf_index_dev / Codec.bgzf_gzi                      (the member walk on the GPU, for a CUDA tensor)
+    Codec.bgzf_read_chunks / _file / Codec.bgzf_chunk_sizes    (random access: chunks (vbeg, vend) of virtual offsets, no index)
+    bgzf_voffsets                                              (decoded offsets -> virtual offsets by a .gzi, host only)
 and ordinary DEFLATE data of any size, a batch of independent streams in one launch (no reference counterpart):
     Codec.inflate_streams / Codec.inflate_streams_dev          (raw, zlib or gzip; bytes or device tensors)
     Codec.inflate_stream / Codec.inflate_split_streams_dev     (one long stream with full-flush points: a wave per piece)
@@ -114,6 +117,13 @@ def lib():
         L.zwz_bgzf_gzi_file.argtypes = [c.c_char_p, c.c_char_p]
         L.zwz_bgzf_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp]
         L.zwz_bgzf_read_ranges_file.argtypes = [vp, c.c_char_p, c.c_char_p, vp, u32, vp]
+        L.zwz_bgzf_index_dev.argtypes = [vp, vp, u64, vp, u32, c.POINTER(u32), c.POINTER(u64)]
+        L.zwz_bgzf_gzi_dev.argtypes = [vp, vp, u64, vp, u64, c.POINTER(u64)]
+        L.zwz_bgzf_voffsets.argtypes = [vp, u64, vp, u32, vp]
+        L.zwz_bgzf_chunk_sizes_dev.argtypes = [vp, vp, u64, vp, u32, vp]
+        L.zwz_bgzf_read_chunks_dev.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp]
+        L.zwz_bgzf_chunk_sizes_file.argtypes = [c.c_char_p, vp, u32, vp]
+        L.zwz_bgzf_read_chunks_file.argtypes = [vp, c.c_char_p, vp, u32, vp, u64, vp]
         L.zwz_inflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         L.zwz_inflate_split_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
         L.zwz_inflate_stream_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
@@ -906,18 +916,20 @@ class Codec:
         return out if as_tensor else out.cpu().numpy().tobytes()
 
     def bgzf_decompress(self, data):
-        """BGZF bytes -> bytes; a CUDA uint8 tensor -> a CUDA uint8 tensor.  The member headers are walked on the host (a tensor's
-        bytes are copied there for it); everything else runs on the GPU.  ZwzError with status E_FORMAT / E_CHECKSUM on damage."""
+        """BGZF bytes -> bytes; a CUDA uint8 tensor -> a CUDA uint8 tensor.  The member headers of bytes are walked on the host, those
+        of a tensor on the GPU (nothing of it is copied to the host); everything else runs on the GPU.  ZwzError with status E_FORMAT /
+        E_CHECKSUM on damage."""
         import numpy as np
         import torch
-        as_tensor = isinstance(data, torch.Tensor)
-        host = data.detach().cpu().numpy().tobytes() if as_tensor else bytes(data)
+        if isinstance(data, torch.Tensor):
+            return self._bgzf_decompress_tensor(torch, np, data)
+        host = bytes(data)
         count, raw = ctypes.c_uint32(0), ctypes.c_uint64(0)
         _check(lib().zwz_bgzf_index(host, len(host), None, 0, ctypes.byref(count), ctypes.byref(raw)), "zwz_bgzf_index")
         offs = np.zeros(max(count.value, 1), dtype=np.uint64)
         _check(lib().zwz_bgzf_index(host, len(host), offs.ctypes.data, count.value, ctypes.byref(count), ctypes.byref(raw)), "zwz_bgzf_index")
         dev = torch.device("cuda", self.device)
-        d_gz = _device_input(torch, data if as_tensor else host, self.device)
+        d_gz = _device_input(torch, host, self.device)
         d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
         d_out = torch.empty(max(raw.value, 1), dtype=torch.uint8, device=dev)
         d_len = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -934,8 +946,122 @@ class Codec:
             err = ZwzError("zwz_bgzf_decompress_dev: member %d at byte offset %d: status %d" % (i, int(offs[i]), s))
             err.status = code
             raise err
-        out = d_out[:int(d_len.item())]
-        return out if as_tensor else out.cpu().numpy().tobytes()
+        return d_out[:int(d_len.item())].cpu().numpy().tobytes()
+
+    def _bgzf_decompress_tensor(self, torch, np, data):
+        d_gz = _device_input(torch, data, self.device)
+        n = data.numel()
+        d_off, raw = self._bgzf_index_dev(torch, d_gz, n, "zwz_bgzf_index")
+        count = d_off.numel()
+        dev = d_gz.device
+        if not count:
+            d_off = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_out = torch.empty(max(raw, 1), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(max(count, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        _check(lib().zwz_bgzf_decompress_dev(self._h, d_gz.data_ptr(), n, d_off.data_ptr(), count, d_out.data_ptr(), d_len.data_ptr(),
+                                             d_st.data_ptr()), "zwz_bgzf_decompress_dev")
+        self.sync()
+        bad = torch.nonzero(d_st[:count])
+        if bad.numel():
+            i = int(bad[0].item())
+            s = int(d_st[i].item())
+            code = E_CHECKSUM if s in (BGZF_ISIZE_MISMATCH, BGZF_CRC_MISMATCH) else E_FORMAT
+            err = ZwzError("zwz_bgzf_decompress_dev: member %d at byte offset %d: status %d" % (i, int(d_off[i].item()), s))
+            err.status = code
+            raise err
+        return d_out[:int(d_len.item())]
+
+    def _bgzf_index_dev(self, torch, d_gz, n, what):
+        """zwz_bgzf_index_dev on an aligned CUDA tensor -> (int64 CUDA tensor of the member offsets, decoded size).  The offsets go
+        into a guessed room first (a member per 512 bytes); only a stream of smaller members is walked a second time."""
+        count, raw = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        cap = n // 512 + 64
+        torch.cuda.synchronize(d_gz.device)
+        for _ in range(2):
+            d_off = torch.empty(cap, dtype=torch.int64, device=d_gz.device)
+            torch.cuda.synchronize(d_gz.device)
+            rc = lib().zwz_bgzf_index_dev(self._h, d_gz.data_ptr(), n, d_off.data_ptr(), cap, ctypes.byref(count), ctypes.byref(raw))
+            if rc == E_INVALID and count.value > cap:
+                cap = count.value
+                continue
+            break
+        _check(rc, what)
+        return d_off[:count.value], raw.value
+
+    def bgzf_index_dev(self, gz):
+        """The member walk of a BGZF stream in a CUDA uint8 tensor, on the GPU: (int64 CUDA tensor of the members' byte offsets, decoded
+        size).  ZwzError with status E_FORMAT and the words of bgzf_index for anything that is not a whole member."""
+        import torch
+        d_gz = _device_input(torch, gz, self.device)
+        return self._bgzf_index_dev(torch, d_gz, gz.numel(), "zwz_bgzf_index_dev")
+
+    def bgzf_gzi(self, gz, _what="zwz_bgzf_gzi_dev"):
+        """The .gzi bytes of a BGZF stream in a CUDA uint8 tensor (as the module's bgzf_gzi gives them for bytes), walked on the GPU."""
+        import torch
+        d_gz = _device_input(torch, gz, self.device)
+        n = gz.numel()
+        torch.cuda.synchronize(d_gz.device)
+        size = ctypes.c_uint64(0)
+        cap = 8 + 16 * (n // 512 + 64)
+        for _ in range(2):
+            buf = (ctypes.c_uint8 * cap)()
+            rc = lib().zwz_bgzf_gzi_dev(self._h, d_gz.data_ptr(), n, buf, cap, ctypes.byref(size))
+            if rc == E_INVALID and size.value > cap:
+                cap = size.value
+                continue
+            break
+        _check(rc, _what)
+        return ctypes.string_at(buf, size.value)
+
+    def _chunks_dev(self, gz, chunks):
+        import numpy as np
+        import torch
+        d_gz = _device_input(torch, gz, self.device)
+        n = gz.numel() if isinstance(gz, torch.Tensor) else len(gz)
+        ch = _ranges(np, chunks)
+        sizes = np.zeros(max(len(ch), 1), dtype=np.uint64)
+        torch.cuda.synchronize(d_gz.device)
+        return torch, np, d_gz, n, ch, sizes
+
+    def bgzf_chunk_sizes(self, gz, chunks):
+        """Decoded bytes of every chunk (vbeg, vend) of virtual offsets, from the members' ISIZE fields: a list of ints.  gz: BGZF bytes,
+        a CUDA uint8 tensor, or the path of a file (str or os.PathLike; read on the host, no GPU work)."""
+        if isinstance(gz, (str, os.PathLike)):
+            return bgzf_chunk_sizes_file(gz, chunks)
+        torch, np, d_gz, n, ch, sizes = self._chunks_dev(gz, chunks)
+        _check(lib().zwz_bgzf_chunk_sizes_dev(self._h, d_gz.data_ptr(), n, ch.ctypes.data, len(ch), sizes.ctypes.data), "zwz_bgzf_chunk_sizes_dev")
+        return [int(x) for x in sizes[:len(ch)]]
+
+    def bgzf_read_chunks(self, gz, chunks):
+        """Chunks [(vbeg, vend), ...] of virtual offsets (compressed offset of a member << 16 | offset inside its decoded block; what
+        .bai / .csi / .tbi indexes hold) of a BGZF stream, without an index: bytes -> a list of bytes; a CUDA uint8 tensor -> (one CUDA
+        tensor of the chunks concatenated, their sizes).  The member headers between a chunk's compressed offsets are walked on the
+        GPU; members holding a requested byte are decoded and checked.  include/zwz.h says what a valid chunk is."""
+        torch, np, d_gz, n, ch, sizes = self._chunks_dev(gz, chunks)
+        _check(lib().zwz_bgzf_chunk_sizes_dev(self._h, d_gz.data_ptr(), n, ch.ctypes.data, len(ch), sizes.ctypes.data), "zwz_bgzf_chunk_sizes_dev")
+        total = int(sizes[:len(ch)].sum())
+        d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=d_gz.device)
+        torch.cuda.synchronize(d_gz.device)
+        _check(lib().zwz_bgzf_read_chunks_dev(self._h, d_gz.data_ptr(), n, ch.ctypes.data, len(ch), d_out.data_ptr(), total, sizes.ctypes.data),
+               "zwz_bgzf_read_chunks_dev")
+        if isinstance(gz, torch.Tensor):
+            return d_out[:total], [int(x) for x in sizes[:len(ch)]]
+        return _split(d_out[:total].cpu().numpy().tobytes(), sizes[:len(ch)].reshape(-1, 1))
+
+    def bgzf_read_chunks_file(self, src, chunks):
+        """Chunks of virtual offsets of a BGZF file -> a list of bytes.  Only the file's bytes between a chunk's compressed offsets (and
+        the member its end lies in) are read; no .gzi is needed."""
+        import numpy as np
+        ch = _ranges(np, chunks)
+        sizes = np.zeros(max(len(ch), 1), dtype=np.uint64)
+        _check(lib().zwz_bgzf_chunk_sizes_file(os.fsencode(src), ch.ctypes.data, len(ch), sizes.ctypes.data), "zwz_bgzf_chunk_sizes_file")
+        total = int(sizes[:len(ch)].sum())
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        _check(lib().zwz_bgzf_read_chunks_file(self._h, os.fsencode(src), ch.ctypes.data, len(ch), out.ctypes.data, total, sizes.ctypes.data),
+               "zwz_bgzf_read_chunks_file")
+        return _split(out[:total].tobytes(), sizes[:len(ch)].reshape(-1, 1))
 
     def bgzf_compress_file(self, src, dst):
         """src -> dst as BGZF, streamed through pinned staging (any size); dst appears only on success."""
@@ -946,13 +1072,13 @@ class Codec:
 
     def bgzf_read_ranges(self, gz, ranges, gzi=None):
         """Decoded byte ranges [(offset, length), ...] of a BGZF stream: bytes -> a list of bytes; a CUDA uint8 tensor -> one CUDA tensor
-        of the ranges concatenated.  gzi: the stream's .gzi bytes (None: built on the host from the stream).  Only the members holding
-        a requested byte are decoded and checked."""
+        of the ranges concatenated.  gzi: the stream's .gzi bytes (None: built from the stream -- on the host for bytes, on the GPU for
+        a tensor).  Only the members holding a requested byte are decoded and checked."""
         import numpy as np
         import torch
         as_tensor = isinstance(gz, torch.Tensor)
         if gzi is None:
-            gzi = bgzf_gzi(gz.detach().cpu().numpy().tobytes() if as_tensor else bytes(gz))
+            gzi = self.bgzf_gzi(gz, _what="zwz_bgzf_gzi") if as_tensor else bgzf_gzi(bytes(gz))
         rng = _ranges(np, ranges)
         total = int(rng[:, 1].sum()) if len(rng) else 0
         dev = torch.device("cuda", self.device)
@@ -1213,6 +1339,27 @@ def bgzf_gzi(gz):
     buf = ctypes.create_string_buffer(n.value)
     _check(lib().zwz_bgzf_gzi(gz, len(gz), buf, n.value, ctypes.byref(n)), "zwz_bgzf_gzi")
     return buf.raw[:n.value]
+
+
+def bgzf_voffsets(gzi, offsets):
+    """Decoded byte offsets -> virtual offsets (compressed offset of the member << 16 | offset inside its block) by a stream's .gzi
+    bytes: a list of ints.  Host only.  The member of an offset is the last index entry at or below it, as range reads resolve it."""
+    import numpy as np
+    offs = np.ascontiguousarray(np.array([int(x) for x in offsets], dtype=np.uint64))
+    out = np.zeros(max(len(offs), 1), dtype=np.uint64)
+    gzi = bytes(gzi)
+    _check(lib().zwz_bgzf_voffsets(gzi, len(gzi), offs.ctypes.data, len(offs), out.ctypes.data), "zwz_bgzf_voffsets")
+    return [int(x) for x in out[:len(offs)]]
+
+
+def bgzf_chunk_sizes_file(src, chunks):
+    """Decoded bytes of every chunk (vbeg, vend) of virtual offsets of a BGZF file, from a host walk of the member headers between
+    the chunks' compressed offsets: a list of ints.  No GPU."""
+    import numpy as np
+    ch = _ranges(np, chunks)
+    sizes = np.zeros(max(len(ch), 1), dtype=np.uint64)
+    _check(lib().zwz_bgzf_chunk_sizes_file(os.fsencode(src), ch.ctypes.data, len(ch), sizes.ctypes.data), "zwz_bgzf_chunk_sizes_file")
+    return [int(x) for x in sizes[:len(ch)]]
 
 
 def bgzf_gzi_file(src, dst):

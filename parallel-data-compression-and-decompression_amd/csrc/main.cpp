@@ -378,7 +378,7 @@ int zip_main(const std::string& op, const char* src, const char* dst, int world_
 }
 
 void bgzf_usage(const char* argv0) {
-    fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index] [-4|-5|-6] [--huffman|--rle]\n       %s bgunzip <src> <dst> [--offset B [--size S]]\n       %s bgindex <src.gz>\n"
+    fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index] [-4|-5|-6] [--huffman|--rle]\n       %s bgunzip <src> <dst> [--offset B [--size S] | --chunk VBEG:VEND [--chunk ...]]\n       %s bgindex <src.gz>\n"
             "       %s gzip <src> <dst> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle]\n       %s gunzip <src> <dst> [--zlib|--raw] [--index <idx> [--offset B [--size S]]] [--legs [--write-index <dst.zwi> [--span N]]]\n       %s gzindex <src> [<dst.zwi>] [--span N] [--zlib|--raw] [--legs]\n       %s zip <src dir> <dst.zip> [-4|-5|-6] [--huffman|--rle]\n       %s unzip <src.zip> <dst dir>\n"
             "  --legs: decode in legs through staging windows (zwz_inflate_legs_file) whatever the file's size -- the path a file of 2^29 bytes or more takes by itself; one wave, about 36 s a decoded GiB\n"
             "  -4 -5 -6 (behind the operands or, as gzip takes it, in front of them): libz's compression level of that number (default 6, or ZWZ_LEVEL); no other level exists here\n"
@@ -564,8 +564,44 @@ int bgzf_range_to_file(zwz_ctx* ctx, const char* src, const char* dst, uint64_t 
     return rc;
 }
 
+// "VBEG:VEND", two virtual offsets as parse_u64 reads numbers
+bool parse_chunk(const char* s, uint64_t* vb, uint64_t* ve) {
+    const char* colon = s ? strchr(s, ':') : nullptr;
+    if (!colon) return false;
+    const std::string a(s, colon);
+    return parse_u64(a.c_str(), vb) && parse_u64(colon + 1, ve);
+}
+
+// The chunks (pairs of virtual offsets) of src concatenated into dst, through <dst>.part: read in groups of chunks of about 64 MiB
+// (a larger chunk is read in one piece).
+int bgzf_chunks_to_file(zwz_ctx* ctx, const char* src, const char* dst, const std::vector<uint64_t>& chunks) {
+    const uint32_t k = (uint32_t)(chunks.size() / 2);
+    std::vector<uint64_t> sizes(k);
+    if (int rc = zwz_bgzf_chunk_sizes_file(src, chunks.data(), k, sizes.data())) return rc;
+    const std::string part = std::string(dst) + ".part";
+    FILE* out = fopen(part.c_str(), "wb");
+    if (!out) { fprintf(stderr, "cannot create %s\n", part.c_str()); return ZWZ_E_IO; }
+    constexpr uint64_t kPiece = 64ull << 20;
+    std::vector<uint8_t> buf;
+    int rc = ZWZ_OK;
+    for (uint32_t i = 0; i < k && !rc;) {
+        uint32_t e = i + 1;
+        uint64_t n = sizes[i];
+        while (e < k && n + sizes[e] <= kPiece) n += sizes[e++];
+        if (buf.size() < n) buf.resize((size_t)n);
+        rc = zwz_bgzf_read_chunks_file(ctx, src, chunks.data() + 2 * (size_t)i, e - i, buf.data(), n, sizes.data() + i);
+        if (!rc && n && fwrite(buf.data(), 1, n, out) != n) rc = ZWZ_E_IO;
+        i = e;
+    }
+    if (fclose(out) != 0 && !rc) rc = ZWZ_E_IO;
+    if (!rc && rename(part.c_str(), dst) != 0) rc = ZWZ_E_IO;
+    if (rc) unlink(part.c_str());
+    return rc;
+}
+
 // `main bgzip <src> <dst> --index` (also <dst>.gzi), `main bgindex <src.gz>` (<src.gz>.gzi), `main bgunzip <src> <dst> --offset B
-// [--size S]` (decoded bytes [B, B + S) or [B, end)).  Flags after the operands; a flag that is not known, or a malformed number,
+// [--size S]` (decoded bytes [B, B + S) or [B, end)), `main bgunzip <src> <dst> --chunk VBEG:VEND [--chunk ...]` (the chunks of
+// virtual offsets, concatenated; needs no .gzi).  Flags after the operands; a flag that is not known, or a malformed number,
 // prints the usage and exits 1.  Exit codes as bgzf_main's.
 int bgzf_ext_main(int argc, char* argv[], int world_size, int device) {
     const std::string op = argv[1];
@@ -578,18 +614,20 @@ int bgzf_ext_main(int argc, char* argv[], int world_size, int device) {
         return 0;
     }
     bool index = false, have_off = false, have_size = false;
-    uint64_t off = 0, size = 0;
+    uint64_t off = 0, size = 0, vb = 0, ve = 0;
+    std::vector<uint64_t> chunks;
     int level = 0, strategy = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
         if (op == "bgzip" && a == "--index") index = true;
+        else if (op == "bgunzip" && a == "--chunk" && i + 1 < argc && parse_chunk(argv[i + 1], &vb, &ve)) { chunks.push_back(vb); chunks.push_back(ve); i++; }
         else if (op == "bgzip" && level_flag(a, &level) == 1) {}
         else if (op == "bgzip" && strategy_flag(a, &strategy) == 1) {}
         else if (op == "bgunzip" && a == "--offset" && i + 1 < argc && parse_u64(argv[i + 1], &off)) { have_off = true; i++; }
         else if (op == "bgunzip" && a == "--size" && i + 1 < argc && parse_u64(argv[i + 1], &size)) { have_size = true; i++; }
         else { bgzf_usage(argv[0]); return 1; }
     }
-    if (have_size && !have_off) { bgzf_usage(argv[0]); return 1; }
+    if ((have_size && !have_off) || (have_off && !chunks.empty())) { bgzf_usage(argv[0]); return 1; }
     if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", op.c_str(), world_size); return 1; }
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
@@ -600,6 +638,8 @@ int bgzf_ext_main(int argc, char* argv[], int world_size, int device) {
         if (op == "bgzip") {
             rc = zwz_bgzf_compress_file(ctx, argv[2], argv[3]);
             if (rc == ZWZ_OK && index) rc = zwz_bgzf_gzi_file(argv[3], (std::string(argv[3]) + ".gzi").c_str());
+        } else if (!chunks.empty()) {
+            rc = bgzf_chunks_to_file(ctx, argv[2], argv[3], chunks);
         } else {
             rc = bgzf_range_to_file(ctx, argv[2], argv[3], off, size, !have_size);
         }

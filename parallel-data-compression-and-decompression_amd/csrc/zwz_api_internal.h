@@ -39,12 +39,14 @@ enum BufId {
     kBufIndex1,          // seek index: an index uploaded for a call, or the scratch slots of a range read
     kBufLegs,            // decode in legs (zwz_legs.cpp): the per-stream arrays of one call, and their pinned twin
     kBufLegPieces,       // decode in legs: the checksum pieces of one call
+    kBufWalk0, kBufWalk1,                    // BGZF member walk (zwz_bgzf_walk.hip): per span and scan tile / per candidate and member
     kNumDeviceBufs,
     kBufStageHost = kNumDeviceBufs, kBufRangeHost, kBufStreamsHost,
     kBufSplitHost,       // split inflate: the per-stream arrays a call uploads (read by copies that may still be queued when it returns)
     kBufZipHost,
     kBufIndexHost,
     kBufLegsHost,
+    kBufWalkHost,        // BGZF member walk: the spans a call uploads and the results it brings back
     kNumBufs
 };
 

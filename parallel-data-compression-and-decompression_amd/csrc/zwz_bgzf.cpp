@@ -2,7 +2,9 @@
 // (crc32_blocks + zwz_deflate_batch_dev + bgzf_scan + bgzf_pack; bgzf_gather + inflate + bgzf_scan + bgzf_verify_compact), and
 // whole-file streaming through pinned staging with reading, the GPU and writing overlapped.  Random access: the .gzi index
 // (writer, streamed writer, reader), the planning of range reads and their device path (bgzf_gather_list + inflate +
-// bgzf_verify_extract) for data in device memory or in a file.
+// bgzf_verify_extract) for data in device memory or in a file.  The walk on the device (zwz_bgzf_walk.hip) behind
+// zwz_bgzf_index_dev / zwz_bgzf_gzi_dev, and chunks by virtual offset: their spans walked, on the device or from a file's headers, the
+// members walked made an index, the chunks made ranges, and those handed to the same planning and device path.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -16,6 +18,7 @@
 
 #include "zwz_api_internal.h"
 #include "zwz_bgzf.h"
+#include "zwz_bgzf_walk.h"
 #include "zwz_filejob.h"
 
 using namespace zwz;
@@ -416,6 +419,371 @@ int read_file_bytes(const char* path, std::vector<uint8_t>* out) {
     return ZWZ_OK;
 }
 
+// The device path of a plan over data in device memory: slices of at most max_batch touched members, queued one behind the other.
+int run_plan_dev(zwz_ctx* c, const GziIndex& ix, const RangePlan& P, const uint64_t* ranges, const uint8_t* d_gz, uint64_t gz_len, uint8_t* d_out) {
+    const uint32_t T = (uint32_t)P.member.size();
+    if (!T) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const uint32_t M = T < c->max_batch ? T : c->max_batch;
+    if (int rc = ensure_bgzf(c, M)) return rc;
+    // every slice packs into its own part of the plan buffers: the host fills slice s + 1 while the device runs slice s
+    std::vector<Slice> slices;
+    std::vector<size_t> at;
+    size_t bytes = 0;
+    for (uint32_t t0 = 0; t0 < T; t0 += M) {
+        const uint32_t t1 = T - t0 < M ? T : t0 + M;
+        slices.push_back({t0, t1, P.row[t0], P.row[t1]});
+        at.push_back(bytes);
+        bytes += round_up(slice_bytes(t1 - t0, P.row[t1] - P.row[t0]), 16);
+    }
+    if (int rc = ensure_rr(c, bytes)) return rc;
+    std::vector<uint64_t> moff(T);
+    for (uint32_t t = 0; t < T; t++) moff[t] = ix.coff[P.member[t]];
+    uint8_t* h = c->buf[kBufRangeHost].as<uint8_t>();
+    uint8_t* d = c->buf[kBufRangeDev].as<uint8_t>();
+    for (size_t s = 0; s < slices.size(); s++)
+        if (int rc = queue_slice(c, P, slices[s], moff.data(), nullptr, h + at[s], d + at[s], d_gz, gz_len, d_out, false)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t s = 0; s < slices.size(); s++)
+        if (int rc = slice_verdict(P, ix, slices[s], h + at[s], ranges)) return rc;
+    return ZWZ_OK;
+}
+
+// The device path of a plan over a file: its touched members read with one pread per run of consecutive index entries.
+int run_plan_file(zwz_ctx* c, const char* src, const GziIndex& ix, const RangePlan& P, const uint64_t* ranges, uint8_t* out) {
+    const uint32_t T = (uint32_t)P.member.size();
+    if (!T) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    FileJob job;
+    job.fd = open(src, O_RDONLY);
+    if (job.fd < 0) { set_error("cannot open %s", src); return ZWZ_E_IO; }
+    struct stat stt {};
+    if (fstat(job.fd, &stt) != 0) { set_error("cannot stat %s", src); return ZWZ_E_IO; }
+    const uint64_t fsize = (uint64_t)stt.st_size;
+    // member t's bytes in the file: [coff, end), end = the next entry's offset (at most a member's 65 536 bytes further), or the file's end
+    const size_t last = ix.coff.size() - 1;
+    std::vector<uint64_t> fend(T);
+    for (uint32_t t = 0; t < T; t++) {
+        const size_t j = P.member[t];
+        const uint64_t s0 = ix.coff[j];
+        uint64_t e = std::min<uint64_t>(s0 + kBgzfSlot, fsize);
+        if (j < last) e = std::min(e, ix.coff[j + 1]);
+        fend[t] = s0 >= fsize ? s0 : e;                     // (an entry past the file's end: nothing to read, the member does not parse)
+    }
+    const uint32_t S = c->max_batch < kFileSliceBlocks ? c->max_batch : kFileSliceBlocks;
+    const size_t B = (size_t)S * kBgzfSlot;
+    if (int rc = job.alloc({B + 16, kRangeOutSlice + 16}, {B + 16, kRangeOutSlice + 16})) return rc;    // packed members, decoded pieces
+    if (int rc = ensure_bgzf(c, S)) return rc;
+    uint8_t* hin = static_cast<uint8_t*>(job.h[0]);
+    uint8_t* hout = static_cast<uint8_t*>(job.h[1]);
+    std::vector<uint64_t> moff(T), mend(T);
+    uint32_t t = 0, p = 0;
+    while (t < T) {
+        // the slice: whole members while they fit S and kRangeOutSlice, or a part of one member's pieces that alone exceed kRangeOutSlice
+        // (every piece is at most 65 536 bytes: a part holds at least one).  Its first member may continue one cut before.
+        Slice sl{t, t, p, p};
+        uint64_t obytes = 0;
+        while (sl.t1 < T && sl.t1 - sl.t0 < S) {
+            const uint32_t q0 = sl.t1 == t ? p : P.row[sl.t1];
+            uint64_t mb = 0;
+            for (uint32_t q = q0; q < P.row[sl.t1 + 1]; q++) mb += P.piece[q].len;
+            if (obytes + mb <= kRangeOutSlice) { obytes += mb; sl.t1++; sl.p1 = P.row[sl.t1]; continue; }
+            if (sl.t1 == sl.t0) {
+                uint32_t q = q0;
+                while (q < P.row[sl.t1 + 1] && obytes + P.piece[q].len <= kRangeOutSlice) obytes += P.piece[q++].len;
+                sl.t1++;
+                sl.p1 = q;
+            }
+            break;
+        }
+        // read the slice's members: one pread per run of consecutive entries
+        uint64_t packed = 0;
+        for (uint32_t i = sl.t0; i < sl.t1;) {
+            uint32_t e = i + 1;
+            while (e < sl.t1 && P.member[e] == P.member[e - 1] + 1 && fend[e - 1] == ix.coff[P.member[e]]) e++;
+            const uint64_t start = ix.coff[P.member[i]], len = fend[e - 1] - start;
+            size_t got = 0;
+            while (got < len) {
+                const ssize_t r = pread(job.fd, hin + packed + got, len - got, (off_t)(start + got));
+                if (r < 0) { set_error("read error on %s", src); return ZWZ_E_IO; }
+                if (r == 0) break;
+                got += (size_t)r;
+            }
+            for (uint32_t q = i; q < e; q++) {
+                moff[q] = packed + (ix.coff[P.member[q]] - start);
+                mend[q] = std::min(packed + (fend[q] - start), packed + got);
+            }
+            packed += got;
+            i = e;
+        }
+        uint8_t* d_in = static_cast<uint8_t*>(job.d[0]);
+        uint8_t* d_dec = static_cast<uint8_t*>(job.d[1]);
+        const uint32_t m = sl.t1 - sl.t0, np = sl.p1 - sl.p0;
+        if (int rc = ensure_rr(c, slice_bytes(m, np))) return rc;
+        HIPCHK(hipMemcpyAsync(d_in, hin, packed, hipMemcpyHostToDevice, c->stream));
+        if (int rc = queue_slice(c, P, sl, moff.data(), mend.data(), c->buf[kBufRangeHost].as<uint8_t>(), c->buf[kBufRangeDev].as<uint8_t>(), d_in, packed,
+                                 d_dec, true))
+            return rc;
+        if (obytes) HIPCHK(hipMemcpyAsync(hout, d_dec, obytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (int rc = slice_verdict(P, ix, sl, c->buf[kBufRangeHost].as<const uint8_t>(), ranges)) return rc;
+        uint64_t o = 0;
+        for (uint32_t q = sl.p0; q < sl.p1; q++) { memcpy(out + P.piece[q].dst, hout + o, P.piece[q].len); o += P.piece[q].len; }
+        p = sl.p1;
+        t = p < P.row[sl.t1] ? sl.t1 - 1 : sl.t1;         // a member cut in parts: its next part opens the next slice
+    }
+    return ZWZ_OK;
+}
+
+// ---- the member walk on the device, and chunks by virtual offset -----------------------------------------------------------------------
+
+// A failure of the walk (bgzf_core.h) in bgzf_walk_each's words: member number k, byte offset o
+int walk_failure(uint32_t kind, uint64_t k, uint64_t o, uint32_t value) {
+    static const char* const text[kBgzfNumKinds] = {
+        "", "", "truncated member header", "no extra field: a plain gzip member, not BGZF", "unsupported gzip header flags",
+        "extra field runs past the end of the input", "malformed extra field", "no BC subfield: not BGZF",
+        "BSIZE smaller than its header and trailer:", "BSIZE runs past the end of the input:", "ISIZE above 65535:",
+        "the member chain steps over the offset it has to hit: BSIZE"};
+    const char* what = kind == kBgzfMagic ? (k ? "trailing bytes that are not a gzip member" : "not gzip (bad magic or method)")
+                     : kind < kBgzfNumKinds ? text[kind] : "the walk lost the member chain";
+    const bool with_value = kind == kBgzfFlags || kind == kBgzfBsizeSmall || kind == kBgzfBsizePast || kind == kBgzfIsize || kind == kBgzfStepOver;
+    if (!with_value) set_error("bgzf: member %llu at byte offset %llu: %s", (unsigned long long)k, (unsigned long long)o, what);
+    else set_error("bgzf: member %llu at byte offset %llu: %s %llu", (unsigned long long)k, (unsigned long long)o, what, (unsigned long long)value);
+    return ZWZ_E_FORMAT;
+}
+
+// The whole buffer as one span: the strict walk.  *r = its result; the members stay on the device (W).
+int walk_whole_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, BgzfWalk* W, BgzfSpanResult* r) {
+    HIPCHK(hipSetDevice(c->device));
+    const BgzfSpan sp{0, gz_len, 0, 0};
+    if (int rc = bgzf_walk_spans(c, d_gz, gz_len, &sp, 1, W)) return rc;
+    *r = W->res[0];
+    return ZWZ_OK;
+}
+
+// Member slots [first, first + count) of a walk, brought to the host
+int walk_members_host(zwz_ctx* c, const BgzfWalk& W, uint64_t first, uint64_t count, uint64_t* off, uint32_t* isize) {
+    if (!count) return ZWZ_OK;
+    HIPCHK(hipMemcpyAsync(off, W.d_moff + first, 8 * count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(isize, W.d_misize + first, 4 * count, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ZWZ_OK;
+}
+
+// k chunks (vbeg, vend) against a stream of gz_len bytes: what can be refused without looking at the stream, and the merged spans of
+// their compressed offsets, ascending and apart, each chunk's in span_of.  A span has `limit` where a chunk needs the member AT its
+// end: it ends inside that member, or lies in it altogether.
+struct ChunkSpans { std::vector<BgzfSpan> spans; std::vector<uint32_t> span_of; };
+
+int chunk_refuse(uint32_t i, const uint64_t* chunks, const char* why) {
+    set_error("bgzf: chunk %u (%llu, %llu): %s", i, (unsigned long long)chunks[2 * i], (unsigned long long)chunks[2 * i + 1], why);
+    return ZWZ_E_INVALID;
+}
+
+int chunk_spans(const uint64_t* chunks, uint32_t k, uint64_t gz_len, ChunkSpans* S) {
+    std::vector<uint32_t> order(k);
+    for (uint32_t i = 0; i < k; i++) {
+        const uint64_t vb = chunks[2 * i], ve = chunks[2 * i + 1];
+        if (vb > ve) return chunk_refuse(i, chunks, "begins behind its end");
+        if ((vb >> 16) >= gz_len) return chunk_refuse(i, chunks, "begins at or past the end of the stream");
+        if ((ve >> 16) > gz_len) return chunk_refuse(i, chunks, "ends past the end of the stream");
+        if ((ve >> 16) == gz_len && (ve & 0xffffu)) return chunk_refuse(i, chunks, "ends inside a member that would start at the end of the stream");
+        order[i] = i;
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return chunks[2 * a] >> 16 < chunks[2 * b] >> 16; });
+    S->spans.clear();
+    S->span_of.assign(k, 0);
+    for (uint32_t q = 0; q < k; q++) {
+        const uint32_t i = order[q];
+        const uint64_t cb = chunks[2 * i] >> 16, ce = chunks[2 * i + 1] >> 16;
+        const uint32_t limit = ce < gz_len && ((chunks[2 * i + 1] & 0xffffu) || ce == cb) ? 1u : 0u;
+        if (S->spans.empty() || cb > S->spans.back().stop) S->spans.push_back(BgzfSpan{cb, ce, limit, 0});
+        else {
+            BgzfSpan& sp = S->spans.back();
+            if (ce > sp.stop) { sp.stop = ce; sp.limit = limit; }
+            else if (ce == sp.stop) sp.limit |= limit;
+        }
+        S->span_of[i] = (uint32_t)S->spans.size() - 1u;
+    }
+    return ZWZ_OK;
+}
+
+// The first failing span of a walk: a chain that steps over its stop is the request's fault (the first chunk that ends there is
+// named), everything else the stream's.
+int chunk_walk_verdict(const ChunkSpans& S, const BgzfSpanResult* res, const uint64_t* chunks, uint32_t k) {
+    for (size_t s = 0; s < S.spans.size(); s++) {
+        const BgzfSpanResult& r = res[s];
+        if (r.kind == kBgzfOk) continue;
+        if (r.kind != kBgzfStepOver) return walk_failure(r.kind, r.count, r.fail_off, r.value);
+        for (uint32_t i = 0; i < k; i++)
+            if (S.span_of[i] == s && chunks[2 * i + 1] >> 16 == S.spans[s].stop) {
+                set_error("bgzf: chunk %u (%llu, %llu): the member chain steps over its end: the member at byte offset %llu has BSIZE %u", i,
+                          (unsigned long long)chunks[2 * i], (unsigned long long)chunks[2 * i + 1], (unsigned long long)r.fail_off, r.value);
+                return ZWZ_E_INVALID;
+            }
+        return walk_failure(r.kind, r.count, r.fail_off, r.value);
+    }
+    return ZWZ_OK;
+}
+
+// The members walked (all spans, in order) as an index -- uoff the running sum of ISIZE -- and the chunks as (offset, length) ranges
+// in its decoded coordinates.  span_end[s] = the index of the first member behind span s.
+int chunk_ranges(const ChunkSpans& S, const std::vector<size_t>& span_end, const GziIndex& ix, const std::vector<uint32_t>& isize, uint64_t total,
+                 const uint64_t* chunks, uint32_t k, std::vector<uint64_t>* ranges, uint64_t* sizes) {
+    ranges->resize(2 * (size_t)k);
+    auto member_at = [&](uint64_t coff, size_t lo, size_t hi) {
+        const size_t j = std::lower_bound(ix.coff.begin() + lo, ix.coff.begin() + hi, coff) - ix.coff.begin();
+        return j < hi && ix.coff[j] == coff ? j : (size_t)-1;
+    };
+    for (uint32_t i = 0; i < k; i++) {
+        const uint64_t vb = chunks[2 * i], ve = chunks[2 * i + 1];
+        const uint32_t s = S.span_of[i];
+        const size_t lo = s ? span_end[s - 1] : 0, hi = span_end[s];
+        const size_t jb = member_at(vb >> 16, lo, hi);
+        if (jb == (size_t)-1) {
+            set_error("bgzf: chunk %u (%llu, %llu): byte offset %llu is no member of the chain that starts at byte offset %llu", i, (unsigned long long)vb,
+                      (unsigned long long)ve, (unsigned long long)(vb >> 16), (unsigned long long)S.spans[s].head);
+            return ZWZ_E_FORMAT;
+        }
+        if ((vb & 0xffffu) > isize[jb]) return chunk_refuse(i, chunks, "begins past the end of its block (the offset inside the block is above ISIZE)");
+        const uint64_t pb = ix.uoff[jb] + (vb & 0xffffu);
+        uint64_t pe;
+        const size_t je = member_at(ve >> 16, lo, hi);
+        if (je != (size_t)-1) {
+            if ((ve & 0xffffu) > isize[je]) return chunk_refuse(i, chunks, "ends past the end of its block (the offset inside the block is above ISIZE)");
+            pe = ix.uoff[je] + (ve & 0xffffu);
+        } else if (ve >> 16 == S.spans[s].stop) {
+            pe = hi < ix.uoff.size() ? ix.uoff[hi] : total;         // the span's chain ends there
+        } else {
+            return chunk_refuse(i, chunks, "the member chain steps over its end");
+        }
+        (*ranges)[2 * i] = pb;
+        (*ranges)[2 * i + 1] = sizes[i] = pe - pb;
+    }
+    return ZWZ_OK;
+}
+
+// Everything in front of the decode for a stream in device memory: refusals, the walk, the index, the ranges, the sizes
+struct ChunkJob { GziIndex ix; std::vector<uint64_t> ranges; };
+
+int chunk_prepare_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, const uint64_t* chunks, uint32_t k, uint64_t* sizes, ChunkJob* J) {
+    ChunkSpans S;
+    if (int rc = chunk_spans(chunks, k, gz_len, &S)) return rc;
+    J->ix.coff.clear(); J->ix.uoff.clear(); J->ranges.clear();
+    if (!k) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    BgzfWalk W;
+    if (int rc = bgzf_walk_spans(c, d_gz, gz_len, S.spans.data(), (uint32_t)S.spans.size(), &W)) return rc;
+    if (int rc = chunk_walk_verdict(S, W.res.data(), chunks, k)) return rc;
+    std::vector<uint64_t> off(W.slots);
+    std::vector<uint32_t> isz(W.slots);
+    if (int rc = walk_members_host(c, W, 0, W.slots, off.data(), isz.data())) return rc;
+    std::vector<size_t> span_end(S.spans.size());
+    std::vector<uint32_t> isize;
+    uint64_t total = 0;
+    for (size_t s = 0; s < S.spans.size(); s++) {
+        const BgzfSpanResult& r = W.res[s];
+        for (uint64_t j = r.first; j < r.first + r.count; j++) {
+            J->ix.coff.push_back(off[j]); J->ix.uoff.push_back(total); isize.push_back(isz[j]);
+            total += isz[j];
+        }
+        span_end[s] = J->ix.coff.size();
+    }
+    return chunk_ranges(S, span_end, J->ix, isize, total, chunks, k, &J->ranges, sizes);
+}
+
+// The host walk of one span of a file: the chain from head, which must hit stop (limit: the member there is walked too).  Of every
+// member only the header (32 bytes, more where the extra field is longer) and the ISIZE field are read, with pread: nothing in front
+// of head, nothing behind the member at stop, and one member's header in memory.
+struct FileHeaders {
+    int fd = -1;
+    uint64_t fsize = 0;
+    std::vector<uint8_t> buf;                            // a member's header at its place, ISIZE at its: what bgzf_member_parse looks at
+    int fill(uint64_t at, size_t from, size_t to) {      // file bytes [at + from, at + to) -> buf[from, to)
+        while (from < to) {
+            const ssize_t r = pread(fd, buf.data() + from, to - from, (off_t)(at + from));
+            if (r < 0) { set_error("read error"); return ZWZ_E_IO; }
+            if (r == 0) break;                               // (the file shrank under the walk: what is left in buf is zeros or stale, and parses or fails as such)
+            from += (size_t)r;
+        }
+        return ZWZ_OK;
+    }
+    // the member at file offset `at`
+    int parse(uint64_t at, BgzfMember* m) {
+        constexpr size_t kFirst = 32;
+        if (buf.empty()) buf.resize(kBgzfSlot + 16);
+        const uint64_t avail = std::min<uint64_t>(fsize - at, kBgzfSlot + 16);     // (a member is at most 65 536 bytes)
+        size_t have = (size_t)std::min<uint64_t>(avail, kFirst);
+        if (int rc = fill(at, 0, have)) return rc;
+        if (have >= 12) {
+            const size_t header = (size_t)std::min<uint64_t>(avail, 12u + le16_at(buf.data() + 10));
+            if (header > have) { if (int rc = fill(at, have, header)) return rc; have = header; }
+        }
+        *m = bgzf_member_parse(buf.data(), avail);
+        if (m->kind != kBgzfOk && m->kind != kBgzfIsize) return ZWZ_OK;
+        // BSIZE holds: now the ISIZE field, which the first parse read as whatever the buffer held
+        if (m->bsize > have) if (int rc = fill(at, std::max<size_t>(have, m->bsize - 4u), m->bsize)) return rc;
+        *m = bgzf_member_parse(buf.data(), avail);
+        return ZWZ_OK;
+    }
+};
+
+template <class F>
+int walk_file_span(FileHeaders& fh, const BgzfSpan& sp, BgzfSpanResult* r, F&& on_member) {
+    *r = BgzfSpanResult{0, 0, 0, 0, kBgzfOk, 0, 0};
+    uint64_t cur = sp.head, last_off = 0;
+    uint32_t last_bsize = 0;
+    for (;;) {
+        if (cur > sp.stop) { r->kind = kBgzfStepOver; r->value = last_bsize; r->fail_off = last_off; r->count--; return ZWZ_OK; }
+        if (cur == sp.stop && (!sp.limit || cur >= fh.fsize)) return ZWZ_OK;
+        BgzfMember m;
+        if (int rc = fh.parse(cur, &m)) return rc;
+        if (m.kind != kBgzfOk) { r->kind = m.kind; r->value = m.value; r->fail_off = cur; return ZWZ_OK; }
+        on_member(cur, m.isize);
+        r->count++; r->sum += m.isize;
+        if (cur == sp.stop) return ZWZ_OK;
+        last_bsize = m.bsize; last_off = cur;
+        cur += m.bsize;
+    }
+}
+
+int chunk_prepare_file(const char* src, const uint64_t* chunks, uint32_t k, uint64_t* sizes, ChunkJob* J) {
+    J->ix.coff.clear(); J->ix.uoff.clear(); J->ranges.clear();
+    FileHeaders fw;
+    fw.fd = open(src, O_RDONLY);
+    if (fw.fd < 0) { set_error("cannot open %s", src); return ZWZ_E_IO; }
+    struct stat stt {};
+    if (fstat(fw.fd, &stt) != 0) { close(fw.fd); set_error("cannot stat %s", src); return ZWZ_E_IO; }
+    fw.fsize = (uint64_t)stt.st_size;
+    ChunkSpans S;
+    if (int rc = chunk_spans(chunks, k, fw.fsize, &S)) { close(fw.fd); return rc; }
+    std::vector<BgzfSpanResult> res(S.spans.size());
+    std::vector<size_t> span_end(S.spans.size());
+    std::vector<uint32_t> isize;
+    uint64_t total = 0;
+    for (size_t s = 0; s < S.spans.size(); s++) {
+        const int rc = walk_file_span(fw, S.spans[s], &res[s], [&](uint64_t o, uint32_t isz) {
+            J->ix.coff.push_back(o); J->ix.uoff.push_back(total); isize.push_back(isz);
+            total += isz;
+        });
+        if (rc) { close(fw.fd); return rc; }
+        if (res[s].kind == kBgzfStepOver) { J->ix.coff.pop_back(); J->ix.uoff.pop_back(); total -= isize.back(); isize.pop_back(); }
+        span_end[s] = J->ix.coff.size();
+    }
+    close(fw.fd);
+    if (int rc = chunk_walk_verdict(S, res.data(), chunks, k)) return rc;
+    return chunk_ranges(S, span_end, J->ix, isize, total, chunks, k, &J->ranges, sizes);
+}
+
+// sum of sizes against a capacity (the sizes are set either way)
+int chunk_room(const uint64_t* sizes, uint32_t k, uint64_t cap, const char* who) {
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < k; i++) total += sizes[i];
+    if (total <= cap) return ZWZ_OK;
+    set_error("%s: the chunks decode to %llu bytes, room for %llu", who, (unsigned long long)total, (unsigned long long)cap);
+    return ZWZ_E_INVALID;
+}
+
 }  // namespace
 
 extern "C" {
@@ -571,32 +939,7 @@ int zwz_bgzf_read_ranges_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, c
     RangePlan P;
     if (int rc = plan_ranges(ix, ranges, k, &P)) return rc;
     if (P.total && !d_out) return ZWZ_E_INVALID;
-    const uint32_t T = (uint32_t)P.member.size();
-    if (!T) return ZWZ_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const uint32_t M = T < c->max_batch ? T : c->max_batch;
-    if (int rc = ensure_bgzf(c, M)) return rc;
-    // every slice packs into its own part of the plan buffers: the host fills slice s + 1 while the device runs slice s
-    std::vector<Slice> slices;
-    std::vector<size_t> at;
-    size_t bytes = 0;
-    for (uint32_t t0 = 0; t0 < T; t0 += M) {
-        const uint32_t t1 = T - t0 < M ? T : t0 + M;
-        slices.push_back({t0, t1, P.row[t0], P.row[t1]});
-        at.push_back(bytes);
-        bytes += round_up(slice_bytes(t1 - t0, P.row[t1] - P.row[t0]), 16);
-    }
-    if (int rc = ensure_rr(c, bytes)) return rc;
-    std::vector<uint64_t> moff(T);
-    for (uint32_t t = 0; t < T; t++) moff[t] = ix.coff[P.member[t]];
-    uint8_t* h = c->buf[kBufRangeHost].as<uint8_t>();
-    uint8_t* d = c->buf[kBufRangeDev].as<uint8_t>();
-    for (size_t s = 0; s < slices.size(); s++)
-        if (int rc = queue_slice(c, P, slices[s], moff.data(), nullptr, h + at[s], d + at[s], d_gz, gz_len, d_out, false)) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (size_t s = 0; s < slices.size(); s++)
-        if (int rc = slice_verdict(P, ix, slices[s], h + at[s], ranges)) return rc;
-    return ZWZ_OK;
+    return run_plan_dev(c, ix, P, ranges, d_gz, gz_len, d_out);
 }
 
 // Touched members are read with one pread per run of consecutive index entries, into pinned staging of at most kFileSliceBlocks
@@ -624,88 +967,104 @@ int zwz_bgzf_read_ranges_file(zwz_ctx* c, const char* src, const char* gzi_path,
     RangePlan P;
     if (int rc = plan_ranges(ix, ranges, k, &P)) return rc;
     if (P.total && !out) return ZWZ_E_INVALID;
-    const uint32_t T = (uint32_t)P.member.size();
-    if (!T) return ZWZ_OK;
-    HIPCHK(hipSetDevice(c->device));
-    FileJob job;
-    job.fd = open(src, O_RDONLY);
-    if (job.fd < 0) { set_error("cannot open %s", src); return ZWZ_E_IO; }
-    struct stat stt {};
-    if (fstat(job.fd, &stt) != 0) { set_error("cannot stat %s", src); return ZWZ_E_IO; }
-    const uint64_t fsize = (uint64_t)stt.st_size;
-    // member t's bytes in the file: [coff, end), end = the next entry's offset (at most a member's 65 536 bytes further), or the file's end
-    const size_t last = ix.coff.size() - 1;
-    std::vector<uint64_t> fend(T);
-    for (uint32_t t = 0; t < T; t++) {
-        const size_t j = P.member[t];
-        const uint64_t s0 = ix.coff[j];
-        uint64_t e = std::min<uint64_t>(s0 + kBgzfSlot, fsize);
-        if (j < last) e = std::min(e, ix.coff[j + 1]);
-        fend[t] = s0 >= fsize ? s0 : e;                     // (an entry past the file's end: nothing to read, the member does not parse)
-    }
-    const uint32_t S = c->max_batch < kFileSliceBlocks ? c->max_batch : kFileSliceBlocks;
-    const size_t B = (size_t)S * kBgzfSlot;
-    if (int rc = job.alloc({B + 16, kRangeOutSlice + 16}, {B + 16, kRangeOutSlice + 16})) return rc;    // packed members, decoded pieces
-    if (int rc = ensure_bgzf(c, S)) return rc;
-    uint8_t* hin = static_cast<uint8_t*>(job.h[0]);
-    uint8_t* hout = static_cast<uint8_t*>(job.h[1]);
-    std::vector<uint64_t> moff(T), mend(T);
-    uint32_t t = 0, p = 0;
-    while (t < T) {
-        // the slice: whole members while they fit S and kRangeOutSlice, or a part of one member's pieces that alone exceed kRangeOutSlice
-        // (every piece is at most 65 536 bytes: a part holds at least one).  Its first member may continue one cut before.
-        Slice sl{t, t, p, p};
-        uint64_t obytes = 0;
-        while (sl.t1 < T && sl.t1 - sl.t0 < S) {
-            const uint32_t q0 = sl.t1 == t ? p : P.row[sl.t1];
-            uint64_t mb = 0;
-            for (uint32_t q = q0; q < P.row[sl.t1 + 1]; q++) mb += P.piece[q].len;
-            if (obytes + mb <= kRangeOutSlice) { obytes += mb; sl.t1++; sl.p1 = P.row[sl.t1]; continue; }
-            if (sl.t1 == sl.t0) {
-                uint32_t q = q0;
-                while (q < P.row[sl.t1 + 1] && obytes + P.piece[q].len <= kRangeOutSlice) obytes += P.piece[q++].len;
-                sl.t1++;
-                sl.p1 = q;
-            }
-            break;
-        }
-        // read the slice's members: one pread per run of consecutive entries
-        uint64_t packed = 0;
-        for (uint32_t i = sl.t0; i < sl.t1;) {
-            uint32_t e = i + 1;
-            while (e < sl.t1 && P.member[e] == P.member[e - 1] + 1 && fend[e - 1] == ix.coff[P.member[e]]) e++;
-            const uint64_t start = ix.coff[P.member[i]], len = fend[e - 1] - start;
-            size_t got = 0;
-            while (got < len) {
-                const ssize_t r = pread(job.fd, hin + packed + got, len - got, (off_t)(start + got));
-                if (r < 0) { set_error("read error on %s", src); return ZWZ_E_IO; }
-                if (r == 0) break;
-                got += (size_t)r;
-            }
-            for (uint32_t q = i; q < e; q++) {
-                moff[q] = packed + (ix.coff[P.member[q]] - start);
-                mend[q] = std::min(packed + (fend[q] - start), packed + got);
-            }
-            packed += got;
-            i = e;
-        }
-        uint8_t* d_in = static_cast<uint8_t*>(job.d[0]);
-        uint8_t* d_dec = static_cast<uint8_t*>(job.d[1]);
-        const uint32_t m = sl.t1 - sl.t0, np = sl.p1 - sl.p0;
-        if (int rc = ensure_rr(c, slice_bytes(m, np))) return rc;
-        HIPCHK(hipMemcpyAsync(d_in, hin, packed, hipMemcpyHostToDevice, c->stream));
-        if (int rc = queue_slice(c, P, sl, moff.data(), mend.data(), c->buf[kBufRangeHost].as<uint8_t>(), c->buf[kBufRangeDev].as<uint8_t>(), d_in, packed,
-                                 d_dec, true))
-            return rc;
-        if (obytes) HIPCHK(hipMemcpyAsync(hout, d_dec, obytes, hipMemcpyDeviceToHost, c->stream));
+    return run_plan_file(c, src, ix, P, ranges, out);
+}
+
+int zwz_bgzf_index_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, uint64_t* d_member_off, uint32_t cap, uint32_t* n_members, uint64_t* raw_len) {
+    if (!c || (gz_len && !d_gz) || !n_members || !raw_len || ((uintptr_t)d_gz & 15u)) return ZWZ_E_INVALID;
+    BgzfWalk W;
+    BgzfSpanResult r;
+    if (int rc = walk_whole_dev(c, d_gz, gz_len, &W, &r)) return rc;
+    *n_members = r.count;
+    *raw_len = r.sum;
+    const uint32_t give = d_member_off ? std::min(cap, r.count) : 0u;
+    if (give) {
+        HIPCHK(hipMemcpyAsync(d_member_off, W.d_moff + r.first, 8 * (size_t)give, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (int rc = slice_verdict(P, ix, sl, c->buf[kBufRangeHost].as<const uint8_t>(), ranges)) return rc;
-        uint64_t o = 0;
-        for (uint32_t q = sl.p0; q < sl.p1; q++) { memcpy(out + P.piece[q].dst, hout + o, P.piece[q].len); o += P.piece[q].len; }
-        p = sl.p1;
-        t = p < P.row[sl.t1] ? sl.t1 - 1 : sl.t1;         // a member cut in parts: its next part opens the next slice
+    }
+    if (r.kind != kBgzfOk) return walk_failure(r.kind, r.count, r.fail_off, r.value);
+    if (d_member_off && r.count > cap) { set_error("zwz_bgzf_index: %llu members, room for %u", (unsigned long long)r.count, cap); return ZWZ_E_INVALID; }
+    return ZWZ_OK;
+}
+
+int zwz_bgzf_gzi_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, uint8_t* gzi, uint64_t cap, uint64_t* gzi_len) {
+    if (!c || (gz_len && !d_gz) || !gzi_len || ((uintptr_t)d_gz & 15u)) return ZWZ_E_INVALID;
+    *gzi_len = 0;
+    BgzfWalk W;
+    BgzfSpanResult r;
+    if (int rc = walk_whole_dev(c, d_gz, gz_len, &W, &r)) return rc;
+    if (r.kind != kBgzfOk) return walk_failure(r.kind, r.count, r.fail_off, r.value);
+    std::vector<uint64_t> off(r.count);
+    std::vector<uint32_t> isz(r.count);
+    if (int rc = walk_members_host(c, W, r.first, r.count, off.data(), isz.data())) return rc;
+    GziBuilder b;
+    for (uint32_t j = 0; j < r.count; j++) b.member(off[j], isz[j]);
+    b.finish();
+    *gzi_len = 8 + b.buf.size();
+    if (!gzi) return ZWZ_OK;
+    if (cap < *gzi_len) { set_error("zwz_bgzf_gzi: %llu bytes, room for %llu", (unsigned long long)*gzi_len, (unsigned long long)cap); return ZWZ_E_INVALID; }
+    put64(gzi, b.entries);
+    if (!b.buf.empty()) memcpy(gzi + 8, b.buf.data(), b.buf.size());
+    return ZWZ_OK;
+}
+
+int zwz_bgzf_voffsets(const uint8_t* gzi, uint64_t gzi_len, const uint64_t* offsets, uint32_t k, uint64_t* voffsets) {
+    if ((k && (!offsets || !voffsets)) || (gzi_len && !gzi)) return ZWZ_E_INVALID;
+    GziIndex ix;
+    if (int rc = parse_gzi(gzi, gzi_len, &ix)) return rc;
+    for (uint32_t i = 0; i < k; i++) {
+        const uint64_t a = offsets[i];
+        const size_t j = std::upper_bound(ix.uoff.begin(), ix.uoff.end(), a) - ix.uoff.begin() - 1;
+        const uint64_t within = a - ix.uoff[j];
+        if (ix.coff[j] >= kBgzfVoffMaxCoff) {
+            set_error("bgzf: offset %u (%llu): its member starts at byte offset %llu, at or above 2^48", i, (unsigned long long)a, (unsigned long long)ix.coff[j]);
+            return ZWZ_E_INVALID;
+        }
+        if (within >= 65536u) {
+            set_error("bgzf: offset %u (%llu) lies %llu bytes past the index entry below it: more than a block holds", i, (unsigned long long)a,
+                      (unsigned long long)within);
+            return ZWZ_E_INVALID;
+        }
+        voffsets[i] = bgzf_voffset(ix.coff[j], (uint32_t)within);
     }
     return ZWZ_OK;
+}
+
+int zwz_bgzf_chunk_sizes_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, const uint64_t* chunks, uint32_t k, uint64_t* sizes) {
+    if (!c || (k && (!chunks || !sizes)) || (gz_len && !d_gz) || ((uintptr_t)d_gz & 15u)) return ZWZ_E_INVALID;
+    ChunkJob J;
+    return chunk_prepare_dev(c, d_gz, gz_len, chunks, k, sizes, &J);
+}
+
+int zwz_bgzf_read_chunks_dev(zwz_ctx* c, const uint8_t* d_gz, uint64_t gz_len, const uint64_t* chunks, uint32_t k, uint8_t* d_out, uint64_t out_cap,
+                             uint64_t* sizes) {
+    if (!c || (k && (!chunks || !sizes)) || (gz_len && !d_gz) || ((uintptr_t)d_gz & 15u)) return ZWZ_E_INVALID;
+    ChunkJob J;
+    if (int rc = chunk_prepare_dev(c, d_gz, gz_len, chunks, k, sizes, &J)) return rc;
+    if (int rc = chunk_room(sizes, k, out_cap, "zwz_bgzf_read_chunks_dev")) return rc;
+    if (!k) return ZWZ_OK;
+    RangePlan P;
+    if (int rc = plan_ranges(J.ix, J.ranges.data(), k, &P)) return rc;
+    if (P.total && !d_out) return ZWZ_E_INVALID;
+    return run_plan_dev(c, J.ix, P, J.ranges.data(), d_gz, gz_len, d_out);
+}
+
+int zwz_bgzf_chunk_sizes_file(const char* src, const uint64_t* chunks, uint32_t k, uint64_t* sizes) {
+    if (!src || (k && (!chunks || !sizes))) return ZWZ_E_INVALID;
+    ChunkJob J;
+    return chunk_prepare_file(src, chunks, k, sizes, &J);
+}
+
+int zwz_bgzf_read_chunks_file(zwz_ctx* c, const char* src, const uint64_t* chunks, uint32_t k, uint8_t* out, uint64_t out_cap, uint64_t* sizes) {
+    if (!c || !src || (k && (!chunks || !sizes))) return ZWZ_E_INVALID;
+    ChunkJob J;
+    if (int rc = chunk_prepare_file(src, chunks, k, sizes, &J)) return rc;
+    if (int rc = chunk_room(sizes, k, out_cap, "zwz_bgzf_read_chunks_file")) return rc;
+    if (!k) return ZWZ_OK;
+    RangePlan P;
+    if (int rc = plan_ranges(J.ix, J.ranges.data(), k, &P)) return rc;
+    if (P.total && !out) return ZWZ_E_INVALID;
+    return run_plan_file(c, src, J.ix, P, J.ranges.data(), out);
 }
 
 }  // extern "C"
