@@ -384,6 +384,21 @@ int zwz_inflate_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const u
 int zwz_inflate_split_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
                                   uint32_t n, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
                                   uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_segments);
+/* zwz_inflate_split_streams_dev that also writes every stream's seek index (the layout below, under "A seek index for ordinary
+ * streams").  The first twelve arguments, the decoded bytes, d_out_len, d_status and d_segments are exactly that call's; span, d_idx,
+ * d_idx_off, d_idx_cap and d_idx_len are zwz_inflate_streams_index_dev's (device arrays).  A stream that SPLITS gets the index of its
+ * flush points by the rule of zwz_deflate_streams_index_dev (further down): the points are the chain's piece starts, which the
+ * split decode has found and proved with their decoded offsets, so the index costs a flag per piece, a scan and the entries -- hist
+ * 0, no windows, 24 bytes an entry -- and is built at the split decode's rate.  For what zwz_deflate_streams_index_dev wrote it is,
+ * byte for byte, the index that call wrote.  d_idx_len[i] = 0 where the final status is not 0 (a checksum mismatch included) or the
+ * capacity is too small.  A stream that does not split goes through zwz_inflate_streams_index_dev's marking form instead of the plain
+ * stream form and gets exactly that call's bytes, lengths, status and index (none for a stream of several members).
+ * zwz_inflate_index_bound(d_out_cap[i], span) always fits either way.  NOT asynchronous, as zwz_inflate_split_streams_dev. */
+int zwz_inflate_split_streams_index_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *d_in_off,
+                                        const uint64_t *d_in_len, uint32_t n, uint8_t *d_out, const uint64_t *d_out_off,
+                                        const uint64_t *d_out_cap, uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_segments,
+                                        uint32_t span, uint8_t *d_idx, const uint64_t *d_idx_off, const uint64_t *d_idx_cap,
+                                        uint64_t *d_idx_len);
 /* One file of any size holding ONE raw, zlib or gzip stream -> its decoded bytes: the way back from zwz_deflate_stream_file and
  * `main gzip`.  The compressed file passes through the device in slices of "split_slice_bytes" (context option, default 67108864,
  * 4096 .. 2^28); per slice the pieces that end inside it are found and decoded as above and written, and the next slice starts where
@@ -397,6 +412,14 @@ int zwz_inflate_split_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, c
  * one-stream path if it is shorter than 2^29 bytes (which reads further members and names garbage), in legs otherwise.  dst is
  * written as dst.part and renamed on success only.  Synchronous. */
 int zwz_inflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst);
+/* zwz_inflate_stream_file that also writes the file's seek index to dst_idx, at the context's "index_span_bytes"; dst may be NULL
+ * (index only).  A file that splits gets the index of its flush points (zwz_inflate_split_streams_index_dev's, byte for byte what
+ * zwz_deflate_stream_file_index wrote for a file of its own): every slice hands back the starts of the pieces it decoded, the host
+ * applies the rule with the last point carried from slice to slice and seals the header once the trailer is known.  A file that does
+ * not split before any byte was written (or is one piece in all), or in which bytes other than zeros follow the first gzip member, goes through
+ * zwz_inflate_legs_file(ctx, wrap, src, dst, dst_idx, NULL) and gets that call's index.  A chain that breaks after bytes were
+ * written is ZWZ_E_FORMAT, as above.  dst_idx is written as <dst_idx>.part and renamed behind dst: a failure leaves neither. */
+int zwz_inflate_split_index_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst, const char *dst_idx);
 
 /* ---- A seek index for ordinary streams: parallel and ranged inflate ----------------------------------------------------------------
  * An ordinary stream -- gzip, zlib.compress, pigz without -i, git, PNG, anything with sync flushes -- offers no cut: every block may
@@ -424,6 +447,8 @@ int zwz_inflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char 
  * a file of that size from zwz_inflate_legs_file, which zwz_inflate_index_file and zwz_inflate_stream_file call where one launch ends.) */
 /* The most an index of a stream that decodes to decoded_cap bytes takes at this span (0: 1 MiB); 0 for a span that is not allowed. */
 uint64_t zwz_inflate_index_bound(uint64_t decoded_cap, uint32_t span);
+/* The context option "index_span_bytes" as it stands (0 for a null context): what the calls with span 0 and the file calls take */
+uint32_t zwz_ctx_index_span(zwz_ctx *ctx);
 /* zwz_inflate_streams_dev that also writes every stream's index.  The first eleven arguments, the decoded bytes, d_out_len and
  * d_status are exactly that call's.  span: decoded bytes between checkpoints at least, a power of two in 16 KiB .. 1 GiB; 0 takes
  * the context option "index_span_bytes" (default 1048576).  The index of stream i goes to d_idx + d_idx_off[i] (device arrays;
@@ -586,6 +611,30 @@ int zwz_deflate_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const u
 /* One file of any size as one stream, in slices through pinned staging (reading, the GPU and writing overlap; the checksum and the
  * position carry from slice to slice).  dst is written as <dst>.part and renamed only on success; on failure no dst is left. */
 int zwz_deflate_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst);
+/* zwz_deflate_streams_dev that also writes every stream's seek index (the layout above, under "A seek index for ordinary streams") as
+ * it writes the stream: nothing is decoded.  Every piece starts behind a full-flush marker, where nothing refers back, so the entries
+ * have hist 0 and the index holds no windows: 24 bytes an entry.  The POINTS of a stream are the body's first block (decoded offset 0)
+ * and every block that starts behind a flush marker, in stream order; entry 0 is the first point, and a later point at decoded offset
+ * o is an entry when o < the decoded length and floor(o / span) is above that of the point in front of it -- the first point in each
+ * span-sized bucket of the output.  The end bit is 10 bits into the 03 00 behind the last marker.  Every reader of an index takes it:
+ * zwz_inflate_indexed_dev, zwz_inflate_read_ranges_dev, the batch calls and the file forms.
+ * The first eleven arguments, the stream bytes, d_out_len and d_status are exactly zwz_deflate_streams_dev's.  span: a power of two
+ * in 16 KiB .. 1 GiB; 0 takes the context option "index_span_bytes".  The index of stream i goes to d_idx + idx_off[i] (d_idx device
+ * memory; idx_off and idx_cap HOST arrays of n, d_idx and every offset multiples of 16), at most idx_cap[i] bytes, and d_idx_len[i]
+ * (device) receives its length: 0 with status 3 or a capacity too small; no byte outside [idx_off[i], idx_off[i] + idx_cap[i]) is
+ * written.  Asynchronous on the context's stream.
+ * zwz_deflate_stream_index_bound: the exact worst case for n input bytes, 64 + 24 (n / span + 1) rounded up to 16 (span 0: 1 MiB);
+ * 0 for a span that is not allowed.
+ * zwz_deflate_stream_file_index: zwz_deflate_stream_file that also writes the stream's index to dst_idx, for files of any size, at
+ * the context's "index_span_bytes".  The entries of each slice come from the same kernels, told the decoded bytes and the stream
+ * bytes in front of the slice; the host appends them and seals the header once the trailer is known.  dst_idx is written as
+ * <dst_idx>.part and renamed behind dst: a failure leaves neither file. */
+uint64_t zwz_deflate_stream_index_bound(uint64_t n, uint32_t span);
+int zwz_deflate_stream_file_index(zwz_ctx *ctx, int wrap, const char *src, const char *dst, const char *dst_idx);
+int zwz_deflate_streams_index_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
+                                  uint8_t *d_out, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *d_out_len,
+                                  uint32_t *d_status, uint32_t span, uint8_t *d_idx, const uint64_t *idx_off,
+                                  const uint64_t *idx_cap, uint64_t *d_idx_len);
 
 /* ---- ZIP archives ---------------------------------------------------------------------------------------------------------------
  * One raw DEFLATE stream per entry, a CRC-32 per entry and a directory at the end: what unzip, Python's zipfile and every file manager

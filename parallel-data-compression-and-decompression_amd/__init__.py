@@ -22,11 +22,15 @@ and ordinary DEFLATE data of any size, a batch of independent streams in one lau
     Codec.inflate_streams / Codec.inflate_streams_dev          (raw, zlib or gzip; bytes or device tensors)
     Codec.inflate_stream / Codec.inflate_split_streams_dev     (one long stream with full-flush points: a wave per piece)
     Codec.inflate_stream_file                                  (one file of any size, in slices; `main gunzip`)
+    Codec.inflate_split_index_file                                             (the same for a file of any size; `main gunzip --split --write-index`, `main gzindex --split`)
+    Codec.inflate_stream_index / Codec.inflate_split_streams_index_dev         (the split decode that also writes the seek index of the flush points)
     Codec.inflate_index / Codec.inflate_indexed / Codec.read_ranges            (the seek index of one ordinary stream: a wave per segment)
     Codec.inflate_indexed_batch / Codec.read_ranges_batch, pack_indexes        (many indexed streams in one launch; the _dev forms)
     Codec.inflate_legs_file                                    (one file of ANY length through leg windows: its bytes and / or its seek index; one wave)
     Codec.deflate_streams / Codec.deflate_streams_dev          (the way there: libz's level-6 full-flush streams, any size)
     Codec.deflate_stream_file, deflate_stream_bound            (one file as one .gz / zlib / raw stream)
+    Codec.deflate_streams_index / Codec.deflate_streams_index_dev, Codec.deflate_stream_file_index, deflate_stream_index_bound
+                                                               (the same, with the seek index of the flush points written alongside)
 and ZIP archives, a batch of entries per launch (what unzip, zipfile and file managers open; no reference counterpart):
     Codec.zip / Codec.unzip                                    ([(name, bytes)] -> archive bytes and back)
     Codec.zip_dev / Codec.unzip_dev                            (device tensors)
@@ -103,6 +107,8 @@ def lib():
         L.zwz_ctx_set_chunk_size.argtypes = [vp, u32]
         L.zwz_ctx_set_level.argtypes = [vp, c.c_int]
         L.zwz_ctx_level.argtypes = [vp]
+        L.zwz_ctx_index_span.restype = u32
+        L.zwz_ctx_index_span.argtypes = [vp]
         L.zwz_ctx_set_strategy.argtypes = [vp, c.c_int]
         L.zwz_ctx_strategy.argtypes = [vp]
         L.zwz_ctx_set_option.argtypes = [vp, c.c_char_p, c.c_char_p]
@@ -127,6 +133,8 @@ def lib():
         L.zwz_inflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         L.zwz_inflate_split_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
         L.zwz_inflate_stream_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
+        L.zwz_inflate_split_index_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p, c.c_char_p]
+        L.zwz_inflate_split_streams_index_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
         L.zwz_inflate_index_bound.restype = u64
         L.zwz_inflate_index_bound.argtypes = [u64, u32]
         L.zwz_inflate_streams_index_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
@@ -144,6 +152,10 @@ def lib():
         L.zwz_deflate_stream_bound.argtypes = [u64, c.c_int]
         L.zwz_deflate_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         L.zwz_deflate_stream_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
+        L.zwz_deflate_stream_file_index.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p, c.c_char_p]
+        L.zwz_deflate_stream_index_bound.restype = u64
+        L.zwz_deflate_stream_index_bound.argtypes = [u64, u32]
+        L.zwz_deflate_streams_index_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
         L.zwz_zip_index.argtypes = [vp, u64, vp, u32, c.POINTER(u32)]
         L.zwz_zip_bound.restype = u64
         L.zwz_zip_bound.argtypes = [vp, vp, u32]
@@ -321,6 +333,80 @@ class Codec:
         full-flush points, the one-wave path otherwise.  Capacity guessed and regrown as inflate_streams does; raises ZwzError
         (.stream_status) as inflate_streams does."""
         return self.inflate_streams([data], wrap, None if out_size is None else [out_size], split=True)[0]
+
+    def inflate_split_streams_index_dev(self, wrap, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_segments, d_idx,
+                                        d_idx_off, d_idx_cap, d_idx_len, span=0):
+        """zwz_inflate_split_streams_index_dev: inflate_split_streams_dev's arguments and results (d_segments may be None), and the seek
+        index of stream i at d_idx + d_idx_off[i] as inflate_streams_index_dev lays it out.  A stream that splits gets the index of its
+        flush points (no windows), built at the split decode's rate; any other stream the one-wave decode's index.  The results are
+        complete after sync()."""
+        n = d_in_len.numel()
+        _check(lib().zwz_inflate_split_streams_index_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), d_in_off.data_ptr(), d_in_len.data_ptr(), n,
+                                                         d_out.data_ptr(), d_out_off.data_ptr(), d_out_cap.data_ptr(), d_out_len.data_ptr(),
+                                                         d_status.data_ptr(), d_segments.data_ptr() if d_segments is not None else None, int(span),
+                                                         d_idx.data_ptr(), d_idx_off.data_ptr(), d_idx_cap.data_ptr(), d_idx_len.data_ptr()),
+               "zwz_inflate_split_streams_index_dev")
+
+    def inflate_stream_index(self, data, wrap="gzip", span=None, out_size=None):
+        """bytes of ONE raw / zlib / gzip stream -> (decoded bytes, index bytes, segments) through the split decode: a stream with
+        full-flush points is decoded by a wave per piece (segments > 0) and gets the index of those points, without windows; any other
+        stream is decoded by one wave (segments 0) and gets inflate_index's index (b"" for a gzip stream of several members).
+        Capacity and errors as inflate_index."""
+        import numpy as np
+        import torch
+        w = WRAPS.get(wrap, wrap)
+        data = bytes(data)
+        span = int(span or 0)
+        cap = int(out_size) if out_size is not None else max(4 * len(data), 1 << 16)
+        if out_size is None and w == WRAP_GZIP and len(data) >= 4:
+            cap = max(int.from_bytes(data[-4:], "little"), 1)
+        cap = min(cap, STREAM_MAX_OUT - 1)
+        dev = torch.device("cuda", self.device)
+        d_in = _device_input(torch, data, self.device)
+        while True:
+            bound = lib().zwz_inflate_index_bound(cap, span)
+            if bound == 0:
+                raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
+            d_out = torch.empty((cap + 15) // 16 * 16 or 16, dtype=torch.uint8, device=dev)
+            d_idx = torch.empty(bound, dtype=torch.uint8, device=dev)
+            par = torch.from_numpy(np.array([0, len(data), 0, cap, 0, bound, 0, 0], dtype=np.int64)).to(dev)
+            d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+            d_seg = torch.zeros(1, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+            self.inflate_split_streams_index_dev(w, d_in, par[0:1], par[1:2], d_out, par[2:3], par[3:4], par[6:7], d_st, d_seg, d_idx, par[4:5], par[5:6],
+                                                 par[7:8], span)
+            self.sync()
+            st, olen, ilen = int(d_st.item()), int(par[6].item()), int(par[7].item())
+            if st == STREAM_OVERFLOW and out_size is None and cap < STREAM_MAX_OUT - 1:
+                cap = min(2 * cap, STREAM_MAX_OUT - 1)
+                continue
+            if st != STREAM_END:
+                err = ZwzError("inflate_stream_index: status %d" % st)
+                err.status, err.index, err.stream_status = E_FORMAT, 0, st
+                raise err
+            return d_out[:olen].cpu().numpy().tobytes(), d_idx[:ilen].cpu().numpy().tobytes(), int(d_seg.item())
+
+    def _with_span(self, span, call):
+        """call() with the context option "index_span_bytes" at span (None: as it is); afterwards the option is what the context
+        itself held before (zwz_ctx_index_span), however it was set"""
+        if not span:
+            return call()
+        if lib().zwz_inflate_index_bound(1, int(span)) == 0:
+            raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
+        before = str(lib().zwz_ctx_index_span(self._h))
+        self.set_option("index_span_bytes", str(int(span)))
+        try:
+            return call()
+        finally:
+            self.set_option("index_span_bytes", before)
+
+    def inflate_split_index_file(self, src, dst, dst_idx, wrap="gzip", span=None):
+        """inflate_stream_file that also writes the file's seek index to dst_idx (zwz_inflate_split_index_file; `main gunzip --split
+        --write-index`, `main gzindex --split`); dst None: the index only.  A file with full-flush points gets their index, without
+        windows, at the split decode's rate; any other file inflate_legs_file's.  span: for this call.  Both files appear on success only."""
+        self._with_span(span, lambda: _check(lib().zwz_inflate_split_index_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src),
+                                                                                os.fsencode(dst) if dst is not None else None, os.fsencode(dst_idx)),
+                                             "zwz_inflate_split_index_file"))
 
     def inflate_stream_file(self, src, dst, wrap="gzip"):
         """One file holding one raw / zlib / gzip stream of any size -> dst (zwz_inflate_stream_file; `main gunzip`).  ZwzError with
@@ -764,9 +850,78 @@ class Codec:
                 raise ZwzError("deflate_streams: stream %d needs %d bytes, above its bound of %d" % (i, olen[i], caps[i]))
         return [host[ooff[i]:ooff[i] + olen[i]].tobytes() for i in range(n)]
 
+    def deflate_streams_index_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status, d_idx, idx_off, idx_cap,
+                                  d_idx_len, span=0):
+        """zwz_deflate_streams_index_dev: deflate_streams_dev's arguments and results, and the seek index of stream i -- an entry at the
+        first piece start in every `span` decoded bytes, no windows -- at d_idx + idx_off[i] (d_idx a 16-byte aligned CUDA uint8 tensor,
+        idx_off and idx_cap HOST sequences, d_idx_len an int64 device tensor: 0 with status 3 or a capacity too small).  span: a power of
+        two in 16 KiB .. 1 GiB; 0: the context option "index_span_bytes".  Asynchronous."""
+        import numpy as np
+        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap, idx_off, idx_cap)]
+        n = arr[1].size
+        if any(a.size != n for a in arr):
+            raise ValueError("in_off, in_len, out_off, out_cap, idx_off and idx_cap must have one entry per stream")
+        _check(lib().zwz_deflate_streams_index_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n,
+                                                   d_out.data_ptr(), arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(),
+                                                   d_status.data_ptr(), int(span), d_idx.data_ptr(), arr[4].ctypes.data, arr[5].ctypes.data,
+                                                   d_idx_len.data_ptr()), "zwz_deflate_streams_index_dev")
+
+    def deflate_streams_index(self, buffers, wrap="gzip", span=None):
+        """[bytes] -> [(stream, index)]: deflate_streams, and with every stream the seek index of its full-flush points, written as
+        the stream is (nothing is decoded): what inflate_indexed, read_ranges and their batch and file forms take.  span: decoded
+        bytes an entry covers at least, a power of two in 16 KiB .. 1 GiB (None: the context's "index_span_bytes", 1 MiB)."""
+        import numpy as np
+        import torch
+        w = WRAPS.get(wrap, wrap)
+        if w not in (WRAP_RAW, WRAP_ZLIB, WRAP_GZIP):
+            raise ValueError("wrap must be raw, zlib or gzip")
+        span = int(span or 0)
+        if lib().zwz_deflate_stream_index_bound(1, span) == 0:
+            raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
+        buffers = [bytes(b) for b in buffers]
+        n = len(buffers)
+        if n == 0:
+            return []
+        dev = torch.device("cuda", self.device)
+        up = lambda a: (a + 15) // 16 * 16
+        lens = np.array([len(b) for b in buffers], dtype=np.int64)
+        caps = np.array([deflate_stream_bound(int(k), w) for k in lens], dtype=np.int64)
+        # (with span 0 the context's span applies, which may be below the default: the smallest span bounds them all)
+        icap = np.array([lib().zwz_deflate_stream_index_bound(int(k), span or 16384) for k in lens], dtype=np.int64)
+        offs, ooff, ioff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        offs[1:] = np.cumsum(up(lens[:-1]))
+        ooff[1:] = np.cumsum(up(caps[:-1]))
+        ioff[1:] = np.cumsum(icap[:-1])
+        blob = np.zeros(max(int(offs[-1] + up(lens[-1])), 16), dtype=np.uint8)
+        for i, b in enumerate(buffers):
+            blob[offs[i]:offs[i] + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        d_in = torch.from_numpy(blob).to(dev)
+        d_out = torch.empty(int(ooff[-1] + up(caps[-1])), dtype=torch.uint8, device=dev)
+        d_idx = torch.empty(int(ioff[-1] + icap[-1]), dtype=torch.uint8, device=dev)
+        d_olen = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_ilen = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.deflate_streams_index_dev(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st, d_idx, ioff, icap, d_ilen, span)
+        self.sync()
+        st, olen, ilen, host, ihost = d_st.cpu().numpy(), d_olen.cpu().numpy(), d_ilen.cpu().numpy(), d_out.cpu().numpy(), d_idx.cpu().numpy()
+        for i in range(n):
+            if st[i] != 0:
+                raise ZwzError("deflate_streams_index: stream %d needs %d bytes, above its bound of %d" % (i, olen[i], caps[i]))
+            if ilen[i] == 0:
+                raise ZwzError("deflate_streams_index: the index of stream %d does not fit its bound of %d bytes" % (i, icap[i]))
+        return [(host[ooff[i]:ooff[i] + olen[i]].tobytes(), ihost[ioff[i]:ioff[i] + ilen[i]].tobytes()) for i in range(n)]
+
     def deflate_stream_file(self, src, dst, wrap="gzip"):
         """One file of any size as one gzip (.gz), zlib or raw DEFLATE stream, streamed through the GPU in slices."""
         _check(lib().zwz_deflate_stream_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst)), "zwz_deflate_stream_file")
+
+    def deflate_stream_file_index(self, src, dst, dst_idx, wrap="gzip", span=None):
+        """deflate_stream_file that also writes the seek index of the stream's flush points to dst_idx, as it writes the stream
+        (zwz_deflate_stream_file_index; `main gzip --write-index`).  span: as deflate_streams_index, for this call (the context option
+        "index_span_bytes" is put back afterwards).  Both files appear on success only."""
+        self._with_span(span, lambda: _check(lib().zwz_deflate_stream_file_index(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst),
+                                                                                 os.fsencode(dst_idx)), "zwz_deflate_stream_file_index"))
 
     # ---- ZIP archives (include/zwz.h: zwz_zip_*) ------------------------------------------------
     def zip_dev(self, d_in, in_off, in_len, names, d_out, d_out_len, d_status, meta=None, out_cap=None):
@@ -1228,6 +1383,18 @@ def inflate_stream(data, wrap="gzip", out_size=None):
     return _codec().inflate_stream(data, wrap, out_size)
 
 
+def inflate_stream_index(data, wrap="gzip", span=None, out_size=None):
+    return _codec().inflate_stream_index(data, wrap, span, out_size)
+
+
+def inflate_split_index_file(src, dst, dst_idx, wrap="gzip", span=None):
+    return _codec().inflate_split_index_file(src, dst, dst_idx, wrap, span)
+
+
+def deflate_stream_file_index(src, dst, dst_idx, wrap="gzip", span=None):
+    return _codec().deflate_stream_file_index(src, dst, dst_idx, wrap, span)
+
+
 class PackedIndexes:
     """The seek indexes of a batch in one host buffer (pack_indexes): .blob (uint8), .off and .len (uint64, one element a stream)."""
     def __init__(self, blob, off, length):
@@ -1269,6 +1436,12 @@ def inflate_stream_file(src, dst, wrap="gzip"):
 def deflate_stream_bound(n, wrap="gzip"):
     """Worst-case size of one stream of n input bytes from Codec.deflate_streams (about 1.0009 n); needs no GPU."""
     return lib().zwz_deflate_stream_bound(n, WRAPS.get(wrap, wrap))
+
+
+def deflate_stream_index_bound(n, span=None):
+    """Worst-case size of the index Codec.deflate_streams_index writes for a stream of n input bytes: 64 + 24 (n // span + 1) rounded
+    up to 16 (span None: 1 MiB); 0 for a span that is not allowed.  Needs no GPU."""
+    return lib().zwz_deflate_stream_index_bound(n, int(span or 0))
 
 
 def zip_index(data):

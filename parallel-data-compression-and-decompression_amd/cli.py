@@ -220,7 +220,10 @@ def index_main(argv):
     """`gzindex <src> [<dst.zwi>] [--span N] [--zlib|--raw]` and `gunzip <src> <dst> --index <idx> [--offset B [--size S]]`: the seek
     index of an ordinary stream and the reads through it, as csrc/main.cpp's commands of the same names.  One process, one GPU.
     `gzindex ... --legs` and `gunzip <src> <dst> --legs [--write-index <dst.zwi> [--span N]]` decode in legs through staging windows
-    (Codec.inflate_legs_file) whatever the file's size: one wave, about 36 s a decoded GiB."""
+    (Codec.inflate_legs_file) whatever the file's size: one wave, about 36 s a decoded GiB.
+    `gzip <src> <dst> --write-index <dst.zwi> [--span N] [--zlib|--raw]` writes the stream and, as it writes, the seek index of its
+    flush points (Codec.deflate_stream_file_index): no decode, no windows.  `gunzip <src> <dst> --split --write-index <dst.zwi> [--span N]`
+    and `gzindex <src> [<dst.zwi>] --split [--span N]` build that index with the split decode (Codec.inflate_split_index_file)."""
     ap = argparse.ArgumentParser(prog="main " + argv[0])
     ap.add_argument("source")
     ap.add_argument("output", nargs="?" if argv[0] == "gzindex" else None)
@@ -229,21 +232,33 @@ def index_main(argv):
     if argv[0] == "gzindex":
         ap.add_argument("--span", type=int, default=0)
         ap.add_argument("--legs", action="store_true", help="decode in legs through staging windows, whatever the file's size")
+        ap.add_argument("--split", action="store_true", help="through the split decode: the index of the file's full-flush points")
+    elif argv[0] == "gzip":
+        ap.add_argument("--write-index", dest="write_index", required=True, help="the seek index of the stream's flush points")
+        ap.add_argument("--span", type=int, default=0, help="decoded bytes an entry covers at least")
     else:
         ap.add_argument("--index")
         ap.add_argument("--legs", action="store_true", help="decode in legs through staging windows, whatever the file's size")
-        ap.add_argument("--write-index", dest="write_index", help="with --legs: also write the seek index, from the same decode")
+        ap.add_argument("--split", action="store_true", help="the split decode, with --write-index: the index of the full-flush points")
+        ap.add_argument("--write-index", dest="write_index", help="with --legs or --split: also write the seek index, from the same decode")
         ap.add_argument("--span", type=int, default=0, help="with --write-index: decoded bytes between checkpoints")
         ap.add_argument("--offset", type=int)
         ap.add_argument("--size", type=int)
     a = ap.parse_args(argv[1:])
     wrap = "zlib" if a.zlib else "raw" if a.raw else "gzip"
-    if argv[0] == "gunzip" and (bool(a.legs) == bool(a.index) or (a.write_index and not a.legs) or (a.span and not a.write_index)):
-        ap.error("one of --index <idx> and --legs; --write-index needs --legs, --span needs --write-index")
+    if argv[0] == "gunzip" and (bool(a.legs) + bool(a.index) + bool(a.split) != 1 or (a.split and not a.write_index) or (a.span and not a.write_index)):
+        ap.error("one of --index <idx>, --legs and --split; --write-index needs --legs or --split, --split needs --write-index, --span needs --write-index")
+    if argv[0] == "gzindex" and a.legs and a.split:
+        ap.error("one of --legs and --split")
     from . import Codec, index_info
     codec = Codec(int(os.environ.get("LOCAL_RANK", "0")))
     try:
-        if a.legs:
+        if argv[0] == "gzip":
+            codec.deflate_stream_file_index(a.source, a.output, a.write_index, wrap, a.span or None)
+        elif a.split:
+            codec.inflate_split_index_file(a.source, None if argv[0] == "gzindex" else a.output,
+                                           (a.output or a.source + ".zwi") if argv[0] == "gzindex" else a.write_index, wrap, a.span or None)
+        elif a.legs:
             if a.span:
                 codec.set_option("index_span_bytes", str(a.span))
             if argv[0] == "gzindex":
@@ -271,7 +286,7 @@ def index_main(argv):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if argv and (argv[0] == "gzindex" or (argv[0] == "gunzip" and ("--index" in argv or "--legs" in argv))):
+    if argv and (argv[0] == "gzindex" or (argv[0] == "gunzip" and ("--index" in argv or "--legs" in argv or "--split" in argv)) or (argv[0] == "gzip" and "--write-index" in argv)):
         return index_main(argv)
     ap = argparse.ArgumentParser(prog="main", usage="%(prog)s <compress/decompress> <source directory path> <output directory path>")
     ap.add_argument("operation")

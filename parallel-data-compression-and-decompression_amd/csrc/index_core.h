@@ -255,6 +255,25 @@ inline void index_seal(uint8_t* p, uint64_t n, uint32_t wrap, uint32_t span, uin
 // body's first block always.
 ZWZ_HD bool index_mark_due(uint32_t marks, uint32_t out_pos, uint32_t last_mark, uint32_t span) { return marks == 0u || out_pos - last_mark >= span; }
 
+// ---- The index at full-flush points ---------------------------------------------------------------------------
+// Behind a full flush nothing refers back, so a block that starts there is a checkpoint with hist 0 and no window.  The POINTS of a
+// stream are the body's first block (point 0, decoded offset 0) and, in stream order, every block that starts behind a flush marker,
+// at decoded offset o_k.  Entry 0 is point 0; point k >= 1 is an entry when it is the first point in its span-sized bucket of the
+// output and bytes follow it.  The comparison is with the previous POINT, not the previous entry: a flag per point, no chain.
+ZWZ_HD bool index_flush_due(uint64_t prev_off, uint64_t off, uint64_t decoded_len, uint32_t span) { return off < decoded_len && off / span > prev_off / span; }
+// At most one entry a bucket: the exact worst case of a stream of n decoded bytes
+ZWZ_HD uint64_t index_flush_bound(uint64_t n, uint32_t span) { return (kIdxHeader + (n / span + 1u) * kIdxEntry + 15u) & ~15ull; }
+ZWZ_HD uint64_t index_flush_bytes(uint64_t count) { return (kIdxHeader + count * kIdxEntry + 15u) & ~15ull; }
+ZWZ_HD void index_flush_entry(uint8_t* e, uint64_t bit, uint64_t off) { put_le64(e, bit); put_le64(e + 8, off); put_le64(e + 16, 0); }
+// Where the writer's own final block, the 03 00 behind the last marker, ends: ten bits into its two bytes
+ZWZ_HD uint64_t index_flush_end_bit(uint64_t final_byte) { return 8u * final_byte + 10u; }
+// The host's sealing of such an index: `count` entries are in place behind the header of a buffer of index_flush_bytes(count)
+inline void index_flush_seal(uint8_t* p, uint32_t wrap, uint32_t span, uint64_t stream_len, uint64_t decoded_len, uint32_t count, uint64_t end_bit, uint32_t check) {
+    const uint64_t n = index_flush_bytes(count);
+    for (uint64_t z = kIdxHeader + (uint64_t)count * kIdxEntry; z < n; z++) p[z] = 0;
+    index_seal(p, n, wrap, span, stream_len, decoded_len, count, end_bit, check);
+}
+
 // The indexed-segment form's verdict: it must stand at the block header whose first bit is the segment's end bit (or behind the final
 // block, for the last segment), with exactly the indexed count and the decoder still running.
 ZWZ_HD bool index_segment_good(uint32_t status, uint32_t bit_pos, uint32_t end_bit, uint32_t out_pos, uint32_t cap, uint32_t last, uint32_t is_last) {

@@ -21,8 +21,12 @@ namespace zwz {
 
 enum SegKind : uint32_t { kSegBad = 0, kSegFlush = 1, kSegFinal = 2 };
 // What a measuring wave leaves: how it stopped, the stream offset of the byte behind its last block (kSegFlush: the next chain
-// candidate; kSegFinal: where the trailer starts), the bytes it would have written, the decoder's status.
+// candidate; kSegFinal: where the trailer starts), the bytes it would have written, the decoder's status -- which says nothing of
+// a segment that ended at its final block, so there the word holds the final block's end bit within its byte (0: on a boundary).
 struct SegMeasure { uint32_t kind, end, count, status; };
+ZWZ_HD uint32_t split_measure_word(uint32_t kind, uint32_t bit_pos, uint32_t status) { return kind == 2u /* kSegFinal */ ? bit_pos & 7u : status; }
+// The first bit behind the final block, from a kSegFinal measurement's `end` and that word
+ZWZ_HD uint64_t split_final_end_bit(uint64_t end, uint32_t low3) { return low3 ? 8u * (end - 1u) + low3 : 8u * end; }
 
 // Defaults of the context options "split_min_bytes", "split_budget" and "split_max_candidates" 
 constexpr uint32_t kSplitMinBytes = 65536;          // a shorter stream is not scanned: one wave is through it in about 2 ms

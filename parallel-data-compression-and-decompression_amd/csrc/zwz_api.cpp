@@ -335,6 +335,7 @@ int zwz_ctx_set_level(zwz_ctx* c, int level) {
 }
 
 int zwz_ctx_level(zwz_ctx* c) { return c ? (int)c->level : ZWZ_E_INVALID; }
+uint32_t zwz_ctx_index_span(zwz_ctx* c) { return c ? c->index_span_bytes : 0u; }
 
 int zwz_ctx_set_option(zwz_ctx* c, const char* name, const char* value) {
     if (!c || !name || !value) return ZWZ_E_INVALID;

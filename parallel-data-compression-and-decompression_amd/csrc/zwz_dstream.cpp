@@ -4,9 +4,11 @@
 // scan value and checksum) stays in device memory, so the host never waits between slices.
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "dstream_core.h"
+#include "index_core.h"
 #include "zwz_api_internal.h"
 #include "zwz_bgzf.h"
 #include "zwz_dstream.h"
@@ -18,14 +20,15 @@ namespace {
 
 constexpr uint32_t kFileSlicePieces = 256;          // pieces per slice of zwz_deflate_stream_file: 16.7 MB of input
 
-struct PiecesView { DstreamPieces P; uint64_t* base; uint32_t* err; };
+struct PiecesView { DstreamPieces P; uint64_t* base; uint32_t* err; uint64_t* rbase; };     // rbase: the rank scan's base (index)
 PiecesView pieces_layout(Carver& w, size_t m) {
     PiecesView v;
     v.P.slots = w.take<uint8_t>(m * ZWZ_DEV_STRIDE, 256);     // (wg_copy reads up to 3 bytes past a slot's bytes)
     v.P.off = w.take<uint64_t>(m); v.P.x = w.take<uint64_t>(m);
     v.P.len = w.take<uint32_t>(m); v.P.olen = w.take<uint32_t>(m); v.P.crc = w.take<uint32_t>(m); v.P.sidx = w.take<uint32_t>(m);
     v.P.slen = w.take<uint32_t>(m); v.P.hbit = w.take<uint32_t>(m); v.P.ebit = w.take<uint32_t>(m);
-    v.base = w.take<uint64_t>(2); v.err = reinterpret_cast<uint32_t*>(v.base + 1);
+    v.P.due = w.take<uint32_t>(m); v.P.rank = w.take<uint64_t>(m);
+    v.base = w.take<uint64_t>(3); v.err = reinterpret_cast<uint32_t*>(v.base + 1); v.rbase = v.base + 2;
     return v;
 }
 
@@ -34,9 +37,10 @@ PiecesView pieces_view(zwz_ctx* c) {
     return pieces_layout(w, c->buf[kBufPieces].count);
 }
 
-// in_off, in_len, out_off, out_cap (n each), pfirst (n + 1) -- copied from the host -- then xs (n) and chk (n)
-size_t streams_host_bytes(uint32_t n) { return (5 * (size_t)n + 1) * 8; }
-size_t streams_dev_bytes(uint32_t n) { return streams_host_bytes(n) + (size_t)n * 8 + (size_t)n * 4 + 64; }
+// in_off, in_len, out_off, out_cap (n each), pfirst (n + 1), with an index idx_off and idx_cap (n each) -- copied from the host -- then
+// xs, rs, cnt (n each) and chk (n)
+size_t streams_host_bytes(uint32_t n, bool index = true) { return ((index ? 7 : 5) * (size_t)n + 1) * 8; }
+size_t streams_dev_bytes(uint32_t n) { return streams_host_bytes(n) + 3 * (size_t)n * 8 + (size_t)n * 4 + 64; }
 
 int ensure_dstream(zwz_ctx* c, uint32_t pieces, uint32_t streams, bool crc) {
     if (crc) if (int rc = ensure_crc_tables(c)) return rc;
@@ -47,9 +51,11 @@ int ensure_dstream(zwz_ctx* c, uint32_t pieces, uint32_t streams, bool crc) {
 }
 
 // The device part, arguments checked by the caller.  partial: every stream's pieces alone, and its checksum left in *d_chk (the file
-// function's slices).  Returns with everything queued on the context's stream.
+// function's slices).  ix: the index as well, idx_off and idx_cap host arrays of n; sealed here unless partial, when *d_cnt is where
+// the stream's count of entries will stand.  Returns with everything queued on the context's stream.
 int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
-                   const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status, bool partial, const uint32_t** d_chk) {
+                   const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status, bool partial, const uint32_t** d_chk,
+                   const DstreamIndex* ix = nullptr, const uint64_t* idx_off = nullptr, const uint64_t* idx_cap = nullptr, const uint64_t** d_cnt = nullptr) {
     // pieces are counted in 64 bits: the only limit is that they, and the output they need, can be counted at all
     std::vector<uint64_t> pfirst((size_t)n + 1);
     pfirst[0] = 0;
@@ -62,24 +68,27 @@ int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_
     }
     const uint64_t G = pfirst[n];
     const uint32_t M = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(G, 1), c->max_batch);
-    if (int rc = ensure_dstream(c, M, n, wrap == kWrapGzip)) return rc;
+    if (int rc = ensure_dstream(c, M, n, wrap == kWrapGzip || (ix && !partial))) return rc;     // (the index CRC, whatever the wrapper)
     // the pinned arrays may still be the source of the previous call's copy
     HIPCHK(hipEventSynchronize(c->ds_copied));
     uint64_t* h = c->buf[kBufStreamsHost].as<uint64_t>();
     memcpy(h, in_off, (size_t)n * 8); memcpy(h + n, in_len, (size_t)n * 8);
     memcpy(h + 2 * (size_t)n, out_off, (size_t)n * 8); memcpy(h + 3 * (size_t)n, out_cap, (size_t)n * 8);
     memcpy(h + 4 * (size_t)n, pfirst.data(), ((size_t)n + 1) * 8);
+    if (ix) { memcpy(h + 5 * (size_t)n + 1, idx_off, (size_t)n * 8); memcpy(h + 6 * (size_t)n + 1, idx_cap, (size_t)n * 8); }
     uint64_t* d = c->buf[kBufStreamsDev].as<uint64_t>();
-    HIPCHK(hipMemcpyAsync(d, h, streams_host_bytes(n), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d, h, streams_host_bytes(n, ix != nullptr), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ds_copied, c->stream));
     DstreamStreams S;
     S.in_off = d; S.in_len = d + n; S.out_off = d + 2 * (size_t)n; S.out_cap = d + 3 * (size_t)n; S.pfirst = d + 4 * (size_t)n;
-    S.xs = d + 5 * (size_t)n + 1; S.chk = reinterpret_cast<uint32_t*>(S.xs + n); S.n = n;
+    S.idx_off = d + 5 * (size_t)n + 1; S.idx_cap = d + 6 * (size_t)n + 1;
+    S.xs = d + 7 * (size_t)n + 1; S.rs = S.xs + n; S.cnt = S.rs + n; S.chk = reinterpret_cast<uint32_t*>(S.cnt + n); S.n = n;
     if (d_chk) *d_chk = S.chk;
+    if (d_cnt) *d_cnt = S.cnt;
     const DstreamOut O{d_out, d_out_len, d_status, wrap, partial ? 1u : 0u, zlib_flg_of(c->level, c->strategy), gzip_xfl_of(c->strategy)};
     const PiecesView v = pieces_view(c);
     const CrcTables* tab = c->buf[kBufCrcTables].as<const CrcTables>();
-    HIPCHK(hipMemsetAsync(v.base, 0, 16, c->stream));
+    HIPCHK(hipMemsetAsync(v.base, 0, 24, c->stream));
     HIPCHK(launch_dstream_begin(S, O, c->stream));
     uint32_t s0 = 0;                                  // the stream of the slice's first piece
     for (uint64_t g0 = 0; g0 < G; g0 += M) {
@@ -96,8 +105,14 @@ int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_
         HIPCHK(launch_bgzf_scan(v.P.slen, m, 0, ~0u, v.P.x, v.base, v.err + 1, c->stream));
         HIPCHK(launch_dstream_combine(S, v.P, g0, m, s0, s1 - s0 + 1, wrap, c->stream));
         HIPCHK(launch_dstream_pack(S, v.P, g0, m, O, v.err, c->stream));
+        if (ix) {
+            HIPCHK(launch_dstream_due(S, v.P, g0, m, *ix, c->stream));
+            HIPCHK(launch_bgzf_scan(v.P.due, m, 0, ~0u, v.P.rank, v.rbase, v.err + 1, c->stream));
+            HIPCHK(launch_dstream_index(S, v.P, g0, m, O, *ix, c->stream));
+        }
         s0 = s1;
     }
+    if (ix && !partial) HIPCHK(launch_dstream_index_seal(tab, S, O, *ix, c->cu_count, c->stream));
     return ZWZ_OK;
 }
 
@@ -117,9 +132,40 @@ int zwz_deflate_streams_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uin
     return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr);
 }
 
+uint64_t zwz_deflate_stream_index_bound(uint64_t n, uint32_t span) {
+    if (span == 0) span = kIdxSpanDefault;
+    return index_span_ok(span) ? index_flush_bound(n, span) : 0u;
+}
+
+int zwz_deflate_streams_index_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
+                                  const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status, uint32_t span, uint8_t* d_idx,
+                                  const uint64_t* idx_off, const uint64_t* idx_cap, uint64_t* d_idx_len) {
+    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    if (span == 0) span = c->index_span_bytes;
+    if (!index_span_ok(span)) return ZWZ_E_INVALID;
+    if (n && (!d_in || !in_off || !in_len || !d_out || !out_off || !out_cap || !d_out_len || !d_status || !d_idx || !idx_off || !idx_cap || !d_idx_len))
+        return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
+    for (uint32_t i = 0; i < n; i++)
+        if ((in_off[i] & 15u) || (out_off[i] & 15u) || (idx_off[i] & 15u)) {
+            set_error("zwz_deflate_streams_index_dev: stream %u: offsets must be multiples of 16", i);
+            return ZWZ_E_INVALID;
+        }
+    if (n == 0) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const DstreamIndex X{d_idx, d_idx_len, span, 0, 0};
+    return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr, &X, idx_off, idx_cap);
+}
+
 // One slice of kFileSlicePieces whole pieces at a time: its pieces alone (partial), and its own checksum, which the host joins onto
 // the file's by the slice's length.  The header goes in front of the first slice and 03 00 + trailer behind the last.
-int zwz_deflate_stream_file(zwz_ctx* c, int wrap_, const char* src, const char* dst) {
+// With dst_idx the index as well (index_core.h: the index at full-flush points), at the context's "index_span_bytes": the entries of
+// each slice come from the same kernels, which are told the decoded bytes and the stream bytes in front of the slice; the host appends
+// them and seals the header once the trailer is known.  The small buffers then hold, behind the slice's results, its count of
+// entries and, from byte 64, the entries themselves.
+namespace {
+
+int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char* dst, const char* dst_idx) {
     if (!c || !src || !dst || wrap_ < ZWZ_WRAP_RAW || wrap_ > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
     const uint32_t wrap = (uint32_t)wrap_;
     HIPCHK(hipSetDevice(c->device));
@@ -127,7 +173,11 @@ int zwz_deflate_stream_file(zwz_ctx* c, int wrap_, const char* src, const char* 
     if (int rc = job.open(src, dst)) return rc;
     const uint32_t pieces = c->max_batch < kFileSlicePieces ? c->max_batch : kFileSlicePieces;
     const size_t S = (size_t)pieces * kPieceBytes, O = round_up((size_t)pieces * piece_bound(kPieceBytes), 16);
-    if (int rc = job.alloc({S + 16, S + 16, O, O, 64}, {S + 16, O, 64})) return rc;
+    const uint64_t ent_cap = dst_idx ? index_flush_bytes(pieces) : 0u;      // (the header's 64 bytes are the results' place)
+    const size_t small = dst_idx ? (size_t)ent_cap : 64;
+    if (int rc = job.alloc({S + 16, S + 16, O, O, small}, {S + 16, O, small})) return rc;
+    std::vector<uint8_t> ents(kIdxHeader);          // the index as it grows: the header's place, then the entries
+    uint64_t pos = dstream_header_bytes(wrap);      // stream bytes in front of the next slice
     uint8_t frame[kGzipHeaderBytes + 2 + 8];
     const uint32_t hdr = dstream_header_bytes(wrap);
     for (uint32_t i = 0; i < hdr; i++) frame[i] = (uint8_t)dstream_header_byte(wrap, i, zlib_flg_of(c->level, c->strategy), gzip_xfl_of(c->strategy));
@@ -138,21 +188,58 @@ int zwz_deflate_stream_file(zwz_ctx* c, int wrap_, const char* src, const char* 
         [&](size_t n, SliceResult* d_res, SliceResult* h_res) {
             const uint64_t zero = 0, len = n, cap = O;
             const uint32_t* d_chk = nullptr;
-            if (int rc = dstream_launch(c, wrap, job.dp(0), &zero, &len, 1, job.dp(1), &zero, &cap, &d_res->out_len, &d_res->status, true, &d_chk)) return rc;
+            const DstreamIndex X{job.dp(2), nullptr, c->index_span_bytes, total_in, pos};
+            const uint64_t* d_cnt = nullptr;
+            if (int rc = dstream_launch(c, wrap, job.dp(0), &zero, &len, 1, job.dp(1), &zero, &cap, &d_res->out_len, &d_res->status, true, &d_chk,
+                                        dst_idx ? &X : nullptr, &zero, &ent_cap, &d_cnt)) return rc;
             HIPCHK(hipMemcpyAsync(h_res, d_res, 12, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(&h_res->check, d_chk, 4, hipMemcpyDeviceToHost, c->stream));
+            if (dst_idx) {
+                uint8_t* h = reinterpret_cast<uint8_t*>(h_res);
+                HIPCHK(hipMemcpyAsync(h + 16, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(h + kIdxHeader, job.dp(2) + kIdxHeader, (size_t)ent_cap - kIdxHeader, hipMemcpyDeviceToHost, c->stream));
+            }
             return (int)ZWZ_OK;
         },
         [&](size_t n, const SliceResult& r) {
             if (r.status || r.out_len > O) { set_error("deflate stream: a slice needs %llu bytes, above its bound", (unsigned long long)r.out_len); return (int)ZWZ_E_FORMAT; }
             if (wrap == kWrapZlib) check = AdlerSum::join(check, r.check, AdlerSum::pof(n));
             else if (wrap == kWrapGzip) check = CrcSum::join(check, r.check, CrcSum::pof(n));
-            total_in += n;
+            total_in += n; pos += r.out_len;
+            if (dst_idx) {
+                const uint8_t* h = reinterpret_cast<const uint8_t*>(&r);
+                const uint64_t cnt = le64_of(h + 16);
+                if (cnt > pieces) { set_error("deflate stream: a slice of %u pieces reports %llu index entries", pieces, (unsigned long long)cnt); return (int)ZWZ_E_FORMAT; }
+                ents.insert(ents.end(), h + kIdxHeader, h + kIdxHeader + cnt * kIdxEntry);
+            }
             return (int)ZWZ_OK;
         });
     if (rc) return rc;
     const uint32_t tail = 2u + dstream_trailer_bytes(wrap);
     for (uint32_t i = 0; i < tail; i++) frame[i] = (uint8_t)dstream_tail_byte(wrap, i, check, total_in);
     if (fwrite(frame, 1, tail, job.out) != tail) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
-    return job.commit(dst);
+    if (!dst_idx) return job.commit(dst);
+    // the index: an empty input has its one entry from here; written as .part, and renamed only behind the stream
+    if (!total_in) { ents.resize(kIdxHeader + kIdxEntry); index_flush_entry(ents.data() + kIdxHeader, 8u * hdr, 0); }
+    const uint64_t count = (ents.size() - kIdxHeader) / kIdxEntry;
+    if (count > 0xffffffffull) { set_error("deflate stream: more than 2^32 - 1 index entries"); return ZWZ_E_INVALID; }
+    ents.resize((size_t)index_flush_bytes(count));
+    index_flush_seal(ents.data(), wrap, c->index_span_bytes, pos + tail, total_in, (uint32_t)count, index_flush_end_bit(pos), wrap == kWrapRaw ? 0u : check);
+    const std::string ipart = std::string(dst_idx) + ".part";
+    FILE* fi = fopen(ipart.c_str(), "wb");
+    if (!fi) { set_error("cannot create %s", ipart.c_str()); return ZWZ_E_IO; }
+    const bool wrote = fwrite(ents.data(), 1, ents.size(), fi) == ents.size();
+    if ((fclose(fi) != 0) | !wrote) { unlink(ipart.c_str()); set_error("write error on %s", ipart.c_str()); return ZWZ_E_IO; }
+    if (int rc2 = job.commit(dst)) { unlink(ipart.c_str()); return rc2; }
+    if (rename(ipart.c_str(), dst_idx) != 0) { unlink(ipart.c_str()); unlink(dst); set_error("cannot write %s", dst_idx); return ZWZ_E_IO; }
+    return ZWZ_OK;
+}
+
+}  // namespace
+
+int zwz_deflate_stream_file(zwz_ctx* c, int wrap, const char* src, const char* dst) { return deflate_stream_file_core(c, wrap, src, dst, nullptr); }
+
+int zwz_deflate_stream_file_index(zwz_ctx* c, int wrap, const char* src, const char* dst, const char* dst_idx) {
+    if (!dst_idx) return ZWZ_E_INVALID;
+    return deflate_stream_file_core(c, wrap, src, dst, dst_idx);
 }

@@ -14,14 +14,23 @@ struct DstreamStreams {
     uint64_t* xs;              // the scan's value at the stream's first piece, for its pieces in later slices
     uint32_t* chk;             // the checksum of the stream's pieces so far
     uint32_t n;
+    // zwz_deflate_streams_index_dev only
+    const uint64_t *idx_off, *idx_cap;
+    uint64_t *rs, *cnt;        // the rank scan's value at the stream's first piece; its entries, once its last piece is known
 };
 // Per piece of one slice: piece p of the slice is piece g0 + p of the call
 struct DstreamPieces {
     uint8_t* slots;            // ZWZ_DEV_STRIDE bytes each: the piece's zlib stream
     uint64_t *off, *x;         // its input; bytes of spliced output in front of it (over the whole call)
     uint32_t *len, *olen, *crc, *sidx, *slen, *hbit, *ebit;   // input, slot and spliced lengths; CRC-32 (gzip); stream; dstream_core.h's SplicePoints
+    uint32_t* due;             // index: whether the piece's first block is an entry (index_core.h: index_flush_due)
+    uint64_t* rank;            // index: entries in front of it (over the whole call)
 };
 struct DstreamOut { uint8_t* out; uint64_t* out_len; uint32_t* status; uint32_t wrap; uint32_t partial; uint32_t zflg; uint32_t xfl; };   // partial: pieces only (no header, no 03 00, no trailer); zflg: zlib_flg_of(level, strategy); xfl: gzip_xfl_of(strategy)
+
+// The index at the pieces' starts (index_core.h).  off_base, pos_base: the decoded bytes and the stream bytes in front of a partial
+// call's input and output (the file function's slices), 0 otherwise.
+struct DstreamIndex { uint8_t* idx; uint64_t* idx_len; uint32_t span; uint64_t off_base, pos_base; };
 
 hipError_t launch_dstream_begin(const DstreamStreams& S, const DstreamOut& O, hipStream_t s);
 hipError_t launch_dstream_layout(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, hipStream_t s);
@@ -32,5 +41,12 @@ hipError_t launch_dstream_combine(const DstreamStreams& S, const DstreamPieces& 
                                   hipStream_t s);
 hipError_t launch_dstream_pack(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamOut& O, const uint32_t* err,
                                hipStream_t s);
+// The index of a slice: the due flags (before the rank scan) and the entries (behind it and behind pack)
+hipError_t launch_dstream_due(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamIndex& X, hipStream_t s);
+hipError_t launch_dstream_index(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamOut& O, const DstreamIndex& X,
+                                hipStream_t s);
+// Behind the last slice, whole streams only: every stream's header, index CRC and idx_len
+hipError_t launch_dstream_index_seal(const CrcTables* tab, const DstreamStreams& S, const DstreamOut& O, const DstreamIndex& X, uint32_t cu_count,
+                                     hipStream_t s);
 
 }  // namespace zwz

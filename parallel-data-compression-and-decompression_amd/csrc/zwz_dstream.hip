@@ -2,10 +2,15 @@
 // goes through zwz_deflate_batch_dev into its slot, and the kernels here cut the batch into pieces (layout), find where each piece's
 // stream is spliced from the block records the encoder itself was laid out by (size), fold the pieces' checksums into their streams'
 // (combine) and move every piece once, with its marker, to its place in its stream (pack).  dstream_core.h has the format and the
-// arithmetic; the scan between size and pack is BGZF's (launch_bgzf_scan).
+// arithmetic; the scan between size and pack is BGZF's (launch_bgzf_scan).  zwz_deflate_streams_index_dev adds the index at the pieces'
+// starts (index_core.h: the index at full-flush points): a flag per piece (due), the same scan over the flags, the entries (index)
+// and, behind the last slice, every stream's header and index CRC (seal).  Nothing is decoded: a piece's decoded offset is its number
+// times kPieceBytes and its first bit is where pack puts it.
 #include "../../include/zwz.h"
 #include "copy_wg.h"
+#include "crc_wg.h"
 #include "dstream_core.h"
+#include "index_core.h"
 #include "zwz_device.h"
 #include "zwz_dstream.h"
 
@@ -148,6 +153,72 @@ __global__ void __launch_bounds__(256) dstream_pack_kernel(DstreamStreams S, Dst
     if (end <= cap) wg_copy(dst + start, slot + 2, slen);
 }
 
+// Piece k of its stream is point k of the rule, at decoded offset k * kPieceBytes behind X.off_base; the point in front of it is the
+// piece in front of it, whichever slice that was in.
+__global__ void __launch_bounds__(256) dstream_due_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, uint32_t m, DstreamIndex X) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    const uint32_t s = P.sidx[p];
+    const uint64_t off = X.off_base + (g0 + p - S.pfirst[s]) * kPieceBytes;
+    P.due[p] = off == 0u || index_flush_due(off - kPieceBytes, off, X.off_base + S.in_len[s], X.span) ? 1u : 0u;
+}
+
+// A thread per piece, behind the rank scan and behind pack (S.xs): a due piece writes its entry, three 8-byte stores, where its rank
+// within its stream says; a stream's first piece keeps the scan's value for the stream's pieces in later slices, as pack keeps
+// S.xs, and its last piece the stream's count.  No entry is written that would end behind the index's capacity.
+__global__ void __launch_bounds__(256) dstream_index_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, uint32_t m, DstreamOut O, DstreamIndex X) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    const uint32_t s = P.sidx[p], due = P.due[p];
+    const uint64_t g = g0 + p, pf = S.pfirst[s];
+    const uint64_t xs = pf >= g0 ? P.x[pf - g0] : S.xs[s], rs = pf >= g0 ? P.rank[pf - g0] : S.rs[s];
+    const uint64_t r = P.rank[p] - rs;
+    if (g == pf) S.rs[s] = P.rank[p];               // (read by this stream's pieces in later slices only)
+    if (g + 1 == S.pfirst[s + 1]) S.cnt[s] = r + due;
+    if (!due || index_flush_bytes(r + 1u) > S.idx_cap[s]) return;
+    const uint32_t hdr = O.partial ? 0u : dstream_header_bytes(O.wrap);
+    uint64_t* e = reinterpret_cast<uint64_t*>(X.idx + S.idx_off[s] + kIdxHeader + r * kIdxEntry);
+    e[0] = 8u * (X.pos_base + hdr + (P.x[p] - xs));
+    e[1] = X.off_base + (g - pf) * kPieceBytes;
+    e[2] = 0;
+}
+
+// One workgroup per stream, behind the last slice: the entry of a stream without input, the padding, the index CRC and the header.
+// The stream's length and status are pack's (or begin's), its stored check value combine's.
+__global__ void __launch_bounds__(kBgzfThreads) dstream_index_seal_kernel(const CrcTables* tab, DstreamStreams S, DstreamOut O, DstreamIndex X) {
+    __shared__ CrcLds lds;
+    crc_load_tables(lds, tab);
+    const uint32_t t = threadIdx.x;
+    for (uint32_t i = blockIdx.x; i < S.n; i += gridDim.x) {
+        const uint64_t count = S.in_len[i] ? S.cnt[i] : 1u, len = index_flush_bytes(count);      // (workgroup-uniform, as the branch below)
+        if (O.status[i] != 0u || count > 0xffffffffull || len > 0xffffffffull || len > S.idx_cap[i]) {
+            if (t == 0) X.idx_len[i] = 0;
+            continue;
+        }
+        uint8_t* q = X.idx + S.idx_off[i];
+        const uint32_t hdr = dstream_header_bytes(O.wrap);
+        if (t == 0) {
+            uint64_t* e = reinterpret_cast<uint64_t*>(q + kIdxHeader);
+            if (!S.in_len[i]) { e[0] = 8u * hdr; e[1] = 0; e[2] = 0; }
+            if (count & 1u) e[3u * count] = 0;       // 24 count is 8 mod 16: the padding
+        }
+        __threadfence();
+        __syncthreads();
+        const uint32_t crc = crc_block_wg(lds, q + kIdxHeader, (uint32_t)(len - kIdxHeader));
+        if (t == 0) {
+            const uint64_t total = O.out_len[i], end_bit = index_flush_end_bit(total - dstream_trailer_bytes(O.wrap) - 2u), n = S.in_len[i];
+            uint32_t* h = reinterpret_cast<uint32_t*>(q);
+            h[0] = 0x495a575au; h[1] = 0x01005844u;                               // "ZWZIDX\0\1"
+            h[2] = O.wrap; h[3] = X.span;
+            h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32); h[6] = (uint32_t)n; h[7] = (uint32_t)(n >> 32);
+            h[8] = (uint32_t)count; h[9] = 0; h[10] = (uint32_t)end_bit; h[11] = (uint32_t)(end_bit >> 32);
+            h[12] = O.wrap == kWrapRaw ? 0u : S.chk[i]; h[13] = crc; h[14] = 0; h[15] = 0;
+            X.idx_len[i] = len;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 hipError_t launch_dstream_begin(const DstreamStreams& S, const DstreamOut& O, hipStream_t s) {
@@ -182,6 +253,27 @@ hipError_t launch_dstream_pack(const DstreamStreams& S, const DstreamPieces& P, 
                                hipStream_t s) {
     if (!m) return hipSuccess;
     dstream_pack_kernel<<<m, 256, 0, s>>>(S, P, g0, O, err);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstream_due(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamIndex& X, hipStream_t s) {
+    if (!m) return hipSuccess;
+    dstream_due_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, g0, m, X);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstream_index(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamOut& O, const DstreamIndex& X,
+                                hipStream_t s) {
+    if (!m) return hipSuccess;
+    dstream_index_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, g0, m, O, X);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstream_index_seal(const CrcTables* tab, const DstreamStreams& S, const DstreamOut& O, const DstreamIndex& X, uint32_t cu_count,
+                                     hipStream_t s) {
+    if (!S.n) return hipSuccess;
+    const uint32_t g = (cu_count ? cu_count : 256u) * 4u;
+    dstream_index_seal_kernel<<<S.n < g ? S.n : g, kBgzfThreads, 0, s>>>(tab, S, O, X);
     return hipGetLastError();
 }
 

@@ -2723,7 +2723,7 @@ __global__ __launch_bounds__(kInflateThreads, kInflateWavesPerSimd) void inflate
         }
     }
     if constexpr (kSplit == 1) {
-        if (lane == 0) sp.meas[chunk] = make_uint4(seg_fin, seg_base + ((st.br.bit_pos() + 7u) >> 3), st.out_pos, st.status);
+        if (lane == 0) sp.meas[chunk] = make_uint4(seg_fin, seg_base + ((st.br.bit_pos() + 7u) >> 3), st.out_pos, split_measure_word(seg_fin, st.br.bit_pos(), st.status));
     } else if constexpr (kSplit == 2) {
         if (lane == 0 && !(seg_fin != kSegBad && st.out_pos == cap)) sp.bad[seg_stream] = 1;      // (cannot happen: the measuring form decoded the same bits)
     } else if constexpr (kSplit == kFormIndexed) {

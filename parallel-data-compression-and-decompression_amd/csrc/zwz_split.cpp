@@ -4,9 +4,11 @@
 // are; the splitting ones are handed to it with a length of zero and get their results behind it.
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "dstream_core.h"
+#include "index_core.h"
 #include "zwz_api_internal.h"
 #include "zwz_bgzf.h"
 #include "zwz_filejob.h"
@@ -20,7 +22,7 @@ constexpr uint64_t kSplitMaxKept = 8u << 20;        // kept candidates of one ca
 
 // The three device workspaces of a call, each carved for that call's sizes: which is known only once the step before has run.
 // Per stream (body, tile_first, cfirst, kbase, dbase, pbase, res, bad, the lengths handed to the fallback) and per scan tile (count, offset)
-struct StreamArrays { uint32_t *tile_first, *kbase, *dbase, *pbase, *bad, *chk; uint64_t* fb_len; uint4 *res, *res2; };
+struct StreamArrays { uint32_t *tile_first, *kbase, *dbase, *pbase, *bad, *chk, *icount; uint64_t* fb_len; uint4 *res, *res2; };
 StreamArrays streams_layout(Carver& w, size_t n, size_t tiles, SplitStreams& S) {
     StreamArrays A;
     S.body = w.take<uint32_t>(n + 1);
@@ -34,6 +36,7 @@ StreamArrays streams_layout(Carver& w, size_t n, size_t tiles, SplitStreams& S) 
     A.res = w.take<uint4>(n);
     A.res2 = w.take<uint4>(n);
     A.chk = w.take<uint32_t>(n + 1);
+    A.icount = w.take<uint32_t>(n + 1);
     S.tile_cnt = w.take<uint32_t>(tiles);
     S.tile_off = w.take<uint64_t>(tiles);
     S.base = w.take<uint64_t>(2);
@@ -68,14 +71,22 @@ int carve_ws(zwz_ctx* c, BufId id, F&& layout) {
 // in the slice.  Decoded is the longest prefix of the chain that ends cleanly inside the slice and fits the output staging; nothing
 // falls back.  Results (after the call, which then returns synchronised): segments decoded, their bytes, where the prefix ends in
 // the slice, how its last segment ended, the checksum of the bytes.
-struct SlicePart { uint32_t p0; uint32_t nseg, total, end, kind, chk; };
+// points (may be null): the prefix's segment starts, pairs (offset in the slice, decoded bytes of the slice in front), in chain order;
+// low3: a final block's end bit within its byte (split_core.h: split_final_end_bit)
+struct SlicePart { uint32_t p0; uint32_t nseg, total, end, kind, chk; std::vector<uint64_t>* points = nullptr; uint32_t low3 = 0; };
+
+// zwz_inflate_split_streams_index_dev's further arguments (device arrays): the streams that split get the index of their flush points,
+// the others the marking form's instead of the plain stream form
+struct IndexOut { uint32_t span; uint8_t* idx; const uint64_t *idx_off, *idx_cap; uint64_t* idx_len; };
 
 int split_call(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                uint32_t n, uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
-               uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_segments, SlicePart* part) {
+               uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_segments, SlicePart* part, const IndexOut* ix = nullptr) {
     hipStream_t st = c->stream;
     auto fall_back = [&](const uint64_t* lens) {
         if (part) return (int)ZWZ_OK;
+        if (ix) return zwz_inflate_streams_index_dev(c, wrap, d_in, d_in_off, lens, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, ix->span, ix->idx,
+                                                     ix->idx_off, ix->idx_cap, ix->idx_len);
         return zwz_inflate_streams_dev(c, wrap, d_in, d_in_off, lens, n, d_out, d_out_off, d_out_cap, d_out_len, d_status);
     };
     const uint32_t min_bytes = part ? 1u : c->split_min_bytes;
@@ -160,7 +171,7 @@ int split_call(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_o
         const int rc = fall_back(A.fb_len);
         if (rc) return rc;
     }
-    if (wrap == ZWZ_WRAP_GZIP) if (int rc = ensure_crc_tables(c)) return rc;
+    if (wrap == ZWZ_WRAP_GZIP || ix) if (int rc = ensure_crc_tables(c)) return rc;      // (the index CRC, whatever the wrapper)
     SplitDecode D{};
     D.res = A.res; D.dbase = A.dbase;
     SplitPieces P{};
@@ -169,19 +180,36 @@ int split_call(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_o
     HIPCHK(hipMemcpyAsync(A.dbase, dbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(A.pbase, pbase, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(launch_split_emit(S, C, D, st));
+    std::vector<uint64_t> p_off;
+    std::vector<uint4> p_seg;
+    if (part && part->points) {                       // (the records are dense by rank: the prefix is the first res[0].y of them)
+        p_off.resize(nd); p_seg.resize(nd);
+        HIPCHK(hipMemcpyAsync(p_off.data(), D.in_off, nd * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(p_seg.data(), D.seg, nd * sizeof(uint4), hipMemcpyDeviceToHost, st));
+    }
+    SplitIndex X{};
+    if (ix) {
+        X = SplitIndex{ix->idx, ix->idx_off, ix->idx_cap, ix->idx_len, A.icount, ix->span};
+        HIPCHK(launch_split_index(S, D, X, st));
+    }
     {
         InflateSplitArgs a{d_in, D.in_off, D.in_len, (uint32_t)nd, d_out, d_out_off, d_order, D.seg, nullptr, A.bad, 0u, c->inflate_serial_header};
         HIPCHK(launch_inflate_split(a, st));
     }
     HIPCHK(launch_split_finish(S, D, P, c->buf[kBufCrcTables].as<const CrcTables>(), d_out, d_out_off, A.bad, d_out_len, d_status, d_segments,
                                part ? A.chk : nullptr, c->cu_count, st));
+    if (ix) HIPCHK(launch_split_seal(S, D, X, A.res2, c->buf[kBufCrcTables].as<const CrcTables>(), d_status, c->cu_count, st));
     if (part) {
         HIPCHK(hipMemcpyAsync(&part->chk, A.chk, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         uint32_t bad = 0;
         HIPCHK(hipMemcpyAsync(&bad, A.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (bad) { set_error("split inflate: a segment did not decode as it was measured"); return ZWZ_E_FORMAT; }
-        part->nseg = res[0].y; part->total = res[0].z; part->end = res2.x; part->kind = res2.y;
+        part->nseg = res[0].y; part->total = res[0].z; part->end = res2.x; part->kind = res2.y; part->low3 = res2.z;
+        if (part->points) {
+            part->points->clear();
+            for (uint64_t j = 0; j < nd; j++) { part->points->push_back(p_off[j] + p_seg[j].x); part->points->push_back(p_seg[j].z); }
+        }
     }
     return ZWZ_OK;
 }
@@ -199,17 +227,43 @@ extern "C" int zwz_inflate_split_streams_dev(zwz_ctx* c, int wrap, const uint8_t
     return split_call(c, wrap, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_segments, nullptr);
 }
 
+extern "C" int zwz_inflate_split_streams_index_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                                   uint32_t n, uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                                   uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_segments, uint32_t span, uint8_t* d_idx,
+                                                   const uint64_t* d_idx_off, const uint64_t* d_idx_cap, uint64_t* d_idx_len) {
+    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    if (span == 0) span = c->index_span_bytes;
+    if (!index_span_ok(span)) return ZWZ_E_INVALID;
+    if (n && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status || !d_idx || !d_idx_off || !d_idx_cap || !d_idx_len))
+        return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
+    if (n == 0) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const IndexOut ix{span, d_idx, d_idx_off, d_idx_cap, d_idx_len};
+    return split_call(c, wrap, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_segments, nullptr, &ix);
+}
+
 // One file of any size.  The device holds a slice of the compressed file at a time; split_call decodes the chain segments that end
 // inside it and fit the output staging, the host writes them (a writer thread, two pinned buffers), joins their checksum onto the
 // file's and goes on with a slice that starts at the chain's position, rounded down to 16: the bytes behind it are kept, the rest is
 // read.  A chain that makes no progress in a whole slice is broken: before any byte was written the file goes through the one-stream
 // path if it fits its limits, later it is ZWZ_E_FORMAT.
-extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, const char* dst) {
-    if (!c || !src || !dst || wrap_ < ZWZ_WRAP_RAW || wrap_ > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+// With dst_idx (zwz_inflate_split_index_file) the index of the flush points as well: every slice hands back the starts of the segments
+// it decoded, the host applies index_core.h's rule to them with the last point's offset carried from slice to slice, and seals the
+// header once the trailer is known; dst may then be null.  A file that does not split goes to zwz_inflate_legs_file with dst_idx.
+namespace {
+
+int inflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char* dst, const char* dst_idx) {
+    if (!c || !src || (!dst && !dst_idx) || wrap_ < ZWZ_WRAP_RAW || wrap_ > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
     const uint32_t wrap = (uint32_t)wrap_;
     HIPCHK(hipSetDevice(c->device));
     FileJob job;
-    if (int rc = job.open(src, dst)) return rc;
+    if (dst) { if (int rc = job.open(src, dst)) return rc; }
+    else { job.in = fopen(src, "rb"); if (!job.in) { set_error("cannot open %s", src); return ZWZ_E_IO; } }
+    std::vector<uint64_t> points;                     // of one slice
+    std::vector<uint8_t> ents(kIdxHeader);            // the index as it grows: the header's place, then the entries
+    uint64_t prev_off = 0, end_bit = 0;
+    bool first_point = true;
     const size_t S = c->split_slice_bytes, O = std::max<size_t>(4 * S, 4u << 20);
     if (int rc = job.alloc({S + 32, 0, O, O, 64}, {S + 32, O + 16, 64})) return rc;      // (one input buffer: the next slice depends on this one's end)
     uint8_t* hin = static_cast<uint8_t*>(job.h[0]);
@@ -238,15 +292,31 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
         HIPJOB(hipMemcpyAsync(d_in, hin, round_up(have + 16, 16), hipMemcpyHostToDevice, c->stream));
         HIPJOB(hipMemcpyAsync(d_par, h_par, 32, hipMemcpyHostToDevice, c->stream));
         SlicePart part{};
+        if (dst_idx) part.points = &points;
         part.p0 = (uint32_t)(at - base);
         if (int rc = split_call(c, wrap_, d_in, d_par, d_par + 1, 1, d_out, d_par + 2, d_par + 3, d_par + 4, reinterpret_cast<uint32_t*>(d_par + 5), nullptr, &part)) { job.join(); return rc; }
         if (!part.nseg) { chain_ok = false; break; }             // no segment ends inside a whole slice (or its input does)
-        uint8_t* hout = static_cast<uint8_t*>(job.h[2 + b]);
-        if (int rc = job.finish_write()) return rc;               // (two writes back: this buffer is free)
-        HIPJOB(hipMemcpyAsync(hout, d_out, part.total, hipMemcpyDeviceToHost, c->stream));
-        HIPJOB(hipStreamSynchronize(c->stream));
-        job.start_write(hout, part.total);
-        b ^= 1;
+        if (dst_idx && !total && part.nseg == 1 && part.kind == kSegFinal) { chain_ok = false; break; }   // one piece in all: no flush point, the index is the one-wave decode's
+        if (dst) {
+            uint8_t* hout = static_cast<uint8_t*>(job.h[2 + b]);
+            if (int rc = job.finish_write()) return rc;               // (two writes back: this buffer is free)
+            HIPJOB(hipMemcpyAsync(hout, d_out, part.total, hipMemcpyDeviceToHost, c->stream));
+            HIPJOB(hipStreamSynchronize(c->stream));
+            job.start_write(hout, part.total);
+            b ^= 1;
+        }
+        if (dst_idx) {
+            // the prefix's points: offsets in the file and in the output; whether bytes follow a point is known only at the end
+            for (uint32_t j = 0; j < part.nseg; j++) {
+                const uint64_t p = base + points[2 * (size_t)j], o = total + points[2 * (size_t)j + 1];
+                if (first_point || index_flush_due(prev_off, o, ~0ull, c->index_span_bytes)) {
+                    ents.resize(ents.size() + kIdxEntry);
+                    index_flush_entry(ents.data() + ents.size() - kIdxEntry, 8u * p, o);
+                }
+                first_point = false; prev_off = o;
+            }
+            if (part.kind == kSegFinal) end_bit = split_final_end_bit(base + part.end, part.low3);
+        }
         if (wrap == kWrapZlib) check = AdlerSum::join(check, part.chk, AdlerSum::pof(part.total));
         else if (wrap == kWrapGzip) check = CrcSum::join(check, part.chk, CrcSum::pof(part.total));
         total += part.total;
@@ -274,8 +344,8 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
         job.join();
         for (void*& p : job.h) if (p) { (void)hipHostFree(p); p = nullptr; }
         for (void*& p : job.d) if (p) { (void)hipFree(p); p = nullptr; }
-        fclose(job.out); job.out = nullptr; unlink(job.part.c_str());
-        return zwz_inflate_legs_file(c, wrap_, src, dst, nullptr, nullptr);
+        if (job.out) { fclose(job.out); job.out = nullptr; unlink(job.part.c_str()); }
+        return zwz_inflate_legs_file(c, wrap_, src, dst, dst_idx, nullptr);
     };
     // the whole file as one stream through zwz_inflate_streams_dev, the capacity doubled until it fits; what was written is dropped.
     // kGoLegs: the decoded bytes do not fit the largest capacity of one launch
@@ -316,7 +386,7 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
         // the chain broke at `at`
         if (total) { set_error("zwz_inflate_stream_file: %s: no block ends cleanly from compressed offset %llu on", src, (unsigned long long)at); return ZWZ_E_FORMAT; }
         // nothing written yet
-        if (size >= kStreamMaxIn) return in_legs();
+        if (size >= kStreamMaxIn || dst_idx) return in_legs();
         const int rc = one_stream();
         return rc == kGoLegs ? in_legs() : rc;
     }
@@ -335,11 +405,37 @@ extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap_, const char* src, c
                 for (size_t i = 0; i < k; i++)
                     if (buf[i]) {
                         // another member, or garbage: both paths read the one and name the other, from the file's first byte
-                        if (size >= kStreamMaxIn) return in_legs();
+                        if (size >= kStreamMaxIn || dst_idx) return in_legs();
                         const int rc = one_stream();
                         return rc == kGoLegs ? in_legs() : rc;
                     }
         }
     }
-    return job.commit(dst);
+    if (!dst_idx) return job.commit(dst);
+    // entries at the decoded length have no byte behind them (the empty final block, markers in a row at the end)
+    while (ents.size() > kIdxHeader + kIdxEntry && le64_of(ents.data() + ents.size() - kIdxEntry + 8) >= total) ents.resize(ents.size() - kIdxEntry);
+    const uint64_t count = (ents.size() - kIdxHeader) / kIdxEntry;
+    if (count > 0xffffffffull) { set_error("zwz_inflate_split_index_file: more than 2^32 - 1 index entries"); return ZWZ_E_INVALID; }
+    ents.resize((size_t)index_flush_bytes(count));
+    index_flush_seal(ents.data(), wrap, c->index_span_bytes, size, total, (uint32_t)count, end_bit, wrap == kWrapRaw ? 0u : check);
+    const std::string ipart = std::string(dst_idx) + ".part";
+    FILE* fi = fopen(ipart.c_str(), "wb");
+    if (!fi) { set_error("cannot create %s", ipart.c_str()); return ZWZ_E_IO; }
+    const bool wrote = fwrite(ents.data(), 1, ents.size(), fi) == ents.size();
+    if ((fclose(fi) != 0) | !wrote) { unlink(ipart.c_str()); set_error("write error on %s", ipart.c_str()); return ZWZ_E_IO; }
+    if (dst) if (int rc = job.commit(dst)) { unlink(ipart.c_str()); return rc; }
+    if (rename(ipart.c_str(), dst_idx) != 0) { unlink(ipart.c_str()); if (dst) unlink(dst); set_error("cannot write %s", dst_idx); return ZWZ_E_IO; }
+    return ZWZ_OK;
+}
+
+}  // namespace
+
+extern "C" int zwz_inflate_stream_file(zwz_ctx* c, int wrap, const char* src, const char* dst) {
+    if (!dst) return ZWZ_E_INVALID;
+    return inflate_stream_file_core(c, wrap, src, dst, nullptr);
+}
+
+extern "C" int zwz_inflate_split_index_file(zwz_ctx* c, int wrap, const char* src, const char* dst, const char* dst_idx) {
+    if (!dst_idx) return ZWZ_E_INVALID;
+    return inflate_stream_file_core(c, wrap, src, dst, dst_idx);
 }

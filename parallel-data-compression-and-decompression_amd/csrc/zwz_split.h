@@ -40,6 +40,8 @@ struct SplitDecode {
     const uint4* res; const uint32_t* dbase;   // n + 1 (host): chain segments of splitting streams in front of a stream
     uint64_t* in_off; uint64_t* in_len; uint4* seg;   // per chain segment: the segment form's input and record
 };
+// zwz_inflate_split_streams_index_dev: where the indexes go (device arrays, as the caller gave them), and per stream its entries
+struct SplitIndex { uint8_t* idx; const uint64_t *idx_off, *idx_cap; uint64_t* idx_len; uint32_t* count; uint32_t span; };
 struct SplitPieces {
     const uint32_t* pbase;     // n + 1 (host): checksum pieces of splitting streams in front of a stream
     uint32_t p;
@@ -49,7 +51,8 @@ struct SplitPieces {
 hipError_t launch_split_head(const SplitStreams& S, uint32_t min_bytes, hipStream_t s);
 hipError_t launch_split_count(const SplitStreams& S, hipStream_t s);                    // tile_cnt, tile_off, base, cfirst
 hipError_t launch_split_write(const SplitStreams& S, const SplitCands& C, uint32_t budget, hipStream_t s);
-// partial != 0 (one slice of a file): res = the longest prefix of the chain that ended cleanly and fits pcap, res2 = (its end, how it ended)
+// partial != 0 (one slice of a file): res = the longest prefix of the chain that ended cleanly and fits pcap, res2 = (its end, how it ended,
+// a final block's end bit within its byte); partial == 0: res2 = the same of the chain's last segment
 hipError_t launch_split_resolve(const SplitStreams& S, const SplitCands& C, uint32_t levels, uint4* res, uint32_t partial, uint64_t pcap, uint4* res2,
                                 hipStream_t s);
 hipError_t launch_split_emit(const SplitStreams& S, const SplitCands& C, const SplitDecode& D, hipStream_t s);
@@ -58,5 +61,11 @@ hipError_t launch_split_emit(const SplitStreams& S, const SplitCands& C, const S
 hipError_t launch_split_finish(const SplitStreams& S, const SplitDecode& D, const SplitPieces& P, const CrcTables* tab, const uint8_t* out,
                                const uint64_t* out_off, const uint32_t* bad, uint64_t* out_len, uint32_t* status, uint32_t* segments,
                                uint32_t* chk_out, uint32_t cu_count, hipStream_t s);
+// The index at the chain's piece starts (index_core.h: the index at full-flush points).  index: behind emit, the entries of every
+// splitting stream and their count; seal: behind finish, the header, the padding, the index CRC and idx_len (0 where the final status
+// is not 0 or the capacity is too small) of every splitting stream; the others keep what the fallback gave them.
+hipError_t launch_split_index(const SplitStreams& S, const SplitDecode& D, const SplitIndex& X, hipStream_t s);
+hipError_t launch_split_seal(const SplitStreams& S, const SplitDecode& D, const SplitIndex& X, const uint4* res2, const CrcTables* tab, const uint32_t* status,
+                             uint32_t cu_count, hipStream_t s);
 
 }  // namespace zwz

@@ -1,11 +1,13 @@
 // zwz_split.hip -- the device half of zwz_inflate_split_streams_dev on gfx950 around inflate_kernel's two split forms (split_core.h has
 // the method): where the streams' bodies start (head), their candidates in stream order (count, BGZF's scan, write), the chain of
 // every stream by pointer jumping (link, jump, mark, resolve), the records of the segment decode (emit), and the checksum of a
-// splitting stream's output from fixed pieces computed in parallel and joined with dstream_core.h's sums (finish).
+// splitting stream's output from fixed pieces computed in parallel and joined with dstream_core.h's sums (finish).  With an index
+// (zwz_inflate_split_streams_index_dev): the entries at the chain's piece starts (index) and the header behind the verdict (seal).
 #include "../../include/zwz.h"
 #include "adler_wg.h"
 #include "crc_wg.h"
 #include "dstream_core.h"
+#include "index_core.h"
 #include "zwz_bgzf.h"
 #include "zwz_device.h"
 #include "zwz_split.h"
@@ -119,7 +121,7 @@ __global__ void __launch_bounds__(kResolveThreads) split_resolve_kernel(SplitStr
     __shared__ unsigned long long sh_sumok;
     const uint32_t s = blockIdx.x, t = threadIdx.x;
     const uint32_t k0 = S.kbase[s], k1 = S.kbase[s + 1];
-    if (k0 == k1) { if (t == 0) res[s] = make_uint4(0, 0, 0, 0); return; }
+    if (k0 == k1) { if (t == 0) res[s] = make_uint4(0, 0, 0, 0); return; }      // (res2[s] stays unwritten: res[s].x == 0 gates every reader of it)
     if (t == 0) { sh_last = 0; sh_nok = 0; sh_lastok = 0; sh_sumok = 0; }
     uint64_t carry = 0;
     uint32_t ncarry = 0;
@@ -153,7 +155,7 @@ __global__ void __launch_bounds__(kResolveThreads) split_resolve_kernel(SplitStr
     if (partial) {
         const uint4 e = C.meas[k0 + sh_lastok];
         res[s] = sh_nok ? make_uint4(1u, sh_nok, (uint32_t)sh_sumok, 0u) : make_uint4(0, 0, 0, 0);
-        res2[s] = make_uint4(e.y, e.x, 0u, 0u);
+        res2[s] = make_uint4(e.y, e.x, e.w, 0u);
         return;
     }
     const uint4 end = C.meas[k0 + sh_last];
@@ -162,6 +164,7 @@ __global__ void __launch_bounds__(kResolveThreads) split_resolve_kernel(SplitStr
     uint32_t expect = 0;
     if (ok) ok = split_trailer_ok(S.wrap, S.in + S.in_off[s], nin, end.y, (uint32_t)carry, &expect);
     res[s] = ok ? make_uint4(1u, ncarry, (uint32_t)carry, expect) : make_uint4(0, 0, 0, 0);
+    res2[s] = make_uint4(end.y, end.x, end.w, 0u);
 }
 
 __global__ void __launch_bounds__(256) split_emit_kernel(SplitCands C, SplitDecode D) {
@@ -220,6 +223,80 @@ __global__ void __launch_bounds__(256) split_finish_kernel(SplitPieces P, const 
     status[s] = bad[s] ? (uint32_t)ZWZ_INF_DATA_ERROR : kCheck && !chk_out && acc != r.w ? (uint32_t)kStrChecksum : 0u;
     if (chk_out) chk_out[s] = acc;
     if (segments) segments[s] = r.y;
+}
+
+// One workgroup per splitting stream, over the chain's segments in order -- emit's records, dense by rank: segment j starts at
+// point j of the rule, at the stream offset its input and its first byte's place in it give and at the decoded offset resolve summed.
+// A tile of 256 points a round: the due flag from the point's offset and the one in front of it, its rank among the due ones from
+// the wave's ballot, the waves in front of it (LDS) and the tiles in front of it; an entry is three 8-byte stores, and none is
+// written that would end behind the index's capacity.
+constexpr uint32_t kIndexThreads = 256;
+__global__ void __launch_bounds__(kIndexThreads) split_index_kernel(SplitStreams S, SplitDecode D, SplitIndex X) {
+    __shared__ uint32_t wsum[kIndexThreads / 64];
+    const uint32_t s = blockIdx.x, t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    const uint4 r = D.res[s];
+    if (!r.x) return;                                // (workgroup-uniform)
+    const uint32_t d0 = D.dbase[s], nseg = r.y;
+    const uint64_t in0 = S.in_off[s], cap = X.idx_cap[s];
+    uint8_t* ent = X.idx + X.idx_off[s] + kIdxHeader;
+    uint32_t carry = 0;
+    for (uint32_t b = 0; b < nseg; b += kIndexThreads) {
+        const uint32_t j = b + t;
+        const bool on = j < nseg;
+        const uint4 sg = on ? D.seg[d0 + j] : make_uint4(0, 0, 0, 0);
+        const uint32_t prev = on && j ? D.seg[d0 + j - 1u].z : 0u;
+        const bool due = on && (j == 0u || index_flush_due(prev, sg.z, r.z, X.span));
+        const uint64_t vote = __ballot(due);
+        if (lane == 0) wsum[w] = (uint32_t)__popcll(vote);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kIndexThreads / 64; i++) { const uint32_t x = wsum[i]; before += i < w ? x : 0u; total += x; }
+        const uint32_t rank = carry + before + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull));
+        if (due && index_flush_bytes((uint64_t)rank + 1u) <= cap) {
+            uint64_t* e = reinterpret_cast<uint64_t*>(ent + (size_t)rank * kIdxEntry);
+            e[0] = 8u * (D.in_off[d0 + j] - in0 + sg.x);
+            e[1] = sg.z;
+            e[2] = 0;
+        }
+        carry += total;
+        __syncthreads();                             // (wsum is rewritten by the next round)
+    }
+    if (t == 0) X.count[s] = carry;
+}
+
+// One workgroup per splitting stream, behind the verdict: the padding, the index CRC and the header.  The stored check value is the
+// trailer's (resolve read it), the end bit the final segment's (res2).
+__global__ void __launch_bounds__(kBgzfThreads) split_seal_kernel(const CrcTables* tab, SplitStreams S, SplitDecode D, SplitIndex X, const uint4* res2,
+                                                                  const uint32_t* status) {
+    __shared__ CrcLds lds;
+    crc_load_tables(lds, tab);
+    const uint32_t t = threadIdx.x;
+    for (uint32_t s = blockIdx.x; s < S.n; s += gridDim.x) {
+        const uint4 r = D.res[s];
+        if (!r.x) continue;                          // (workgroup-uniform, as the branch below)
+        const uint64_t count = X.count[s], len = index_flush_bytes(count);
+        if (status[s] != 0u || len > X.idx_cap[s]) {
+            if (t == 0) X.idx_len[s] = 0;
+            continue;
+        }
+        uint8_t* q = X.idx + X.idx_off[s];
+        if (t == 0 && (count & 1u)) reinterpret_cast<uint64_t*>(q + kIdxHeader)[3u * count] = 0;      // 24 count is 8 mod 16: the padding
+        __threadfence();
+        __syncthreads();
+        const uint32_t crc = crc_block_wg(lds, q + kIdxHeader, (uint32_t)(len - kIdxHeader));
+        if (t == 0) {
+            const uint64_t n = S.in_len[s], end_bit = split_final_end_bit(res2[s].x, res2[s].z);
+            uint32_t* h = reinterpret_cast<uint32_t*>(q);
+            h[0] = 0x495a575au; h[1] = 0x01005844u;                               // "ZWZIDX\0\1"
+            h[2] = S.wrap; h[3] = X.span;
+            h[4] = (uint32_t)n; h[5] = (uint32_t)(n >> 32); h[6] = r.z; h[7] = 0;
+            h[8] = (uint32_t)count; h[9] = 0; h[10] = (uint32_t)end_bit; h[11] = (uint32_t)(end_bit >> 32);
+            h[12] = S.wrap == kWrapRaw ? 0u : r.w; h[13] = crc; h[14] = 0; h[15] = 0;
+            X.idx_len[s] = len;
+        }
+        __syncthreads();
+    }
 }
 
 inline uint32_t blocks_of(uint32_t n) { return (n + 255u) / 256u; }
@@ -286,6 +363,20 @@ hipError_t launch_split_finish(const SplitStreams& S, const SplitDecode& D, cons
     }
     if (S.wrap == kWrapGzip) split_finish_kernel<CrcSum, true><<<grid, 256, 0, s>>>(P, D.res, bad, S.n, out_len, status, segments, chk_out);
     else split_finish_kernel<AdlerSum, true><<<grid, 256, 0, s>>>(P, D.res, bad, S.n, out_len, status, segments, chk_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_split_index(const SplitStreams& S, const SplitDecode& D, const SplitIndex& X, hipStream_t s) {
+    if (!S.n) return hipSuccess;
+    split_index_kernel<<<S.n, kIndexThreads, 0, s>>>(S, D, X);
+    return hipGetLastError();
+}
+
+hipError_t launch_split_seal(const SplitStreams& S, const SplitDecode& D, const SplitIndex& X, const uint4* res2, const CrcTables* tab, const uint32_t* status,
+                             uint32_t cu_count, hipStream_t s) {
+    if (!S.n) return hipSuccess;
+    const uint32_t g = (cu_count ? cu_count : 256u) * 4u;
+    split_seal_kernel<<<S.n < g ? S.n : g, kBgzfThreads, 0, s>>>(tab, S, D, X, res2, status);
     return hipGetLastError();
 }
 
