@@ -636,6 +636,49 @@ int zwz_deflate_streams_index_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, c
                                   uint32_t *d_status, uint32_t span, uint8_t *d_idx, const uint64_t *idx_off,
                                   const uint64_t *idx_cap, uint64_t *d_idx_len);
 
+/* ---- DEFLATE streams of dependent pieces, written: pigz's default ---------------------------------------------------------------
+ * zwz_deflate_streams_dev gives every piece an empty history, which is what lets a reader cut the stream at the markers and costs
+ * ratio: 5 % on text, almost half the file on data with long-range repeats.  Here the pieces stay independent WORK and stop being
+ * independent streams.  Stream i is, byte for byte, what libz 1.2.11 writes in this way: the input is cut into pieces of 32 768 bytes;
+ * piece k is compressed by a raw deflate stream of its own (windowBits -15, memLevel 8, the default strategy, the context's level)
+ * that was given the 32 512 input bytes in front of the piece -- fewer for nothing in front of piece 0 -- with deflateSetDictionary,
+ * takes the piece in one deflate call and is ended with deflate(Z_SYNC_FLUSH), whose bytes (00 00 ff ff on a byte boundary) are a
+ * full flush's; the pieces' outputs follow one another and 03 00 ends the body.  The wrapper is zwz_deflate_streams_dev's: nothing for
+ * ZWZ_WRAP_RAW; 78 9c (78 5e at levels 4 and 5) and the Adler-32 of the whole input; 1f 8b 08 00 00 00 00 00 00 03 and the CRC-32 and
+ * ISIZE of the whole input.  No FDICT bit is set: the result is an ordinary stream that gzip -d, zlib.decompress and pigz read.  An
+ * empty input is header, 03 00, trailer.
+ * Arguments, results, alignment, statuses and the refusals are zwz_deflate_streams_dev's; input i is read, as there, up to its length
+ * rounded up to 16, and nowhere else: a piece's dictionary is the caller's own bytes in front of it, nothing is copied.  out_cap[i]
+ * >= zwz_deflate_dep_stream_bound(in_len[i], wrap) never overflows (1.002 n).  Under zwz_ctx_set_strategy(2 or 3) these calls return
+ * ZWZ_E_INVALID with the reason in zwz_last_error(): there is nothing to gain there.  Every value of the "match" option and the levels
+ * 4, 5 and 6 write the same bytes as libz at that level.
+ * A reader without an index finds sync markers and no cut where nothing refers back: zwz_inflate_streams_dev and the decode in legs read
+ * such a stream with one wave, and the split decode falls back to that.  So the writer can hand the reader the index along with the
+ * stream, decoding nothing (zwz_deflate_dep_streams_index_dev): the points are the piece starts, bit 8 * byte and decoded offset
+ * 32 768 k, chosen by zwz_deflate_streams_index_dev's rule; entry 0 has hist 0, every later entry hist 32 512, and its window is the
+ * input [offset - 32 512, offset), which the writer holds.  The layout is "A seek index for ordinary streams" as it stands, windows
+ * included, and every reader of an index takes it.  The entries are every max(span, 32 768) / 32 768-th piece, so their number is
+ * ceil(n / max(span, 32 768)) (1 for n = 0), and zwz_deflate_dep_stream_index_bound(n, span) = 64 + 24 count + 32 512 (count - 1)
+ * rounded up to 16 is exact: the index has that length (span 0: 1 MiB; 0 for a span that is not allowed).  With span 0 the call takes
+ * the context option "index_span_bytes".  d_idx_len[i] is 0 with status 3 or a capacity too small, and then nothing of the index is
+ * promised; no byte outside [idx_off[i], idx_off[i] + idx_cap[i]) is written.
+ * The file forms run zwz_deflate_stream_file's slice loop, the last 32 512 input bytes of a slice carried in front of the next; with
+ * dst_idx the slices' entries and windows are appended by the host and sealed at the end.  A failure leaves neither file.
+ * Memory of the _file_index form: the windows are kept on the host until the index is sealed, 32 512 bytes an entry -- 1/32 of the
+ * input at the default span of 1 MiB, about the size of the input at a span of 32 KiB or less -- and the call's small device and
+ * pinned buffers hold a slice's windows, up to 16.6 MB each.  Choose the span with that in mind for files of many GiB. */
+uint64_t zwz_deflate_dep_stream_bound(uint64_t n, int wrap);
+int zwz_deflate_dep_streams_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
+                                uint8_t *d_out, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *d_out_len,
+                                uint32_t *d_status);
+int zwz_deflate_dep_stream_file(zwz_ctx *ctx, int wrap, const char *src, const char *dst);
+uint64_t zwz_deflate_dep_stream_index_bound(uint64_t n, uint32_t span);
+int zwz_deflate_dep_streams_index_dev(zwz_ctx *ctx, int wrap, const uint8_t *d_in, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
+                                      uint8_t *d_out, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *d_out_len,
+                                      uint32_t *d_status, uint32_t span, uint8_t *d_idx, const uint64_t *idx_off,
+                                      const uint64_t *idx_cap, uint64_t *d_idx_len);
+int zwz_deflate_dep_stream_file_index(zwz_ctx *ctx, int wrap, const char *src, const char *dst, const char *dst_idx);
+
 /* ---- ZIP archives ---------------------------------------------------------------------------------------------------------------
  * One raw DEFLATE stream per entry, a CRC-32 per entry and a directory at the end: what unzip, Python's zipfile and every file manager
  * open.  Written here: method 8 always; the data of entry i is, byte for byte, zwz_deflate_streams_dev's ZWZ_WRAP_RAW stream of buffer i

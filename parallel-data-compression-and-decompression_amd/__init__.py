@@ -156,6 +156,14 @@ def lib():
         L.zwz_deflate_stream_index_bound.restype = u64
         L.zwz_deflate_stream_index_bound.argtypes = [u64, u32]
         L.zwz_deflate_streams_index_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+        L.zwz_deflate_dep_stream_bound.restype = u64
+        L.zwz_deflate_dep_stream_bound.argtypes = [u64, c.c_int]
+        L.zwz_deflate_dep_streams_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.zwz_deflate_dep_stream_file.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p]
+        L.zwz_deflate_dep_stream_index_bound.restype = u64
+        L.zwz_deflate_dep_stream_index_bound.argtypes = [u64, u32]
+        L.zwz_deflate_dep_streams_index_dev.argtypes = [vp, c.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+        L.zwz_deflate_dep_stream_file_index.argtypes = [vp, c.c_int, c.c_char_p, c.c_char_p, c.c_char_p]
         L.zwz_zip_index.argtypes = [vp, u64, vp, u32, c.POINTER(u32)]
         L.zwz_zip_bound.restype = u64
         L.zwz_zip_bound.argtypes = [vp, vp, u32]
@@ -923,6 +931,107 @@ class Codec:
         self._with_span(span, lambda: _check(lib().zwz_deflate_stream_file_index(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst),
                                                                                  os.fsencode(dst_idx)), "zwz_deflate_stream_file_index"))
 
+    # ---- dependent pieces: pigz's default (include/zwz.h: zwz_deflate_dep_*) ----------------------
+    def deflate_dep_streams_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status):
+        """zwz_deflate_dep_streams_dev: deflate_streams_dev's arguments and results; every piece of 32 768 bytes is compressed with the
+        32 512 bytes in front of it as its dictionary.  Needs the default strategy (ZwzError with status E_INVALID otherwise)."""
+        import numpy as np
+        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
+        n = arr[1].size
+        if any(a.size != n for a in arr):
+            raise ValueError("in_off, in_len, out_off and out_cap must have one entry per stream")
+        _check(lib().zwz_deflate_dep_streams_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n,
+                                                 d_out.data_ptr(), arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(),
+                                                 d_status.data_ptr()), "zwz_deflate_dep_streams_dev")
+
+    def deflate_dep_streams_index_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status, d_idx, idx_off, idx_cap,
+                                      d_idx_len, span=0):
+        """zwz_deflate_dep_streams_index_dev: deflate_streams_index_dev's arguments and results for streams of dependent pieces; every
+        entry but the first carries the 32 512 input bytes in front of it as its window."""
+        import numpy as np
+        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap, idx_off, idx_cap)]
+        n = arr[1].size
+        if any(a.size != n for a in arr):
+            raise ValueError("in_off, in_len, out_off, out_cap, idx_off and idx_cap must have one entry per stream")
+        _check(lib().zwz_deflate_dep_streams_index_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n,
+                                                       d_out.data_ptr(), arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(),
+                                                       d_status.data_ptr(), int(span), d_idx.data_ptr(), arr[4].ctypes.data, arr[5].ctypes.data,
+                                                       d_idx_len.data_ptr()), "zwz_deflate_dep_streams_index_dev")
+
+    def _dep_streams(self, buffers, wrap, span, index):
+        import numpy as np
+        import torch
+        w = WRAPS.get(wrap, wrap)
+        if w not in (WRAP_RAW, WRAP_ZLIB, WRAP_GZIP):
+            raise ValueError("wrap must be raw, zlib or gzip")
+        span = int(span or 0)
+        if index and lib().zwz_deflate_dep_stream_index_bound(1, span) == 0:
+            raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
+        buffers = [bytes(b) for b in buffers]
+        n = len(buffers)
+        if n == 0:
+            return []
+        dev = torch.device("cuda", self.device)
+        up = lambda a: (a + 15) // 16 * 16
+        lens = np.array([len(b) for b in buffers], dtype=np.int64)
+        caps = np.array([deflate_dep_stream_bound(int(k), w) for k in lens], dtype=np.int64)
+        # (with span 0 the context's span applies, which may be below the default: the smallest span bounds them all)
+        icap = np.array([lib().zwz_deflate_dep_stream_index_bound(int(k), span or 16384) if index else 16 for k in lens], dtype=np.int64)
+        offs, ooff, ioff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        offs[1:] = np.cumsum(up(lens[:-1]))
+        ooff[1:] = np.cumsum(up(caps[:-1]))
+        ioff[1:] = np.cumsum(icap[:-1])
+        blob = np.zeros(max(int(offs[-1] + up(lens[-1])), 16), dtype=np.uint8)
+        for i, b in enumerate(buffers):
+            blob[offs[i]:offs[i] + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        d_in = torch.from_numpy(blob).to(dev)
+        d_out = torch.empty(int(ooff[-1] + up(caps[-1])), dtype=torch.uint8, device=dev)
+        d_olen = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        if index:
+            d_idx = torch.empty(int(ioff[-1] + icap[-1]), dtype=torch.uint8, device=dev)
+            d_ilen = torch.zeros(n, dtype=torch.int64, device=dev)
+            self.deflate_dep_streams_index_dev(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st, d_idx, ioff, icap, d_ilen, span)
+        else:
+            self.deflate_dep_streams_dev(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st)
+        self.sync()
+        st, olen, host = d_st.cpu().numpy(), d_olen.cpu().numpy(), d_out.cpu().numpy()
+        for i in range(n):
+            if st[i] != 0:
+                raise ZwzError("deflate_dep_streams: stream %d needs %d bytes, above its bound of %d" % (i, olen[i], caps[i]))
+        out = [host[ooff[i]:ooff[i] + olen[i]].tobytes() for i in range(n)]
+        if not index:
+            return out
+        ilen, ihost = d_ilen.cpu().numpy(), d_idx.cpu().numpy()
+        for i in range(n):
+            if ilen[i] == 0:
+                raise ZwzError("deflate_dep_streams_index: the index of stream %d does not fit its bound of %d bytes" % (i, icap[i]))
+        return [(out[i], ihost[ioff[i]:ioff[i] + ilen[i]].tobytes()) for i in range(n)]
+
+    def deflate_dep_streams(self, buffers, wrap="gzip"):
+        """[bytes] -> [bytes]: every buffer as one raw / zlib / gzip stream of dependent pieces, pigz's default: pieces of 32 768 bytes,
+        each primed with the 32 512 bytes in front of it and closed with a sync flush.  Smaller than deflate_streams' (5 % on text,
+        almost half on data with long-range repeats) and as parallel to write; zlib.decompress / gzip.decompress read it, the split
+        decode finds no cut in it -- write its index along with it (deflate_dep_streams_index) for parallel reads."""
+        return self._dep_streams(buffers, wrap, None, False)
+
+    def deflate_dep_streams_index(self, buffers, wrap="gzip", span=None):
+        """[bytes] -> [(stream, index)]: deflate_dep_streams, and with every stream its seek index, written as the stream is: an entry
+        at the first piece start in every `span` decoded bytes, each but the first with the 32 512 input bytes in front of it as its
+        window.  What inflate_indexed, read_ranges and their batch and file forms take.  span: as deflate_streams_index."""
+        return self._dep_streams(buffers, wrap, span, True)
+
+    def deflate_dep_stream_file(self, src, dst, wrap="gzip"):
+        """One file of any size as one stream of dependent pieces (`main gzip --dependent`)."""
+        _check(lib().zwz_deflate_dep_stream_file(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst)), "zwz_deflate_dep_stream_file")
+
+    def deflate_dep_stream_file_index(self, src, dst, dst_idx, wrap="gzip", span=None):
+        """deflate_dep_stream_file that also writes the stream's seek index, windows included, to dst_idx (`main gzip --dependent
+        --write-index`).  span: as deflate_stream_file_index.  Both files appear on success only."""
+        self._with_span(span, lambda: _check(lib().zwz_deflate_dep_stream_file_index(self._h, WRAPS.get(wrap, wrap), os.fsencode(src), os.fsencode(dst),
+                                                                                     os.fsencode(dst_idx)), "zwz_deflate_dep_stream_file_index"))
+
     # ---- ZIP archives (include/zwz.h: zwz_zip_*) ------------------------------------------------
     def zip_dev(self, d_in, in_off, in_len, names, d_out, d_out_len, d_status, meta=None, out_cap=None):
         """zwz_zip_dev: d_in / d_out uint8 device tensors, d_out_len an int64 and d_status an int32 device tensor of one element;
@@ -1442,6 +1551,18 @@ def deflate_stream_index_bound(n, span=None):
     """Worst-case size of the index Codec.deflate_streams_index writes for a stream of n input bytes: 64 + 24 (n // span + 1) rounded
     up to 16 (span None: 1 MiB); 0 for a span that is not allowed.  Needs no GPU."""
     return lib().zwz_deflate_stream_index_bound(n, int(span or 0))
+
+
+def deflate_dep_stream_bound(n, wrap="gzip"):
+    """Worst-case size of one stream of n input bytes from Codec.deflate_dep_streams (about 1.002 n); needs no GPU."""
+    return lib().zwz_deflate_dep_stream_bound(n, WRAPS.get(wrap, wrap))
+
+
+def deflate_dep_stream_index_bound(n, span=None):
+    """The exact size of the index Codec.deflate_dep_streams_index writes for a stream of n input bytes: with step = max(span, 32 768)
+    and count = ceil(n / step) entries (1 for n = 0), 64 + 24 count + 32 512 (count - 1) rounded up to 16 (span None: 1 MiB); 0 for a
+    span that is not allowed.  Needs no GPU."""
+    return lib().zwz_deflate_dep_stream_index_bound(n, int(span or 0))
 
 
 def zip_index(data):

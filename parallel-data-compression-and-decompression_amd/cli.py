@@ -223,7 +223,10 @@ def index_main(argv):
     (Codec.inflate_legs_file) whatever the file's size: one wave, about 36 s a decoded GiB.
     `gzip <src> <dst> --write-index <dst.zwi> [--span N] [--zlib|--raw]` writes the stream and, as it writes, the seek index of its
     flush points (Codec.deflate_stream_file_index): no decode, no windows.  `gunzip <src> <dst> --split --write-index <dst.zwi> [--span N]`
-    and `gzindex <src> [<dst.zwi>] --split [--span N]` build that index with the split decode (Codec.inflate_split_index_file)."""
+    and `gzindex <src> [<dst.zwi>] --split [--span N]` build that index with the split decode (Codec.inflate_split_index_file).
+    `gzip <src> <dst> --dependent [--zlib|--raw] [-4|-5|-6] [--write-index <dst.zwi> [--span N]]` writes pigz's default, dependent
+    pieces (Codec.deflate_dep_stream_file / deflate_dep_stream_file_index): a smaller file, and its index with windows; --huffman and
+    --rle are refused with it."""
     ap = argparse.ArgumentParser(prog="main " + argv[0])
     ap.add_argument("source")
     ap.add_argument("output", nargs="?" if argv[0] == "gzindex" else None)
@@ -234,8 +237,13 @@ def index_main(argv):
         ap.add_argument("--legs", action="store_true", help="decode in legs through staging windows, whatever the file's size")
         ap.add_argument("--split", action="store_true", help="through the split decode: the index of the file's full-flush points")
     elif argv[0] == "gzip":
-        ap.add_argument("--write-index", dest="write_index", required=True, help="the seek index of the stream's flush points")
+        ap.add_argument("--write-index", dest="write_index", required="--dependent" not in argv, help="the seek index of the stream's flush points")
         ap.add_argument("--span", type=int, default=0, help="decoded bytes an entry covers at least")
+        ap.add_argument("--dependent", action="store_true", help="pieces of 32 768 bytes, each primed with the 32 512 bytes in front of it")
+        for lv in (4, 5, 6):
+            ap.add_argument("-%d" % lv, dest="level", action="store_const", const=lv, help="with --dependent: libz's level")
+        ap.add_argument("--huffman", action="store_true", help="(refused with --dependent)")
+        ap.add_argument("--rle", action="store_true", help="(refused with --dependent)")
     else:
         ap.add_argument("--index")
         ap.add_argument("--legs", action="store_true", help="decode in legs through staging windows, whatever the file's size")
@@ -250,10 +258,26 @@ def index_main(argv):
         ap.error("one of --index <idx>, --legs and --split; --write-index needs --legs or --split, --split needs --write-index, --span needs --write-index")
     if argv[0] == "gzindex" and a.legs and a.split:
         ap.error("one of --legs and --split")
+    if argv[0] == "gzip":
+        if a.dependent and (a.huffman or a.rle):
+            ap.error("--dependent needs the default strategy: not with --huffman or --rle")
+        if a.huffman or a.rle:
+            ap.error("--huffman and --rle are flags of csrc/main.cpp's `main gzip`; this command line writes the default strategy")
+        if a.level and not a.dependent:
+            ap.error("-4, -5 and -6 go with --dependent here (csrc/main.cpp's `main gzip` takes them by themselves)")
+        if a.span and not a.write_index:
+            ap.error("--span needs --write-index")
     from . import Codec, index_info
     codec = Codec(int(os.environ.get("LOCAL_RANK", "0")))
     try:
-        if argv[0] == "gzip":
+        if argv[0] == "gzip" and a.dependent:
+            if a.level:
+                codec.set_level(a.level)
+            if a.write_index:
+                codec.deflate_dep_stream_file_index(a.source, a.output, a.write_index, wrap, a.span or None)
+            else:
+                codec.deflate_dep_stream_file(a.source, a.output, wrap)
+        elif argv[0] == "gzip":
             codec.deflate_stream_file_index(a.source, a.output, a.write_index, wrap, a.span or None)
         elif a.split:
             codec.inflate_split_index_file(a.source, None if argv[0] == "gzindex" else a.output,
@@ -286,7 +310,7 @@ def index_main(argv):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if argv and (argv[0] == "gzindex" or (argv[0] == "gunzip" and ("--index" in argv or "--legs" in argv or "--split" in argv)) or (argv[0] == "gzip" and "--write-index" in argv)):
+    if argv and (argv[0] == "gzindex" or (argv[0] == "gunzip" and ("--index" in argv or "--legs" in argv or "--split" in argv)) or (argv[0] == "gzip" and ("--write-index" in argv or "--dependent" in argv))):
         return index_main(argv)
     ap = argparse.ArgumentParser(prog="main", usage="%(prog)s <compress/decompress> <source directory path> <output directory path>")
     ap.add_argument("operation")

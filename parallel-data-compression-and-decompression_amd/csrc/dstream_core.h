@@ -83,6 +83,44 @@ ZWZ_HD uint64_t dstream_bound(uint64_t n, uint32_t wrap) {
     return dstream_header_bytes(wrap) + full * piece_bound(kPieceBytes) + (rest ? piece_bound(rest) : 0u) + 2u + dstream_trailer_bytes(wrap);
 }
 
+// ---- dependent pieces (zwz_deflate_dep_streams_dev) ------------------------------------------------------------
+// pigz's default: pieces of kDepPieceBytes, each compressed with the kDepDictBytes of input in front of it as a preset dictionary
+// (deflateSetDictionary on a raw stream, no FDICT) and closed with Z_SYNC_FLUSH, which writes the bytes of a full flush; 03 00 behind the
+// last.  A piece and its dictionary are ONE chunk of the codec, [dictionary | piece], at most kDepDictBytes + kDepPieceBytes = kPieceBytes
+// bytes: libz puts the dictionary at window position 0, so window and chunk positions coincide, it inserts every dictionary position
+// into the chains, and it reads the whole piece in one fill_window (room 65 536 - 32 512 >= 32 768) -- the chains, the distance rules
+// and the one slide at strstart >= kSlidePos are those of the whole chunk.  What differs is where the walk starts: at position
+// `skip` = the dictionary's length, fresh (prev_length 2, no match pending), and symbols, blocks and the checksum count from there.
+// kDepDictBytes >= kMaxDist, so no match libz could reach with a 32 768-byte dictionary is lost; it is a multiple of 64 (lz_parse's
+// blocks), of 128 (lz_lazy's segments) and of 256 (a wave's trip of lz_match's screening pass).
+constexpr uint32_t kDepPieceBytes = 32768, kDepDictBytes = 32512;
+static_assert(kDepDictBytes + kDepPieceBytes == kPieceBytes && kDepDictBytes >= kMaxDist && kDepDictBytes % 256u == 0, "a dependent piece and its dictionary are one chunk");
+
+// The dictionary of piece k of a stream whose first piece has `lead` dictionary bytes in front of it (0 but in the file call's later slices)
+ZWZ_HD uint32_t dep_skip(uint64_t k, uint32_t lead) { return k ? kDepDictBytes : lead; }
+
+// Worst case of spliced_bytes for a dependent piece of L <= kDepPieceBytes input bytes behind `skip` dictionary bytes: piece_bound's
+// count, in chunk coordinates.  At most L / kSymsPerBlock + 1 blocks of at most 8n + 42 bits.  The block that may not be stored starts
+// before kWSize -- behind a dictionary that is the piece's FIRST block, at skip = 32 512, and no other: the next one starts 16 383
+// symbols on -- and is flushed at or after kSlidePos, so the piece has skip + L >= kSlidePos: every full piece behind a dictionary
+// whose first block reaches 65 274, and on compressible data a full piece is one block.  Such a block holds n >= kSlidePos - skip
+// = 32 762 bytes, so piece_bound's count gives 8n + 10 + 2 * 16 383 - 32 762 = 8n + 14 bits for it; the 227 bits piece_bound adds for
+// its own case (n > 32 506) are carried here all the same, for every such piece: one rule for both writers, 28 bytes a piece.
+ZWZ_HD uint32_t dep_piece_bound(uint32_t L, uint32_t skip) {
+    const uint32_t nb = L / kSymsPerBlock + 1u;
+    const uint32_t bits = 42u * nb + (skip + L >= kSlidePos ? 227u : 0u);
+    return L + (bits + 3u + 7u) / 8u + 4u;
+}
+// header + the first piece (no dictionary) + the full pieces behind it + the last + 03 00 + trailer; an empty input has no piece
+ZWZ_HD uint64_t dep_stream_bound(uint64_t n, uint32_t wrap) {
+    uint64_t b = dstream_header_bytes(wrap) + 2u + dstream_trailer_bytes(wrap);
+    if (!n) return b;
+    const uint64_t pieces = (n + kDepPieceBytes - 1u) / kDepPieceBytes;
+    const uint32_t last = (uint32_t)(n - (pieces - 1u) * kDepPieceBytes);
+    if (pieces == 1u) return b + dep_piece_bound(last, 0u);
+    return b + dep_piece_bound(kDepPieceBytes, 0u) + (pieces - 2u) * dep_piece_bound(kDepPieceBytes, kDepDictBytes) + dep_piece_bound(last, kDepDictBytes);
+}
+
 // ---- checksums of a concatenation -----------------------------------------------------------------------------------------------
 // Both checksums are monoids under "append": join(l, r, p) is the checksum of A || B from those of A and B and a parameter p that
 // depends on |B| alone; pof(n) is that parameter for n bytes and pjoin(p, q) the parameter of the two lengths added.  The identity

@@ -274,6 +274,21 @@ inline void index_flush_seal(uint8_t* p, uint32_t wrap, uint32_t span, uint64_t 
     index_seal(p, n, wrap, span, stream_len, decoded_len, count, end_bit, check);
 }
 
+// ---- The index of a stream of dependent pieces (dstream_core.h) ---------------------------------------------
+// The points are the piece starts, bit 8 * byte and decoded offset kIdxDepPiece * k, chosen by index_flush_due; entry 0 has hist 0,
+// every later entry hist = kIdxDepDict, and its window is the input in front of it, which the writer holds: nothing is decoded.  The
+// offsets are multiples of 32 768 and a span is a power of two from 16 384 up, so the entries are every `step`-th piece and their
+// number is known before a byte is written -- and with it where the windows start.
+constexpr uint32_t kIdxDepPiece = 32768, kIdxDepDict = 32512;     // dstream_core.h's kDepPieceBytes, kDepDictBytes
+ZWZ_HD uint64_t index_dep_step(uint32_t span) { return span > kIdxDepPiece ? span / kIdxDepPiece : 1u; }       // pieces from entry to entry
+ZWZ_HD uint64_t index_dep_count(uint64_t n, uint32_t span) {
+    const uint64_t reach = index_dep_step(span) * kIdxDepPiece;
+    return n ? (n + reach - 1u) / reach : 1u;
+}
+// count entries, the first without a window: the exact length, padded
+ZWZ_HD uint64_t index_dep_bytes(uint64_t count) { return (kIdxHeader + count * kIdxEntry + (count - 1u) * kIdxDepDict + 15u) & ~15ull; }
+ZWZ_HD uint64_t index_dep_bound(uint64_t n, uint32_t span) { return index_dep_bytes(index_dep_count(n, span)); }
+
 // The indexed-segment form's verdict: it must stand at the block header whose first bit is the segment's end bit (or behind the final
 // block, for the last segment), with exactly the indexed count and the decoder still running.
 ZWZ_HD bool index_segment_good(uint32_t status, uint32_t bit_pos, uint32_t end_bit, uint32_t out_pos, uint32_t cap, uint32_t last, uint32_t is_last) {

@@ -124,14 +124,18 @@ struct ParseResult { uint32_t n_sym; uint32_t n_match; uint32_t last_is_match; }
 
 template <class Lv = LzDefaultLevel, class EntryFn, class HasFn>
 ZWZ_HD ParseResult lz_parse(EntryFn entries /* (p, which32) -> packed entry */, HasFn has128 /* word index -> mask */, uint32_t L,
-                            uint64_t* sym, uint64_t* mst, uint64_t* m32) {
+                            uint64_t* sym, uint64_t* mst, uint64_t* m32, uint32_t start = 0 /* the walk enters here, fresh: [0, start) is a dictionary (dstream_core.h) and starts no symbol */) {
     const uint32_t nwords = (L + 63) >> 6;
     // masks are built word by word: the walk is monotone in position
     uint32_t w = 0;                 // current output word
     uint64_t sym_w = ~0ull, mst_w = 0, m32_w = 0;
     uint32_t n_match = 0, covered = 0;
-    uint32_t p = 0, b = kMinMatch - 1, b_entry = 0, b_sel = 0;
+    uint32_t p = start, b = kMinMatch - 1, b_entry = 0, b_sel = 0;
     ParseResult r; r.last_is_match = 0;
+    if (start) {                    // no symbol starts in the dictionary
+        for (; w < (start >> 6); w++) { sym[w] = 0; mst[w] = 0; m32[w] = 0; }
+        sym_w = ~0ull << (start & 63);
+    }
 
     auto flush_to = [&](uint32_t nw) {   // emit words [w, nw)
         while (w < nw) {
@@ -202,7 +206,7 @@ ZWZ_HD ParseResult lz_parse(EntryFn entries /* (p, which32) -> packed entry */, 
         sym[nwords - 1] &= keep;
     }
     r.n_match = n_match;
-    r.n_sym = L - covered;
+    r.n_sym = L - start - covered;
     return r;
 }
 

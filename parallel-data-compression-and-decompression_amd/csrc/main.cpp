@@ -379,11 +379,11 @@ int zip_main(const std::string& op, const char* src, const char* dst, int world_
 
 void bgzf_usage(const char* argv0) {
     fprintf(stderr, "Usage: %s bgzip <src> <dst> [--index] [-4|-5|-6] [--huffman|--rle]\n       %s bgunzip <src> <dst> [--offset B [--size S] | --chunk VBEG:VEND [--chunk ...]]\n       %s bgindex <src.gz>\n"
-            "       %s gzip <src> <dst> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle] [--write-index <dst.zwi> [--span N]]\n       %s gunzip <src> <dst> [--zlib|--raw] [--index <idx> [--offset B [--size S]]] [--legs|--split [--write-index <dst.zwi> [--span N]]]\n       %s gzindex <src> [<dst.zwi>] [--span N] [--zlib|--raw] [--legs|--split]\n       %s zip <src dir> <dst.zip> [-4|-5|-6] [--huffman|--rle]\n       %s unzip <src.zip> <dst dir>\n"
+            "       %s gzip <src> <dst> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle] [--write-index <dst.zwi> [--span N]]\n       %s gzip <src> <dst> --dependent [--zlib|--raw] [-4|-5|-6] [--write-index <dst.zwi> [--span N]]\n       %s gunzip <src> <dst> [--zlib|--raw] [--index <idx> [--offset B [--size S]]] [--legs|--split [--write-index <dst.zwi> [--span N]]]\n       %s gzindex <src> [<dst.zwi>] [--span N] [--zlib|--raw] [--legs|--split]\n       %s zip <src dir> <dst.zip> [-4|-5|-6] [--huffman|--rle]\n       %s unzip <src.zip> <dst dir>\n"
             "  --legs: decode in legs through staging windows (zwz_inflate_legs_file) whatever the file's size -- the path a file of 2^29 bytes or more takes by itself; one wave, about 36 s a decoded GiB\n"
             "  -4 -5 -6 (behind the operands or, as gzip takes it, in front of them): libz's compression level of that number (default 6, or ZWZ_LEVEL); no other level exists here\n"
             "  --huffman | --rle (before or behind the operands; not both): libz's strategy Z_HUFFMAN_ONLY (entropy coding only) or Z_RLE (runs of a byte only); default: neither, or ZWZ_STRATEGY\n",
-            argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
+            argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
 }
 
 bool parse_u64(const char* s, uint64_t* v);
@@ -451,6 +451,8 @@ int gunzip_indexed(zwz_ctx* ctx, const char* src, const char* dst, const char* i
 
 // `main gzip <src file> <dst file> [--zlib|--raw] [-4|-5|-6] [--huffman|--rle]`: one file as one ordinary gzip (zlib, raw DEFLATE) stream, one process, one GPU.
 // `main gzip <src> <dst> --write-index <dst.zwi> [--span N]`: also the seek index of the stream's flush points, written as the stream is (zwz_deflate_stream_file_index).
+// `main gzip <src> <dst> --dependent [--zlib|--raw] [-4|-5|-6] [--write-index <dst.zwi> [--span N]]`: pigz's default, pieces of 32 768 bytes each primed with the 32 512 in
+// front of it (zwz_deflate_dep_stream_file): a smaller file; its index, windows included, is written with it.  Not with --huffman or --rle.
 // `main gunzip <src file> <dst file> [--zlib|--raw]`: the way back (zwz_inflate_stream_file), for any stream other encoders wrote too.
 // `main gunzip <src> <dst> --legs [--write-index <dst.zwi> [--span N]]`: through zwz_inflate_legs_file at any size, the seek index from the same decode.
 // `main gunzip <src> <dst> --split --write-index <dst.zwi> [--span N]`: the split decode that also writes the index of the flush points (zwz_inflate_split_index_file).
@@ -459,7 +461,7 @@ int gzip_main(int argc, char** argv, int world_size, int device) {
     if (world_size > 1) { fprintf(stderr, "%s: single process only (world size %d in the environment)\n", argv[1], world_size); return 1; }
     int wrap = ZWZ_WRAP_GZIP, level = 0, strategy = 0;
     const char *idx_path = nullptr, *write_idx = nullptr;
-    bool have_off = false, have_size = false, legs = false, split = false;
+    bool have_off = false, have_size = false, legs = false, split = false, dependent = false;
     uint64_t off = 0, size = 0, span = 0;
     for (int i = 4; i < argc; i++) {
         const std::string a = argv[i];
@@ -472,11 +474,12 @@ int gzip_main(int argc, char** argv, int world_size, int device) {
         else if (back && a == "--split") split = true;
         else if (a == "--write-index" && i + 1 < argc) write_idx = argv[++i];
         else if (a == "--span" && i + 1 < argc && parse_u64(argv[i + 1], &span) && span) i++;
+        else if (!back && a == "--dependent") dependent = true;
         else if (!back && level_flag(a, &level) == 1) {}
         else if (!back && strategy_flag(a, &strategy) == 1) {}
         else { bgzf_usage(argv[0]); return 1; }
     }
-    if ((have_off && !idx_path) || (have_size && !have_off) || (legs && idx_path) || (split && (legs || idx_path || !write_idx)) || (back && write_idx && !legs && !split) || (span && !write_idx)) { bgzf_usage(argv[0]); return 1; }
+    if ((have_off && !idx_path) || (have_size && !have_off) || (legs && idx_path) || (split && (legs || idx_path || !write_idx)) || (back && write_idx && !legs && !split) || (span && !write_idx) || (dependent && strategy)) { bgzf_usage(argv[0]); return 1; }
     const auto t0 = std::chrono::steady_clock::now();
     zwz_ctx* ctx = nullptr;
     int rc = zwz_ctx_create(device, 0, &ctx);
@@ -486,6 +489,7 @@ int gzip_main(int argc, char** argv, int world_size, int device) {
     if (rc == ZWZ_OK && legs) rc = zwz_inflate_legs_file(ctx, wrap, argv[2], argv[3], write_idx, nullptr);
     else if (rc == ZWZ_OK && split) rc = zwz_inflate_split_index_file(ctx, wrap, argv[2], argv[3], write_idx);
     else if (rc == ZWZ_OK && idx_path) rc = gunzip_indexed(ctx, argv[2], argv[3], idx_path, have_off, off, have_size, size);
+    else if (rc == ZWZ_OK && dependent) rc = write_idx ? zwz_deflate_dep_stream_file_index(ctx, wrap, argv[2], argv[3], write_idx) : zwz_deflate_dep_stream_file(ctx, wrap, argv[2], argv[3]);
     else if (rc == ZWZ_OK && !back && write_idx) rc = zwz_deflate_stream_file_index(ctx, wrap, argv[2], argv[3], write_idx);
     else if (rc == ZWZ_OK) rc = back ? zwz_inflate_stream_file(ctx, wrap, argv[2], argv[3]) : zwz_deflate_stream_file(ctx, wrap, argv[2], argv[3]);
     zwz_ctx_destroy(ctx);

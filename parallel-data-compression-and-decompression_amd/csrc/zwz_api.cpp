@@ -441,6 +441,13 @@ int zwz_ctx_stage_ms(zwz_ctx* c, float* ms, int reset) {
 
 int zwz_deflate_batch_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                           uint8_t* d_out, uint64_t out_stride, uint32_t* d_out_len) {
+    return zwz::deflate_batch_dev_skip(c, d_in, d_in_off, d_in_len, nullptr, n, d_out, out_stride, d_out_len);
+}
+
+}  // extern "C"
+
+int zwz::deflate_batch_dev_skip(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const uint32_t* d_skip, uint32_t n,
+                                uint8_t* d_out, uint64_t out_stride, uint32_t* d_out_len) {
     if (!c || (n && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_len))) return ZWZ_E_INVALID;
     if (out_stride < ZWZ_DEV_STRIDE || (out_stride & 15u) || ((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return ZWZ_E_INVALID;
     HIPCHK(hipSetDevice(c->device));
@@ -455,6 +462,7 @@ int zwz_deflate_batch_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_
         a.in = d_in; a.in_off = d_in_off + done; a.in_len = d_in_len + done; a.n = m;
         a.out = d_out + (size_t)done * out_stride; a.out_stride = out_stride; a.out_len = d_out_len + done;
         carve_workspace(c, a);
+        a.skip = d_skip ? d_skip + done : nullptr;
         a.match_mode = c->match_mode; a.plan_serial = c->plan_serial; a.level = c->level; a.strategy = c->strategy;
         HIPCHK(launch_deflate(a, c->stream, c->profiling ? c->ev : nullptr));
         if (c->profiling) {   // profiling serialises slices: stage times are read back per slice
@@ -468,6 +476,8 @@ int zwz_deflate_batch_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_
     }
     return ZWZ_OK;
 }
+
+extern "C" {
 
 int zwz_md5_files_dev(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const uint32_t* d_files,
                       uint32_t n_files, uint8_t* d_digests) {

@@ -98,6 +98,11 @@ void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 int ensure_workspace(zwz_ctx* c, uint32_t chunks);
 void carve_workspace(zwz_ctx* c, DeflateArgs& a);
+// zwz_deflate_batch_dev with a start offset per chunk (d_skip, device memory, or null: none): chunk i's first d_skip[i] bytes are a dictionary,
+// searched against and never coded (zwz_kernels.h: DeflateArgs::skip).  The slot's Adler-32 still covers the whole chunk.  Internal: the
+// stream writer's dependent pieces (zwz_dstream.cpp); the public call has no such argument.
+int deflate_batch_dev_skip(zwz_ctx* c, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const uint32_t* d_skip, uint32_t n,
+                           uint8_t* d_out, uint64_t out_stride, uint32_t* d_out_len);
 int ensure_staging(zwz_ctx* c, uint32_t chunks);
 int ensure_inf_order(zwz_ctx* c, uint32_t n);
 int ensure_crc_tables(zwz_ctx* c);            // builds the tables on first use, on the context's stream

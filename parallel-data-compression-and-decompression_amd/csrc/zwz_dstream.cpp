@@ -20,7 +20,7 @@ namespace {
 
 constexpr uint32_t kFileSlicePieces = 256;          // pieces per slice of zwz_deflate_stream_file: 16.7 MB of input
 
-struct PiecesView { DstreamPieces P; uint64_t* base; uint32_t* err; uint64_t* rbase; };     // rbase: the rank scan's base (index)
+struct PiecesView { DstreamPieces P; uint64_t* base; uint32_t* err; uint64_t* rbase; DstreamDep Q; };     // rbase: the rank scan's base (index); Q: dependent pieces
 PiecesView pieces_layout(Carver& w, size_t m) {
     PiecesView v;
     v.P.slots = w.take<uint8_t>(m * ZWZ_DEV_STRIDE, 256);     // (wg_copy reads up to 3 bytes past a slot's bytes)
@@ -29,6 +29,7 @@ PiecesView pieces_layout(Carver& w, size_t m) {
     v.P.slen = w.take<uint32_t>(m); v.P.hbit = w.take<uint32_t>(m); v.P.ebit = w.take<uint32_t>(m);
     v.P.due = w.take<uint32_t>(m); v.P.rank = w.take<uint64_t>(m);
     v.base = w.take<uint64_t>(3); v.err = reinterpret_cast<uint32_t*>(v.base + 1); v.rbase = v.base + 2;
+    v.Q.skip = w.take<uint32_t>(m); v.Q.poff = w.take<uint64_t>(m); v.Q.plen = w.take<uint32_t>(m);
     return v;
 }
 
@@ -53,18 +54,23 @@ int ensure_dstream(zwz_ctx* c, uint32_t pieces, uint32_t streams, bool crc) {
 // The device part, arguments checked by the caller.  partial: every stream's pieces alone, and its checksum left in *d_chk (the file
 // function's slices).  ix: the index as well, idx_off and idx_cap host arrays of n; sealed here unless partial, when *d_cnt is where
 // the stream's count of entries will stand.  Returns with everything queued on the context's stream.
+// dep: dependent pieces (dstream_core.h) -- pieces of kDepPieceBytes, each compressed behind the kDepDictBytes of input in front of it;
+// lead: the dictionary bytes that lie in front of in_off[i] for every stream's first piece (the file function's later slices), else 0.
+struct DepMode { bool on = false; uint32_t lead = 0; };
 int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
                    const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status, bool partial, const uint32_t** d_chk,
-                   const DstreamIndex* ix = nullptr, const uint64_t* idx_off = nullptr, const uint64_t* idx_cap = nullptr, const uint64_t** d_cnt = nullptr) {
+                   const DstreamIndex* ix = nullptr, const uint64_t* idx_off = nullptr, const uint64_t* idx_cap = nullptr, const uint64_t** d_cnt = nullptr,
+                   DepMode dep = DepMode{}, uint64_t win_base = 0) {
     // pieces are counted in 64 bits: the only limit is that they, and the output they need, can be counted at all
+    const uint64_t piece = dep.on ? kDepPieceBytes : kPieceBytes;
     std::vector<uint64_t> pfirst((size_t)n + 1);
     pfirst[0] = 0;
     for (uint32_t i = 0; i < n; i++) {
-        if (in_len[i] > ~0ull - kPieceBytes || (in_len[i] + kPieceBytes - 1) / kPieceBytes > (~0ull >> 18) - pfirst[i]) {
-            set_error("zwz_deflate_streams_dev: the streams up to stream %u have more than 2^46 pieces", i);
+        if (in_len[i] > ~0ull - piece || (in_len[i] + piece - 1) / piece > (~0ull >> 18) - pfirst[i]) {
+            set_error("%s: the streams up to stream %u have more than 2^46 pieces", dep.on ? "zwz_deflate_dep_streams_dev" : "zwz_deflate_streams_dev", i);
             return ZWZ_E_INVALID;
         }
-        pfirst[i + 1] = pfirst[i] + (in_len[i] + kPieceBytes - 1) / kPieceBytes;
+        pfirst[i + 1] = pfirst[i] + (in_len[i] + piece - 1) / piece;
     }
     const uint64_t G = pfirst[n];
     const uint32_t M = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(G, 1), c->max_batch);
@@ -96,24 +102,45 @@ int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_
         while (pfirst[s0 + 1] <= g0) s0++;
         uint32_t s1 = s0;                             // the stream of its last
         while (pfirst[s1 + 1] < g0 + m) s1++;
+        if (dep.on) {
+            // the chunk of a piece is [dictionary | piece], read where it lies in the caller's input; the checksum is the piece's alone
+            HIPCHK(launch_dstream_dep_layout(S, v.P, v.Q, g0, m, dep.lead, c->stream));
+            if (wrap == kWrapGzip) HIPCHK(launch_crc32_blocks(tab, d_in, v.Q.poff, v.Q.plen, m, v.P.crc, c->cu_count, c->stream));
+            else if (wrap == kWrapZlib) HIPCHK(launch_dstream_dep_adler(d_in, v.P, v.Q, m, c->cu_count, c->stream));
+            if (int rc = deflate_batch_dev_skip(c, d_in, v.P.off, v.P.len, v.Q.skip, m, v.P.slots, ZWZ_DEV_STRIDE, v.P.olen)) return rc;
+        } else {
         HIPCHK(launch_dstream_layout(S, v.P, g0, m, c->stream));
         if (wrap == kWrapGzip) HIPCHK(launch_crc32_blocks(tab, d_in, v.P.off, v.P.len, m, v.P.crc, c->cu_count, c->stream));
         if (int rc = zwz_deflate_batch_dev(c, d_in, v.P.off, v.P.len, m, v.P.slots, ZWZ_DEV_STRIDE, v.P.olen)) return rc;
+        }
         DeflateArgs a;                                // the slice's block records are still in the codec's workspace
         carve_workspace(c, a);
         HIPCHK(launch_dstream_size(a.info, a.blocks, a.plans, v.P, m, v.err, c->stream));
         HIPCHK(launch_bgzf_scan(v.P.slen, m, 0, ~0u, v.P.x, v.base, v.err + 1, c->stream));
-        HIPCHK(launch_dstream_combine(S, v.P, g0, m, s0, s1 - s0 + 1, wrap, c->stream));
+        if (dep.on) HIPCHK(launch_dstream_dep_combine(S, v.P, v.Q, g0, m, s0, s1 - s0 + 1, wrap, c->stream));
+        else HIPCHK(launch_dstream_combine(S, v.P, g0, m, s0, s1 - s0 + 1, wrap, c->stream));
         HIPCHK(launch_dstream_pack(S, v.P, g0, m, O, v.err, c->stream));
-        if (ix) {
+        if (ix && dep.on) {
+            HIPCHK(launch_dstream_dep_due(S, v.P, g0, m, *ix, c->stream));
+            HIPCHK(launch_bgzf_scan(v.P.due, m, 0, ~0u, v.P.rank, v.rbase, v.err + 1, c->stream));
+            HIPCHK(launch_dstream_dep_index(d_in, S, v.P, v.Q, g0, m, O, *ix, win_base, c->stream));
+        } else if (ix) {
             HIPCHK(launch_dstream_due(S, v.P, g0, m, *ix, c->stream));
             HIPCHK(launch_bgzf_scan(v.P.due, m, 0, ~0u, v.P.rank, v.rbase, v.err + 1, c->stream));
             HIPCHK(launch_dstream_index(S, v.P, g0, m, O, *ix, c->stream));
         }
         s0 = s1;
     }
-    if (ix && !partial) HIPCHK(launch_dstream_index_seal(tab, S, O, *ix, c->cu_count, c->stream));
+    if (ix && !partial) HIPCHK(dep.on ? launch_dstream_dep_index_seal(tab, S, O, *ix, c->cu_count, c->stream) : launch_dstream_index_seal(tab, S, O, *ix, c->cu_count, c->stream));
     return ZWZ_OK;
+}
+
+// What the dependent calls refuse beyond the independent ones' checks
+int dep_strategy_ok(zwz_ctx* c, const char* who) {
+    if (c->strategy == kStrategyDefault) return ZWZ_OK;
+    set_error("%s: dependent pieces need the default strategy (the context's is %u): under Z_HUFFMAN_ONLY and Z_RLE there is nothing "
+              "to gain from the bytes in front of a piece -- use the independent call", who, c->strategy);
+    return ZWZ_E_INVALID;
 }
 
 }  // namespace
@@ -157,6 +184,49 @@ int zwz_deflate_streams_index_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, con
     return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr, &X, idx_off, idx_cap);
 }
 
+uint64_t zwz_deflate_dep_stream_bound(uint64_t n, int wrap) { return dep_stream_bound(n, (uint32_t)wrap); }
+
+int zwz_deflate_dep_streams_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
+                                const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status) {
+    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    if (n && (!d_in || !in_off || !in_len || !d_out || !out_off || !out_cap || !d_out_len || !d_status)) return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return ZWZ_E_INVALID;
+    for (uint32_t i = 0; i < n; i++)
+        if ((in_off[i] & 15u) || (out_off[i] & 15u)) { set_error("zwz_deflate_dep_streams_dev: stream %u: offsets must be multiples of 16", i); return ZWZ_E_INVALID; }
+    if (int rc = dep_strategy_ok(c, "zwz_deflate_dep_streams_dev")) return rc;
+    if (n == 0) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          DepMode{true, 0u});
+}
+
+uint64_t zwz_deflate_dep_stream_index_bound(uint64_t n, uint32_t span) {
+    if (span == 0) span = kIdxSpanDefault;
+    return index_span_ok(span) ? index_dep_bound(n, span) : 0u;
+}
+
+int zwz_deflate_dep_streams_index_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
+                                      const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status, uint32_t span, uint8_t* d_idx,
+                                      const uint64_t* idx_off, const uint64_t* idx_cap, uint64_t* d_idx_len) {
+    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    if (span == 0) span = c->index_span_bytes;
+    if (!index_span_ok(span)) return ZWZ_E_INVALID;
+    if (n && (!d_in || !in_off || !in_len || !d_out || !out_off || !out_cap || !d_out_len || !d_status || !d_idx || !idx_off || !idx_cap || !d_idx_len))
+        return ZWZ_E_INVALID;
+    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
+    for (uint32_t i = 0; i < n; i++)
+        if ((in_off[i] & 15u) || (out_off[i] & 15u) || (idx_off[i] & 15u)) {
+            set_error("zwz_deflate_dep_streams_index_dev: stream %u: offsets must be multiples of 16", i);
+            return ZWZ_E_INVALID;
+        }
+    if (int rc = dep_strategy_ok(c, "zwz_deflate_dep_streams_index_dev")) return rc;
+    if (n == 0) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const DstreamIndex X{d_idx, d_idx_len, span, 0, 0};
+    return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr, &X, idx_off, idx_cap, nullptr,
+                          DepMode{true, 0u});
+}
+
 // One slice of kFileSlicePieces whole pieces at a time: its pieces alone (partial), and its own checksum, which the host joins onto
 // the file's by the slice's length.  The header goes in front of the first slice and 03 00 + trailer behind the last.
 // With dst_idx the index as well (index_core.h: the index at full-flush points), at the context's "index_span_bytes": the entries of
@@ -165,17 +235,32 @@ int zwz_deflate_streams_index_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, con
 // entries and, from byte 64, the entries themselves.
 namespace {
 
-int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char* dst, const char* dst_idx) {
+// dep: dependent pieces (zwz_deflate_dep_stream_file).  A slice's input then runs through a second device buffer that keeps the last
+// kDepDictBytes of the slice before in front of it, so that the slice's first piece finds its dictionary where every other piece does;
+// with an index, the slice's windows come back behind its entries (the host knows how many: index_dep_step) and are appended to the
+// file's, which go behind all entries when the index is sealed.
+struct DevBytes { uint8_t* p = nullptr; ~DevBytes() { if (p) (void)hipFree(p); } };
+
+int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char* dst, const char* dst_idx, bool dep = false) {
     if (!c || !src || !dst || wrap_ < ZWZ_WRAP_RAW || wrap_ > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    if (dep) if (int rc = dep_strategy_ok(c, dst_idx ? "zwz_deflate_dep_stream_file_index" : "zwz_deflate_dep_stream_file")) return rc;
     const uint32_t wrap = (uint32_t)wrap_;
     HIPCHK(hipSetDevice(c->device));
     FileJob job;
     if (int rc = job.open(src, dst)) return rc;
-    const uint32_t pieces = c->max_batch < kFileSlicePieces ? c->max_batch : kFileSlicePieces;
-    const size_t S = (size_t)pieces * kPieceBytes, O = round_up((size_t)pieces * piece_bound(kPieceBytes), 16);
-    const uint64_t ent_cap = dst_idx ? index_flush_bytes(pieces) : 0u;      // (the header's 64 bytes are the results' place)
+    const uint32_t file_pieces = dep ? 2u * kFileSlicePieces : kFileSlicePieces;       // (the same 16.7 MB of input)
+    const uint32_t pieces = c->max_batch < file_pieces ? c->max_batch : file_pieces;
+    const size_t S = (size_t)pieces * (dep ? kDepPieceBytes : kPieceBytes);
+    const size_t O = round_up((size_t)pieces * (dep ? dep_piece_bound(kDepPieceBytes, kDepDictBytes) : piece_bound(kPieceBytes)), 16);
+    const uint64_t win_base = index_flush_bytes(pieces);                                // dep: where a slice's windows come back
+    const uint64_t ent_cap = !dst_idx ? 0u : dep ? win_base + (uint64_t)pieces * kDepDictBytes : index_flush_bytes(pieces);      // (the header's 64 bytes are the results' place)
     const size_t small = dst_idx ? (size_t)ent_cap : 64;
     if (int rc = job.alloc({S + 16, S + 16, O, O, small}, {S + 16, O, small})) return rc;
+    DevBytes work;                                  // dep: [the dictionary | the slice]
+    if (dep) HIPCHK(hipMalloc(reinterpret_cast<void**>(&work.p), kDepDictBytes + S + 16));
+    std::vector<uint8_t> wins;                      // dep: the index's windows as they grow
+    const uint64_t step = index_dep_step(c->index_span_bytes);
+    uint64_t slice_cnt = 0;                         // dep: the entries the slice in flight must report
     std::vector<uint8_t> ents(kIdxHeader);          // the index as it grows: the header's place, then the entries
     uint64_t pos = dstream_header_bytes(wrap);      // stream bytes in front of the next slice
     uint8_t frame[kGzipHeaderBytes + 2 + 8];
@@ -190,6 +275,14 @@ int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
             const uint32_t* d_chk = nullptr;
             const DstreamIndex X{job.dp(2), nullptr, c->index_span_bytes, total_in, pos};
             const uint64_t* d_cnt = nullptr;
+            if (dep) {
+                const uint64_t dict = kDepDictBytes, k0 = total_in / kDepPieceBytes, k1 = k0 + (n + kDepPieceBytes - 1) / kDepPieceBytes;
+                slice_cnt = (k1 + step - 1) / step - (k0 + step - 1) / step;          // pieces k0 .. k1 - 1 whose number is a multiple of step
+                HIPCHK(hipMemcpyAsync(work.p + dict, job.dp(0), n, hipMemcpyDeviceToDevice, c->stream));
+                if (int rc = dstream_launch(c, wrap, work.p, &dict, &len, 1, job.dp(1), &zero, &cap, &d_res->out_len, &d_res->status, true, &d_chk,
+                                            dst_idx ? &X : nullptr, &zero, &ent_cap, &d_cnt, DepMode{true, total_in ? kDepDictBytes : 0u}, win_base)) return rc;
+                if (n == S) HIPCHK(hipMemcpyAsync(work.p, work.p + n, dict, hipMemcpyDeviceToDevice, c->stream));      // the next slice's dictionary (S >= 2 dict: no overlap)
+            } else
             if (int rc = dstream_launch(c, wrap, job.dp(0), &zero, &len, 1, job.dp(1), &zero, &cap, &d_res->out_len, &d_res->status, true, &d_chk,
                                         dst_idx ? &X : nullptr, &zero, &ent_cap, &d_cnt)) return rc;
             HIPCHK(hipMemcpyAsync(h_res, d_res, 12, hipMemcpyDeviceToHost, c->stream));
@@ -197,7 +290,9 @@ int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
             if (dst_idx) {
                 uint8_t* h = reinterpret_cast<uint8_t*>(h_res);
                 HIPCHK(hipMemcpyAsync(h + 16, d_cnt, 8, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipMemcpyAsync(h + kIdxHeader, job.dp(2) + kIdxHeader, (size_t)ent_cap - kIdxHeader, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(h + kIdxHeader, job.dp(2) + kIdxHeader, (size_t)index_flush_bytes(pieces) - kIdxHeader, hipMemcpyDeviceToHost, c->stream));
+                const uint64_t nwin = dep ? slice_cnt - (total_in ? 0u : 1u) : 0u;       // (the file's first entry has no window)
+                if (nwin) HIPCHK(hipMemcpyAsync(h + win_base, job.dp(2) + win_base, (size_t)(nwin * kDepDictBytes), hipMemcpyDeviceToHost, c->stream));
             }
             return (int)ZWZ_OK;
         },
@@ -209,8 +304,9 @@ int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
             if (dst_idx) {
                 const uint8_t* h = reinterpret_cast<const uint8_t*>(&r);
                 const uint64_t cnt = le64_of(h + 16);
-                if (cnt > pieces) { set_error("deflate stream: a slice of %u pieces reports %llu index entries", pieces, (unsigned long long)cnt); return (int)ZWZ_E_FORMAT; }
+                if (cnt > pieces || (dep && cnt != slice_cnt)) { set_error("deflate stream: a slice of %u pieces reports %llu index entries", pieces, (unsigned long long)cnt); return (int)ZWZ_E_FORMAT; }
                 ents.insert(ents.end(), h + kIdxHeader, h + kIdxHeader + cnt * kIdxEntry);
+                if (dep) wins.insert(wins.end(), h + win_base, h + win_base + (cnt - (total_in == n ? 1u : 0u)) * kDepDictBytes);
             }
             return (int)ZWZ_OK;
         });
@@ -223,8 +319,15 @@ int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
     if (!total_in) { ents.resize(kIdxHeader + kIdxEntry); index_flush_entry(ents.data() + kIdxHeader, 8u * hdr, 0); }
     const uint64_t count = (ents.size() - kIdxHeader) / kIdxEntry;
     if (count > 0xffffffffull) { set_error("deflate stream: more than 2^32 - 1 index entries"); return ZWZ_E_INVALID; }
+    if (dep) {
+        if (count != index_dep_count(total_in, c->index_span_bytes) || wins.size() != (count - 1u) * kDepDictBytes) { set_error("deflate stream: the index's entries and windows do not add up"); return ZWZ_E_FORMAT; }
+        ents.insert(ents.end(), wins.begin(), wins.end());
+        ents.resize((size_t)index_dep_bytes(count), 0);
+        index_seal(ents.data(), ents.size(), wrap, c->index_span_bytes, pos + tail, total_in, (uint32_t)count, index_flush_end_bit(pos), wrap == kWrapRaw ? 0u : check);
+    } else {
     ents.resize((size_t)index_flush_bytes(count));
     index_flush_seal(ents.data(), wrap, c->index_span_bytes, pos + tail, total_in, (uint32_t)count, index_flush_end_bit(pos), wrap == kWrapRaw ? 0u : check);
+    }
     const std::string ipart = std::string(dst_idx) + ".part";
     FILE* fi = fopen(ipart.c_str(), "wb");
     if (!fi) { set_error("cannot create %s", ipart.c_str()); return ZWZ_E_IO; }
@@ -242,4 +345,11 @@ int zwz_deflate_stream_file(zwz_ctx* c, int wrap, const char* src, const char* d
 int zwz_deflate_stream_file_index(zwz_ctx* c, int wrap, const char* src, const char* dst, const char* dst_idx) {
     if (!dst_idx) return ZWZ_E_INVALID;
     return deflate_stream_file_core(c, wrap, src, dst, dst_idx);
+}
+
+int zwz_deflate_dep_stream_file(zwz_ctx* c, int wrap, const char* src, const char* dst) { return deflate_stream_file_core(c, wrap, src, dst, nullptr, true); }
+
+int zwz_deflate_dep_stream_file_index(zwz_ctx* c, int wrap, const char* src, const char* dst, const char* dst_idx) {
+    if (!dst_idx) return ZWZ_E_INVALID;
+    return deflate_stream_file_core(c, wrap, src, dst, dst_idx, true);
 }

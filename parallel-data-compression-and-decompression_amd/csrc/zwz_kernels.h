@@ -131,6 +131,9 @@ struct DeflateArgs {
     uint32_t strategy;         // rle_core.h: kStrategyDefault (deflate_slow at `level`) | kStrategyHuffman | kStrategyRle -- under the last two no search
                                // kernel and no lz_parse runs (strategy_parse_kernel, zwz_rle.hip, in their place), match_mode and level choose nothing,
                                // and the zlib header is 78 01.  Anything else makes launch_deflate fail
+    const uint32_t* skip = nullptr;   // null, or per chunk (device memory): the bytes at the chunk's head that are a dictionary -- searched against, never
+                               // coded (dstream_core.h: dependent pieces; 0 or kDepDictBytes, a multiple of 128).  The parse enters there with nothing pending, symbols
+                               // and blocks count from there: the start-offset forms of lz_match_kernel, lz_parse_kernel, lz_lazy_kernel and blockify_kernel (lz_match_band_kernel has none: it searches the dictionary too).  Default strategy only
     ChunkInfo* info; BlockInfo* blocks; BlockOut* plans;
     BlockProbe* probes;        // = links (dead once lz_match has run): chunk c's kMaxBlocks probes open ITS link space
     // The chosen record of every match symbol, compact and in stream order (lz_parse -> blockify, encode): a chunk's

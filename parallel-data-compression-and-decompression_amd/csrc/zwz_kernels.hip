@@ -615,17 +615,24 @@ static __device__ __forceinline__ void lz_search_wave(const uint8_t* data, const
 // searched, and they go where the oldest tile's were (a tile-per-workgroup version re-read the whole
 // 147 KB window per tile and spent 58% of its wave-cycles waiting on it; rounds 1-3 slid a linear
 // window down after every tile).
-template <class Lv>      // the compression level (zwz_common.h): the walk's bound, the snapshot and the nice stop of lz_search_wave
+// Skip: empty, or one `const uint32_t*` -- per chunk the bytes at its head that are a dictionary (dstream_core.h: dependent pieces; 0 or a
+// multiple of 256): positions in front of it are candidates and never queries, so they get no record and no has128 bit.  A parameter
+// PACK, so that the form without it has the arguments, and is the code, it was.
+template <class Lv, class... Skip>      // the compression level (zwz_common.h): the walk's bound, the snapshot and the nice stop of lz_search_wave
 __global__ __launch_bounds__(kMatchThreads) void lz_match_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                  const uint32_t* __restrict__ in_len, const uint16_t* __restrict__ links,
                                                                  uint2* __restrict__ entries, uint64_t* __restrict__ has128,
                                                                  uint16_t* __restrict__ perms, const uint32_t* __restrict__ link_stat,
                                                                  uint32_t band /* 0: every chunk is this kernel's, 1: chain-heavy chunks are lz_match_band's, 2: all are */,
-                                                                 uint32_t* __restrict__ mtimes /* experiment builds: phase cycles */) {
+                                                                 uint32_t* __restrict__ mtimes /* experiment builds: phase cycles */, Skip... skips) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr bool kSkip = sizeof...(Skip) != 0;
+    static_assert(sizeof...(Skip) <= 1, "at most one array of start offsets");
     const uint32_t chunk = blockIdx.x, tid = threadIdx.x;
     const uint32_t L = in_len[chunk];
     if (L == 0 || band == 2u || (band == 1u && link_stat[chunk] == kDenseMark)) return;
+    uint32_t skip = 0;                               // workgroup-uniform
+    if constexpr (kSkip) { const uint32_t* const sk[] = {skips...}; skip = __builtin_amdgcn_readfirstlane(sk[0][chunk]); }
     uint8_t* sdata = smem;
     uint16_t* slink = reinterpret_cast<uint16_t*>(smem + kMatchDataBytes);
     uint32_t* s_has = reinterpret_cast<uint32_t*>(smem + kMatchDataBytes + kMatchLinkBytes);      // 2 KiB: has128 bits of a tile
@@ -707,7 +714,8 @@ __global__ __launch_bounds__(kMatchThreads) void lz_match_kernel(const uint8_t* 
 #pragma unroll
                 for (uint32_t j = 0; j < 4; j++) {
                     p[j] = ts + q0 + j * kMatchThreads;
-                    const bool ok = p[j] < te && p[j] + kMinMatch <= L;
+                    bool ok = p[j] < te && p[j] + kMinMatch <= L;
+                    if constexpr (kSkip) ok = ok && p[j] >= skip;                  // (a dictionary position: key 0, off the list)
                     const uint32_t l1 = slink[ok ? match_ring(p[j]) : 0u];
                     live[j] = (uint32_t)(ok && l1 != 0 && p[j] - l1 <= kMaxDist && !(p[j] >= kSlidePos && l1 <= kWSize));
                     cur[j] = live[j] ? l1 : (ok ? p[j] : 0u);          // (out of play: any readable position)
@@ -868,6 +876,7 @@ __global__ __launch_bounds__(kMatchThreads) void lz_match_kernel(const uint8_t* 
             for (uint32_t t4 = 0; t4 < 4u; t4++) {
                 const uint32_t qb = t4 * 4096u + wave * 256u;                              // wave-uniform; the waves interleave: later positions have more history
                 if (qb >= n_ok) break;
+                if constexpr (kSkip) if (ts + qb + 256u <= skip) continue;                 // the trip's 256 positions lie in the dictionary (skip is a multiple of 256)
                 if (nl + 256u > kListCap) drain(false);
                 const uint32_t q0 = qb + lane * 4u, p0 = ts + q0, wi = match_ring(p0);      // wi: ring index, a multiple of 4 (the ring's size is one of 16: the four positions do not straddle its end)
                 const uint2 lk2 = *reinterpret_cast<const uint2*>(slink + wi);
@@ -952,12 +961,16 @@ struct ParseWaveMem {
     uint8_t flag[64];
 };
 
-template <class Lv>      // the compression level: fresh_step's max_lazy and good_length
+// kSkip: the walk enters at skips[chunk], a multiple of 64, fresh -- the chunk's first bytes are a dictionary (dstream_core.h: dependent
+// pieces) -- and no symbol starts in front of it.  A template argument, so that the form without it is the code it was (its last
+// argument is unused).
+template <class Lv, bool kSkip = false>      // the compression level: fresh_step's max_lazy and good_length
 __global__ __launch_bounds__(kParseThreads) void lz_parse_kernel(const uint32_t* __restrict__ in_len, uint32_t n,
                                                                 const uint2* __restrict__ entries, const uint64_t* __restrict__ has128,
                                                                 uint64_t* __restrict__ sym, uint64_t* __restrict__ mst,
                                                                 ChunkInfo* __restrict__ info, uint16_t* __restrict__ links,
-                                                                const uint32_t* __restrict__ parsed_marks /* link_stat: kDenseMark = lz_lazy has parsed this chunk; or null */) {
+                                                                const uint32_t* __restrict__ parsed_marks /* link_stat: kDenseMark = lz_lazy has parsed this chunk; or null */,
+                                                                const uint32_t* __restrict__ skips /* kSkip */) {
     __shared__ ParseWaveMem s_mem[kParseThreads / 64];
     const uint32_t chunk = blockIdx.x * (kParseThreads / 64) + (threadIdx.x >> 6);
     if (chunk >= n) return;
@@ -971,6 +984,12 @@ __global__ __launch_bounds__(kParseThreads) void lz_parse_kernel(const uint32_t*
     const uint32_t L = in_len[chunk];
     const uint32_t nwords = (L + 63) >> 6;
 
+    uint32_t blk0 = 0;                               // the block the walk enters at, at its first position
+    if constexpr (kSkip) {
+        blk0 = __builtin_amdgcn_readfirstlane(skips[chunk] >> 6);
+        if (lane < 16) { m.ring_r[lane] = lane == 2u * (blk0 & 7u) ? 1u : 0u; m.ring_s[lane] = 0; m.ring_m[lane] = 0; m.ring_m32[lane] = 0; }
+        for (uint32_t w = lane; w < blk0 && w < nwords; w += 64u) { gsym[w] = 0; gmst[w] = 0; }
+    } else
     if (lane < 16) { m.ring_r[lane] = lane == 0 ? 1u : 0u; m.ring_s[lane] = 0; m.ring_m[lane] = 0; m.ring_m32[lane] = 0; }
     // records exist only where lz_match found something: gate every lane on its has128 bit
     uint64_t hw_pre = 0;                             // has128 word of the window in `pre`
@@ -997,10 +1016,11 @@ __global__ __launch_bounds__(kParseThreads) void lz_parse_kernel(const uint32_t*
     // the compiler's wait in front of the window write is vmcnt(0): it waits for the younger request as well.  The wait for the
     // records is 21 % of the kernel on text and 46 % on 7 KB chunks, ZWZ_PARSE_EXP; counted waits would need every block to issue
     // the same number of loads and stores.)
-    uint2 pre = fetch(0);
+    uint2 pre = fetch(kSkip ? blk0 : 0u);
+    if constexpr (kSkip) m.win[((blk0 << 6) + lane) & 127u] = pre; else
     m.win[lane] = pre;
     uint64_t hw_cur = hw_pre;                        // has128 word of the block being processed
-    pre = fetch(1);
+    pre = fetch(kSkip ? blk0 + 1u : 1u);
     uint32_t carry_open = 0, n_sym = 0, last_is_match = 0;
     uint32_t* chosen = chosen_of(links, chunk);      // the chosen record of every match, compact, in stream order
     uint32_t n_match = 0;                            // wave-uniform
@@ -1010,7 +1030,7 @@ __global__ __launch_bounds__(kParseThreads) void lz_parse_kernel(const uint32_t*
     uint64_t pstamp_ = __builtin_amdgcn_s_memtime();
     uint32_t pacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    for (uint32_t blk = 0; blk < nwords; blk++) {
+    for (uint32_t blk = kSkip ? blk0 : 0u; blk < nwords; blk++) {
         const uint32_t base = blk << 6, q = base + lane;
         ZWZ_PSTAMP(5);                                   // the tail of the block before: outputs, ring reset
         {   // run of literal-only blocks entered at a block start with nothing pending: settle up to 64
@@ -1154,12 +1174,14 @@ static __device__ __forceinline__ uint32_t select_bit(uint64_t w, uint32_t k) { 
 }
 
 // kStrategy (rle_core.h) chooses the flush_pos rule, nothing else: a template argument, so that the default form is the kernel it was.
-template <uint32_t kStrategy>
+// kSkip (the default strategy only): the first block starts at skips[chunk] -- the parse wrote no symbol in front of it -- and the histogram
+// pass starts there too.  A template argument, so that the forms without it are the code they were (their last argument is unused).
+template <uint32_t kStrategy, bool kSkip = false>
 __global__ __launch_bounds__(kBlockifyThreads) void blockify_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                    const uint32_t* __restrict__ in_len, const uint2* __restrict__ entries,
                                                                    const uint64_t* __restrict__ sym, const uint64_t* __restrict__ mst,
                                                                    const ChunkInfo* __restrict__ info,
-                                                                   BlockInfo* __restrict__ blocks, const uint16_t* __restrict__ links) {
+                                                                   BlockInfo* __restrict__ blocks, const uint16_t* __restrict__ links, const uint32_t* __restrict__ skips /* kSkip */) {
     __shared__ uint64_t s_sym[kMaskWords];
     __shared__ uint32_t s_rank[kMaskWords + 1];   // symbols before word w
     __shared__ uint16_t s_mrank[kMaskWords];      // matches before word w (< 21 846)
@@ -1208,6 +1230,7 @@ __global__ __launch_bounds__(kBlockifyThreads) void blockify_kernel(const uint8_
             if (lastprev >= r0 && lastprev < r1) s_flush[b - 1] = (wi << 6) + select_bit(w[k], lastprev - r0) + 1;
         }
     }
+    if constexpr (kSkip) { if (tid == 0) s_start[0] = skips[chunk]; } else
     if (tid == 0) s_start[0] = 0;
     __syncthreads();
 
@@ -1222,7 +1245,7 @@ __global__ __launch_bounds__(kBlockifyThreads) void blockify_kernel(const uint8_
     const uint32_t c3 = ci.n_blocks > 3 ? s_start[3] : 0xffffffffu, c4 = ci.n_blocks > 4 ? s_start[4] : 0xffffffffu;
     auto block_of = [&](uint32_t p) { return (uint32_t)(p >= c1) + (uint32_t)(p >= c2) + (uint32_t)(p >= c3) + (uint32_t)(p >= c4); };
     const uint32_t ngroups = (L + 15u) >> 4;
-    for (uint32_t g0 = tid; g0 < ngroups; g0 += 4 * kBlockifyThreads) {
+    for (uint32_t g0 = tid + (kSkip ? skips[chunk] >> 4 : 0u); g0 < ngroups; g0 += 4 * kBlockifyThreads) {
         uint4 bytes[4]; uint32_t lits[4], mats[4]; uint64_t mword[4];
 #pragma unroll
         for (uint32_t u = 0; u < 4; u++) {
@@ -2890,6 +2913,9 @@ hipError_t configure_kernels() {
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<4>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<5>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<6>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<4>, const uint32_t*>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<5>, const uint32_t*>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
+    ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lz_match_kernel<LzLevel<6>, const uint32_t*>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMatchLdsBytes));
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kEncodeThreads, kOutWords, 8, 0x9cu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEncodeLdsBytes));
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kEncodeThreads, kOutWords, 8, 0x5eu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEncodeLdsBytes));
     ZWZ_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(encode_kernel<kSmallEncThreads, kSmallEncOutWords, kSmallEncWgs, 0x9cu>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallEncLdsBytes));
@@ -2918,7 +2944,13 @@ static hipError_t launch_search_parse(const DeflateArgs& a, hipStream_t s, hipEv
         ZWZ_TRY(launch_place(a, s));
     }
     if (ev) ZWZ_TRY(hipEventRecord(ev[1], s));
-    switch (a.level) {
+    if (a.skip) switch (a.level) {                   // dependent pieces: no queries inside the chunk's dictionary
+#define ZWZ_MATCH_LAUNCH(N) case N: hipLaunchKernelGGL((lz_match_kernel<LzLevel<N>, const uint32_t*>), dim3(a.n), dim3(kMatchThreads), kMatchLdsBytes, s, a.in, a.in_off, a.in_len, \
+                                                  a.links, a.entries, a.has128, a.perm, a.link_stat, which == 1u ? 0u : force == 2u ? 2u : 1u, a.tickets + 40, a.skip); break;
+        ZWZ_MATCH_LAUNCH(4) ZWZ_MATCH_LAUNCH(5) ZWZ_MATCH_LAUNCH(6)
+#undef ZWZ_MATCH_LAUNCH
+    }
+    else switch (a.level) {
 #define ZWZ_MATCH_LAUNCH(N) case N: hipLaunchKernelGGL(lz_match_kernel<LzLevel<N>>, dim3(a.n), dim3(kMatchThreads), kMatchLdsBytes, s, a.in, a.in_off, a.in_len, \
                                                   a.links, a.entries, a.has128, a.perm, a.link_stat, which == 1u ? 0u : force == 2u ? 2u : 1u, a.tickets + 40); break;
         ZWZ_MATCH_LAUNCH(4) ZWZ_MATCH_LAUNCH(5) ZWZ_MATCH_LAUNCH(6)
@@ -2932,7 +2964,7 @@ static hipError_t launch_search_parse(const DeflateArgs& a, hipStream_t s, hipEv
         fprintf(stderr, "ZWZ_MATCH_TIMES n=%u stage0=%u stage=%u screen=%u refine=%u search=%u wait=%u flush_slide=%u\n", a.n, h[40], h[46], h[41], h[42], h[43], h[44], h[45]);
     }
 #endif
-    if (which != 1u && lazy) ZWZ_TRY(launch_lazy(a, s));
+    if (which != 1u && lazy) ZWZ_TRY(launch_lazy(a, s));          // (with a.skip: its own entry point, zwz_lazy.hip)
     if (which != 1u && !lazy) {
         ZWZ_TRY(launch_match_band(a, s));
         if ((exp_flags_band() & 16u) && getenv("ZWZ_BAND_TIMES")) {       // experiment builds (zwz_band.hip, ZWZ_BAND_EXP & 16): cycles >> 8 per phase, summed over the workgroups' first threads
@@ -2943,9 +2975,15 @@ static hipError_t launch_search_parse(const DeflateArgs& a, hipStream_t s, hipEv
         }
     }
     if (ev) ZWZ_TRY(hipEventRecord(ev[2], s));
-    switch (a.level) {
+    if (a.skip) switch (a.level) {                   // dependent pieces: the walk enters behind the chunk's dictionary
+#define ZWZ_PARSE_LAUNCH(N) case N: hipLaunchKernelGGL((lz_parse_kernel<LzLevel<N>, true>), dim3((a.n + kParseThreads / 64 - 1) / (kParseThreads / 64)), dim3(kParseThreads), 0, s, a.in_len, a.n, \
+                                                  a.entries, a.has128, a.sym, a.mst, a.info, a.links, (which != 1u && lazy) ? a.link_stat : (const uint32_t*)nullptr, a.skip); break;
+        ZWZ_PARSE_LAUNCH(4) ZWZ_PARSE_LAUNCH(5) ZWZ_PARSE_LAUNCH(6)
+#undef ZWZ_PARSE_LAUNCH
+    }
+    else switch (a.level) {
 #define ZWZ_PARSE_LAUNCH(N) case N: hipLaunchKernelGGL(lz_parse_kernel<LzLevel<N>>, dim3((a.n + kParseThreads / 64 - 1) / (kParseThreads / 64)), dim3(kParseThreads), 0, s, a.in_len, a.n, \
-                                                  a.entries, a.has128, a.sym, a.mst, a.info, a.links, (which != 1u && lazy) ? a.link_stat : (const uint32_t*)nullptr); break;
+                                                  a.entries, a.has128, a.sym, a.mst, a.info, a.links, (which != 1u && lazy) ? a.link_stat : (const uint32_t*)nullptr, (const uint32_t*)nullptr); break;
         ZWZ_PARSE_LAUNCH(4) ZWZ_PARSE_LAUNCH(5) ZWZ_PARSE_LAUNCH(6)
 #undef ZWZ_PARSE_LAUNCH
     }
@@ -2967,6 +3005,7 @@ hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /*
     ZWZ_TRY(hipMemsetAsync(a.tickets, 0, kTicketBytes, s));
     if (ev) ZWZ_TRY(hipEventRecord(ev[0], s));
     const bool searched = a.strategy == kStrategyDefault;
+    if (a.skip && !searched) return hipErrorInvalidValue;               // a start offset exists for deflate_slow's parse only
     if (searched) ZWZ_TRY(launch_search_parse(a, s, ev));
     else {
         // Z_HUFFMAN_ONLY / Z_RLE (rle_core.h): no chain, no search, no lazy parse -- one kernel writes what lz_parse would.  The profile's
@@ -2977,8 +3016,9 @@ hipError_t launch_deflate(const DeflateArgs& a, hipStream_t s, hipEvent_t* ev /*
     }
     if (ev) ZWZ_TRY(hipEventRecord(ev[3], s));
 #define ZWZ_BLOCKIFY_LAUNCH(S) hipLaunchKernelGGL(blockify_kernel<S>, dim3(a.n), dim3(kBlockifyThreads), 0, s, a.in, a.in_off, a.in_len, a.entries, a.sym, a.mst, \
-                                                 a.info, a.blocks, a.links)
-    if (searched) ZWZ_BLOCKIFY_LAUNCH(kStrategyDefault); else if (a.strategy == kStrategyHuffman) ZWZ_BLOCKIFY_LAUNCH(kStrategyHuffman); else ZWZ_BLOCKIFY_LAUNCH(kStrategyRle);
+                                                 a.info, a.blocks, a.links, (const uint32_t*)nullptr)
+    if (a.skip) hipLaunchKernelGGL((blockify_kernel<kStrategyDefault, true>), dim3(a.n), dim3(kBlockifyThreads), 0, s, a.in, a.in_off, a.in_len, a.entries, a.sym, a.mst, a.info, a.blocks, a.links, a.skip);
+    else if (searched) ZWZ_BLOCKIFY_LAUNCH(kStrategyDefault); else if (a.strategy == kStrategyHuffman) ZWZ_BLOCKIFY_LAUNCH(kStrategyHuffman); else ZWZ_BLOCKIFY_LAUNCH(kStrategyRle);
 #undef ZWZ_BLOCKIFY_LAUNCH
     if (ev) ZWZ_TRY(hipEventRecord(ev[4], s));
     ZWZ_TRY(launch_plan(a, s));

@@ -64,13 +64,18 @@ struct __attribute__((packed, aligned(2))) LazyVec { uint32_t x, y, z, w; };    
 // (u = sorted index, bs = how many) and the first eight on their way, 3 those are in, 4 it has no candidates.
 struct LazySlot { uint32_t pos, stage, u, bs, first0; LazyVec vec; };
 
-template <class Lv>      // the compression level (zwz_common.h): longest_match's and deflate_slow's five numbers
+// kSkip: the chunk's first skips[chunk] bytes, a multiple of kLazySeg, are a dictionary (dstream_core.h: dependent pieces): the lanes of
+// those segments do nothing, the chain of true lanes starts at the lane that owns position skip, fresh, and no symbol starts in front of
+// it.  The array is a parameter PACK, empty or one `const uint32_t*`: the form without it has the arguments, and is the code, it was.
+template <class Lv, class... Skip>      // the compression level (zwz_common.h): longest_match's and deflate_slow's five numbers
 __global__ __launch_bounds__(kLazyThreads, 2) void lz_lazy_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                                   const uint32_t* __restrict__ in_len, const uint32_t* __restrict__ list,
                                                                   uint32_t* __restrict__ tickets, const uint32_t* __restrict__ sorted,
                                                                   uint32_t* __restrict__ scratch /* the chunks' entries space */,
                                                                   uint64_t* __restrict__ sym, uint64_t* __restrict__ mst,
-                                                                  ChunkInfo* __restrict__ info, uint16_t* __restrict__ links) {
+                                                                  ChunkInfo* __restrict__ info, uint16_t* __restrict__ links, Skip... skips) {
+    constexpr bool kSkip = sizeof...(Skip) != 0;
+    static_assert(sizeof...(Skip) <= 1, "at most one array of start offsets");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t* sdata = smem;
     uint32_t* sF = reinterpret_cast<uint32_t*>(smem + kLazyDataBytes);
@@ -90,6 +95,8 @@ __global__ __launch_bounds__(kLazyThreads, 2) void lz_lazy_kernel(const uint8_t*
         if (t >= n_list) break;
         const uint32_t chunk = list[t];
         const uint32_t L = in_len[chunk];
+        uint32_t skip = 0;
+        if constexpr (kSkip) { const uint32_t* const sk[] = {skips...}; skip = sk[0][chunk]; }
         const uint16_t* dest = reinterpret_cast<const uint16_t*>(sorted + (size_t)chunk * kSortedStride);
         const uint16_t* spos = dest + 65536;
         uint32_t* scr = scratch + (size_t)chunk * kLazyScratchWords;
@@ -120,6 +127,7 @@ __global__ __launch_bounds__(kLazyThreads, 2) void lz_lazy_kernel(const uint8_t*
         const uint32_t own_end = p + kLazySeg;
         uint32_t b = kMinMatch - 1u, bpos = 0, q0 = 0, term = L;
         uint32_t st = p < L ? kLzPick : kLzDone;
+        if constexpr (kSkip) if (p < skip) st = kLzDone;
         bool have = false;                                        // a search has ended: its result waits for deflate_slow's decision
         uint32_t ui = 0, nleft = 0, best = 0, best_pos = 0, f_off = 0, f_mask = 0, scan_w = 0, kfirst = 0, max_len = 0, nice = 0;
         LazyVec cur = {0, 0, 0, 0}, nxt = {0, 0, 0, 0};
@@ -274,10 +282,13 @@ __global__ __launch_bounds__(kLazyThreads, 2) void lz_lazy_kernel(const uint8_t*
         uint32_t* s_merge = reinterpret_cast<uint32_t*>(smem + kLazyOffMerge);
         uint32_t* s_cnt = reinterpret_cast<uint32_t*>(smem + kLazyOffCnt);
         uint32_t* s_wave = reinterpret_cast<uint32_t*>(smem + kLazyOffWave);
-        s_term[tid] = term; s_merge[tid] = tid == 0u ? 0u : 0xffffffffu;
+        s_term[tid] = term;
+        if constexpr (kSkip) s_merge[tid] = tid == skip / kLazySeg ? skip : 0xffffffffu; else
+        s_merge[tid] = tid == 0u ? 0u : 0xffffffffu;
         for (uint32_t i = tid; i < 2048u; i += kLazyThreads) {
             const uint32_t lo = i << 5;
             s_sym[i] = lo + 32u <= L ? 0xffffffffu : lo < L ? (1u << (L - lo)) - 1u : 0u;
+            if constexpr (kSkip) if (lo < skip) s_sym[i] = 0u;
             s_mst[i] = 0u;
         }
         __threadfence();                                       // the steps and G marks of phase 1 are read by other lanes below
@@ -380,13 +391,26 @@ hipError_t configure_lazy_kernels() {
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<5>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<6>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<6>>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<4>, const uint32_t*>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<5>, const uint32_t*>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(lz_lazy_kernel<LzLevel<6>, const uint32_t*>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLazyLdsBytes);
 }
 
 hipError_t launch_lazy(const DeflateArgs& a, hipStream_t s) {
     const uint32_t cus = a.cu_count ? a.cu_count : 256u;
     const uint32_t G = a.n < 2u * cus ? a.n : 2u * cus;
-    switch (a.level) {
+    if (a.skip) switch (a.level) {                   // dependent pieces: the parse enters behind the chunk's dictionary
+#define ZWZ_LAZY_LAUNCH(N) case N: hipLaunchKernelGGL((lz_lazy_kernel<LzLevel<N>, const uint32_t*>), dim3(G), dim3(kLazyThreads), kLazyLdsBytes, s, a.in, a.in_off, a.in_len, a.dense_list, a.tickets, \
+                                                 a.sorted, reinterpret_cast<uint32_t*>(a.entries), a.sym, a.mst, a.info, a.links, a.skip); break;
+        ZWZ_LAZY_LAUNCH(4) ZWZ_LAZY_LAUNCH(5) ZWZ_LAZY_LAUNCH(6)
+#undef ZWZ_LAZY_LAUNCH
+        default: return hipErrorInvalidValue;
+    }
+    else switch (a.level) {
 #define ZWZ_LAZY_LAUNCH(N) case N: hipLaunchKernelGGL(lz_lazy_kernel<LzLevel<N>>, dim3(G), dim3(kLazyThreads), kLazyLdsBytes, s, a.in, a.in_off, a.in_len, a.dense_list, a.tickets, \
                                                  a.sorted, reinterpret_cast<uint32_t*>(a.entries), a.sym, a.mst, a.info, a.links); break;
         ZWZ_LAZY_LAUNCH(4) ZWZ_LAZY_LAUNCH(5) ZWZ_LAZY_LAUNCH(6)

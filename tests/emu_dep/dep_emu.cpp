@@ -1,0 +1,230 @@
+// Host build of the dependent-piece stream writer for tests/test_deflate_dep_cpu.py (g++ -shared; no HIP): zwz_deflate_dep_streams_dev and
+// zwz_deflate_dep_streams_index_dev with the kernels' glue replaced by loops.  A piece and its dictionary are one chunk of the codec
+// cores (lz_core.h's search over the whole chunk, lz_parse entered at `skip`, blocks and plan_block in chunk coordinates, as
+// ../emu/zwz_emu.cpp lays a chunk out); the splice points, the marker, the framing, the checksum joins, the bounds and the index
+// arithmetic are dstream_core.h's and index_core.h's, the code the device runs.  Test code: nothing here is part of the product.
+#include "../emu/zwz_emu.cpp"
+
+#include "../../parallel-data-compression-and-decompression_amd/csrc/dstream_core.h"
+#include "../../parallel-data-compression-and-decompression_amd/csrc/index_core.h"
+
+namespace {
+
+struct BlockRec { uint32_t type, hdr_bits, body_bits, stored, start, flush_pos, n_sym; };
+
+struct Piece {
+    std::vector<uint8_t> slot;          // 78 xx, the blocks from `skip` on (the last one final), padding; no checksum
+    std::vector<BlockRec> rec;
+    std::vector<uint32_t> tok;          // two words a token: 0, byte | length, distance
+};
+
+// The chunk [0, L) entered at skip: emu_chunk_stream's stages at level Lv with the start offset
+template <class Lv>
+bool dep_chunk(const uint8_t* in, uint32_t L, uint32_t skip, Piece& pc) {
+    std::vector<uint8_t> data(L + 16, 0);
+    if (L) memcpy(data.data(), in, L);
+    std::vector<uint16_t> link(L + 1, 0), head(32768, 0);
+    for (uint32_t p = 0; p + 3 <= L; p++) { const uint32_t h = hash3(data[p], data[p + 1], data[p + 2]); link[p] = head[h]; head[h] = (uint16_t)p; }
+    std::vector<uint32_t> e128(L + 1, 0), e32(L + 1, 0);
+    std::vector<uint64_t> has((L + 63) / 64 + 1, 0), sym(has.size(), 0), mst(has.size(), 0), m32(has.size(), 0);
+    for (uint32_t p = skip; p < L; p++) {                // (queries below skip are never consulted)
+        lz_search<Lv>(data.data(), link.data(), 0, p, L, e128[p], e32[p]);
+        if (e128[p]) has[p >> 6] |= 1ull << (p & 63);
+    }
+    auto ent = [&](uint32_t p, uint32_t sel) { return p < L ? (sel ? e32[p] : e128[p]) : 0u; };
+    const ParseResult pr = lz_parse<Lv>(ent, [&](uint32_t wi) { return has[wi]; }, L, sym.data(), mst.data(), m32.data(), skip);
+    {   // the block-parallel form from the same entry: the orbit of `skip` under fresh_step
+        std::vector<uint64_t> s2(has.size(), 0);
+        uint32_t n = 0;
+        for (uint32_t q = skip; q < L;) {
+            const FreshStep st = fresh_step<Lv>(ent, q, L);
+            if (st.is_lit) { s2[q >> 6] |= 1ull << (q & 63); n++; }
+            else { for (uint32_t x = q; x <= st.mpos; x++) { s2[x >> 6] |= 1ull << (x & 63); n++; } }
+            q = st.next;
+        }
+        if (n != pr.n_sym) return false;
+        for (size_t w = 0; w < (L + 63) / 64; w++) if (s2[w] != sym[w]) return false;
+    }
+    const uint32_t S = pr.n_sym, S_in = (S > 0 && !pr.last_is_match) ? S - 1 : S, nblocks = S_in / kSymsPerBlock + 1;
+    std::vector<uint32_t> blk_start(nblocks + 1, L), flush_pos(nblocks, L), nsym(nblocks, 0);
+    std::vector<std::vector<uint16_t>> lf(nblocks, std::vector<uint16_t>(kLCodes, 0)), df(nblocks, std::vector<uint16_t>(kDCodes, 0));
+    uint32_t idx = 0;
+    for (uint32_t p = skip; p < L; p++) {
+        if (!((sym[p >> 6] >> (p & 63)) & 1)) continue;
+        uint32_t b = idx / kSymsPerBlock;
+        if (b >= nblocks) b = nblocks - 1;
+        if (idx % kSymsPerBlock == 0 && idx / kSymsPerBlock < nblocks) blk_start[idx / kSymsPerBlock] = p;
+        if (idx % kSymsPerBlock == kSymsPerBlock - 1 && b + 1 < nblocks) flush_pos[b] = p + 1;
+        if ((mst[p >> 6] >> (p & 63)) & 1) {
+            const uint32_t e = ((m32[p >> 6] >> (p & 63)) & 1) ? e32[p] : e128[p];
+            lf[b][257 + length_code(entry_len(e) - 3)]++;
+            df[b][dist_code(entry_dist(e) - 1)]++;
+            pc.tok.push_back(entry_len(e)); pc.tok.push_back(entry_dist(e));
+        } else { lf[b][data[p]]++; pc.tok.push_back(0); pc.tok.push_back(data[p]); }
+        nsym[b]++;
+        idx++;
+    }
+    blk_start[0] = skip;
+    Out o;
+    o.put(0x78, 8); o.put(zlib_flg((uint32_t)Lv::level), 8);
+    TreeScratch ts; BlockCodes bc; uint32_t hdr[kHdrWords];
+    for (uint32_t b = 0; b < nblocks; b++) {
+        lf[b][256] = 1;
+        const uint32_t bs = blk_start[b], be = blk_start[b + 1], last = b + 1 == nblocks;
+        const bool stored_ok = !(flush_pos[b] >= kSlidePos && bs < kWSize);
+        const BlockPlan bp = plan_block(ts, lf[b].data(), df[b].data(), be - bs, stored_ok, last, bc, hdr);
+        if (split_vs_plan_block(lf[b].data(), df[b].data(), be - bs, stored_ok, last)) return false;
+        pc.rec.push_back({bp.type, bp.hdr_bits, bp.body_bits, be - bs, bs, flush_pos[b], nsym[b]});
+        for (uint32_t i = 0; i < bp.hdr_bits; i += 32) {
+            const uint32_t n = bp.hdr_bits - i < 32 ? bp.hdr_bits - i : 32;
+            o.put(hdr[i >> 5] & (n == 32 ? 0xffffffffu : ((1u << n) - 1)), n);
+        }
+        if (bp.type == kStored) {
+            o.align();
+            const uint32_t len = be - bs;
+            o.put(len & 0xffff, 16); o.put(~len & 0xffff, 16);
+            for (uint32_t i = bs; i < be; i++) o.put(data[i], 8);
+        } else {
+            const uint64_t before = (uint64_t)o.bytes.size() * 8 + o.nacc;
+            for (uint32_t p = bs; p < be; p++) {
+                if (!((sym[p >> 6] >> (p & 63)) & 1)) continue;
+                uint32_t e = 0;
+                if ((mst[p >> 6] >> (p & 63)) & 1) e = ((m32[p >> 6] >> (p & 63)) & 1) ? e32[p] : e128[p];
+                uint64_t v; uint32_t n;
+                symbol_bits(bc.lcode, bc.llen, bc.dcode, bc.dlen, e, data[p], v, n);
+                o.put(v, n);
+            }
+            o.put(bc.lcode[256], bc.llen[256]);
+            if ((uint64_t)o.bytes.size() * 8 + o.nacc - before != bp.body_bits) return false;
+        }
+        if (last) o.align();
+    }
+    pc.slot = o.bytes;
+    pc.slot.resize(pc.slot.size() + 8, 0);
+    return true;
+}
+
+bool dep_chunk_level(int level, const uint8_t* in, uint32_t L, uint32_t skip, Piece& pc) {
+    switch (level) {
+        case 4: return dep_chunk<LzLevel<4>>(in, L, skip, pc);
+        case 5: return dep_chunk<LzLevel<5>>(in, L, skip, pc);
+        case 6: return dep_chunk<LzLevel<6>>(in, L, skip, pc);
+    }
+    return false;
+}
+
+// dstream_combine_kernel's schedule with the piece length as an argument (../emu_dstream has it for kPieceBytes)
+template <class Sum>
+uint32_t join_slice(uint32_t acc, const std::vector<uint32_t>& val, const std::vector<uint32_t>& len, size_t lo, size_t hi, uint32_t piece) {
+    const uint32_t full = (uint32_t)(hi - lo) - 1u, p1 = Sum::pof(piece);
+    if (full) {
+        const uint32_t K = (full + kSumRow - 1u) / kSumRow, pad = K * kSumRow - full;
+        uint32_t row[kSumRow];
+        for (uint32_t l = 0; l < kSumRow; l++) {
+            row[l] = Sum::identity();
+            for (uint32_t j = 0; j < K; j++) { const uint32_t v = l * K + j; if (v >= pad) row[l] = Sum::join(row[l], val[lo + v - pad], p1); }
+        }
+        acc = Sum::join(acc, sum_fold_row_host<Sum>(row, sum_ptimes<Sum>(p1, K)), sum_ptimes<Sum>(p1, full));
+    }
+    return Sum::join(acc, val[hi - 1], Sum::pof(len[hi - 1]));
+}
+
+struct Stream { std::vector<uint8_t> bytes; std::vector<uint64_t> piece_at; uint32_t check = 0; };     // piece_at: the byte every piece starts at
+
+// 0: fine; else which of the emu's own checks failed
+uint32_t dep_stream(int level, uint32_t wrap, const uint8_t* in, uint64_t n, uint32_t slice, Stream& st) {
+    std::vector<uint8_t>& o = st.bytes;
+    for (uint32_t i = 0; i < dstream_header_bytes(wrap); i++) o.push_back((uint8_t)dstream_header_byte(wrap, i, zlib_flg((uint32_t)level)));
+    std::vector<uint32_t> val, len;
+    for (uint64_t at = 0, k = 0; at < n; at += kDepPieceBytes, k++) {
+        const uint32_t skip = dep_skip(k, 0u), L = (uint32_t)std::min<uint64_t>(kDepPieceBytes, n - at);
+        Piece pc;
+        if (!dep_chunk_level(level, in + at - skip, skip + L, skip, pc)) return 1;
+        const uint32_t nb = (uint32_t)pc.rec.size();
+        auto block = [&](uint32_t b, uint32_t& type, uint32_t& hdr_bits, uint32_t& body_bits, uint32_t& stored) {
+            type = pc.rec[b].type; hdr_bits = pc.rec[b].hdr_bits; body_bits = pc.rec[b].body_bits; stored = pc.rec[b].stored;
+        };
+        const SplicePoints sp_ = splice_points(nb, block);
+        SplicePoints sp = sp_;           // dstream_size_kernel: an empty last block is left out
+        if (nb > 1u && pc.rec[nb - 1].stored == 0 && pc.rec[nb - 1].type != kStored) sp = splice_points(nb - 1u, block);
+        const uint32_t src = spliced_source_bytes(sp.end_bit), slen = spliced_bytes(sp.end_bit);
+        if (2u + spliced_source_bytes(sp_.end_bit) + 8u != pc.slot.size() || sp.hdr_bit >= sp.end_bit) return 2;
+        if (slen > dep_piece_bound(L, skip)) return 3;
+        val.push_back(wrap == kWrapZlib ? adler32(in + at, L) : crc_lanes_host(in + at, L, 256));
+        len.push_back(L);
+        uint8_t* slot = pc.slot.data();  // dstream_pack_kernel's thread 0
+        slot[sp.hdr_bit >> 3] &= (uint8_t)~(1u << (sp.hdr_bit & 7u));
+        if (sp.end_bit & 7u) slot[sp.end_bit >> 3] &= (uint8_t)((1u << (sp.end_bit & 7u)) - 1u);
+        if (slen - 4u > src) slot[2u + src] = 0;
+        uint8_t* mk = slot + 2u + slen - 4u;
+        mk[0] = 0; mk[1] = 0; mk[2] = 0xff; mk[3] = 0xff;
+        st.piece_at.push_back(o.size());
+        o.insert(o.end(), slot + 2, slot + 2 + slen);
+    }
+    uint32_t check = dstream_check_init(wrap);
+    for (size_t lo = 0; lo < val.size(); lo += slice) {
+        const size_t hi = std::min(val.size(), lo + slice);
+        if (wrap == kWrapZlib) check = join_slice<AdlerSum>(check, val, len, lo, hi, kDepPieceBytes);
+        else if (wrap == kWrapGzip) check = join_slice<CrcSum>(check, val, len, lo, hi, kDepPieceBytes);
+    }
+    st.check = check;
+    for (uint32_t i = 0; i < 2u + dstream_trailer_bytes(wrap); i++) o.push_back((uint8_t)dstream_tail_byte(wrap, i, check, n));
+    return 0;
+}
+
+}  // namespace
+
+// The dependent stream of in[0, n) under `wrap` at `level`, its pieces' checksums joined `slice` at a time; returns the length it needs
+// (out receives at most cap bytes), or ~0 - i where the emu's own check i failed
+extern "C" uint64_t emu_dep_stream(int level, uint32_t wrap, const uint8_t* in, uint64_t n, uint32_t slice, uint8_t* out, uint64_t cap) {
+    Stream st;
+    if (const uint32_t bad = dep_stream(level, wrap, in, n, slice, st)) return ~0ull - bad;
+    memcpy(out, st.bytes.data(), (size_t)std::min<uint64_t>(cap, st.bytes.size()));
+    return st.bytes.size();
+}
+
+extern "C" uint64_t emu_dep_stream_bound(uint64_t n, uint32_t wrap) { return dep_stream_bound(n, wrap); }
+extern "C" uint32_t emu_dep_piece_bound(uint32_t L, uint32_t skip) { return dep_piece_bound(L, skip); }
+
+// One chunk entered at skip: its tokens (two words each) and block records (seven words each: type, header bits, body bits, bytes,
+// start, flush position, symbols).  Returns the token count, *n_blocks the blocks; 0xffffffff: a check of the emu's own failed
+extern "C" uint32_t emu_dep_piece(int level, const uint8_t* in, uint32_t L, uint32_t skip, uint32_t* tok, uint32_t tok_cap, uint32_t* rec, uint32_t* n_blocks) {
+    Piece pc;
+    if (!dep_chunk_level(level, in, L, skip, pc)) return 0xffffffffu;
+    const uint32_t n = (uint32_t)(pc.tok.size() / 2);
+    memcpy(tok, pc.tok.data(), 8 * (size_t)std::min(n, tok_cap));
+    *n_blocks = (uint32_t)pc.rec.size();
+    for (size_t b = 0; b < pc.rec.size() && b < kMaxBlocks; b++) memcpy(rec + 7 * b, &pc.rec[b], 28);
+    return n;
+}
+
+// The stream's index as the device composes it: the due flags by index_flush_due, ranks by a running count, entries and windows at
+// the places index_dep_count fixes beforehand, sealed by index_seal.  Returns the index's length (idx receives at most cap bytes);
+// ~0 - i: a check failed (4: the count is not index_dep_count's, 5: index_parse refuses the result)
+extern "C" uint64_t emu_dep_index(int level, uint32_t wrap, const uint8_t* in, uint64_t n, uint32_t span, uint8_t* idx, uint64_t cap) {
+    Stream st;
+    if (const uint32_t bad = dep_stream(level, wrap, in, n, 8192, st)) return ~0ull - bad;
+    const uint64_t count = index_dep_count(n, span), len = index_dep_bytes(count), win_off = kIdxHeader + count * kIdxEntry;
+    std::vector<uint8_t> x((size_t)len, 0);
+    uint64_t r = 0;
+    for (uint64_t k = 0; k < st.piece_at.size(); k++) {
+        const uint64_t off = k * kDepPieceBytes;
+        if (!(off == 0u || index_flush_due(off - kDepPieceBytes, off, n, span))) continue;
+        if (r >= count) return ~0ull - 4;
+        uint8_t* e = x.data() + kIdxHeader + r * kIdxEntry;
+        const uint32_t hist = dep_skip(k, 0u);
+        put_le64(e, 8u * st.piece_at[k]); put_le64(e + 8, off); put_le32(e + 16, hist); put_le32(e + 20, 0);
+        if (hist) memcpy(x.data() + win_off + (r - 1u) * kIdxDepDict, in + off - hist, hist);
+        r++;
+    }
+    if (!n) { index_flush_entry(x.data() + kIdxHeader, 8u * dstream_header_bytes(wrap), 0); r = 1; }
+    if (r != count) return ~0ull - 4;
+    const uint64_t total = st.bytes.size();
+    index_seal(x.data(), len, wrap, span, total, n, (uint32_t)count, index_flush_end_bit(total - dstream_trailer_bytes(wrap) - 2u), wrap == kWrapRaw ? 0u : st.check);
+    IndexView v;
+    if (index_parse(x.data(), len, &v) != kIdxOk) return ~0ull - 5;
+    memcpy(idx, x.data(), (size_t)std::min<uint64_t>(cap, len));
+    return len;
+}
+
+extern "C" uint64_t emu_dep_index_bound(uint64_t n, uint32_t span) { return index_span_ok(span) ? index_dep_bound(n, span) : 0u; }
