@@ -28,7 +28,7 @@ def load():
     lib.emu_dep_piece_bound.restype = u32
     lib.emu_dep_piece_bound.argtypes = [u32, u32]
     lib.emu_dep_piece.restype = u32
-    lib.emu_dep_piece.argtypes = [i32, ctypes.c_char_p, u32, u32, vp, u32, vp, vp]
+    lib.emu_dep_piece.argtypes = [i32, ctypes.c_char_p, u32, u32, vp, u32, vp, vp, u32]
     lib.emu_dep_index.restype = u64
     lib.emu_dep_index.argtypes = [i32, u32, ctypes.c_char_p, u64, u32, vp, u64]
     lib.emu_dep_index_bound.restype = u64
@@ -46,15 +46,16 @@ def stream(lib, data, wrap="gzip", level=6, slice_pieces=8192):
     return buf.raw[:need]
 
 
-def piece(lib, chunk, skip, level=6):
-    """One chunk entered at skip -> (tokens [(0, byte) | (length, distance)], block records [dict])"""
+def piece(lib, chunk, skip, level=6, behind=b""):
+    """One chunk entered at skip -> (tokens [(0, byte) | (length, distance)], block records [dict]).  `behind` stands in memory
+    directly behind the chunk, as a stream's next piece does, and is no part of it."""
     cap = len(chunk) - skip + 1
     tok = np.zeros((cap, 2), dtype=np.uint32)
     rec = np.zeros((5, 7), dtype=np.uint32)
     nb = ctypes.c_uint32(0)
-    n = lib.emu_dep_piece(level, chunk, len(chunk), skip, tok.ctypes.data, cap, rec.ctypes.data, ctypes.byref(nb))
+    n = lib.emu_dep_piece(level, chunk + behind, len(chunk), skip, tok.ctypes.data, cap, rec.ctypes.data, ctypes.byref(nb), len(behind))
     assert n != 0xffffffff and n <= cap
-    return [tuple(int(x) for x in t) for t in tok[:n]], [dict(zip(REC, (int(x) for x in r))) for r in rec[:nb.value]]
+    return list(zip(tok[:n, 0].tolist(), tok[:n, 1].tolist())), [dict(zip(REC, r)) for r in rec[:nb.value].tolist()]
 
 
 def index(lib, data, wrap="gzip", level=6, span=1 << 20):

@@ -18,11 +18,12 @@ struct Piece {
     std::vector<uint32_t> tok;          // two words a token: 0, byte | length, distance
 };
 
-// The chunk [0, L) entered at skip: emu_chunk_stream's stages at level Lv with the start offset
+// The chunk [0, L) entered at skip: emu_chunk_stream's stages at level Lv with the start offset.  The search reads up to 16 bytes
+// behind the chunk and may use none of them: `behind` <= 16 of them are the caller's (a stream's next piece), the rest zeros
 template <class Lv>
-bool dep_chunk(const uint8_t* in, uint32_t L, uint32_t skip, Piece& pc) {
+bool dep_chunk(const uint8_t* in, uint32_t L, uint32_t skip, Piece& pc, uint32_t behind = 0) {
     std::vector<uint8_t> data(L + 16, 0);
-    if (L) memcpy(data.data(), in, L);
+    if (L) memcpy(data.data(), in, L + std::min(behind, 16u));
     std::vector<uint16_t> link(L + 1, 0), head(32768, 0);
     for (uint32_t p = 0; p + 3 <= L; p++) { const uint32_t h = hash3(data[p], data[p + 1], data[p + 2]); link[p] = head[h]; head[h] = (uint16_t)p; }
     std::vector<uint32_t> e128(L + 1, 0), e32(L + 1, 0);
@@ -104,11 +105,11 @@ bool dep_chunk(const uint8_t* in, uint32_t L, uint32_t skip, Piece& pc) {
     return true;
 }
 
-bool dep_chunk_level(int level, const uint8_t* in, uint32_t L, uint32_t skip, Piece& pc) {
+bool dep_chunk_level(int level, const uint8_t* in, uint32_t L, uint32_t skip, Piece& pc, uint32_t behind = 0) {
     switch (level) {
-        case 4: return dep_chunk<LzLevel<4>>(in, L, skip, pc);
-        case 5: return dep_chunk<LzLevel<5>>(in, L, skip, pc);
-        case 6: return dep_chunk<LzLevel<6>>(in, L, skip, pc);
+        case 4: return dep_chunk<LzLevel<4>>(in, L, skip, pc, behind);
+        case 5: return dep_chunk<LzLevel<5>>(in, L, skip, pc, behind);
+        case 6: return dep_chunk<LzLevel<6>>(in, L, skip, pc, behind);
     }
     return false;
 }
@@ -139,7 +140,7 @@ uint32_t dep_stream(int level, uint32_t wrap, const uint8_t* in, uint64_t n, uin
     for (uint64_t at = 0, k = 0; at < n; at += kDepPieceBytes, k++) {
         const uint32_t skip = dep_skip(k, 0u), L = (uint32_t)std::min<uint64_t>(kDepPieceBytes, n - at);
         Piece pc;
-        if (!dep_chunk_level(level, in + at - skip, skip + L, skip, pc)) return 1;
+        if (!dep_chunk_level(level, in + at - skip, skip + L, skip, pc, (uint32_t)std::min<uint64_t>(16u, n - at - L))) return 1;   // the next piece stands behind, as on the device
         const uint32_t nb = (uint32_t)pc.rec.size();
         auto block = [&](uint32_t b, uint32_t& type, uint32_t& hdr_bits, uint32_t& body_bits, uint32_t& stored) {
             type = pc.rec[b].type; hdr_bits = pc.rec[b].hdr_bits; body_bits = pc.rec[b].body_bits; stored = pc.rec[b].stored;
@@ -188,9 +189,10 @@ extern "C" uint32_t emu_dep_piece_bound(uint32_t L, uint32_t skip) { return dep_
 
 // One chunk entered at skip: its tokens (two words each) and block records (seven words each: type, header bits, body bits, bytes,
 // start, flush position, symbols).  Returns the token count, *n_blocks the blocks; 0xffffffff: a check of the emu's own failed
-extern "C" uint32_t emu_dep_piece(int level, const uint8_t* in, uint32_t L, uint32_t skip, uint32_t* tok, uint32_t tok_cap, uint32_t* rec, uint32_t* n_blocks) {
+extern "C" uint32_t emu_dep_piece(int level, const uint8_t* in, uint32_t L, uint32_t skip, uint32_t* tok, uint32_t tok_cap, uint32_t* rec, uint32_t* n_blocks,
+                                  uint32_t behind /* readable bytes behind in[L), at most 16 are looked at */) {
     Piece pc;
-    if (!dep_chunk_level(level, in, L, skip, pc)) return 0xffffffffu;
+    if (!dep_chunk_level(level, in, L, skip, pc, behind)) return 0xffffffffu;
     const uint32_t n = (uint32_t)(pc.tok.size() / 2);
     memcpy(tok, pc.tok.data(), 8 * (size_t)std::min(n, tok_cap));
     *n_blocks = (uint32_t)pc.rec.size();

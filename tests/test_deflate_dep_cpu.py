@@ -10,6 +10,7 @@ import corpus
 import deflate_dep_emu_binding as emu_binding
 import deflate_dep_ref as ref
 import deflate_stream_ref
+import dep_cases
 import flush_index_emu_binding
 import index_ref
 
@@ -87,19 +88,8 @@ def test_slid_window_hides_dictionary_bytes_from_the_last_positions(emu):
     # a full piece: at chunk positions >= 65 274 libz's window has slid and a chain entry at chunk position <= 32 768 reads as NIL
     rng = random.Random(2)
     q = K_SLIDE                                 # the first position behind the slide; K_WSIZE lies MAX_DIST in front of it
-
-    def bucket(c, p):
-        return ((c[p] << 10) ^ (c[p + 1] << 5) ^ c[p + 2]) & 0x7fff
-
     for at, hit in ((K_WSIZE, False), (K_WSIZE + 1, True)):
-        while True:
-            chunk = bytearray(rng.randbytes(D + P))
-            chunk[q:q + 4] = chunk[at:at + 4]   # four bytes: the three that still match one position on are too far for a match of three
-            chunk[q + 4] = chunk[at + 4] ^ 0x55
-            # `at` is the chain's first entry for q (at distance MAX_DIST only the first is looked at)
-            if all(bucket(chunk, p) != bucket(chunk, q) for p in range(at + 1, q)):
-                break
-        chunk = bytes(chunk)
+        chunk = dep_cases.slid_window_chunk(rng, at)      # `at` is the chain's first entry for q
         tok, rec = emu_binding.piece(emu, chunk, D)
         if hit:
             assert tok[-3] == (4, q - at) and tok[-2][0] == 0 and tok[-1][0] == 0, tok[-3:]
@@ -113,11 +103,9 @@ def test_slid_window_hides_dictionary_bytes_from_the_last_positions(emu):
 def test_full_piece_of_one_block_is_not_stored(emu):
     # a full piece behind a dictionary that is one block: it starts at 32 512 < 32 768 and is flushed at 65 280 >= 65 274
     rng = random.Random(3)
-    run = bytes(258)
     seen = 0
     for lit in (1, 2, 3, 8):
-        body = b"".join(rng.randbytes(lit) + run for _ in range(2 * P // (258 + lit) + 1))[:2 * P]
-        for data in (body, rng.randbytes(P + 4000) + body[P + 4000:], corpus.text_like(lit, 2 * P)):
+        for data in dep_cases.one_block_bodies(rng, lit):
             tok, rec = emu_binding.piece(emu, data[P - D:], D)
             assert len(rec) == 1 and len(tok) <= K_SYMS and rec[0]["start"] == D < K_WSIZE and rec[0]["flush_pos"] == D + P >= K_SLIDE
             assert rec[0]["type"] != emu_binding.STORED
@@ -129,7 +117,7 @@ def test_full_piece_of_one_block_is_not_stored(emu):
 
 def test_pieces_of_several_blocks_and_stored_pieces(emu):
     rng = random.Random(4)
-    data = rng.randbytes(2 * P + 10000)
+    data = dep_cases.stored_pieces_input(rng)
     # piece 1, full and incompressible: several blocks, all stored (the first is flushed before the window slides)
     tok, rec = emu_binding.piece(emu, data[P - D:2 * P], D)
     assert len(rec) >= 2 and rec[0]["n_sym"] == K_SYMS and sum(r["n_sym"] for r in rec) == len(tok)
