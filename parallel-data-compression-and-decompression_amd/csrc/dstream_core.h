@@ -99,6 +99,14 @@ static_assert(kDepDictBytes + kDepPieceBytes == kPieceBytes && kDepDictBytes >= 
 // The dictionary of piece k of a stream whose first piece has `lead` dictionary bytes in front of it (0 but in the file call's later slices)
 ZWZ_HD uint32_t dep_skip(uint64_t k, uint32_t lead) { return k ? kDepDictBytes : lead; }
 
+// A piece form: the input bytes of a piece and of the dictionary in front of it.  The kernels around the codec (zwz_dstream.hip) and
+// their host driver take one of these two and are otherwise the same code for both.
+struct PieceForm {
+    uint32_t piece, dict;
+    ZWZ_HD uint32_t skip(uint64_t k, uint32_t lead) const { return k ? dict : lead; }      // dep_skip; 0 for independent pieces, whose lead is 0
+};
+constexpr PieceForm kPiecesAlone{kPieceBytes, 0u}, kPiecesDep{kDepPieceBytes, kDepDictBytes};
+
 // Worst case of spliced_bytes for a dependent piece of L <= kDepPieceBytes input bytes behind `skip` dictionary bytes: piece_bound's
 // count, in chunk coordinates.  At most L / kSymsPerBlock + 1 blocks of at most 8n + 42 bits.  The block that may not be stored starts
 // before kWSize -- behind a dictionary that is the piece's FIRST block, at skip = 32 512, and no other: the next one starts 16 383
@@ -165,6 +173,22 @@ inline uint32_t sum_fold_row_host(uint32_t* v, uint32_t p1) {
         pd = Sum::pjoin(pd, pd);
     }
     return v[0];
+}
+// dstream_combine_kernel on the host: the checksums val[0, cnt) of one stream's pieces in one slice joined onto acc.  Of all but the last,
+// `piece` bytes each, K in a row per lane, the short share in front; the lanes folded; then the last piece by its own length.
+template <class Sum>
+inline uint32_t sum_join_slice_host(uint32_t acc, const uint32_t* val, const uint32_t* len, uint64_t cnt, uint32_t piece) {
+    const uint32_t full = (uint32_t)cnt - 1u, p1 = Sum::pof(piece);
+    if (full) {
+        const uint32_t K = (full + kSumRow - 1u) / kSumRow, pad = K * kSumRow - full;
+        uint32_t row[kSumRow];
+        for (uint32_t l = 0; l < kSumRow; l++) {
+            row[l] = Sum::identity();
+            for (uint32_t j = 0; j < K; j++) { const uint32_t v = l * K + j; if (v >= pad) row[l] = Sum::join(row[l], val[v - pad], p1); }
+        }
+        acc = Sum::join(acc, sum_fold_row_host<Sum>(row, sum_ptimes<Sum>(p1, K)), sum_ptimes<Sum>(p1, full));
+    }
+    return Sum::join(acc, val[cnt - 1], Sum::pof(len[cnt - 1]));
 }
 
 }  // namespace zwz

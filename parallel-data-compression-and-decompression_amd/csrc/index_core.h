@@ -240,15 +240,27 @@ ZWZ_HD uint32_t index_piece_bytes(uint32_t head, uint64_t total, uint64_t j) {
     return left < kIdxPieceBytes ? (uint32_t)left : kIdxPieceBytes;
 }
 
+// The header's fields (check: the stream's stored check value, 0 for raw; crc: the index CRC) and its sixteen little-endian words: the
+// one place the header is spelled out, for every writer on the host and on the device
+constexpr uint32_t kIdxMagicLo = 0x495a575au, kIdxMagicHi = 0x01005844u;      // "ZWZIDX\0\1"
+struct IndexHeader { uint32_t wrap, span; uint64_t stream_len, decoded_len; uint32_t count; uint64_t end_bit; uint32_t check, crc; };
+ZWZ_HD void index_header_words(uint32_t* h, const IndexHeader& f) {
+    h[0] = kIdxMagicLo; h[1] = kIdxMagicHi; h[2] = f.wrap; h[3] = f.span;
+    h[4] = (uint32_t)f.stream_len; h[5] = (uint32_t)(f.stream_len >> 32); h[6] = (uint32_t)f.decoded_len; h[7] = (uint32_t)(f.decoded_len >> 32);
+    h[8] = f.count; h[9] = 0; h[10] = (uint32_t)f.end_bit; h[11] = (uint32_t)(f.end_bit >> 32);
+    h[12] = f.check; h[13] = f.crc; h[14] = 0; h[15] = 0;
+}
+// The host's store of it, at any alignment
+inline void index_put_header(uint8_t* p, const IndexHeader& f) {
+    uint32_t h[kIdxHeader / 4];
+    index_header_words(h, f);
+    for (uint32_t i = 0; i < kIdxHeader / 4; i++) put_le32(p + 4u * i, h[i]);
+}
+
 // Header and index CRC of an index whose entries and windows are in place (n: its padded length)
 inline void index_seal(uint8_t* p, uint64_t n, uint32_t wrap, uint32_t span, uint64_t stream_len, uint64_t decoded_len, uint32_t count, uint64_t end_bit,
                        uint32_t check) {
-    const uint8_t magic[8] = {'Z', 'W', 'Z', 'I', 'D', 'X', 0, 1};
-    for (uint32_t i = 0; i < 8; i++) p[i] = magic[i];
-    put_le32(p + 8, wrap); put_le32(p + 12, span); put_le64(p + 16, stream_len); put_le64(p + 24, decoded_len);
-    put_le32(p + 32, count); put_le32(p + 36, 0); put_le64(p + 40, end_bit); put_le32(p + 48, check);
-    put_le32(p + 52, crc_raw_long(0xffffffffu, p + kIdxHeader, n - kIdxHeader) ^ 0xffffffffu);
-    put_le64(p + 56, 0);
+    index_put_header(p, IndexHeader{wrap, span, stream_len, decoded_len, count, end_bit, check, crc_raw_long(0xffffffffu, p + kIdxHeader, n - kIdxHeader) ^ 0xffffffffu});
 }
 
 // The marking form's rule at a block header (lane 0): a checkpoint when the output has moved at least `span` since the last one; the

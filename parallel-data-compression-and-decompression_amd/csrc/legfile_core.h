@@ -75,14 +75,11 @@ struct LegIndexParts {
     uint32_t pad() const { return (uint32_t)(padded() - kIdxHeader - entries.size() - win_bytes); }
     // The sealed header (index_seal's fields): the index CRC joined from the entries' and that of the windows and the zero padding
     void header(uint8_t* h, uint32_t wrap, uint32_t span, uint64_t stream_len, const LegState& s) const {
-        const uint8_t magic[8] = {'Z', 'W', 'Z', 'I', 'D', 'X', 0, 1}, zeros[16] = {};
+        const uint8_t zeros[16] = {};
         const uint32_t crc_e = crc_raw_long(0xffffffffu, entries.data(), entries.size()) ^ 0xffffffffu;
         const uint32_t crc_w = crc_raw_long(win_reg, zeros, pad()) ^ 0xffffffffu;
-        for (uint32_t i = 0; i < 8; i++) h[i] = magic[i];
-        put_le32(h + 8, wrap); put_le32(h + 12, span); put_le64(h + 16, stream_len); put_le64(h + 24, s.end_out);
-        put_le32(h + 32, count()); put_le32(h + 36, 0); put_le64(h + 40, s.mk_end); put_le32(h + 48, s.has_check ? s.expect : 0u);
-        put_le32(h + 52, CrcSum::join(crc_e, crc_w, CrcSum::pof(win_bytes + pad())));
-        put_le64(h + 56, 0);
+        index_put_header(h, IndexHeader{wrap, span, stream_len, s.end_out, count(), s.mk_end, s.has_check ? s.expect : 0u,
+                                        CrcSum::join(crc_e, crc_w, CrcSum::pof(win_bytes + pad()))});
     }
 };
 

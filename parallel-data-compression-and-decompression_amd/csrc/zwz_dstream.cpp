@@ -1,7 +1,9 @@
 // zwz_dstream.cpp -- zwz_deflate_streams_dev / zwz_deflate_stream_file of include/zwz.h: the host driver around the codec.  Per slice
 // of at most max_batch pieces: dstream_layout + crc32_blocks (gzip) + zwz_deflate_batch_dev + dstream_size + the scan +
 // dstream_combine + dstream_pack, all on the context's stream; what runs from slice to slice (the scan's base, every stream's first
-// scan value and checksum) stays in device memory, so the host never waits between slices.
+// scan value and checksum) stays in device memory, so the host never waits between slices.  The dependent calls
+// (zwz_deflate_dep_streams_dev, zwz_deflate_dep_stream_file) are the same driver with the other PieceForm of dstream_core.h: the piece's
+// own Adler-32 under zlib, the codec entered behind the dictionary, and windows with the index's entries are all that differs.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -20,7 +22,7 @@ namespace {
 
 constexpr uint32_t kFileSlicePieces = 256;          // pieces per slice of zwz_deflate_stream_file: 16.7 MB of input
 
-struct PiecesView { DstreamPieces P; uint64_t* base; uint32_t* err; uint64_t* rbase; DstreamDep Q; };     // rbase: the rank scan's base (index); Q: dependent pieces
+struct PiecesView { DstreamPieces P; uint64_t* base; uint32_t* err; uint64_t* rbase; };     // rbase: the rank scan's base (index)
 PiecesView pieces_layout(Carver& w, size_t m) {
     PiecesView v;
     v.P.slots = w.take<uint8_t>(m * ZWZ_DEV_STRIDE, 256);     // (wg_copy reads up to 3 bytes past a slot's bytes)
@@ -29,7 +31,7 @@ PiecesView pieces_layout(Carver& w, size_t m) {
     v.P.slen = w.take<uint32_t>(m); v.P.hbit = w.take<uint32_t>(m); v.P.ebit = w.take<uint32_t>(m);
     v.P.due = w.take<uint32_t>(m); v.P.rank = w.take<uint64_t>(m);
     v.base = w.take<uint64_t>(3); v.err = reinterpret_cast<uint32_t*>(v.base + 1); v.rbase = v.base + 2;
-    v.Q.skip = w.take<uint32_t>(m); v.Q.poff = w.take<uint64_t>(m); v.Q.plen = w.take<uint32_t>(m);
+    v.P.skip = w.take<uint32_t>(m); v.P.poff = w.take<uint64_t>(m); v.P.plen = w.take<uint32_t>(m);
     return v;
 }
 
@@ -51,47 +53,59 @@ int ensure_dstream(zwz_ctx* c, uint32_t pieces, uint32_t streams, bool crc) {
     return c->buf[kBufStreamsHost].reserve(c, streams, streams_host_bytes(streams));
 }
 
-// The device part, arguments checked by the caller.  partial: every stream's pieces alone, and its checksum left in *d_chk (the file
-// function's slices).  ix: the index as well, idx_off and idx_cap host arrays of n; sealed here unless partial, when *d_cnt is where
-// the stream's count of entries will stand.  Returns with everything queued on the context's stream.
-// dep: dependent pieces (dstream_core.h) -- pieces of kDepPieceBytes, each compressed behind the kDepDictBytes of input in front of it;
-// lead: the dictionary bytes that lie in front of in_off[i] for every stream's first piece (the file function's later slices), else 0.
-struct DepMode { bool on = false; uint32_t lead = 0; };
-int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
-                   const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status, bool partial, const uint32_t** d_chk,
-                   const DstreamIndex* ix = nullptr, const uint64_t* idx_off = nullptr, const uint64_t* idx_cap = nullptr, const uint64_t** d_cnt = nullptr,
-                   DepMode dep = DepMode{}, uint64_t win_base = 0) {
+// One call of the device part: n streams of d_in (host arrays in_off, in_len) into d_out (host arrays out_off, out_cap), lengths and
+// statuses into device memory.
+struct DstreamCall {
+    uint32_t wrap;
+    const uint8_t* d_in; const uint64_t *in_off, *in_len; uint32_t n;
+    uint8_t* d_out; const uint64_t *out_off, *out_cap; uint64_t* d_out_len; uint32_t* d_status;
+    // partial: every stream's pieces alone, and its checksum left in *d_chk (the file function's slices)
+    bool partial = false;
+    // ix: the index as well, idx_off and idx_cap host arrays of n; sealed by the call unless partial, when *d_cnt is where the stream's
+    // count of entries will stand
+    const DstreamIndex* ix = nullptr; const uint64_t *idx_off = nullptr, *idx_cap = nullptr;
+    // form: independent pieces, or dependent ones (dstream_core.h) -- each compressed behind the kDepDictBytes of input in front of it;
+    // lead: the dictionary bytes that lie in front of in_off[i] for every stream's first piece (the dependent file function's later
+    // slices), else 0; win_base: where a partial call's index windows go (zwz_dstream.h)
+    PieceForm form = kPiecesAlone; uint32_t lead = 0; uint64_t win_base = 0;
+    const uint32_t** d_chk = nullptr; const uint64_t** d_cnt = nullptr;
+};
+
+// The device part, arguments checked by the caller.  Returns with everything queued on the context's stream.
+int dstream_launch(zwz_ctx* c, const DstreamCall& k) {
+    const uint32_t n = k.n, wrap = k.wrap;
+    const PieceForm F = k.form;
     // pieces are counted in 64 bits: the only limit is that they, and the output they need, can be counted at all
-    const uint64_t piece = dep.on ? kDepPieceBytes : kPieceBytes;
+    const uint64_t piece = F.piece;
     std::vector<uint64_t> pfirst((size_t)n + 1);
     pfirst[0] = 0;
     for (uint32_t i = 0; i < n; i++) {
-        if (in_len[i] > ~0ull - piece || (in_len[i] + piece - 1) / piece > (~0ull >> 18) - pfirst[i]) {
-            set_error("%s: the streams up to stream %u have more than 2^46 pieces", dep.on ? "zwz_deflate_dep_streams_dev" : "zwz_deflate_streams_dev", i);
+        if (k.in_len[i] > ~0ull - piece || (k.in_len[i] + piece - 1) / piece > (~0ull >> 18) - pfirst[i]) {
+            set_error("%s: the streams up to stream %u have more than 2^46 pieces", F.dict ? "zwz_deflate_dep_streams_dev" : "zwz_deflate_streams_dev", i);
             return ZWZ_E_INVALID;
         }
-        pfirst[i + 1] = pfirst[i] + (in_len[i] + piece - 1) / piece;
+        pfirst[i + 1] = pfirst[i] + (k.in_len[i] + piece - 1) / piece;
     }
     const uint64_t G = pfirst[n];
     const uint32_t M = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(G, 1), c->max_batch);
-    if (int rc = ensure_dstream(c, M, n, wrap == kWrapGzip || (ix && !partial))) return rc;     // (the index CRC, whatever the wrapper)
+    if (int rc = ensure_dstream(c, M, n, wrap == kWrapGzip || (k.ix && !k.partial))) return rc;     // (the index CRC, whatever the wrapper)
     // the pinned arrays may still be the source of the previous call's copy
     HIPCHK(hipEventSynchronize(c->ds_copied));
     uint64_t* h = c->buf[kBufStreamsHost].as<uint64_t>();
-    memcpy(h, in_off, (size_t)n * 8); memcpy(h + n, in_len, (size_t)n * 8);
-    memcpy(h + 2 * (size_t)n, out_off, (size_t)n * 8); memcpy(h + 3 * (size_t)n, out_cap, (size_t)n * 8);
+    memcpy(h, k.in_off, (size_t)n * 8); memcpy(h + n, k.in_len, (size_t)n * 8);
+    memcpy(h + 2 * (size_t)n, k.out_off, (size_t)n * 8); memcpy(h + 3 * (size_t)n, k.out_cap, (size_t)n * 8);
     memcpy(h + 4 * (size_t)n, pfirst.data(), ((size_t)n + 1) * 8);
-    if (ix) { memcpy(h + 5 * (size_t)n + 1, idx_off, (size_t)n * 8); memcpy(h + 6 * (size_t)n + 1, idx_cap, (size_t)n * 8); }
+    if (k.ix) { memcpy(h + 5 * (size_t)n + 1, k.idx_off, (size_t)n * 8); memcpy(h + 6 * (size_t)n + 1, k.idx_cap, (size_t)n * 8); }
     uint64_t* d = c->buf[kBufStreamsDev].as<uint64_t>();
-    HIPCHK(hipMemcpyAsync(d, h, streams_host_bytes(n, ix != nullptr), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d, h, streams_host_bytes(n, k.ix != nullptr), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ds_copied, c->stream));
     DstreamStreams S;
     S.in_off = d; S.in_len = d + n; S.out_off = d + 2 * (size_t)n; S.out_cap = d + 3 * (size_t)n; S.pfirst = d + 4 * (size_t)n;
     S.idx_off = d + 5 * (size_t)n + 1; S.idx_cap = d + 6 * (size_t)n + 1;
     S.xs = d + 7 * (size_t)n + 1; S.rs = S.xs + n; S.cnt = S.rs + n; S.chk = reinterpret_cast<uint32_t*>(S.cnt + n); S.n = n;
-    if (d_chk) *d_chk = S.chk;
-    if (d_cnt) *d_cnt = S.cnt;
-    const DstreamOut O{d_out, d_out_len, d_status, wrap, partial ? 1u : 0u, zlib_flg_of(c->level, c->strategy), gzip_xfl_of(c->strategy)};
+    if (k.d_chk) *k.d_chk = S.chk;
+    if (k.d_cnt) *k.d_cnt = S.cnt;
+    const DstreamOut O{k.d_out, k.d_out_len, k.d_status, wrap, k.partial ? 1u : 0u, zlib_flg_of(c->level, c->strategy), gzip_xfl_of(c->strategy)};
     const PiecesView v = pieces_view(c);
     const CrcTables* tab = c->buf[kBufCrcTables].as<const CrcTables>();
     HIPCHK(hipMemsetAsync(v.base, 0, 24, c->stream));
@@ -102,36 +116,27 @@ int dstream_launch(zwz_ctx* c, uint32_t wrap, const uint8_t* d_in, const uint64_
         while (pfirst[s0 + 1] <= g0) s0++;
         uint32_t s1 = s0;                             // the stream of its last
         while (pfirst[s1 + 1] < g0 + m) s1++;
-        if (dep.on) {
-            // the chunk of a piece is [dictionary | piece], read where it lies in the caller's input; the checksum is the piece's alone
-            HIPCHK(launch_dstream_dep_layout(S, v.P, v.Q, g0, m, dep.lead, c->stream));
-            if (wrap == kWrapGzip) HIPCHK(launch_crc32_blocks(tab, d_in, v.Q.poff, v.Q.plen, m, v.P.crc, c->cu_count, c->stream));
-            else if (wrap == kWrapZlib) HIPCHK(launch_dstream_dep_adler(d_in, v.P, v.Q, m, c->cu_count, c->stream));
-            if (int rc = deflate_batch_dev_skip(c, d_in, v.P.off, v.P.len, v.Q.skip, m, v.P.slots, ZWZ_DEV_STRIDE, v.P.olen)) return rc;
-        } else {
-        HIPCHK(launch_dstream_layout(S, v.P, g0, m, c->stream));
-        if (wrap == kWrapGzip) HIPCHK(launch_crc32_blocks(tab, d_in, v.P.off, v.P.len, m, v.P.crc, c->cu_count, c->stream));
-        if (int rc = zwz_deflate_batch_dev(c, d_in, v.P.off, v.P.len, m, v.P.slots, ZWZ_DEV_STRIDE, v.P.olen)) return rc;
-        }
+        // the chunk of a piece is [dictionary | piece], read where it lies in the caller's input; the checksum is the piece's alone
+        HIPCHK(launch_dstream_layout(S, v.P, F, k.lead, g0, m, c->stream));
+        if (wrap == kWrapGzip) HIPCHK(launch_crc32_blocks(tab, k.d_in, v.P.poff, v.P.plen, m, v.P.crc, c->cu_count, c->stream));
+        else if (wrap == kWrapZlib && F.dict) HIPCHK(launch_dstream_adler(k.d_in, v.P, m, c->cu_count, c->stream));
+        // (without a dictionary the codec is entered with no skip array at all, not one of zeros: its kernels are the batch call's)
+        if (int rc = F.dict ? deflate_batch_dev_skip(c, k.d_in, v.P.off, v.P.len, v.P.skip, m, v.P.slots, ZWZ_DEV_STRIDE, v.P.olen)
+                            : zwz_deflate_batch_dev(c, k.d_in, v.P.off, v.P.len, m, v.P.slots, ZWZ_DEV_STRIDE, v.P.olen)) return rc;
         DeflateArgs a;                                // the slice's block records are still in the codec's workspace
         carve_workspace(c, a);
         HIPCHK(launch_dstream_size(a.info, a.blocks, a.plans, v.P, m, v.err, c->stream));
         HIPCHK(launch_bgzf_scan(v.P.slen, m, 0, ~0u, v.P.x, v.base, v.err + 1, c->stream));
-        if (dep.on) HIPCHK(launch_dstream_dep_combine(S, v.P, v.Q, g0, m, s0, s1 - s0 + 1, wrap, c->stream));
-        else HIPCHK(launch_dstream_combine(S, v.P, g0, m, s0, s1 - s0 + 1, wrap, c->stream));
+        HIPCHK(launch_dstream_combine(S, v.P, F, g0, m, s0, s1 - s0 + 1, wrap, c->stream));
         HIPCHK(launch_dstream_pack(S, v.P, g0, m, O, v.err, c->stream));
-        if (ix && dep.on) {
-            HIPCHK(launch_dstream_dep_due(S, v.P, g0, m, *ix, c->stream));
+        if (k.ix) {
+            HIPCHK(launch_dstream_due(S, v.P, F, g0, m, *k.ix, c->stream));
             HIPCHK(launch_bgzf_scan(v.P.due, m, 0, ~0u, v.P.rank, v.rbase, v.err + 1, c->stream));
-            HIPCHK(launch_dstream_dep_index(d_in, S, v.P, v.Q, g0, m, O, *ix, win_base, c->stream));
-        } else if (ix) {
-            HIPCHK(launch_dstream_due(S, v.P, g0, m, *ix, c->stream));
-            HIPCHK(launch_bgzf_scan(v.P.due, m, 0, ~0u, v.P.rank, v.rbase, v.err + 1, c->stream));
-            HIPCHK(launch_dstream_index(S, v.P, g0, m, O, *ix, c->stream));
+            HIPCHK(launch_dstream_index(k.d_in, S, v.P, F, g0, m, O, *k.ix, k.win_base, c->stream));
         }
         s0 = s1;
     }
-    if (ix && !partial) HIPCHK(dep.on ? launch_dstream_dep_index_seal(tab, S, O, *ix, c->cu_count, c->stream) : launch_dstream_index_seal(tab, S, O, *ix, c->cu_count, c->stream));
+    if (k.ix && !k.partial) HIPCHK(launch_dstream_index_seal(tab, S, F, O, *k.ix, c->cu_count, c->stream));
     return ZWZ_OK;
 }
 
@@ -143,20 +148,33 @@ int dep_strategy_ok(zwz_ctx* c, const char* who) {
     return ZWZ_E_INVALID;
 }
 
+// The four _dev entry points: the checks, in `who`'s name, and the launch.  span: null without an index, else the caller's (0: the
+// context's), with d_idx and d_idx_len.
+int dstream_dev(zwz_ctx* c, const char* who, int wrap, DstreamCall k, const uint32_t* span_ = nullptr, uint8_t* d_idx = nullptr, uint64_t* d_idx_len = nullptr) {
+    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    const uint32_t span = span_ ? (*span_ ? *span_ : c->index_span_bytes) : kIdxSpanDefault;
+    if (!index_span_ok(span)) return ZWZ_E_INVALID;
+    if (k.n && (!k.d_in || !k.in_off || !k.in_len || !k.d_out || !k.out_off || !k.out_cap || !k.d_out_len || !k.d_status)) return ZWZ_E_INVALID;
+    if (k.n && span_ && (!d_idx || !k.idx_off || !k.idx_cap || !d_idx_len)) return ZWZ_E_INVALID;
+    if (((uintptr_t)k.d_in & 15u) || ((uintptr_t)k.d_out & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
+    for (uint32_t i = 0; i < k.n; i++)
+        if ((k.in_off[i] & 15u) || (k.out_off[i] & 15u) || (span_ && (k.idx_off[i] & 15u))) { set_error("%s: stream %u: offsets must be multiples of 16", who, i); return ZWZ_E_INVALID; }
+    if (k.form.dict) if (int rc = dep_strategy_ok(c, who)) return rc;
+    if (k.n == 0) return ZWZ_OK;
+    HIPCHK(hipSetDevice(c->device));
+    k.wrap = (uint32_t)wrap;
+    const DstreamIndex X{d_idx, d_idx_len, span, 0, 0};
+    if (span_) k.ix = &X;
+    return dstream_launch(c, k);
+}
+
 }  // namespace
 
 uint64_t zwz_deflate_stream_bound(uint64_t n, int wrap) { return dstream_bound(n, (uint32_t)wrap); }
 
 int zwz_deflate_streams_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
                             const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status) {
-    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
-    if (n && (!d_in || !in_off || !in_len || !d_out || !out_off || !out_cap || !d_out_len || !d_status)) return ZWZ_E_INVALID;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return ZWZ_E_INVALID;
-    for (uint32_t i = 0; i < n; i++)
-        if ((in_off[i] & 15u) || (out_off[i] & 15u)) { set_error("zwz_deflate_streams_dev: stream %u: offsets must be multiples of 16", i); return ZWZ_E_INVALID; }
-    if (n == 0) return ZWZ_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr);
+    return dstream_dev(c, "zwz_deflate_streams_dev", wrap, DstreamCall{0, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status});
 }
 
 uint64_t zwz_deflate_stream_index_bound(uint64_t n, uint32_t span) {
@@ -167,37 +185,18 @@ uint64_t zwz_deflate_stream_index_bound(uint64_t n, uint32_t span) {
 int zwz_deflate_streams_index_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
                                   const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status, uint32_t span, uint8_t* d_idx,
                                   const uint64_t* idx_off, const uint64_t* idx_cap, uint64_t* d_idx_len) {
-    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
-    if (span == 0) span = c->index_span_bytes;
-    if (!index_span_ok(span)) return ZWZ_E_INVALID;
-    if (n && (!d_in || !in_off || !in_len || !d_out || !out_off || !out_cap || !d_out_len || !d_status || !d_idx || !idx_off || !idx_cap || !d_idx_len))
-        return ZWZ_E_INVALID;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
-    for (uint32_t i = 0; i < n; i++)
-        if ((in_off[i] & 15u) || (out_off[i] & 15u) || (idx_off[i] & 15u)) {
-            set_error("zwz_deflate_streams_index_dev: stream %u: offsets must be multiples of 16", i);
-            return ZWZ_E_INVALID;
-        }
-    if (n == 0) return ZWZ_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const DstreamIndex X{d_idx, d_idx_len, span, 0, 0};
-    return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr, &X, idx_off, idx_cap);
+    DstreamCall k{0, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status};
+    k.idx_off = idx_off; k.idx_cap = idx_cap;
+    return dstream_dev(c, "zwz_deflate_streams_index_dev", wrap, k, &span, d_idx, d_idx_len);
 }
 
 uint64_t zwz_deflate_dep_stream_bound(uint64_t n, int wrap) { return dep_stream_bound(n, (uint32_t)wrap); }
 
 int zwz_deflate_dep_streams_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
                                 const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status) {
-    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
-    if (n && (!d_in || !in_off || !in_len || !d_out || !out_off || !out_cap || !d_out_len || !d_status)) return ZWZ_E_INVALID;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u)) return ZWZ_E_INVALID;
-    for (uint32_t i = 0; i < n; i++)
-        if ((in_off[i] & 15u) || (out_off[i] & 15u)) { set_error("zwz_deflate_dep_streams_dev: stream %u: offsets must be multiples of 16", i); return ZWZ_E_INVALID; }
-    if (int rc = dep_strategy_ok(c, "zwz_deflate_dep_streams_dev")) return rc;
-    if (n == 0) return ZWZ_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          DepMode{true, 0u});
+    DstreamCall k{0, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status};
+    k.form = kPiecesDep;
+    return dstream_dev(c, "zwz_deflate_dep_streams_dev", wrap, k);
 }
 
 uint64_t zwz_deflate_dep_stream_index_bound(uint64_t n, uint32_t span) {
@@ -208,23 +207,9 @@ uint64_t zwz_deflate_dep_stream_index_bound(uint64_t n, uint32_t span) {
 int zwz_deflate_dep_streams_index_dev(zwz_ctx* c, int wrap, const uint8_t* d_in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* d_out,
                                       const uint64_t* out_off, const uint64_t* out_cap, uint64_t* d_out_len, uint32_t* d_status, uint32_t span, uint8_t* d_idx,
                                       const uint64_t* idx_off, const uint64_t* idx_cap, uint64_t* d_idx_len) {
-    if (!c || wrap < ZWZ_WRAP_RAW || wrap > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
-    if (span == 0) span = c->index_span_bytes;
-    if (!index_span_ok(span)) return ZWZ_E_INVALID;
-    if (n && (!d_in || !in_off || !in_len || !d_out || !out_off || !out_cap || !d_out_len || !d_status || !d_idx || !idx_off || !idx_cap || !d_idx_len))
-        return ZWZ_E_INVALID;
-    if (((uintptr_t)d_in & 15u) || ((uintptr_t)d_out & 15u) || ((uintptr_t)d_idx & 15u)) return ZWZ_E_INVALID;
-    for (uint32_t i = 0; i < n; i++)
-        if ((in_off[i] & 15u) || (out_off[i] & 15u) || (idx_off[i] & 15u)) {
-            set_error("zwz_deflate_dep_streams_index_dev: stream %u: offsets must be multiples of 16", i);
-            return ZWZ_E_INVALID;
-        }
-    if (int rc = dep_strategy_ok(c, "zwz_deflate_dep_streams_index_dev")) return rc;
-    if (n == 0) return ZWZ_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const DstreamIndex X{d_idx, d_idx_len, span, 0, 0};
-    return dstream_launch(c, (uint32_t)wrap, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status, false, nullptr, &X, idx_off, idx_cap, nullptr,
-                          DepMode{true, 0u});
+    DstreamCall k{0, d_in, in_off, in_len, n, d_out, out_off, out_cap, d_out_len, d_status};
+    k.idx_off = idx_off; k.idx_cap = idx_cap; k.form = kPiecesDep;
+    return dstream_dev(c, "zwz_deflate_dep_streams_index_dev", wrap, k, &span, d_idx, d_idx_len);
 }
 
 // One slice of kFileSlicePieces whole pieces at a time: its pieces alone (partial), and its own checksum, which the host joins onto
@@ -241,8 +226,9 @@ namespace {
 // file's, which go behind all entries when the index is sealed.
 struct DevBytes { uint8_t* p = nullptr; ~DevBytes() { if (p) (void)hipFree(p); } };
 
-int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char* dst, const char* dst_idx, bool dep = false) {
+int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char* dst, const char* dst_idx, PieceForm F) {
     if (!c || !src || !dst || wrap_ < ZWZ_WRAP_RAW || wrap_ > ZWZ_WRAP_GZIP) return ZWZ_E_INVALID;
+    const bool dep = F.dict != 0u;
     if (dep) if (int rc = dep_strategy_ok(c, dst_idx ? "zwz_deflate_dep_stream_file_index" : "zwz_deflate_dep_stream_file")) return rc;
     const uint32_t wrap = (uint32_t)wrap_;
     HIPCHK(hipSetDevice(c->device));
@@ -250,7 +236,7 @@ int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
     if (int rc = job.open(src, dst)) return rc;
     const uint32_t file_pieces = dep ? 2u * kFileSlicePieces : kFileSlicePieces;       // (the same 16.7 MB of input)
     const uint32_t pieces = c->max_batch < file_pieces ? c->max_batch : file_pieces;
-    const size_t S = (size_t)pieces * (dep ? kDepPieceBytes : kPieceBytes);
+    const size_t S = (size_t)pieces * F.piece;
     const size_t O = round_up((size_t)pieces * (dep ? dep_piece_bound(kDepPieceBytes, kDepDictBytes) : piece_bound(kPieceBytes)), 16);
     const uint64_t win_base = index_flush_bytes(pieces);                                // dep: where a slice's windows come back
     const uint64_t ent_cap = !dst_idx ? 0u : dep ? win_base + (uint64_t)pieces * kDepDictBytes : index_flush_bytes(pieces);      // (the header's 64 bytes are the results' place)
@@ -271,20 +257,22 @@ int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
     uint64_t total_in = 0;
     const int rc = run_slices(c, job, S,
         [&](size_t n, SliceResult* d_res, SliceResult* h_res) {
-            const uint64_t zero = 0, len = n, cap = O;
+            const uint64_t zero = 0, dict = F.dict, len = n, cap = O;
             const uint32_t* d_chk = nullptr;
             const DstreamIndex X{job.dp(2), nullptr, c->index_span_bytes, total_in, pos};
             const uint64_t* d_cnt = nullptr;
+            // the slice's input: where it was copied to, or (dep) behind its dictionary in `work`
+            DstreamCall k{wrap, dep ? work.p : job.dp(0), &dict, &len, 1, job.dp(1), &zero, &cap, &d_res->out_len, &d_res->status};
+            k.partial = true; k.d_chk = &d_chk; k.d_cnt = &d_cnt;
+            if (dst_idx) { k.ix = &X; k.idx_off = &zero; k.idx_cap = &ent_cap; }
+            k.form = F; k.lead = total_in ? F.dict : 0u; k.win_base = win_base;
             if (dep) {
-                const uint64_t dict = kDepDictBytes, k0 = total_in / kDepPieceBytes, k1 = k0 + (n + kDepPieceBytes - 1) / kDepPieceBytes;
+                const uint64_t k0 = total_in / kDepPieceBytes, k1 = k0 + (n + kDepPieceBytes - 1) / kDepPieceBytes;
                 slice_cnt = (k1 + step - 1) / step - (k0 + step - 1) / step;          // pieces k0 .. k1 - 1 whose number is a multiple of step
                 HIPCHK(hipMemcpyAsync(work.p + dict, job.dp(0), n, hipMemcpyDeviceToDevice, c->stream));
-                if (int rc = dstream_launch(c, wrap, work.p, &dict, &len, 1, job.dp(1), &zero, &cap, &d_res->out_len, &d_res->status, true, &d_chk,
-                                            dst_idx ? &X : nullptr, &zero, &ent_cap, &d_cnt, DepMode{true, total_in ? kDepDictBytes : 0u}, win_base)) return rc;
-                if (n == S) HIPCHK(hipMemcpyAsync(work.p, work.p + n, dict, hipMemcpyDeviceToDevice, c->stream));      // the next slice's dictionary (S >= 2 dict: no overlap)
-            } else
-            if (int rc = dstream_launch(c, wrap, job.dp(0), &zero, &len, 1, job.dp(1), &zero, &cap, &d_res->out_len, &d_res->status, true, &d_chk,
-                                        dst_idx ? &X : nullptr, &zero, &ent_cap, &d_cnt)) return rc;
+            }
+            if (int rc = dstream_launch(c, k)) return rc;
+            if (dep && n == S) HIPCHK(hipMemcpyAsync(work.p, work.p + n, dict, hipMemcpyDeviceToDevice, c->stream));      // the next slice's dictionary (S >= 2 dict: no overlap)
             HIPCHK(hipMemcpyAsync(h_res, d_res, 12, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(&h_res->check, d_chk, 4, hipMemcpyDeviceToHost, c->stream));
             if (dst_idx) {
@@ -319,37 +307,26 @@ int deflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
     if (!total_in) { ents.resize(kIdxHeader + kIdxEntry); index_flush_entry(ents.data() + kIdxHeader, 8u * hdr, 0); }
     const uint64_t count = (ents.size() - kIdxHeader) / kIdxEntry;
     if (count > 0xffffffffull) { set_error("deflate stream: more than 2^32 - 1 index entries"); return ZWZ_E_INVALID; }
-    if (dep) {
-        if (count != index_dep_count(total_in, c->index_span_bytes) || wins.size() != (count - 1u) * kDepDictBytes) { set_error("deflate stream: the index's entries and windows do not add up"); return ZWZ_E_FORMAT; }
-        ents.insert(ents.end(), wins.begin(), wins.end());
-        ents.resize((size_t)index_dep_bytes(count), 0);
-        index_seal(ents.data(), ents.size(), wrap, c->index_span_bytes, pos + tail, total_in, (uint32_t)count, index_flush_end_bit(pos), wrap == kWrapRaw ? 0u : check);
-    } else {
-    ents.resize((size_t)index_flush_bytes(count));
-    index_flush_seal(ents.data(), wrap, c->index_span_bytes, pos + tail, total_in, (uint32_t)count, index_flush_end_bit(pos), wrap == kWrapRaw ? 0u : check);
-    }
-    const std::string ipart = std::string(dst_idx) + ".part";
-    FILE* fi = fopen(ipart.c_str(), "wb");
-    if (!fi) { set_error("cannot create %s", ipart.c_str()); return ZWZ_E_IO; }
-    const bool wrote = fwrite(ents.data(), 1, ents.size(), fi) == ents.size();
-    if ((fclose(fi) != 0) | !wrote) { unlink(ipart.c_str()); set_error("write error on %s", ipart.c_str()); return ZWZ_E_IO; }
-    if (int rc2 = job.commit(dst)) { unlink(ipart.c_str()); return rc2; }
-    if (rename(ipart.c_str(), dst_idx) != 0) { unlink(ipart.c_str()); unlink(dst); set_error("cannot write %s", dst_idx); return ZWZ_E_IO; }
-    return ZWZ_OK;
+    if (dep && (count != index_dep_count(total_in, c->index_span_bytes) || wins.size() != (count - 1u) * kDepDictBytes)) { set_error("deflate stream: the index's entries and windows do not add up"); return ZWZ_E_FORMAT; }
+    // the windows (dep) behind the entries, zero padding behind them (index_dep_bytes without windows is index_flush_bytes)
+    ents.insert(ents.end(), wins.begin(), wins.end());
+    ents.resize((size_t)((kIdxHeader + count * kIdxEntry + wins.size() + 15u) & ~15ull), 0);
+    index_seal(ents.data(), ents.size(), wrap, c->index_span_bytes, pos + tail, total_in, (uint32_t)count, index_flush_end_bit(pos), wrap == kWrapRaw ? 0u : check);
+    return commit_with_index_bytes(dst_idx, dst, ents.data(), ents.size(), [&] { return job.commit(dst); });
 }
 
 }  // namespace
 
-int zwz_deflate_stream_file(zwz_ctx* c, int wrap, const char* src, const char* dst) { return deflate_stream_file_core(c, wrap, src, dst, nullptr); }
+int zwz_deflate_stream_file(zwz_ctx* c, int wrap, const char* src, const char* dst) { return deflate_stream_file_core(c, wrap, src, dst, nullptr, kPiecesAlone); }
 
 int zwz_deflate_stream_file_index(zwz_ctx* c, int wrap, const char* src, const char* dst, const char* dst_idx) {
     if (!dst_idx) return ZWZ_E_INVALID;
-    return deflate_stream_file_core(c, wrap, src, dst, dst_idx);
+    return deflate_stream_file_core(c, wrap, src, dst, dst_idx, kPiecesAlone);
 }
 
-int zwz_deflate_dep_stream_file(zwz_ctx* c, int wrap, const char* src, const char* dst) { return deflate_stream_file_core(c, wrap, src, dst, nullptr, true); }
+int zwz_deflate_dep_stream_file(zwz_ctx* c, int wrap, const char* src, const char* dst) { return deflate_stream_file_core(c, wrap, src, dst, nullptr, kPiecesDep); }
 
 int zwz_deflate_dep_stream_file_index(zwz_ctx* c, int wrap, const char* src, const char* dst, const char* dst_idx) {
     if (!dst_idx) return ZWZ_E_INVALID;
-    return deflate_stream_file_core(c, wrap, src, dst, dst_idx, true);
+    return deflate_stream_file_core(c, wrap, src, dst, dst_idx, kPiecesDep);
 }

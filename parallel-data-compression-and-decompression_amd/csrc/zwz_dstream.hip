@@ -5,12 +5,16 @@
 // arithmetic; the scan between size and pack is BGZF's (launch_bgzf_scan).  zwz_deflate_streams_index_dev adds the index at the pieces'
 // starts (index_core.h: the index at full-flush points): a flag per piece (due), the same scan over the flags, the entries (index)
 // and, behind the last slice, every stream's header and index CRC (seal).  Nothing is decoded: a piece's decoded offset is its number
-// times kPieceBytes and its first bit is where pack puts it.
+// times the piece length and its first bit is where pack puts it.
+// The dependent form (zwz_deflate_dep_streams_dev) runs through the same kernels: they take the PieceForm
+// (dstream_core.h), and a piece of kDepPieceBytes with the kDepDictBytes of input in front of it is one chunk of the codec, which enters it
+// behind the dictionary (zwz_kernels.h: DeflateArgs::skip).  Two kernels are that form's alone: the Adler-32 of the piece's own bytes
+// (the slot's covers the dictionary too) and the index entries with their windows.
 #include "../../include/zwz.h"
+#include "adler_wg.h"
 #include "copy_wg.h"
-#include "crc_wg.h"
 #include "dstream_core.h"
-#include "index_core.h"
+#include "index_seal_wg.h"
 #include "zwz_device.h"
 #include "zwz_dstream.h"
 
@@ -38,7 +42,8 @@ __global__ void __launch_bounds__(256) dstream_begin_kernel(DstreamStreams S, Ds
 }
 
 // Piece g0 + p: its stream is the last one whose first piece is not behind it (streams without pieces share their successor's first).
-__global__ void __launch_bounds__(256) dstream_layout_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, uint32_t m) {
+// The codec's chunk starts `skip` bytes in front of the piece, in the caller's own input: the piece's dictionary (none: the piece itself).
+__global__ void __launch_bounds__(256) dstream_layout_kernel(DstreamStreams S, DstreamPieces P, PieceForm F, uint32_t lead, uint64_t g0, uint32_t m) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= m) return;
     const uint64_t g = g0 + p;
@@ -47,10 +52,21 @@ __global__ void __launch_bounds__(256) dstream_layout_kernel(DstreamStreams S, D
         const uint32_t mid = lo + (hi - lo) / 2u;
         if (S.pfirst[mid] <= g) lo = mid; else hi = mid;
     }
-    const uint64_t at = (g - S.pfirst[lo]) * kPieceBytes, left = S.in_len[lo] - at;
-    P.off[p] = S.in_off[lo] + at;
-    P.len[p] = (uint32_t)min<uint64_t>(left, kPieceBytes);
+    const uint64_t k = g - S.pfirst[lo], at = k * F.piece, left = S.in_len[lo] - at;
+    const uint32_t skip = F.skip(k, lead), len = (uint32_t)min<uint64_t>(left, F.piece);
+    P.poff[p] = S.in_off[lo] + at; P.plen[p] = len; P.skip[p] = skip;
+    P.off[p] = S.in_off[lo] + at - skip;
+    P.len[p] = skip + len;
     P.sidx[p] = lo;
+}
+
+// Dependent pieces under zlib: the Adler-32 of every piece's own bytes, a workgroup a piece at a time
+__global__ void __launch_bounds__(kBgzfThreads) dstream_adler_kernel(const uint8_t* __restrict__ in, DstreamPieces P, uint32_t m) {
+    __shared__ uint32_t part[2 * (kBgzfThreads / 64)];
+    for (uint32_t p = blockIdx.x; p < m; p += gridDim.x) {
+        const uint32_t a = adler_range_wg(part, in + P.poff[p], P.plen[p]);       // (the piece starts on a multiple of 16, as the chunk does)
+        if (threadIdx.x == 0) P.crc[p] = a;
+    }
 }
 
 // (The records are the ones the slot's stream was written from; should they ever contradict its length, *err is set, the piece gets
@@ -78,13 +94,14 @@ __global__ void __launch_bounds__(256) dstream_size_kernel(const ChunkInfo* info
 }
 
 // One wave per stream with a piece in the slice: the checksums of its pieces there, in order, joined onto the stream's running value.
-// All but the last of them are kPieceBytes long (only a stream's last piece is shorter).  Lane l joins K = ceil(full / 64) consecutive
+// All but the last of them are F.piece bytes long (only a stream's last piece is shorter).  Lane l joins K = ceil(full / 64) consecutive
 // ones one after the other -- the short share is lane 0's, padded in front with nothing -- and the 64 lanes' values, each now the
 // checksum of K pieces, are folded pairwise at distances 1, 2, 4, ... with the parameter of K, 2K, 4K, ... pieces
 // (dstream_core.h: sum_fold_row_host is that fold on the host).  A stream of 8 192 pieces a slice costs 128 + 6 joins deep instead of 8 192.
-// The last piece is joined by its own length.
+// The last piece is joined by its own length.  A piece's value is the slot's trailing Adler-32 (kFromSlot: independent pieces under
+// zlib) or P.crc: crc32_blocks' under gzip, dstream_adler_kernel's for dependent pieces under zlib.
 template <class Sum, bool kFromSlot>
-__global__ void __launch_bounds__(256) dstream_combine_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, uint32_t m, uint32_t s0, uint32_t ns) {
+__global__ void __launch_bounds__(256) dstream_combine_kernel(DstreamStreams S, DstreamPieces P, PieceForm F, uint64_t g0, uint32_t m, uint32_t s0, uint32_t ns) {
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = lane_id();
     if (wave >= ns) return;
     const uint32_t s = s0 + wave;
@@ -98,7 +115,7 @@ __global__ void __launch_bounds__(256) dstream_combine_kernel(DstreamStreams S, 
     };
     uint32_t acc = S.chk[s];
     if (full) {
-        const uint32_t p1 = Sum::pof(kPieceBytes), K = (full + kSumRow - 1u) / kSumRow, pad = K * kSumRow - full;
+        const uint32_t p1 = Sum::pof(F.piece), K = (full + kSumRow - 1u) / kSumRow, pad = K * kSumRow - full;
         uint32_t x = Sum::identity();
         for (uint32_t j = 0; j < K; j++) {
             const uint32_t v = lane * K + j;
@@ -114,7 +131,7 @@ __global__ void __launch_bounds__(256) dstream_combine_kernel(DstreamStreams S, 
         x = (uint32_t)__shfl((int)x, 0, 64);
         acc = Sum::join(acc, x, sum_ptimes<Sum>(p1, full));
     }
-    acc = Sum::join(acc, value(p0 + full), Sum::pof(P.len[p0 + full]));
+    acc = Sum::join(acc, value(p0 + full), Sum::pof(P.plen[p0 + full]));
     if (lane == 0) S.chk[s] = acc;
 }
 
@@ -153,68 +170,97 @@ __global__ void __launch_bounds__(256) dstream_pack_kernel(DstreamStreams S, Dst
     if (end <= cap) wg_copy(dst + start, slot + 2, slen);
 }
 
-// Piece k of its stream is point k of the rule, at decoded offset k * kPieceBytes behind X.off_base; the point in front of it is the
+// Piece k of its stream is point k of the rule, at decoded offset k * F.piece behind X.off_base; the point in front of it is the
 // piece in front of it, whichever slice that was in.
-__global__ void __launch_bounds__(256) dstream_due_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, uint32_t m, DstreamIndex X) {
+__global__ void __launch_bounds__(256) dstream_due_kernel(DstreamStreams S, DstreamPieces P, PieceForm F, uint64_t g0, uint32_t m, DstreamIndex X) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= m) return;
     const uint32_t s = P.sidx[p];
-    const uint64_t off = X.off_base + (g0 + p - S.pfirst[s]) * kPieceBytes;
-    P.due[p] = off == 0u || index_flush_due(off - kPieceBytes, off, X.off_base + S.in_len[s], X.span) ? 1u : 0u;
+    const uint64_t off = X.off_base + (g0 + p - S.pfirst[s]) * F.piece;
+    P.due[p] = off == 0u || index_flush_due(off - F.piece, off, X.off_base + S.in_len[s], X.span) ? 1u : 0u;
 }
 
-// A thread per piece, behind the rank scan and behind pack (S.xs): a due piece writes its entry, three 8-byte stores, where its rank
-// within its stream says; a stream's first piece keeps the scan's value for the stream's pieces in later slices, as pack keeps
-// S.xs, and its last piece the stream's count.  No entry is written that would end behind the index's capacity.
-__global__ void __launch_bounds__(256) dstream_index_kernel(DstreamStreams S, DstreamPieces P, uint64_t g0, uint32_t m, DstreamOut O, DstreamIndex X) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= m) return;
+// What the two index kernels share, behind the rank scan and behind pack (S.xs).  A piece's rank within its stream: with `book`, a
+// stream's first piece keeps the scan's value for the stream's pieces in later slices, as pack keeps S.xs, and its last piece the
+// stream's count.
+struct PieceRank { uint32_t s, due; uint64_t r; };
+__device__ PieceRank dstream_rank(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t p, bool book) {
     const uint32_t s = P.sidx[p], due = P.due[p];
     const uint64_t g = g0 + p, pf = S.pfirst[s];
-    const uint64_t xs = pf >= g0 ? P.x[pf - g0] : S.xs[s], rs = pf >= g0 ? P.rank[pf - g0] : S.rs[s];
-    const uint64_t r = P.rank[p] - rs;
-    if (g == pf) S.rs[s] = P.rank[p];               // (read by this stream's pieces in later slices only)
-    if (g + 1 == S.pfirst[s + 1]) S.cnt[s] = r + due;
-    if (!due || index_flush_bytes(r + 1u) > S.idx_cap[s]) return;
+    const uint64_t r = P.rank[p] - (pf >= g0 ? P.rank[pf - g0] : S.rs[s]);
+    if (book && g == pf) S.rs[s] = P.rank[p];       // (read by this stream's pieces in later slices only)
+    if (book && g + 1 == S.pfirst[s + 1]) S.cnt[s] = r + due;
+    return PieceRank{s, due, r};
+}
+// The entry of a due piece, three 8-byte stores where its rank says: its first bit is where pack put it, hist its dictionary's length
+__device__ void dstream_entry(const DstreamStreams& S, const DstreamPieces& P, PieceForm F, uint64_t g0, uint32_t p, const PieceRank& k, const DstreamOut& O,
+                              const DstreamIndex& X, uint32_t hist) {
+    const uint64_t pf = S.pfirst[k.s], xs = pf >= g0 ? P.x[pf - g0] : S.xs[k.s];
     const uint32_t hdr = O.partial ? 0u : dstream_header_bytes(O.wrap);
-    uint64_t* e = reinterpret_cast<uint64_t*>(X.idx + S.idx_off[s] + kIdxHeader + r * kIdxEntry);
+    uint64_t* e = reinterpret_cast<uint64_t*>(X.idx + S.idx_off[k.s] + kIdxHeader + k.r * kIdxEntry);
     e[0] = 8u * (X.pos_base + hdr + (P.x[p] - xs));
-    e[1] = X.off_base + (g - pf) * kPieceBytes;
-    e[2] = 0;
+    e[1] = X.off_base + (g0 + p - pf) * F.piece;
+    e[2] = hist;
 }
 
+// Independent pieces, a thread per piece: no entry is written that would end behind the index's capacity.
+__global__ void __launch_bounds__(256) dstream_index_kernel(DstreamStreams S, DstreamPieces P, PieceForm F, uint64_t g0, uint32_t m, DstreamOut O, DstreamIndex X) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    const PieceRank k = dstream_rank(S, P, g0, p, true);
+    if (!k.due || index_flush_bytes(k.r + 1u) > S.idx_cap[k.s]) return;
+    dstream_entry(S, P, F, g0, p, k, O, X, 0u);
+}
+
+// Dependent pieces, a workgroup per piece.  Thread 0 does dstream_index_kernel's work -- the entry's hist is the piece's dictionary --
+// and the workgroup copies the window, the input in front of the piece (the chunk's head), to its place: window w of the index belongs to
+// entry w + 1 (entry 0, at offset 0, has none).  A whole call knows the number of entries, and so where the windows start and whether
+// the index fits, before it writes any (index_dep_count); a partial call's windows go to win_base, in the order of its entries.
+__global__ void __launch_bounds__(256) dstream_index_windows_kernel(const uint8_t* __restrict__ in, DstreamStreams S, DstreamPieces P, PieceForm F, uint64_t g0,
+                                                                    DstreamOut O, DstreamIndex X, uint64_t win_base) {
+    const uint32_t p = blockIdx.x, t = threadIdx.x;
+    const PieceRank k = dstream_rank(S, P, g0, p, t == 0);
+    if (!k.due) return;
+    const uint32_t hist = P.skip[p];
+    const uint64_t r = k.r;
+    uint64_t win_at;                                // of the stream's index space: where this entry's window goes (meaningless without one)
+    if (O.partial) {
+        if (index_flush_bytes(r + 1u) > win_base) return;
+        win_at = win_base + (r - (X.off_base == 0u ? 1u : 0u)) * F.dict;
+    } else {
+        const uint64_t count = index_dep_count(S.in_len[k.s], X.span);
+        if (r >= count || index_dep_bytes(count) > S.idx_cap[k.s]) return;
+        win_at = kIdxHeader + count * kIdxEntry + (r - 1u) * F.dict;
+    }
+    if (hist && win_at + hist > S.idx_cap[k.s]) return;
+    if (t == 0) dstream_entry(S, P, F, g0, p, k, O, X, hist);
+    if (hist) wg_copy(X.idx + S.idx_off[k.s] + win_at, in + P.off[p], hist);
+}
+static_assert(kIdxDepPiece == kDepPieceBytes && kIdxDepDict == kDepDictBytes, "index_core.h's dependent geometry is dstream_core.h's");
+
 // One workgroup per stream, behind the last slice: the entry of a stream without input, the padding, the index CRC and the header.
-// The stream's length and status are pack's (or begin's), its stored check value combine's.
-__global__ void __launch_bounds__(kBgzfThreads) dstream_index_seal_kernel(const CrcTables* tab, DstreamStreams S, DstreamOut O, DstreamIndex X) {
+// The stream's length and status are pack's (or begin's), its stored check value combine's.  With windows (F.dict) they lie behind the
+// entries and the padding behind them, and the count must be the one the windows were placed by.
+__global__ void __launch_bounds__(kBgzfThreads) dstream_index_seal_kernel(const CrcTables* tab, DstreamStreams S, PieceForm F, DstreamOut O, DstreamIndex X) {
     __shared__ CrcLds lds;
     crc_load_tables(lds, tab);
     const uint32_t t = threadIdx.x;
     for (uint32_t i = blockIdx.x; i < S.n; i += gridDim.x) {
-        const uint64_t count = S.in_len[i] ? S.cnt[i] : 1u, len = index_flush_bytes(count);      // (workgroup-uniform, as the branch below)
-        if (O.status[i] != 0u || count > 0xffffffffull || len > 0xffffffffull || len > S.idx_cap[i]) {
+        const uint64_t n = S.in_len[i], count = n ? S.cnt[i] : 1u, len = F.dict ? index_dep_bytes(count) : index_flush_bytes(count);      // (workgroup-uniform, as the branch below)
+        if (O.status[i] != 0u || count > 0xffffffffull || len > 0xffffffffull || len > S.idx_cap[i] || (F.dict && count != index_dep_count(n, X.span))) {
             if (t == 0) X.idx_len[i] = 0;
             continue;
         }
         uint8_t* q = X.idx + S.idx_off[i];
-        const uint32_t hdr = dstream_header_bytes(O.wrap);
         if (t == 0) {
             uint64_t* e = reinterpret_cast<uint64_t*>(q + kIdxHeader);
-            if (!S.in_len[i]) { e[0] = 8u * hdr; e[1] = 0; e[2] = 0; }
-            if (count & 1u) e[3u * count] = 0;       // 24 count is 8 mod 16: the padding
+            if (!n) { e[0] = 8u * dstream_header_bytes(O.wrap); e[1] = 0; e[2] = 0; }
+            if (count & 1u) *reinterpret_cast<uint64_t*>(q + len - 8u) = 0;       // 24 count is 8 mod 16, a window 0: the padding
         }
-        __threadfence();
-        __syncthreads();
-        const uint32_t crc = crc_block_wg(lds, q + kIdxHeader, (uint32_t)(len - kIdxHeader));
-        if (t == 0) {
-            const uint64_t total = O.out_len[i], end_bit = index_flush_end_bit(total - dstream_trailer_bytes(O.wrap) - 2u), n = S.in_len[i];
-            uint32_t* h = reinterpret_cast<uint32_t*>(q);
-            h[0] = 0x495a575au; h[1] = 0x01005844u;                               // "ZWZIDX\0\1"
-            h[2] = O.wrap; h[3] = X.span;
-            h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32); h[6] = (uint32_t)n; h[7] = (uint32_t)(n >> 32);
-            h[8] = (uint32_t)count; h[9] = 0; h[10] = (uint32_t)end_bit; h[11] = (uint32_t)(end_bit >> 32);
-            h[12] = O.wrap == kWrapRaw ? 0u : S.chk[i]; h[13] = crc; h[14] = 0; h[15] = 0;
-            X.idx_len[i] = len;
-        }
+        const uint64_t total = O.out_len[i];
+        index_seal_wg(lds, q, (uint32_t)len, IndexHeader{O.wrap, X.span, total, n, (uint32_t)count, index_flush_end_bit(total - dstream_trailer_bytes(O.wrap) - 2u),
+                                                         O.wrap == kWrapRaw ? 0u : S.chk[i], 0u});
+        if (t == 0) X.idx_len[i] = len;
         __syncthreads();
     }
 }
@@ -227,9 +273,16 @@ hipError_t launch_dstream_begin(const DstreamStreams& S, const DstreamOut& O, hi
     return hipGetLastError();
 }
 
-hipError_t launch_dstream_layout(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, hipStream_t s) {
+hipError_t launch_dstream_layout(const DstreamStreams& S, const DstreamPieces& P, PieceForm F, uint32_t lead, uint64_t g0, uint32_t m, hipStream_t s) {
     if (!m) return hipSuccess;
-    dstream_layout_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, g0, m);
+    dstream_layout_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, F, lead, g0, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_dstream_adler(const uint8_t* in, const DstreamPieces& P, uint32_t m, uint32_t cu_count, hipStream_t s) {
+    if (!m) return hipSuccess;
+    const uint32_t g = (cu_count ? cu_count : 256u) * 8u;
+    dstream_adler_kernel<<<m < g ? m : g, kBgzfThreads, 0, s>>>(in, P, m);
     return hipGetLastError();
 }
 
@@ -240,12 +293,13 @@ hipError_t launch_dstream_size(const ChunkInfo* info, const BlockInfo* blocks, c
     return hipGetLastError();
 }
 
-hipError_t launch_dstream_combine(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, uint32_t s0, uint32_t ns, uint32_t wrap,
+hipError_t launch_dstream_combine(const DstreamStreams& S, const DstreamPieces& P, PieceForm F, uint64_t g0, uint32_t m, uint32_t s0, uint32_t ns, uint32_t wrap,
                                   hipStream_t s) {
     if (!m || !ns || wrap == kWrapRaw) return hipSuccess;
     const uint32_t grid = (ns + 3u) / 4u;
-    if (wrap == kWrapZlib) dstream_combine_kernel<AdlerSum, true><<<grid, 256, 0, s>>>(S, P, g0, m, s0, ns);
-    else dstream_combine_kernel<CrcSum, false><<<grid, 256, 0, s>>>(S, P, g0, m, s0, ns);
+    if (wrap == kWrapGzip) dstream_combine_kernel<CrcSum, false><<<grid, 256, 0, s>>>(S, P, F, g0, m, s0, ns);
+    else if (F.dict) dstream_combine_kernel<AdlerSum, false><<<grid, 256, 0, s>>>(S, P, F, g0, m, s0, ns);
+    else dstream_combine_kernel<AdlerSum, true><<<grid, 256, 0, s>>>(S, P, F, g0, m, s0, ns);
     return hipGetLastError();
 }
 
@@ -256,24 +310,25 @@ hipError_t launch_dstream_pack(const DstreamStreams& S, const DstreamPieces& P, 
     return hipGetLastError();
 }
 
-hipError_t launch_dstream_due(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamIndex& X, hipStream_t s) {
+hipError_t launch_dstream_due(const DstreamStreams& S, const DstreamPieces& P, PieceForm F, uint64_t g0, uint32_t m, const DstreamIndex& X, hipStream_t s) {
     if (!m) return hipSuccess;
-    dstream_due_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, g0, m, X);
+    dstream_due_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, F, g0, m, X);
     return hipGetLastError();
 }
 
-hipError_t launch_dstream_index(const DstreamStreams& S, const DstreamPieces& P, uint64_t g0, uint32_t m, const DstreamOut& O, const DstreamIndex& X,
-                                hipStream_t s) {
+hipError_t launch_dstream_index(const uint8_t* in, const DstreamStreams& S, const DstreamPieces& P, PieceForm F, uint64_t g0, uint32_t m, const DstreamOut& O,
+                                const DstreamIndex& X, uint64_t win_base, hipStream_t s) {
     if (!m) return hipSuccess;
-    dstream_index_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, g0, m, O, X);
+    if (F.dict) dstream_index_windows_kernel<<<m, 256, 0, s>>>(in, S, P, F, g0, O, X, win_base);
+    else dstream_index_kernel<<<(m + 255u) / 256u, 256, 0, s>>>(S, P, F, g0, m, O, X);
     return hipGetLastError();
 }
 
-hipError_t launch_dstream_index_seal(const CrcTables* tab, const DstreamStreams& S, const DstreamOut& O, const DstreamIndex& X, uint32_t cu_count,
+hipError_t launch_dstream_index_seal(const CrcTables* tab, const DstreamStreams& S, PieceForm F, const DstreamOut& O, const DstreamIndex& X, uint32_t cu_count,
                                      hipStream_t s) {
     if (!S.n) return hipSuccess;
     const uint32_t g = (cu_count ? cu_count : 256u) * 4u;
-    dstream_index_seal_kernel<<<S.n < g ? S.n : g, kBgzfThreads, 0, s>>>(tab, S, O, X);
+    dstream_index_seal_kernel<<<S.n < g ? S.n : g, kBgzfThreads, 0, s>>>(tab, S, F, O, X);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // zwz_filejob.h -- what the whole-file entry points share (zwz_bgzf.cpp, zwz_dstream.cpp, zwz_split.cpp): the open files, the pinned
-// double buffers and the reader and writer threads of one call, and the slice loop of the two compressing ones.  Host code.
+// double buffers and the reader and writer threads of one call, the slice loop of the two compressing ones, the commit of an output
+// that an index goes with, and the decode of a whole file by one launch.  Host code.
 #pragma once
 #include <unistd.h>
 
@@ -7,6 +8,7 @@
 #include <initializer_list>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include "zwz_api_internal.h"
 
@@ -79,6 +81,35 @@ struct FileJob {
         return ZWZ_OK;
     }
 };
+
+// An index goes with this output.  <dst_idx>.part is created and body(f) writes it (false: a write failed); commit() puts the data file
+// `dst` in place (null: there is none, and commit() returns ZWZ_OK); the index is renamed last.  Whatever fails, no index, no .part of
+// it and no data file is left: a failed commit() has removed its own .part, and dst is unlinked if the last rename fails.
+// write_fail, names_part: a failed write's message, and whether it names the .part or the index.
+template <class Body, class Commit>
+int commit_with_index(const char* dst_idx, const char* dst, Body&& body, Commit&& commit, const char* write_fail = "write error on %s", bool names_part = true) {
+    const std::string ipart = std::string(dst_idx) + ".part";
+    FILE* f = fopen(ipart.c_str(), "wb");
+    if (!f) { set_error("cannot create %s", ipart.c_str()); return ZWZ_E_IO; }
+    const bool wrote = body(f);
+    if ((fclose(f) != 0) | !wrote) { unlink(ipart.c_str()); set_error(write_fail, names_part ? ipart.c_str() : dst_idx); return ZWZ_E_IO; }
+    if (int rc = commit()) { unlink(ipart.c_str()); return rc; }
+    if (rename(ipart.c_str(), dst_idx) != 0) { unlink(ipart.c_str()); if (dst) unlink(dst); set_error("cannot write %s", dst_idx); return ZWZ_E_IO; }
+    return ZWZ_OK;
+}
+// The index is the n bytes at p
+template <class Commit>
+int commit_with_index_bytes(const char* dst_idx, const char* dst, const uint8_t* p, size_t n, Commit&& commit, const char* write_fail = "write error on %s", bool names_part = true) {
+    return commit_with_index(dst_idx, dst, [&](FILE* f) { return fwrite(p, 1, n, f) == n; }, commit, write_fail, names_part);
+}
+
+// A whole file of n < kStreamMaxIn bytes as ONE stream through one launch -- zwz_inflate_streams_dev, with idx
+// zwz_inflate_streams_index_dev at the context's span -- its output capacity doubled until the decoded bytes fit.  in: the file's bytes
+// and 32 zero bytes behind them; out, idx (either may be null): the decoded bytes, the index (empty: the launch made none).  A stream
+// that does not end well is an error in `who`'s name (zwz_index.cpp).  kGoLegs: the decoded bytes do not fit the launch's largest
+// capacity, and the file goes through zwz_inflate_legs_file.
+constexpr int kGoLegs = 1;
+int inflate_whole_file(zwz_ctx* c, int wrap, const char* who, const char* src, const uint8_t* in, uint64_t n, std::vector<uint8_t>* out, std::vector<uint8_t>* idx);
 
 #define HIPJOB(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { job.join(); return hip_fail(e_, #x); } } while (0)
 

@@ -462,55 +462,39 @@ extern "C" int zwz_inflate_index_info(const uint8_t* idx, uint64_t idx_len, int*
     return ZWZ_OK;
 }
 
-namespace {
-
-// A file within the one-launch limits through zwz_inflate_streams_index_dev whole.  kGoLegs: its decoded bytes do not fit the launch's
-// largest capacity.
-constexpr int kGoLegs = 1;
-int index_file_one_launch(zwz_ctx* c, int wrap, const char* src, const char* dst_idx) {
-    std::vector<uint8_t> in;
-    if (int rc = read_whole_file(src, &in, 32)) return rc;
-    const uint64_t n = in.size() - 32;
+// zwz_filejob.h: the whole file through one launch
+int zwz::inflate_whole_file(zwz_ctx* c, int wrap, const char* who, const char* src, const uint8_t* in, uint64_t n, std::vector<uint8_t>* out, std::vector<uint8_t>* idx) {
     DevMem d_in, d_out, d_idx, d_par;
     if (int rc = d_in.get(round_up((size_t)n + 16, 16))) return rc;
-    if (int rc = d_par.get(64)) return rc;
-    HIPCHK(hipMemcpy(d_in.p, in.data(), round_up((size_t)n + 16, 16), hipMemcpyHostToDevice));
+    if (int rc = d_par.get(80)) return rc;
+    HIPCHK(hipMemcpy(d_in.p, in, round_up((size_t)n + 16, 16), hipMemcpyHostToDevice));
     const uint32_t span = c->index_span_bytes;
-    uint64_t cap = std::max<uint64_t>(8 * n, 1u << 20), h_par[8];
+    uint64_t cap = std::max<uint64_t>(8 * n, 1u << 20), h_par[10];
+    uint64_t* q = d_par.as<uint64_t>();
     for (;;) {
         cap = std::min<uint64_t>(cap, kStreamMaxOut - 16);
-        const uint64_t bound = index_bound(cap, span);
+        const uint64_t bound = idx ? index_bound(cap, span) : 0u;
         if (int rc = d_out.get((size_t)cap + 16)) return rc;
-        if (int rc = d_idx.get((size_t)bound)) return rc;
-        const uint64_t par[8] = {0, n, 0, cap, 0, bound, 0, 0};      // in_off, in_len, out_off, out_cap, idx_off, idx_cap, out_len, idx_len
+        if (idx) if (int rc = d_idx.get((size_t)bound)) return rc;
+        const uint64_t par[10] = {0, n, 0, cap, 0, bound, 0, 0, 0, 0};      // in_off, in_len, out_off, out_cap, idx_off, idx_cap, out_len, idx_len, status
         HIPCHK(hipMemcpy(d_par.p, par, sizeof par, hipMemcpyHostToDevice));
-        uint64_t* q = d_par.as<uint64_t>();
-        DevMem st_mem;
-        if (int rc = st_mem.get(16)) return rc;
-        if (int rc = zwz_inflate_streams_index_dev(c, wrap, d_in.as<uint8_t>(), q, q + 1, 1, d_out.as<uint8_t>(), q + 2, q + 3, q + 6, st_mem.as<uint32_t>(), span,
-                                                   d_idx.as<uint8_t>(), q + 4, q + 5, q + 7)) return rc;
+        uint32_t* d_status = reinterpret_cast<uint32_t*>(q + 8);
+        if (int rc = idx ? zwz_inflate_streams_index_dev(c, wrap, d_in.as<uint8_t>(), q, q + 1, 1, d_out.as<uint8_t>(), q + 2, q + 3, q + 6, d_status, span,
+                                                         d_idx.as<uint8_t>(), q + 4, q + 5, q + 7)
+                         : zwz_inflate_streams_dev(c, wrap, d_in.as<uint8_t>(), q, q + 1, 1, d_out.as<uint8_t>(), q + 2, q + 3, q + 6, d_status)) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
-        uint32_t status = 0;
         HIPCHK(hipMemcpy(h_par, d_par.p, sizeof h_par, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&status, st_mem.p, 4, hipMemcpyDeviceToHost));
+        const uint32_t status = (uint32_t)h_par[8];
         if (status == kInfOverflow && cap < kStreamMaxOut - 16) { cap *= 2; continue; }
         if (status == kInfOverflow) return kGoLegs;
-        if (status == kStrChecksum || status == kStrLength) { set_error("zwz_inflate_index_file: %s: %s mismatch", src, status == kStrLength ? "length" : "checksum"); return ZWZ_E_CHECKSUM; }
-        if (status != kInfEnd) { set_error("zwz_inflate_index_file: %s: stream status %u after %llu decoded bytes", src, status, (unsigned long long)h_par[6]); return ZWZ_E_FORMAT; }
+        if (status == kStrChecksum || status == kStrLength) { set_error("%s: %s: %s mismatch", who, src, status == kStrLength ? "length" : "checksum"); return ZWZ_E_CHECKSUM; }
+        if (status != kInfEnd) { set_error("%s: %s: stream status %u after %llu decoded bytes", who, src, status, (unsigned long long)h_par[6]); return ZWZ_E_FORMAT; }
         break;
     }
-    if (h_par[7] == 0) { set_error("zwz_inflate_index_file: %s decodes, but no index is made for a gzip file of several members", src); return ZWZ_E_FORMAT; }
-    std::vector<uint8_t> idx((size_t)h_par[7]);
-    HIPCHK(hipMemcpy(idx.data(), d_idx.p, idx.size(), hipMemcpyDeviceToHost));
-    const std::string part = std::string(dst_idx) + ".part";
-    FILE* f = fopen(part.c_str(), "wb");
-    if (!f) { set_error("cannot create %s", part.c_str()); return ZWZ_E_IO; }
-    const bool ok = fwrite(idx.data(), 1, idx.size(), f) == idx.size();
-    if (fclose(f) != 0 || !ok || rename(part.c_str(), dst_idx) != 0) { unlink(part.c_str()); set_error("cannot write %s", dst_idx); return ZWZ_E_IO; }
+    if (out) { out->resize((size_t)h_par[6]); if (!out->empty()) HIPCHK(hipMemcpy(out->data(), d_out.p, out->size(), hipMemcpyDeviceToHost)); }
+    if (idx) { idx->resize((size_t)h_par[7]); if (!idx->empty()) HIPCHK(hipMemcpy(idx->data(), d_idx.p, idx->size(), hipMemcpyDeviceToHost)); }
     return ZWZ_OK;
 }
-
-}  // namespace
 
 // A file of 2^29 bytes or more, or one whose decoded bytes one launch cannot hold, goes through the file loop in legs (zwz_legs_file.cpp).
 extern "C" int zwz_inflate_index_file(zwz_ctx* c, int wrap, const char* src, const char* dst_idx) {
@@ -519,8 +503,12 @@ extern "C" int zwz_inflate_index_file(zwz_ctx* c, int wrap, const char* src, con
     struct stat sb;
     if (stat(src, &sb) != 0) { set_error("cannot open %s", src); return ZWZ_E_IO; }
     if ((uint64_t)sb.st_size >= kStreamMaxIn) return zwz_inflate_legs_file(c, wrap, src, nullptr, dst_idx, nullptr);
-    const int rc = index_file_one_launch(c, wrap, src, dst_idx);
-    return rc == kGoLegs ? zwz_inflate_legs_file(c, wrap, src, nullptr, dst_idx, nullptr) : rc;
+    std::vector<uint8_t> in, idx;
+    if (int rc = read_whole_file(src, &in, 32)) return rc;
+    const int rc = inflate_whole_file(c, wrap, "zwz_inflate_index_file", src, in.data(), in.size() - 32, nullptr, &idx);
+    if (rc) return rc == kGoLegs ? zwz_inflate_legs_file(c, wrap, src, nullptr, dst_idx, nullptr) : rc;
+    if (idx.empty()) { set_error("zwz_inflate_index_file: %s decodes, but no index is made for a gzip file of several members", src); return ZWZ_E_FORMAT; }
+    return commit_with_index_bytes(dst_idx, nullptr, idx.data(), idx.size(), [] { return (int)ZWZ_OK; }, "cannot write %s", false);
 }
 
 namespace {

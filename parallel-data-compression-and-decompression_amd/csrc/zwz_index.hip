@@ -6,8 +6,8 @@
 #include "../../include/zwz.h"
 #include "adler_wg.h"
 #include "copy_wg.h"
-#include "crc_wg.h"
 #include "dstream_core.h"
+#include "index_seal_wg.h"
 #include "zwz_device.h"
 #include "zwz_index.h"
 
@@ -43,12 +43,10 @@ __global__ void __launch_bounds__(kBgzfThreads) index_windows_kernel(const CrcTa
             at += h;
         }
         for (uint64_t z = kIdxHeader + (uint64_t)count * kIdxEntry + at + t; z < len; z += kBgzfThreads) p[z] = 0;
-        __threadfence();
-        __syncthreads();
-        const uint32_t crc = crc_block_wg(s, p + kIdxHeader, (uint32_t)(len - kIdxHeader));
-        if (t == 0) {
+        const uint32_t crc = index_crc_wg(s, p, (uint32_t)len);
+        if (t == 0) {                                                         // (the words the marking form has not left: index_header_words' others)
             uint32_t* h = reinterpret_cast<uint32_t*>(p);
-            h[0] = 0x495a575au; h[1] = 0x01005844u;                           // "ZWZIDX\0\1"
+            h[0] = kIdxMagicLo; h[1] = kIdxMagicHi;
             h[2] = b.wrap; h[3] = b.span;
             const uint64_t n = b.in_len[i];
             h[4] = (uint32_t)n; h[5] = (uint32_t)(n >> 32);

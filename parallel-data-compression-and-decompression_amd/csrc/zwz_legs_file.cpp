@@ -34,7 +34,7 @@ struct LegFileJob {
     const char* src = nullptr;
     uint32_t wrap = 0, span = 0;
     FILE *in = nullptr, *out = nullptr, *spool = nullptr;
-    std::string out_part, idx_part, spool_path;
+    std::string out_part, spool_path;
     Mem h_in{nullptr, 0, true}, h_commit[2] = {{nullptr, 0, true}, {nullptr, 0, true}}, h_pack{nullptr, 0, true}, h_small{nullptr, 0, true}, h_pieces{nullptr, 0, true};
     Mem d_in, d_out, d_carry, d_ent, d_pack, d_small, d_pieces;
     uint64_t live = 0, peak = 0;
@@ -184,10 +184,8 @@ struct LegFileJob {
     }
 };
 
-// header, entries, the spooled windows, zero padding -> idx_part
-int write_index(LegFileJob& job, const LegIndexParts& parts, uint64_t stream_len, const LegState& s) {
-    FILE* f = fopen(job.idx_part.c_str(), "wb");
-    if (!f) { set_error("cannot create %s", job.idx_part.c_str()); return ZWZ_E_IO; }
+// header, entries, the spooled windows, zero padding -> f, the index's .part (commit_with_index's body)
+bool write_index(FILE* f, LegFileJob& job, const LegIndexParts& parts, uint64_t stream_len, const LegState& s) {
     uint8_t head[kIdxHeader];
     const uint8_t zeros[16] = {};
     parts.header(head, job.wrap, job.span, stream_len, s);
@@ -199,9 +197,7 @@ int write_index(LegFileJob& job, const LegIndexParts& parts, uint64_t stream_len
         ok = fread(buf.data(), 1, k, job.spool) == k && fwrite(buf.data(), 1, k, f) == k;
         left -= k;
     }
-    ok = ok && fwrite(zeros, 1, parts.pad(), f) == parts.pad();
-    if (fclose(f) != 0 || !ok) { unlink(job.idx_part.c_str()); set_error("cannot write %s", job.idx_part.c_str()); return ZWZ_E_IO; }
-    return ZWZ_OK;
+    return ok && fwrite(zeros, 1, parts.pad(), f) == parts.pad();
 }
 
 }  // namespace
@@ -225,8 +221,7 @@ extern "C" int zwz_inflate_legs_file(zwz_ctx* c, int wrap, const char* src, cons
         if (!job.out) { set_error("cannot create %s", job.out_part.c_str()); return ZWZ_E_IO; }
     }
     if (dst_idx) {
-        job.idx_part = std::string(dst_idx) + ".part";
-        job.spool_path = job.idx_part + ".windows";
+        job.spool_path = std::string(dst_idx) + ".part.windows";
         job.spool = fopen(job.spool_path.c_str(), "w+b");
         if (!job.spool) { set_error("cannot create %s", job.spool_path.c_str()); return ZWZ_E_IO; }
     }
@@ -257,23 +252,14 @@ extern "C" int zwz_inflate_legs_file(zwz_ctx* c, int wrap, const char* src, cons
         if (s.mk_full) { set_error("zwz_inflate_legs_file: %s decodes, but its index would take 2^32 bytes or more at this span: none is made", src); return ZWZ_E_FORMAT; }
         if (s.mk_second || !s.mk_have_end || !s.mk_count) { set_error("zwz_inflate_index_file: %s decodes, but no index is made for a gzip file of several members", src); return ZWZ_E_FORMAT; }
         if (parts.count() != s.mk_count || kIdxHeader + parts.entries.size() + parts.win_bytes != s.mk_bytes) { set_error("zwz_inflate_legs_file: %s: the committed index parts do not add up", src); return ZWZ_E_FORMAT; }
-        if (int r = write_index(job, parts, size, s)) return r;
     }
-    if (dst) {
+    auto commit = [&]() -> int {
+        if (!dst) return ZWZ_OK;
         FILE* f = job.out;
         job.out = nullptr;
-        if (fclose(f) != 0 || rename(job.out_part.c_str(), dst) != 0) {
-            unlink(job.out_part.c_str());
-            if (dst_idx) unlink(job.idx_part.c_str());
-            set_error("cannot write %s", dst);
-            return ZWZ_E_IO;
-        }
-    }
-    if (dst_idx && rename(job.idx_part.c_str(), dst_idx) != 0) {
-        unlink(job.idx_part.c_str());
-        if (dst) unlink(dst);
-        set_error("cannot write %s", dst_idx);
-        return ZWZ_E_IO;
-    }
-    return ZWZ_OK;
+        if (fclose(f) != 0 || rename(job.out_part.c_str(), dst) != 0) { unlink(job.out_part.c_str()); set_error("cannot write %s", dst); return ZWZ_E_IO; }
+        return ZWZ_OK;
+    };
+    if (!dst_idx) return commit();
+    return commit_with_index(dst_idx, dst, [&](FILE* f) { return write_index(f, job, parts, size, s); }, commit, "cannot write %s");
 }

@@ -347,38 +347,15 @@ int inflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
         if (job.out) { fclose(job.out); job.out = nullptr; unlink(job.part.c_str()); }
         return zwz_inflate_legs_file(c, wrap_, src, dst, dst_idx, nullptr);
     };
-    // the whole file as one stream through zwz_inflate_streams_dev, the capacity doubled until it fits; what was written is dropped.
-    // kGoLegs: the decoded bytes do not fit the largest capacity of one launch
-    constexpr int kGoLegs = 1;
+    // the whole file as one stream through one launch (inflate_whole_file); what was written is dropped
     auto one_stream = [&]() -> int {
         job.join();
         if (fflush(job.out) != 0 || ftruncate(fileno(job.out), 0) != 0 || fseeko(job.out, 0, SEEK_SET) != 0) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
         for (int i = 0; i < 4; i++) { if (job.h[i]) { (void)hipHostFree(job.h[i]); job.h[i] = nullptr; } if (i < 2 && job.d[i]) { (void)hipFree(job.d[i]); job.d[i] = nullptr; } }
-        std::vector<uint8_t> whole((size_t)size + 16, 0);
+        std::vector<uint8_t> whole((size_t)size + 32, 0), outv;
         fseeko(job.in, 0, SEEK_SET);
         if (read_full(job.in, whole.data(), (size_t)size, &io_err) != size || io_err) { set_error("read error on %s", src); return ZWZ_E_IO; }
-        HIPCHK(hipMalloc(&job.d[0], round_up((size_t)size + 16, 16)));
-        HIPCHK(hipMemcpy(job.d[0], whole.data(), round_up((size_t)size, 16), hipMemcpyHostToDevice));
-        uint64_t cap = std::max<uint64_t>(8 * size, 1u << 20);
-        for (;;) {
-            cap = std::min<uint64_t>(cap, kStreamMaxOut - 16);
-            if (job.d[1]) { (void)hipFree(job.d[1]); job.d[1] = nullptr; }
-            HIPCHK(hipMalloc(&job.d[1], cap + 16));
-            h_par[0] = 0; h_par[1] = size; h_par[2] = 0; h_par[3] = cap;
-            HIPCHK(hipMemcpy(d_par, h_par, 32, hipMemcpyHostToDevice));
-            if (int rc = zwz_inflate_streams_dev(c, wrap_, static_cast<uint8_t*>(job.d[0]), d_par, d_par + 1, 1, static_cast<uint8_t*>(job.d[1]), d_par + 2, d_par + 3,
-                                                 d_par + 4, reinterpret_cast<uint32_t*>(d_par + 5))) return rc;
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipMemcpy(h_par + 4, d_par + 4, 16, hipMemcpyDeviceToHost));
-            const uint32_t status = (uint32_t)h_par[5];
-            if (status == kInfOverflow && cap < kStreamMaxOut - 16) { cap *= 2; continue; }
-            if (status == kInfOverflow) return kGoLegs;
-            if (status == kStrChecksum || status == kStrLength) { set_error("zwz_inflate_stream_file: %s: %s mismatch", src, status == kStrLength ? "length" : "checksum"); return ZWZ_E_CHECKSUM; }
-            if (status != kInfEnd) { set_error("zwz_inflate_stream_file: %s: stream status %u after %llu decoded bytes", src, status, (unsigned long long)h_par[4]); return ZWZ_E_FORMAT; }
-            break;
-        }
-        std::vector<uint8_t> outv((size_t)h_par[4]);
-        if (!outv.empty()) HIPCHK(hipMemcpy(outv.data(), job.d[1], outv.size(), hipMemcpyDeviceToHost));
+        if (int rc = inflate_whole_file(c, wrap_, "zwz_inflate_stream_file", src, whole.data(), size, &outv, nullptr)) return rc;
         if (!outv.empty() && fwrite(outv.data(), 1, outv.size(), job.out) != outv.size()) { set_error("write error on %s", job.part.c_str()); return ZWZ_E_IO; }
         return job.commit(dst);
     };
@@ -418,14 +395,7 @@ int inflate_stream_file_core(zwz_ctx* c, int wrap_, const char* src, const char*
     if (count > 0xffffffffull) { set_error("zwz_inflate_split_index_file: more than 2^32 - 1 index entries"); return ZWZ_E_INVALID; }
     ents.resize((size_t)index_flush_bytes(count));
     index_flush_seal(ents.data(), wrap, c->index_span_bytes, size, total, (uint32_t)count, end_bit, wrap == kWrapRaw ? 0u : check);
-    const std::string ipart = std::string(dst_idx) + ".part";
-    FILE* fi = fopen(ipart.c_str(), "wb");
-    if (!fi) { set_error("cannot create %s", ipart.c_str()); return ZWZ_E_IO; }
-    const bool wrote = fwrite(ents.data(), 1, ents.size(), fi) == ents.size();
-    if ((fclose(fi) != 0) | !wrote) { unlink(ipart.c_str()); set_error("write error on %s", ipart.c_str()); return ZWZ_E_IO; }
-    if (dst) if (int rc = job.commit(dst)) { unlink(ipart.c_str()); return rc; }
-    if (rename(ipart.c_str(), dst_idx) != 0) { unlink(ipart.c_str()); if (dst) unlink(dst); set_error("cannot write %s", dst_idx); return ZWZ_E_IO; }
-    return ZWZ_OK;
+    return commit_with_index_bytes(dst_idx, dst, ents.data(), ents.size(), [&] { return dst ? job.commit(dst) : (int)ZWZ_OK; });
 }
 
 }  // namespace

@@ -7,7 +7,7 @@
 #include "adler_wg.h"
 #include "crc_wg.h"
 #include "dstream_core.h"
-#include "index_core.h"
+#include "index_seal_wg.h"
 #include "zwz_bgzf.h"
 #include "zwz_device.h"
 #include "zwz_split.h"
@@ -282,19 +282,9 @@ __global__ void __launch_bounds__(kBgzfThreads) split_seal_kernel(const CrcTable
         }
         uint8_t* q = X.idx + X.idx_off[s];
         if (t == 0 && (count & 1u)) reinterpret_cast<uint64_t*>(q + kIdxHeader)[3u * count] = 0;      // 24 count is 8 mod 16: the padding
-        __threadfence();
-        __syncthreads();
-        const uint32_t crc = crc_block_wg(lds, q + kIdxHeader, (uint32_t)(len - kIdxHeader));
-        if (t == 0) {
-            const uint64_t n = S.in_len[s], end_bit = split_final_end_bit(res2[s].x, res2[s].z);
-            uint32_t* h = reinterpret_cast<uint32_t*>(q);
-            h[0] = 0x495a575au; h[1] = 0x01005844u;                               // "ZWZIDX\0\1"
-            h[2] = S.wrap; h[3] = X.span;
-            h[4] = (uint32_t)n; h[5] = (uint32_t)(n >> 32); h[6] = r.z; h[7] = 0;
-            h[8] = (uint32_t)count; h[9] = 0; h[10] = (uint32_t)end_bit; h[11] = (uint32_t)(end_bit >> 32);
-            h[12] = S.wrap == kWrapRaw ? 0u : r.w; h[13] = crc; h[14] = 0; h[15] = 0;
-            X.idx_len[s] = len;
-        }
+        index_seal_wg(lds, q, (uint32_t)len, IndexHeader{S.wrap, X.span, S.in_len[s], r.z, (uint32_t)count, split_final_end_bit(res2[s].x, res2[s].z),
+                                                         S.wrap == kWrapRaw ? 0u : r.w, 0u});
+        if (t == 0) X.idx_len[s] = len;
         __syncthreads();
     }
 }

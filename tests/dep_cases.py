@@ -487,7 +487,7 @@ def slice_counts(lens, m):
 
 
 def check_long_stream_order(names, lens):
-    """What dstream_dep_combine_kernel sees of the long streams: it joins the full pieces of a stream in a slice (all but the last
+    """What dstream_combine_kernel sees of the long streams: it joins the full pieces of a stream in a slice (all but the last
     one there) in rows of K = ceil(full / 64) values -- full = 63, 64, 65 and 128 and more, and the checksum carried between slices"""
     assert list(names) == [s[0] for s in LONG_STREAMS] and len(lens) == len(names)
     full = {m: [[c - 1 for c in s] for s in slice_counts(lens, m)] for m in LONG_SLICES}

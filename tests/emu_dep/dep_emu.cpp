@@ -114,22 +114,6 @@ bool dep_chunk_level(int level, const uint8_t* in, uint32_t L, uint32_t skip, Pi
     return false;
 }
 
-// dstream_combine_kernel's schedule with the piece length as an argument (../emu_dstream has it for kPieceBytes)
-template <class Sum>
-uint32_t join_slice(uint32_t acc, const std::vector<uint32_t>& val, const std::vector<uint32_t>& len, size_t lo, size_t hi, uint32_t piece) {
-    const uint32_t full = (uint32_t)(hi - lo) - 1u, p1 = Sum::pof(piece);
-    if (full) {
-        const uint32_t K = (full + kSumRow - 1u) / kSumRow, pad = K * kSumRow - full;
-        uint32_t row[kSumRow];
-        for (uint32_t l = 0; l < kSumRow; l++) {
-            row[l] = Sum::identity();
-            for (uint32_t j = 0; j < K; j++) { const uint32_t v = l * K + j; if (v >= pad) row[l] = Sum::join(row[l], val[lo + v - pad], p1); }
-        }
-        acc = Sum::join(acc, sum_fold_row_host<Sum>(row, sum_ptimes<Sum>(p1, K)), sum_ptimes<Sum>(p1, full));
-    }
-    return Sum::join(acc, val[hi - 1], Sum::pof(len[hi - 1]));
-}
-
 struct Stream { std::vector<uint8_t> bytes; std::vector<uint64_t> piece_at; uint32_t check = 0; };     // piece_at: the byte every piece starts at
 
 // 0: fine; else which of the emu's own checks failed
@@ -165,8 +149,8 @@ uint32_t dep_stream(int level, uint32_t wrap, const uint8_t* in, uint64_t n, uin
     uint32_t check = dstream_check_init(wrap);
     for (size_t lo = 0; lo < val.size(); lo += slice) {
         const size_t hi = std::min(val.size(), lo + slice);
-        if (wrap == kWrapZlib) check = join_slice<AdlerSum>(check, val, len, lo, hi, kDepPieceBytes);
-        else if (wrap == kWrapGzip) check = join_slice<CrcSum>(check, val, len, lo, hi, kDepPieceBytes);
+        if (wrap == kWrapZlib) check = sum_join_slice_host<AdlerSum>(check, val.data() + lo, len.data() + lo, hi - lo, kDepPieceBytes);
+        else if (wrap == kWrapGzip) check = sum_join_slice_host<CrcSum>(check, val.data() + lo, len.data() + lo, hi - lo, kDepPieceBytes);
     }
     st.check = check;
     for (uint32_t i = 0; i < 2u + dstream_trailer_bytes(wrap); i++) o.push_back((uint8_t)dstream_tail_byte(wrap, i, check, n));

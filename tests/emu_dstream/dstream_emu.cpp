@@ -48,23 +48,6 @@ uint32_t piece_records(const uint8_t* in, uint32_t L, const uint32_t* e128, cons
     return nblocks;
 }
 
-template <class Sum>
-uint32_t join_slice(uint32_t acc, const std::vector<uint32_t>& val, const std::vector<uint32_t>& len, size_t lo, size_t hi) {
-    // dstream_combine_kernel: of all but the slice's last piece, K in a row per lane, the short share in front; the lanes folded; then
-    // the last piece by its length
-    const uint32_t full = (uint32_t)(hi - lo) - 1u, p1 = Sum::pof(kPieceBytes);
-    if (full) {
-        const uint32_t K = (full + kSumRow - 1u) / kSumRow, pad = K * kSumRow - full;
-        uint32_t row[kSumRow];
-        for (uint32_t l = 0; l < kSumRow; l++) {
-            row[l] = Sum::identity();
-            for (uint32_t j = 0; j < K; j++) { const uint32_t v = l * K + j; if (v >= pad) row[l] = Sum::join(row[l], val[lo + v - pad], p1); }
-        }
-        acc = Sum::join(acc, sum_fold_row_host<Sum>(row, sum_ptimes<Sum>(p1, K)), sum_ptimes<Sum>(p1, full));
-    }
-    return Sum::join(acc, val[hi - 1], Sum::pof(len[hi - 1]));
-}
-
 }  // namespace
 
 // The stream of in[0, n) under `wrap`, its pieces joined `slice` at a time; returns the length it needs (out receives at most cap bytes)
@@ -99,8 +82,8 @@ extern "C" uint64_t emu_deflate_stream(uint32_t wrap, const uint8_t* in, uint64_
     uint32_t check = dstream_check_init(wrap);
     for (size_t lo = 0; lo < val.size(); lo += slice) {
         const size_t hi = std::min(val.size(), lo + slice);
-        if (wrap == kWrapZlib) check = join_slice<AdlerSum>(check, val, len, lo, hi);
-        else if (wrap == kWrapGzip) check = join_slice<CrcSum>(check, val, len, lo, hi);
+        if (wrap == kWrapZlib) check = sum_join_slice_host<AdlerSum>(check, val.data() + lo, len.data() + lo, hi - lo, kPieceBytes);
+        else if (wrap == kWrapGzip) check = sum_join_slice_host<CrcSum>(check, val.data() + lo, len.data() + lo, hi - lo, kPieceBytes);
     }
     for (uint32_t i = 0; i < 2u + dstream_trailer_bytes(wrap); i++) o.push_back((uint8_t)dstream_tail_byte(wrap, i, check, n));
     memcpy(out, o.data(), (size_t)std::min<uint64_t>(cap, o.size()));
@@ -111,11 +94,10 @@ extern "C" uint64_t emu_deflate_stream_bound(uint64_t n, uint32_t wrap) { return
 
 // The checksum of pieces joined as the device joins them (values and lengths given; all lengths but each slice's last are kPieceBytes)
 extern "C" uint32_t emu_join(uint32_t wrap, const uint32_t* val, const uint32_t* len, uint64_t k, uint32_t slice) {
-    std::vector<uint32_t> v(val, val + k), l(len, len + k);
     uint32_t check = dstream_check_init(wrap);
     for (size_t lo = 0; lo < k; lo += slice) {
         const size_t hi = std::min<size_t>(k, lo + slice);
-        check = wrap == kWrapZlib ? join_slice<AdlerSum>(check, v, l, lo, hi) : join_slice<CrcSum>(check, v, l, lo, hi);
+        check = wrap == kWrapZlib ? sum_join_slice_host<AdlerSum>(check, val + lo, len + lo, hi - lo, kPieceBytes) : sum_join_slice_host<CrcSum>(check, val + lo, len + lo, hi - lo, kPieceBytes);
     }
     return check;
 }

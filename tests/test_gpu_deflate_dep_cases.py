@@ -1,7 +1,7 @@
 """zwz_deflate_dep_streams_dev on the GPU where tests/test_gpu_deflate_dep.py's corpus kinds do not reach: the hand-built pieces of
 tests/dep_cases.py (the entry at `skip` of lz_match, lz_parse, lz_lazy and blockify; blocks counted from there) under every value of
-the match option at every level, streams of 64 to 1 030 pieces whose checksums go through dstream_dep_combine_kernel's rows of two and
-more values, 0xff bytes through dstream_dep_adler_kernel, and twenty thousand streams through the layout's search.  Every output is
+the match option at every level, streams of 64 to 1 030 pieces whose checksums go through dstream_combine_kernel's rows of two and
+more values, 0xff bytes through dstream_adler_kernel, and twenty thousand streams through the layout's search.  Every output is
 compared with libz's (tests/deflate_dep_ref.py), byte for byte."""
 import random
 

@@ -11,10 +11,11 @@ bench.py is the project's yardstick and does not run this).  Fails without a GPU
   W4   256 MiB of random bytes as one raw stream
 --scale multiplies stream counts (W1, W2b, W3) and sizes (W2a, W4).  The text is workloads.text_rows_device (corpus.text_like's
 language, made on the device); streams are windows of one buffer.  Per workload the variants alternate in one process -- streams
-(zwz_deflate_streams_dev), bare (zwz_deflate_batch_dev on the same 65 280-byte pieces) and, where the input is one buffer, bgzf
-(zwz_bgzf_compress_dev) -- each a synchronised call, --warmup rounds untimed, then --steps rounds: the median per variant, and its
-spread (max - min) / median over the same rounds.  Every status must be 0; on a sample of at most 256 MiB per workload the output must be
-what Python's zlib inflates back to the input, the same sample gives the zlib rate on 16 threads (level 6, one window per stream)
+(zwz_deflate_streams_dev), dep (zwz_deflate_dep_streams_dev: the same call on dependent pieces, into buffers of its own), bare
+(zwz_deflate_batch_dev on the same 65 280-byte pieces) and, where the input is one buffer, bgzf (zwz_bgzf_compress_dev) -- each a
+synchronised call, --warmup rounds untimed, then --steps rounds: the median per variant, and its
+spread (max - min) / median over the same rounds.  Every status must be 0; on a sample of at most 256 MiB per workload the output of
+streams and of dep must be what Python's zlib inflates back to the input, the same sample gives the zlib rate on 16 threads (level 6, one window per stream)
 and the size against that one-window stream.  One JSON line on stdout (and in --out).
 """
 import argparse
@@ -150,6 +151,17 @@ def main():
         def streams():
             codec.deflate_streams_dev(wrap, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st)
         variants["streams"] = streams
+        # the same call shape on dependent pieces
+        dcaps = np.array([z.deflate_dep_stream_bound(int(k), wrap) for k in lens], dtype=np.int64)
+        doff = np.zeros(n, dtype=np.int64)
+        doff[1:] = np.cumsum((dcaps[:-1] + 15) // 16 * 16)
+        d_dout = torch.empty(int(doff[-1] + dcaps[-1] + 16), dtype=torch.uint8, device=dev)
+        d_dlen = torch.zeros(n, dtype=torch.int64, device=dev)
+        d_dst = torch.zeros(n, dtype=torch.int32, device=dev)
+
+        def dep():
+            codec.deflate_dep_streams_dev(wrap, d_in, offs, lens, d_dout, doff, dcaps, d_dlen, d_dst)
+        variants["dep"] = dep
 
         def bare():
             z._check(L.zwz_deflate_batch_dev(codec.handle, d_in.data_ptr(), d_poff.data_ptr(), d_plen.data_ptr(), nb, d_slots.data_ptr(), STRIDE,
@@ -186,11 +198,15 @@ def main():
         st, olen = d_st.cpu().numpy(), d_olen.cpu().numpy()
         r["out_bytes"] = int(olen.sum())
         ok = bool((st == 0).all()) and bool((olen <= caps).all())
+        dst, dlen = d_dst.cpu().numpy(), d_dlen.cpu().numpy()
+        r["dep_out_bytes"] = int(dlen.sum())
+        ok = ok and bool((dst == 0).all()) and bool((dlen <= dcaps).all())
         # sample: the first streams up to SAMPLE input bytes (at least one; a longer single stream is cut to its first SAMPLE bytes' pieces)
         m = max(1, int(np.searchsorted(np.cumsum(lens), SAMPLE, side="right")))
         hin = d_in[int(offs[:m].min()):int((offs[:m] + lens[:m]).max())].cpu().numpy()
         base = int(offs[:m].min())
         hout = [d_out[int(ooff[i]):int(ooff[i] + olen[i])].cpu().numpy().tobytes() for i in range(m)]
+        hdep = [d_dout[int(doff[i]):int(doff[i] + dlen[i])].cpu().numpy().tobytes() for i in range(m)]
         srcs = [hin[int(offs[i]) - base:int(offs[i]) - base + int(lens[i])].tobytes() for i in range(m)]
         if m == 1 and len(srcs[0]) > SAMPLE:              # one long stream: libz on its first SAMPLE bytes only
             srcs_cpu = [srcs[0][:SAMPLE]]
@@ -205,7 +221,8 @@ def main():
             one_window = sum(ex.map(one, srcs_cpu, chunksize=max(1, len(srcs_cpu) // (4 * THREADS))))
             dt = time.perf_counter() - t0
             back = list(ex.map(lambda s: zlib.decompress(s, WBITS[wrap]), hout, chunksize=max(1, m // (4 * THREADS))))
-        ok = ok and back == srcs
+            dback = list(ex.map(lambda s: zlib.decompress(s, WBITS[wrap]), hdep, chunksize=max(1, m // (4 * THREADS))))
+        ok = ok and back == srcs and dback == srcs
         cpu_bytes = sum(len(s) for s in srcs_cpu)
         r["cpu16_GBps"] = round(cpu_bytes / dt / 1e9, 3)
         r["streams_over_cpu16"] = round(r["streams_GBps"] / r["cpu16_GBps"], 1)
