@@ -22,15 +22,24 @@ and ordinary DEFLATE data of any size, a batch of independent streams in one lau
     Codec.inflate_streams / Codec.inflate_streams_dev          (raw, zlib or gzip; bytes or device tensors)
     Codec.inflate_stream / Codec.inflate_split_streams_dev     (one long stream with full-flush points: a wave per piece)
     Codec.inflate_stream_file                                  (one file of any size, in slices; `main gunzip`)
-    Codec.inflate_split_index_file                                             (the same for a file of any size; `main gunzip --split --write-index`, `main gzindex --split`)
-    Codec.inflate_stream_index / Codec.inflate_split_streams_index_dev         (the split decode that also writes the seek index of the flush points)
-    Codec.inflate_index / Codec.inflate_indexed / Codec.read_ranges            (the seek index of one ordinary stream: a wave per segment)
-    Codec.inflate_indexed_batch / Codec.read_ranges_batch, pack_indexes        (many indexed streams in one launch; the _dev forms)
-    Codec.inflate_legs_file                                    (one file of ANY length through leg windows: its bytes and / or its seek index; one wave)
+    Codec.inflate_split_index_file                             (the same with the file's seek index; `main gunzip --split --write-index`,
+                                                               `main gzindex --split`)
+    Codec.inflate_stream_index / Codec.inflate_split_streams_index_dev
+                                                               (the split decode that also writes the seek index of the flush points)
+    Codec.inflate_index / Codec.inflate_indexed / Codec.read_ranges
+                                                               (the seek index of one ordinary stream: a wave per segment)
+    Codec.inflate_indexed_batch / Codec.read_ranges_batch, pack_indexes
+                                                               (many indexed streams in one launch; the _dev forms)
+    Codec.inflate_legs / Codec.inflate_legs_dev                (streams of ANY length, decoded and indexed in legs; one wave a stream)
+    Codec.inflate_legs_file                                    (one file of ANY length through leg windows: its bytes and / or its index)
     Codec.deflate_streams / Codec.deflate_streams_dev          (the way there: libz's level-6 full-flush streams, any size)
     Codec.deflate_stream_file, deflate_stream_bound            (one file as one .gz / zlib / raw stream)
     Codec.deflate_streams_index / Codec.deflate_streams_index_dev, Codec.deflate_stream_file_index, deflate_stream_index_bound
                                                                (the same, with the seek index of the flush points written alongside)
+    Codec.deflate_dep_streams / Codec.deflate_dep_streams_dev  (streams of dependent pieces, pigz's default: smaller, no cut for a reader)
+    Codec.deflate_dep_stream_file, deflate_dep_stream_bound    (one file as one such stream; `main gzip --dependent`)
+    Codec.deflate_dep_streams_index / Codec.deflate_dep_streams_index_dev, Codec.deflate_dep_stream_file_index,
+    deflate_dep_stream_index_bound                             (the same, with the seek index, windows included, written alongside)
 and ZIP archives, a batch of entries per launch (what unzip, zipfile and file managers open; no reference counterpart):
     Codec.zip / Codec.unzip                                    ([(name, bytes)] -> archive bytes and back)
     Codec.zip_dev / Codec.unzip_dev                            (device tensors)
@@ -360,15 +369,17 @@ class Codec:
         full-flush points is decoded by a wave per piece (segments > 0) and gets the index of those points, without windows; any other
         stream is decoded by one wave (segments 0) and gets inflate_index's index (b"" for a gzip stream of several members).
         Capacity and errors as inflate_index."""
+        return self._inflate_index("inflate_stream_index", True, data, wrap, span, out_size)
+
+    def _inflate_index(self, who, split, data, wrap, span, out_size):
+        """inflate_index (split False) and inflate_stream_index (split True): one stream with its capacity guessed and doubled while it
+        overflows -> (decoded bytes, index bytes, segments)"""
         import numpy as np
         import torch
         w = WRAPS.get(wrap, wrap)
         data = bytes(data)
         span = int(span or 0)
-        cap = int(out_size) if out_size is not None else max(4 * len(data), 1 << 16)
-        if out_size is None and w == WRAP_GZIP and len(data) >= 4:
-            cap = max(int.from_bytes(data[-4:], "little"), 1)
-        cap = min(cap, STREAM_MAX_OUT - 1)
+        cap = min(int(out_size), STREAM_MAX_OUT - 1) if out_size is not None else _guess_cap(data, w)
         dev = torch.device("cuda", self.device)
         d_in = _device_input(torch, data, self.device)
         while True:
@@ -380,18 +391,19 @@ class Codec:
             par = torch.from_numpy(np.array([0, len(data), 0, cap, 0, bound, 0, 0], dtype=np.int64)).to(dev)
             d_st = torch.zeros(1, dtype=torch.int32, device=dev)
             d_seg = torch.zeros(1, dtype=torch.int32, device=dev)
+            streams = (w, d_in, par[0:1], par[1:2], d_out, par[2:3], par[3:4], par[6:7], d_st)
             torch.cuda.synchronize(dev)
-            self.inflate_split_streams_index_dev(w, d_in, par[0:1], par[1:2], d_out, par[2:3], par[3:4], par[6:7], d_st, d_seg, d_idx, par[4:5], par[5:6],
-                                                 par[7:8], span)
+            if split:
+                self.inflate_split_streams_index_dev(*streams, d_seg, d_idx, par[4:5], par[5:6], par[7:8], span)
+            else:
+                self.inflate_streams_index_dev(*streams, d_idx, par[4:5], par[5:6], par[7:8], span)
             self.sync()
             st, olen, ilen = int(d_st.item()), int(par[6].item()), int(par[7].item())
             if st == STREAM_OVERFLOW and out_size is None and cap < STREAM_MAX_OUT - 1:
                 cap = min(2 * cap, STREAM_MAX_OUT - 1)
                 continue
             if st != STREAM_END:
-                err = ZwzError("inflate_stream_index: status %d" % st)
-                err.status, err.index, err.stream_status = E_FORMAT, 0, st
-                raise err
+                raise _stream_error(who, st)
             return d_out[:olen].cpu().numpy().tobytes(), d_idx[:ilen].cpu().numpy().tobytes(), int(d_seg.item())
 
     def _with_span(self, span, call):
@@ -439,15 +451,13 @@ class Codec:
         d_out_len, d_idx_len (int64), d_status (int32): CUDA tensors of n.  d_idx None: decode only.  legs: a numpy uint32 array of 3 n
         that receives per stream the legs run, the legs rewound and the windows grown, or None.  The results are complete after sync()."""
         import numpy as np
-        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
-        n = len(arr[0])
-        if any(len(a) != n for a in arr):
-            raise ValueError("in_off, in_len, out_off and out_cap must have one element per stream")
+        arr, n = _u64_arrays(np, "in_off, in_len, out_off and out_cap must have one element per stream", (in_off, in_len, out_off, out_cap))
         ia = None
         if d_idx is not None:
-            ia = [np.ascontiguousarray(a, dtype=np.uint64) for a in (idx_off, idx_cap)]
-            if any(len(a) != n for a in ia) or d_idx_len is None:
-                raise ValueError("idx_off, idx_cap and d_idx_len go with d_idx, one element per stream")
+            what = "idx_off, idx_cap and d_idx_len go with d_idx, one element per stream"
+            ia, _ = _u64_arrays(np, what, (idx_off, idx_cap), n)
+            if d_idx_len is None:
+                raise ValueError(what)
         if legs is not None and (legs.dtype != np.uint32 or legs.size != 3 * n or not legs.flags["C_CONTIGUOUS"]):
             raise ValueError("legs must be a contiguous uint32 array of 3 n")
         _check(lib().zwz_inflate_legs_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n, d_out.data_ptr(),
@@ -476,18 +486,15 @@ class Codec:
         d_in, offs, lens = self._batch_input(torch, np, datas)
         caps = np.array([max(4 * len(d), 1 << 16) for d in datas] if out_caps is None else [int(x) for x in out_caps], dtype=np.uint64)
         while True:
-            slot = (caps + np.uint64(15)) // np.uint64(16) * np.uint64(16) + np.uint64(16)
-            ooff = np.zeros(n, dtype=np.uint64)
-            ooff[1:] = np.cumsum(slot[:-1])
-            d_out = torch.empty(int(ooff[-1] + slot[-1]), dtype=torch.uint8, device=dev)
+            ooff, total = _layout(np, caps, slack=16)
+            d_out = torch.empty(total, dtype=torch.uint8, device=dev)
             d_len = torch.zeros(n, dtype=torch.int64, device=dev)
             d_st = torch.zeros(n, dtype=torch.int32, device=dev)
             d_idx = ioff = icap = d_ilen = None
             if index:
                 icap = np.array([lib().zwz_inflate_index_bound(int(x), span) for x in caps], dtype=np.uint64)
-                ioff = np.zeros(n, dtype=np.uint64)
-                ioff[1:] = np.cumsum(icap[:-1])
-                d_idx = torch.empty(int(ioff[-1] + icap[-1]), dtype=torch.uint8, device=dev)
+                ioff, itotal = _layout(np, icap)            # (a bound is a multiple of 16: the slots are the bounds)
+                d_idx = torch.empty(itotal, dtype=torch.uint8, device=dev)
                 d_ilen = torch.zeros(n, dtype=torch.int64, device=dev)
             legs = np.zeros(3 * n, dtype=np.uint32)
             torch.cuda.synchronize(dev)
@@ -519,37 +526,7 @@ class Codec:
         """bytes of ONE ordinary raw / zlib / gzip stream -> (decoded bytes, index bytes): the one-wave decode that also keeps a
         checkpoint every `span` decoded bytes (None: the context's "index_span_bytes", 1 MiB).  The index is b"" where none is made
         (a gzip stream of several members).  Capacity as inflate_streams guesses and regrows it; raises ZwzError as it does."""
-        import numpy as np
-        import torch
-        w = WRAPS.get(wrap, wrap)
-        data = bytes(data)
-        span = int(span or 0)
-        cap = int(out_size) if out_size is not None else max(4 * len(data), 1 << 16)
-        if out_size is None and w == WRAP_GZIP and len(data) >= 4:
-            cap = max(int.from_bytes(data[-4:], "little"), 1)
-        cap = min(cap, STREAM_MAX_OUT - 1)
-        dev = torch.device("cuda", self.device)
-        d_in = _device_input(torch, data, self.device)
-        while True:
-            bound = lib().zwz_inflate_index_bound(cap, span)
-            if bound == 0:
-                raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
-            d_out = torch.empty((cap + 15) // 16 * 16 or 16, dtype=torch.uint8, device=dev)
-            d_idx = torch.empty(bound, dtype=torch.uint8, device=dev)
-            par = torch.from_numpy(np.array([0, len(data), 0, cap, 0, bound, 0, 0], dtype=np.int64)).to(dev)
-            d_st = torch.zeros(1, dtype=torch.int32, device=dev)
-            torch.cuda.synchronize(dev)
-            self.inflate_streams_index_dev(w, d_in, par[0:1], par[1:2], d_out, par[2:3], par[3:4], par[6:7], d_st, d_idx, par[4:5], par[5:6], par[7:8], span)
-            self.sync()
-            st, olen, ilen = int(d_st.item()), int(par[6].item()), int(par[7].item())
-            if st == STREAM_OVERFLOW and out_size is None and cap < STREAM_MAX_OUT - 1:
-                cap = min(2 * cap, STREAM_MAX_OUT - 1)
-                continue
-            if st != STREAM_END:
-                err = ZwzError("inflate_index: status %d" % st)
-                err.status, err.index, err.stream_status = E_FORMAT, 0, st
-                raise err
-            return d_out[:olen].cpu().numpy().tobytes(), d_idx[:ilen].cpu().numpy().tobytes()
+        return self._inflate_index("inflate_index", False, data, wrap, span, out_size)[:2]
 
     def inflate_indexed(self, data, index):
         """bytes of one stream and its index (inflate_index's, or any index of the layout in include/zwz.h) -> decoded bytes, one
@@ -568,9 +545,7 @@ class Codec:
         self.sync()
         st = int(d_st.item())
         if st != STREAM_END:
-            err = ZwzError("inflate_indexed: status %d" % st)
-            err.status, err.index, err.stream_status = E_FORMAT, 0, st
-            raise err
+            raise _stream_error("inflate_indexed", st)
         return d_out[:int(d_len.item())].cpu().numpy().tobytes()
 
     def read_ranges_dev(self, d_in, in_len, index, ranges, d_out, d_idx=None):
@@ -590,11 +565,11 @@ class Codec:
         d_status (int32), d_segments (int32, optional): n elements each, complete after sync().  ZwzError with status E_FORMAT,
         naming the stream, for a malformed index."""
         import numpy as np
-        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
+        what = "in_off, in_len, out_off, out_cap and the indexes must have one element per stream"
+        arr, n = _u64_arrays(np, what, (in_off, in_len, out_off, out_cap))
         pk = indexes if isinstance(indexes, PackedIndexes) else pack_indexes(indexes, idx_off)
-        n = len(arr[0])
-        if any(len(a) != n for a in arr) or pk.n != n:
-            raise ValueError("in_off, in_len, out_off, out_cap and the indexes must have one element per stream")
+        if pk.n != n:
+            raise ValueError(what)
         _check(lib().zwz_inflate_indexed_batch_dev(self._h, d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n, pk.blob.ctypes.data, pk.off.ctypes.data,
                                                    pk.len.ctypes.data, d_idx.data_ptr() if d_idx is not None else None, d_out.data_ptr(),
                                                    arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(), d_status.data_ptr(),
@@ -605,11 +580,11 @@ class Codec:
         streams of a batch laid out as inflate_indexed_batch_dev's, concatenated into d_out.  Only the touched segments are decoded;
         only the indexes of named streams are read; no checksum verdict.  Synchronous."""
         import numpy as np
-        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len)]
+        what = "in_off, in_len and the indexes must have one element per stream"
+        arr, n = _u64_arrays(np, what, (in_off, in_len))
         pk = indexes if isinstance(indexes, PackedIndexes) else pack_indexes(indexes, idx_off)
-        n = len(arr[0])
-        if len(arr[1]) != n or pk.n != n:
-            raise ValueError("in_off, in_len and the indexes must have one element per stream")
+        if pk.n != n:
+            raise ValueError(what)
         _check(lib().zwz_inflate_read_ranges_batch_dev(self._h, d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n, pk.blob.ctypes.data,
                                                        pk.off.ctypes.data, pk.len.ctypes.data, d_idx.data_ptr() if d_idx is not None else None,
                                                        ranges.ctypes.data, len(ranges), d_out.data_ptr()), "zwz_inflate_read_ranges_batch_dev")
@@ -617,20 +592,15 @@ class Codec:
     def _batch_input(self, torch, np, datas):
         """[bytes or CUDA uint8 tensor] -> (one 16-byte aligned CUDA tensor holding them at multiples of 16, offsets, lengths)"""
         dev = torch.device("cuda", self.device)
+        if not any(isinstance(d, torch.Tensor) for d in datas):
+            blob, offs, lens = _pack_host(np, datas)
+            return torch.from_numpy(blob).to(dev), offs, lens
         lens = np.array([d.numel() if isinstance(d, torch.Tensor) else len(d) for d in datas], dtype=np.uint64)
-        offs = np.zeros(len(datas), dtype=np.uint64)
-        if len(datas):
-            offs[1:] = np.cumsum((lens[:-1] + 15) // 16 * 16)
-        total = int(offs[-1] + (lens[-1] + 15) // 16 * 16) if len(datas) else 0
-        if any(isinstance(d, torch.Tensor) for d in datas):
-            d_in = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
-            for d, o, n in zip(datas, offs.tolist(), lens.tolist()):
-                d_in[o:o + n].copy_(d.reshape(-1) if isinstance(d, torch.Tensor) else torch.frombuffer(bytearray(d), dtype=torch.uint8))
-            return d_in, offs, lens
-        blob = np.zeros(max(total, 16), dtype=np.uint8)
+        offs, total = _layout(np, lens)
+        d_in = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
         for d, o, n in zip(datas, offs.tolist(), lens.tolist()):
-            blob[o:o + n] = np.frombuffer(d, dtype=np.uint8)
-        return torch.from_numpy(blob).to(dev), offs, lens
+            d_in[o:o + n].copy_(d.reshape(-1) if isinstance(d, torch.Tensor) else torch.frombuffer(bytearray(d), dtype=torch.uint8))
+        return d_in, offs, lens
 
     def inflate_indexed_batch(self, datas, indexes):
         """[bytes of one stream each] and their indexes -> [decoded bytes], every segment of every stream in one launch; the streams
@@ -646,11 +616,10 @@ class Codec:
         if n == 0:
             return []
         totals = np.array([index_info(x)["decoded_len"] for x in indexes], dtype=np.uint64)      # (validated before anything is sized by it)
-        ooff = np.zeros(n, dtype=np.uint64)
-        ooff[1:] = np.cumsum((totals[:-1] + 15) // 16 * 16)
+        ooff, total = _layout(np, totals)
         dev = torch.device("cuda", self.device)
         d_in, offs, lens = self._batch_input(torch, np, datas)
-        d_out = torch.empty(int(ooff[-1] + (totals[-1] + 15) // 16 * 16) or 16, dtype=torch.uint8, device=dev)
+        d_out = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
         d_len = torch.zeros(n, dtype=torch.int64, device=dev)
         d_st = torch.zeros(n, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
@@ -659,10 +628,8 @@ class Codec:
         st, olen, host = d_st.cpu().numpy(), d_len.cpu().numpy(), d_out.cpu().numpy()
         for i in range(n):
             if st[i] != STREAM_END:
-                err = ZwzError("inflate_indexed_batch: stream %d: status %d" % (i, st[i]))
-                err.status, err.index, err.stream_status = E_FORMAT, i, int(st[i])
-                raise err
-        return [host[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes() for i in range(n)]
+                raise _stream_error("inflate_indexed_batch", st[i], i)
+        return _cut(host, ooff, olen)
 
     def read_ranges_batch(self, datas, indexes, ranges):
         """Decoded byte ranges [(stream, offset, length), ...] out of a batch of ordinary streams with their seek indexes, in one call:
@@ -675,15 +642,18 @@ class Codec:
         if len(datas) != len(indexes):
             raise ValueError("one index per stream")
         rng = _ranges(np, ranges, 3)
-        total = int(rng[:, 2].sum()) if len(rng) else 0
-        dev = torch.device("cuda", self.device)
         d_in, offs, lens = self._batch_input(torch, np, datas)
+        return self._ranges_dev(torch, rng, as_tensor, lambda d_out: self.read_ranges_batch_dev(d_in, offs, lens, indexes, rng, d_out))
+
+    def _ranges_dev(self, torch, rng, as_tensor, call):
+        """The tail of the range and chunk reads on the device: room for what the rows' last column sums to, call(d_out) -- a
+        synchronous call, nothing to wait for behind it --, then the CUDA tensor of the ranges concatenated or the list of their bytes"""
+        total = int(rng[:, -1].sum()) if len(rng) else 0
+        dev = torch.device("cuda", self.device)
         d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
-        self.read_ranges_batch_dev(d_in, offs, lens, indexes, rng, d_out)
-        if as_tensor:
-            return d_out[:total]
-        return _split(d_out[:total].cpu().numpy().tobytes(), rng)
+        call(d_out)
+        return d_out[:total] if as_tensor else _split(d_out[:total].cpu().numpy().tobytes(), rng)
 
     def inflate_index_file(self, src, dst_idx, wrap="gzip", span=None):
         """One file holding one ordinary stream -> its seek index at dst_idx (zwz_inflate_index_file; `main gzindex`).  span: as
@@ -720,11 +690,8 @@ class Codec:
         segments are read (zwz_inflate_read_ranges_file)."""
         import numpy as np
         rng = _ranges(np, ranges)
-        total = int(rng[:, 1].sum()) if len(rng) else 0
-        out = np.empty(max(total, 1), dtype=np.uint8)
-        _check(lib().zwz_inflate_read_ranges_file(self._h, os.fsencode(src), os.fsencode(index_path), rng.ctypes.data, len(rng), out.ctypes.data),
-               "zwz_inflate_read_ranges_file")
-        return _split(out[:total].tobytes(), rng)
+        return _ranges_host(np, rng, lambda out: _check(lib().zwz_inflate_read_ranges_file(
+            self._h, os.fsencode(src), os.fsencode(index_path), rng.ctypes.data, len(rng), out.ctypes.data), "zwz_inflate_read_ranges_file"))
 
     def read_ranges(self, data, index, ranges):
         """Decoded byte ranges [(offset, length), ...] of an ordinary stream with its seek index: bytes -> a list of bytes; a CUDA uint8
@@ -734,38 +701,20 @@ class Codec:
         import torch
         as_tensor = isinstance(data, torch.Tensor)
         rng = _ranges(np, ranges)
-        total = int(rng[:, 1].sum()) if len(rng) else 0
-        dev = torch.device("cuda", self.device)
         d_in = _device_input(torch, data, self.device)
         n = data.numel() if as_tensor else len(data)
-        d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        self.read_ranges_dev(d_in, n, index, rng, d_out)
-        if as_tensor:
-            return d_out[:total]
-        return _split(d_out[:total].cpu().numpy().tobytes(), rng)
+        return self._ranges_dev(torch, rng, as_tensor, lambda d_out: self.read_ranges_dev(d_in, n, index, rng, d_out))
 
     def _streams_once(self, torch, np, wrap, streams, caps, split=False):
         """One call over host streams with the given capacities -> (statuses, [bytes])."""
         n = len(streams)
         dev = torch.device("cuda", self.device)
-        lens = np.array([len(s) for s in streams], dtype=np.int64)
-        offs = np.zeros(n, dtype=np.int64)
-        if n:
-            offs[1:] = np.cumsum((lens[:-1] + 15) // 16 * 16)
-        total_in = int(offs[-1] + (lens[-1] + 15) // 16 * 16) if n else 0
-        blob = np.zeros(max(total_in, 16), dtype=np.uint8)
-        for i, s in enumerate(streams):
-            blob[offs[i]:offs[i] + len(s)] = np.frombuffer(s, dtype=np.uint8)
-        cap = np.array(caps, dtype=np.int64)
-        ooff = np.zeros(n, dtype=np.int64)
-        if n:
-            ooff[1:] = np.cumsum((cap[:-1] + 15) // 16 * 16)
-        total_out = int(ooff[-1] + (cap[-1] + 15) // 16 * 16) if n else 0
+        blob, offs, lens = _pack_host(np, streams)
+        ooff, total_out = _layout(np, caps)
         d_in = torch.from_numpy(blob).to(dev)
         d_out = torch.empty(max(total_out, 16), dtype=torch.uint8, device=dev)
-        t = lambda a: torch.from_numpy(a).to(dev)
-        d_off, d_len, d_ooff, d_cap = t(offs), t(lens), t(ooff), t(cap)
+        t = lambda a: torch.from_numpy(np.asarray(a).astype(np.int64)).to(dev)      # (this family reads device arrays: int64 tensors)
+        d_off, d_len, d_ooff, d_cap = t(offs), t(lens), t(ooff), t(caps)
         d_olen = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
         d_st = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
@@ -774,7 +723,7 @@ class Codec:
         st = d_st[:n].cpu().numpy()
         olen = d_olen[:n].cpu().numpy()
         host = d_out.cpu().numpy()
-        return [int(x) for x in st], [host[ooff[i]:ooff[i] + olen[i]].tobytes() for i in range(n)]
+        return [int(x) for x in st], _cut(host, ooff, olen)
 
     def inflate_streams(self, streams, wrap="gzip", out_sizes=None, split=False):
         """[bytes] -> [decoded bytes]: a batch of independent raw / zlib / gzip streams of any size in one pass on the GPU.  Raises
@@ -791,12 +740,7 @@ class Codec:
         if out_sizes is not None:
             caps, grow = [int(c) for c in out_sizes], False
         else:
-            caps, grow = [], True
-            for s in streams:
-                guess = max(4 * len(s), 1 << 16)
-                if w == WRAP_GZIP and len(s) >= 4:
-                    guess = max(int.from_bytes(s[-4:], "little"), 1)
-                caps.append(min(guess, STREAM_MAX_OUT - 1))
+            caps, grow = [_guess_cap(s, w) for s in streams], True
         st, out = self._streams_once(torch, np, w, streams, caps, split)
         for i in range(len(streams)):
             while grow and st[i] == STREAM_OVERFLOW and caps[i] < STREAM_MAX_OUT - 1:
@@ -804,59 +748,88 @@ class Codec:
                 s1, o1 = self._streams_once(torch, np, w, [streams[i]], [caps[i]], split)
                 st[i], out[i] = s1[0], o1[0]
             if st[i] != STREAM_END:
-                err = ZwzError("inflate_streams: stream %d: status %d" % (i, st[i]))
-                err.status, err.index, err.stream_status = E_FORMAT, i, st[i]
-                raise err
+                raise _stream_error("inflate_streams", st[i], i)
         return out
 
     def deflate_streams_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status):
         """zwz_deflate_streams_dev: d_in / d_out uint8 device tensors, d_out_len int64 and d_status int32 device tensors; in_off, in_len,
         out_off, out_cap HOST sequences or numpy arrays (include/zwz.h has the alignment rules).  wrap: "raw" | "zlib" | "gzip" or
         WRAP_*.  Asynchronous; an output that does not fit is status 3 with the needed length in d_out_len, never an exception."""
-        import numpy as np
-        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
-        n = arr[1].size
-        if any(a.size != n for a in arr):
-            raise ValueError("in_off, in_len, out_off and out_cap must have one entry per stream")
-        _check(lib().zwz_deflate_streams_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n,
-                                             d_out.data_ptr(), arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(),
-                                             d_status.data_ptr()), "zwz_deflate_streams_dev")
+        self._deflate_streams_dev("zwz_deflate_streams_dev", wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status)
 
-    def deflate_streams(self, buffers, wrap="gzip"):
-        """[bytes] -> [bytes]: every buffer as one raw / zlib / gzip stream of its own, all in one pass on the GPU.  Each is what libz
-        writes at level 6 (or at this codec's level: set_level) with a full flush after every 65 280 bytes, so zlib.decompress /
-        gzip.decompress read it."""
+    def _deflate_streams_dev(self, fn, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status):
+        """the C function `fn` of zwz_deflate_streams_dev's arguments: either piece form"""
+        import numpy as np
+        arr, n = _u64_arrays(np, "in_off, in_len, out_off and out_cap must have one entry per stream", (in_off, in_len, out_off, out_cap))
+        _check(getattr(lib(), fn)(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n, d_out.data_ptr(),
+                                  arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(), d_status.data_ptr()), fn)
+
+    def _deflate_streams_index_dev(self, fn, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status, d_idx, idx_off, idx_cap,
+                                   d_idx_len, span):
+        """the C function `fn` of zwz_deflate_streams_index_dev's arguments: either piece form"""
+        import numpy as np
+        arr, n = _u64_arrays(np, "in_off, in_len, out_off, out_cap, idx_off and idx_cap must have one entry per stream",
+                             (in_off, in_len, out_off, out_cap, idx_off, idx_cap))
+        _check(getattr(lib(), fn)(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n, d_out.data_ptr(),
+                                  arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(), d_status.data_ptr(), int(span), d_idx.data_ptr(),
+                                  arr[4].ctypes.data, arr[5].ctypes.data, d_idx_len.data_ptr()), fn)
+
+    def _deflate_streams(self, dep, index, buffers, wrap, span):
+        """deflate_streams, deflate_streams_index and their deflate_dep_ forms: the buffers packed into one blob, every stream given its
+        bound, one call of the piece form's _dev wrapper -> [stream bytes], or [(stream bytes, index bytes)] with index"""
         import numpy as np
         import torch
+        if dep:
+            form, bound, index_bound = "deflate_dep_streams", deflate_dep_stream_bound, deflate_dep_stream_index_bound
+            call, index_call = self.deflate_dep_streams_dev, self.deflate_dep_streams_index_dev
+        else:
+            form, bound, index_bound = "deflate_streams", deflate_stream_bound, deflate_stream_index_bound
+            call, index_call = self.deflate_streams_dev, self.deflate_streams_index_dev
+        who = form + "_index" if index else form
         w = WRAPS.get(wrap, wrap)
         if w not in (WRAP_RAW, WRAP_ZLIB, WRAP_GZIP):
             raise ValueError("wrap must be raw, zlib or gzip")
+        span = int(span or 0)
+        if index and index_bound(1, span) == 0:
+            raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
         buffers = [bytes(b) for b in buffers]
         n = len(buffers)
         if n == 0:
             return []
         dev = torch.device("cuda", self.device)
-        up = lambda a: (a + 15) // 16 * 16
-        lens = np.array([len(b) for b in buffers], dtype=np.int64)
-        caps = np.array([deflate_stream_bound(int(k), w) for k in lens], dtype=np.int64)
-        offs, ooff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-        offs[1:] = np.cumsum(up(lens[:-1]))
-        ooff[1:] = np.cumsum(up(caps[:-1]))
-        blob = np.zeros(max(int(offs[-1] + up(lens[-1])), 16), dtype=np.uint8)
-        for i, b in enumerate(buffers):
-            blob[offs[i]:offs[i] + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        blob, offs, lens = _pack_host(np, buffers)
+        caps = np.array([bound(k, w) for k in lens.tolist()], dtype=np.uint64)
+        ooff, total = _layout(np, caps)
         d_in = torch.from_numpy(blob).to(dev)
-        d_out = torch.empty(int(ooff[-1] + up(caps[-1])), dtype=torch.uint8, device=dev)
+        d_out = torch.empty(total, dtype=torch.uint8, device=dev)
         d_olen = torch.zeros(n, dtype=torch.int64, device=dev)
         d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        if index:
+            # (with span 0 the context's span applies, which may be below the default: the smallest span bounds them all)
+            icap = np.array([index_bound(k, span or 16384) for k in lens.tolist()], dtype=np.uint64)
+            ioff, itotal = _layout(np, icap)
+            d_idx = torch.empty(itotal, dtype=torch.uint8, device=dev)
+            d_ilen = torch.zeros(n, dtype=torch.int64, device=dev)
         torch.cuda.synchronize(dev)
-        self.deflate_streams_dev(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st)
+        if index:
+            index_call(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st, d_idx, ioff, icap, d_ilen, span)
+        else:
+            call(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st)
         self.sync()
-        st, olen, host = d_st.cpu().numpy(), d_olen.cpu().numpy(), d_out.cpu().numpy()
+        st, olen, ilen = d_st.cpu().numpy(), d_olen.cpu().numpy(), d_ilen.cpu().numpy() if index else None
         for i in range(n):
-            if st[i] != 0:
-                raise ZwzError("deflate_streams: stream %d needs %d bytes, above its bound of %d" % (i, olen[i], caps[i]))
-        return [host[ooff[i]:ooff[i] + olen[i]].tobytes() for i in range(n)]
+            if st[i] != 0:      # (the dependent form has named deflate_dep_streams here for both of its calls since it was written)
+                raise ZwzError("%s: stream %d needs %d bytes, above its bound of %d" % (form if dep else who, i, olen[i], caps[i]))
+            if index and ilen[i] == 0:
+                raise ZwzError("%s: the index of stream %d does not fit its bound of %d bytes" % (who, i, icap[i]))
+        out = _cut(d_out.cpu().numpy(), ooff, olen)
+        return list(zip(out, _cut(d_idx.cpu().numpy(), ioff, ilen))) if index else out
+
+    def deflate_streams(self, buffers, wrap="gzip"):
+        """[bytes] -> [bytes]: every buffer as one raw / zlib / gzip stream of its own, all in one pass on the GPU.  Each is what libz
+        writes at level 6 (or at this codec's level: set_level) with a full flush after every 65 280 bytes, so zlib.decompress /
+        gzip.decompress read it."""
+        return self._deflate_streams(False, False, buffers, wrap, None)
 
     def deflate_streams_index_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status, d_idx, idx_off, idx_cap,
                                   d_idx_len, span=0):
@@ -864,61 +837,14 @@ class Codec:
         first piece start in every `span` decoded bytes, no windows -- at d_idx + idx_off[i] (d_idx a 16-byte aligned CUDA uint8 tensor,
         idx_off and idx_cap HOST sequences, d_idx_len an int64 device tensor: 0 with status 3 or a capacity too small).  span: a power of
         two in 16 KiB .. 1 GiB; 0: the context option "index_span_bytes".  Asynchronous."""
-        import numpy as np
-        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap, idx_off, idx_cap)]
-        n = arr[1].size
-        if any(a.size != n for a in arr):
-            raise ValueError("in_off, in_len, out_off, out_cap, idx_off and idx_cap must have one entry per stream")
-        _check(lib().zwz_deflate_streams_index_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n,
-                                                   d_out.data_ptr(), arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(),
-                                                   d_status.data_ptr(), int(span), d_idx.data_ptr(), arr[4].ctypes.data, arr[5].ctypes.data,
-                                                   d_idx_len.data_ptr()), "zwz_deflate_streams_index_dev")
+        self._deflate_streams_index_dev("zwz_deflate_streams_index_dev", wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status,
+                                        d_idx, idx_off, idx_cap, d_idx_len, span)
 
     def deflate_streams_index(self, buffers, wrap="gzip", span=None):
         """[bytes] -> [(stream, index)]: deflate_streams, and with every stream the seek index of its full-flush points, written as
         the stream is (nothing is decoded): what inflate_indexed, read_ranges and their batch and file forms take.  span: decoded
         bytes an entry covers at least, a power of two in 16 KiB .. 1 GiB (None: the context's "index_span_bytes", 1 MiB)."""
-        import numpy as np
-        import torch
-        w = WRAPS.get(wrap, wrap)
-        if w not in (WRAP_RAW, WRAP_ZLIB, WRAP_GZIP):
-            raise ValueError("wrap must be raw, zlib or gzip")
-        span = int(span or 0)
-        if lib().zwz_deflate_stream_index_bound(1, span) == 0:
-            raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
-        buffers = [bytes(b) for b in buffers]
-        n = len(buffers)
-        if n == 0:
-            return []
-        dev = torch.device("cuda", self.device)
-        up = lambda a: (a + 15) // 16 * 16
-        lens = np.array([len(b) for b in buffers], dtype=np.int64)
-        caps = np.array([deflate_stream_bound(int(k), w) for k in lens], dtype=np.int64)
-        # (with span 0 the context's span applies, which may be below the default: the smallest span bounds them all)
-        icap = np.array([lib().zwz_deflate_stream_index_bound(int(k), span or 16384) for k in lens], dtype=np.int64)
-        offs, ooff, ioff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-        offs[1:] = np.cumsum(up(lens[:-1]))
-        ooff[1:] = np.cumsum(up(caps[:-1]))
-        ioff[1:] = np.cumsum(icap[:-1])
-        blob = np.zeros(max(int(offs[-1] + up(lens[-1])), 16), dtype=np.uint8)
-        for i, b in enumerate(buffers):
-            blob[offs[i]:offs[i] + len(b)] = np.frombuffer(b, dtype=np.uint8)
-        d_in = torch.from_numpy(blob).to(dev)
-        d_out = torch.empty(int(ooff[-1] + up(caps[-1])), dtype=torch.uint8, device=dev)
-        d_idx = torch.empty(int(ioff[-1] + icap[-1]), dtype=torch.uint8, device=dev)
-        d_olen = torch.zeros(n, dtype=torch.int64, device=dev)
-        d_ilen = torch.zeros(n, dtype=torch.int64, device=dev)
-        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)
-        self.deflate_streams_index_dev(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st, d_idx, ioff, icap, d_ilen, span)
-        self.sync()
-        st, olen, ilen, host, ihost = d_st.cpu().numpy(), d_olen.cpu().numpy(), d_ilen.cpu().numpy(), d_out.cpu().numpy(), d_idx.cpu().numpy()
-        for i in range(n):
-            if st[i] != 0:
-                raise ZwzError("deflate_streams_index: stream %d needs %d bytes, above its bound of %d" % (i, olen[i], caps[i]))
-            if ilen[i] == 0:
-                raise ZwzError("deflate_streams_index: the index of stream %d does not fit its bound of %d bytes" % (i, icap[i]))
-        return [(host[ooff[i]:ooff[i] + olen[i]].tobytes(), ihost[ioff[i]:ioff[i] + ilen[i]].tobytes()) for i in range(n)]
+        return self._deflate_streams(False, True, buffers, wrap, span)
 
     def deflate_stream_file(self, src, dst, wrap="gzip"):
         """One file of any size as one gzip (.gz), zlib or raw DEFLATE stream, streamed through the GPU in slices."""
@@ -935,92 +861,27 @@ class Codec:
     def deflate_dep_streams_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status):
         """zwz_deflate_dep_streams_dev: deflate_streams_dev's arguments and results; every piece of 32 768 bytes is compressed with the
         32 512 bytes in front of it as its dictionary.  Needs the default strategy (ZwzError with status E_INVALID otherwise)."""
-        import numpy as np
-        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap)]
-        n = arr[1].size
-        if any(a.size != n for a in arr):
-            raise ValueError("in_off, in_len, out_off and out_cap must have one entry per stream")
-        _check(lib().zwz_deflate_dep_streams_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n,
-                                                 d_out.data_ptr(), arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(),
-                                                 d_status.data_ptr()), "zwz_deflate_dep_streams_dev")
+        self._deflate_streams_dev("zwz_deflate_dep_streams_dev", wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status)
 
     def deflate_dep_streams_index_dev(self, wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status, d_idx, idx_off, idx_cap,
                                       d_idx_len, span=0):
         """zwz_deflate_dep_streams_index_dev: deflate_streams_index_dev's arguments and results for streams of dependent pieces; every
         entry but the first carries the 32 512 input bytes in front of it as its window."""
-        import numpy as np
-        arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in (in_off, in_len, out_off, out_cap, idx_off, idx_cap)]
-        n = arr[1].size
-        if any(a.size != n for a in arr):
-            raise ValueError("in_off, in_len, out_off, out_cap, idx_off and idx_cap must have one entry per stream")
-        _check(lib().zwz_deflate_dep_streams_index_dev(self._h, WRAPS.get(wrap, wrap), d_in.data_ptr(), arr[0].ctypes.data, arr[1].ctypes.data, n,
-                                                       d_out.data_ptr(), arr[2].ctypes.data, arr[3].ctypes.data, d_out_len.data_ptr(),
-                                                       d_status.data_ptr(), int(span), d_idx.data_ptr(), arr[4].ctypes.data, arr[5].ctypes.data,
-                                                       d_idx_len.data_ptr()), "zwz_deflate_dep_streams_index_dev")
-
-    def _dep_streams(self, buffers, wrap, span, index):
-        import numpy as np
-        import torch
-        w = WRAPS.get(wrap, wrap)
-        if w not in (WRAP_RAW, WRAP_ZLIB, WRAP_GZIP):
-            raise ValueError("wrap must be raw, zlib or gzip")
-        span = int(span or 0)
-        if index and lib().zwz_deflate_dep_stream_index_bound(1, span) == 0:
-            raise ValueError("span must be a power of two in 16 KiB .. 1 GiB")
-        buffers = [bytes(b) for b in buffers]
-        n = len(buffers)
-        if n == 0:
-            return []
-        dev = torch.device("cuda", self.device)
-        up = lambda a: (a + 15) // 16 * 16
-        lens = np.array([len(b) for b in buffers], dtype=np.int64)
-        caps = np.array([deflate_dep_stream_bound(int(k), w) for k in lens], dtype=np.int64)
-        # (with span 0 the context's span applies, which may be below the default: the smallest span bounds them all)
-        icap = np.array([lib().zwz_deflate_dep_stream_index_bound(int(k), span or 16384) if index else 16 for k in lens], dtype=np.int64)
-        offs, ooff, ioff = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-        offs[1:] = np.cumsum(up(lens[:-1]))
-        ooff[1:] = np.cumsum(up(caps[:-1]))
-        ioff[1:] = np.cumsum(icap[:-1])
-        blob = np.zeros(max(int(offs[-1] + up(lens[-1])), 16), dtype=np.uint8)
-        for i, b in enumerate(buffers):
-            blob[offs[i]:offs[i] + len(b)] = np.frombuffer(b, dtype=np.uint8)
-        d_in = torch.from_numpy(blob).to(dev)
-        d_out = torch.empty(int(ooff[-1] + up(caps[-1])), dtype=torch.uint8, device=dev)
-        d_olen = torch.zeros(n, dtype=torch.int64, device=dev)
-        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)
-        if index:
-            d_idx = torch.empty(int(ioff[-1] + icap[-1]), dtype=torch.uint8, device=dev)
-            d_ilen = torch.zeros(n, dtype=torch.int64, device=dev)
-            self.deflate_dep_streams_index_dev(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st, d_idx, ioff, icap, d_ilen, span)
-        else:
-            self.deflate_dep_streams_dev(w, d_in, offs, lens, d_out, ooff, caps, d_olen, d_st)
-        self.sync()
-        st, olen, host = d_st.cpu().numpy(), d_olen.cpu().numpy(), d_out.cpu().numpy()
-        for i in range(n):
-            if st[i] != 0:
-                raise ZwzError("deflate_dep_streams: stream %d needs %d bytes, above its bound of %d" % (i, olen[i], caps[i]))
-        out = [host[ooff[i]:ooff[i] + olen[i]].tobytes() for i in range(n)]
-        if not index:
-            return out
-        ilen, ihost = d_ilen.cpu().numpy(), d_idx.cpu().numpy()
-        for i in range(n):
-            if ilen[i] == 0:
-                raise ZwzError("deflate_dep_streams_index: the index of stream %d does not fit its bound of %d bytes" % (i, icap[i]))
-        return [(out[i], ihost[ioff[i]:ioff[i] + ilen[i]].tobytes()) for i in range(n)]
+        self._deflate_streams_index_dev("zwz_deflate_dep_streams_index_dev", wrap, d_in, in_off, in_len, d_out, out_off, out_cap, d_out_len, d_status,
+                                        d_idx, idx_off, idx_cap, d_idx_len, span)
 
     def deflate_dep_streams(self, buffers, wrap="gzip"):
         """[bytes] -> [bytes]: every buffer as one raw / zlib / gzip stream of dependent pieces, pigz's default: pieces of 32 768 bytes,
         each primed with the 32 512 bytes in front of it and closed with a sync flush.  Smaller than deflate_streams' (5 % on text,
         almost half on data with long-range repeats) and as parallel to write; zlib.decompress / gzip.decompress read it, the split
         decode finds no cut in it -- write its index along with it (deflate_dep_streams_index) for parallel reads."""
-        return self._dep_streams(buffers, wrap, None, False)
+        return self._deflate_streams(True, False, buffers, wrap, None)
 
     def deflate_dep_streams_index(self, buffers, wrap="gzip", span=None):
         """[bytes] -> [(stream, index)]: deflate_dep_streams, and with every stream its seek index, written as the stream is: an entry
         at the first piece start in every `span` decoded bytes, each but the first with the 32 512 input bytes in front of it as its
         window.  What inflate_indexed, read_ranges and their batch and file forms take.  span: as deflate_streams_index."""
-        return self._dep_streams(buffers, wrap, span, True)
+        return self._deflate_streams(True, True, buffers, wrap, span)
 
     def deflate_dep_stream_file(self, src, dst, wrap="gzip"):
         """One file of any size as one stream of dependent pieces (`main gzip --dependent`)."""
@@ -1038,11 +899,10 @@ class Codec:
         in_off, in_len HOST sequences; names a list of bytes (or str, stored as UTF-8); meta None or a list of (dos_time, dos_date,
         external_attr).  Asynchronous; an archive that does not fit out_cap (default: d_out's size) is status 3, never an exception."""
         import numpy as np
-        off = np.ascontiguousarray(in_off, dtype=np.uint64)
-        ln = np.ascontiguousarray(in_len, dtype=np.uint64)
-        n = len(names)
-        if off.size != n or ln.size != n or (meta is not None and len(meta) != n):
-            raise ValueError("in_off, in_len, names and meta must have one entry per buffer")
+        what = "in_off, in_len, names and meta must have one entry per buffer"
+        (off, ln), n = _u64_arrays(np, what, (in_off, in_len), len(names))
+        if meta is not None and len(meta) != n:
+            raise ValueError(what)
         c_names = _c_names(names)
         c_meta = (ZipMeta * max(n, 1))(*[ZipMeta(*m) for m in meta]) if meta is not None else None
         _check(lib().zwz_zip_dev(self._h, d_in.data_ptr() if n else None, off.ctypes.data, ln.ctypes.data, c_names, c_meta, n, d_out.data_ptr(),
@@ -1053,20 +913,12 @@ class Codec:
         import numpy as np
         import torch
         entries = [(n, bytes(b)) for n, b in entries]
-        n = len(entries)
         dev = torch.device("cuda", self.device)
-        up = lambda a: (a + 15) // 16 * 16
-        lens = np.array([len(b) for _, b in entries], dtype=np.int64)
-        offs = np.zeros(n, dtype=np.int64)
-        if n:
-            offs[1:] = np.cumsum(up(lens[:-1]))
-        blob = np.zeros(max(int(offs[-1] + up(lens[-1])) if n else 0, 16), dtype=np.uint8)
-        for i, (_, b) in enumerate(entries):
-            blob[offs[i]:offs[i] + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        blob, offs, lens = _pack_host(np, [b for _, b in entries])
         names = [e[0] for e in entries]
         cap = zip_bound(lens, names)
         d_in = torch.from_numpy(blob).to(dev)
-        d_out = torch.empty(up(cap), dtype=torch.uint8, device=dev)
+        d_out = torch.empty((cap + 15) // 16 * 16, dtype=torch.uint8, device=dev)
         d_len = torch.zeros(1, dtype=torch.int64, device=dev)
         d_st = torch.zeros(1, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
@@ -1081,10 +933,7 @@ class Codec:
         sequence; d_out_len int64, d_status and d_segments int32 device tensors.  Waits for the context's stream while it runs; the
         results are complete after sync().  Never raises for an entry's status."""
         import numpy as np
-        n = len(entries)
-        off = np.ascontiguousarray(out_off, dtype=np.uint64)
-        if off.size != n:
-            raise ValueError("out_off must have one entry per entry")
+        (off,), n = _u64_arrays(np, "out_off must have one entry per entry", (out_off,), len(entries))
         _check(lib().zwz_unzip_dev(self._h, d_zip.data_ptr(), zip_len, ctypes.addressof(entries) if n else None, n, d_out.data_ptr(), off.ctypes.data,
                                    d_out_len.data_ptr(), d_status.data_ptr(), d_segments.data_ptr() if d_segments is not None else None),
                "zwz_unzip_dev")
@@ -1100,11 +949,7 @@ class Codec:
         if n == 0:
             return []
         dev = torch.device("cuda", self.device)
-        up = lambda a: (a + 15) // 16 * 16
-        ooff, total = [], 0
-        for e in ents:
-            ooff.append(total)
-            total += up(e.usize)
+        ooff, total = _layout(np, [e.usize for e in ents])
         d_zip = _device_input(torch, data, self.device)
         d_out = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
         d_len = torch.zeros(n, dtype=torch.int64, device=dev)
@@ -1113,10 +958,10 @@ class Codec:
         torch.cuda.synchronize(dev)
         self.unzip_dev(d_zip, len(data), ents, d_out, ooff, d_len, d_st, d_seg)
         self.sync()
-        host, olen, st, seg = d_out.cpu().numpy(), d_len.cpu().numpy(), d_st.cpu().numpy(), d_seg.cpu().numpy()
+        olen, st, seg = d_len.cpu().numpy(), d_st.cpu().numpy(), d_seg.cpu().numpy()
         out = []
-        for i, e in enumerate(ents):
-            item = (data[e.name_off:e.name_off + e.name_len], host[ooff[i]:ooff[i] + int(olen[i])].tobytes(), int(st[i]))
+        for i, (e, dec) in enumerate(zip(ents, _cut(d_out.cpu().numpy(), ooff, olen))):
+            item = (data[e.name_off:e.name_off + e.name_len], dec, int(st[i]))
             out.append(item + (int(seg[i]),) if with_segments else item)
         return out
 
@@ -1183,39 +1028,19 @@ class Codec:
         """BGZF bytes -> bytes; a CUDA uint8 tensor -> a CUDA uint8 tensor.  The member headers of bytes are walked on the host, those
         of a tensor on the GPU (nothing of it is copied to the host); everything else runs on the GPU.  ZwzError with status E_FORMAT /
         E_CHECKSUM on damage."""
-        import numpy as np
         import torch
         if isinstance(data, torch.Tensor):
-            return self._bgzf_decompress_tensor(torch, np, data)
+            d_gz, n = _device_input(torch, data, self.device), data.numel()
+            d_off, raw = self._bgzf_index_dev(torch, d_gz, n, "zwz_bgzf_index")
+            return self._bgzf_decompress_dev(torch, d_gz, n, d_off, raw)
         host = bytes(data)
-        count, raw = ctypes.c_uint32(0), ctypes.c_uint64(0)
-        _check(lib().zwz_bgzf_index(host, len(host), None, 0, ctypes.byref(count), ctypes.byref(raw)), "zwz_bgzf_index")
-        offs = np.zeros(max(count.value, 1), dtype=np.uint64)
-        _check(lib().zwz_bgzf_index(host, len(host), offs.ctypes.data, count.value, ctypes.byref(count), ctypes.byref(raw)), "zwz_bgzf_index")
-        dev = torch.device("cuda", self.device)
-        d_gz = _device_input(torch, host, self.device)
-        d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
-        d_out = torch.empty(max(raw.value, 1), dtype=torch.uint8, device=dev)
-        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
-        d_st = torch.zeros(max(count.value, 1), dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)
-        _check(lib().zwz_bgzf_decompress_dev(self._h, d_gz.data_ptr(), len(host), d_off.data_ptr(), count.value, d_out.data_ptr(),
-                                             d_len.data_ptr(), d_st.data_ptr()), "zwz_bgzf_decompress_dev")
-        self.sync()
-        st = d_st[:count.value].cpu().numpy()
-        bad = np.nonzero(st)[0]
-        if len(bad):
-            i, s = int(bad[0]), int(st[bad[0]])
-            code = E_CHECKSUM if s in (BGZF_ISIZE_MISMATCH, BGZF_CRC_MISMATCH) else E_FORMAT
-            err = ZwzError("zwz_bgzf_decompress_dev: member %d at byte offset %d: status %d" % (i, int(offs[i]), s))
-            err.status = code
-            raise err
-        return d_out[:int(d_len.item())].cpu().numpy().tobytes()
+        offs, raw = bgzf_index(host)
+        d_off = torch.tensor(offs, dtype=torch.int64, device=torch.device("cuda", self.device))
+        return self._bgzf_decompress_dev(torch, _device_input(torch, host, self.device), len(host), d_off, raw).cpu().numpy().tobytes()
 
-    def _bgzf_decompress_tensor(self, torch, np, data):
-        d_gz = _device_input(torch, data, self.device)
-        n = data.numel()
-        d_off, raw = self._bgzf_index_dev(torch, d_gz, n, "zwz_bgzf_index")
+    def _bgzf_decompress_dev(self, torch, d_gz, n, d_off, raw):
+        """zwz_bgzf_decompress_dev over the members at d_off (an int64 CUDA tensor) of a stream that decodes to raw bytes, and its
+        verdict -> a CUDA tensor of the decoded bytes.  Only the statuses and the first bad member's offset come to the host."""
         count = d_off.numel()
         dev = d_gz.device
         if not count:
@@ -1231,9 +1056,8 @@ class Codec:
         if bad.numel():
             i = int(bad[0].item())
             s = int(d_st[i].item())
-            code = E_CHECKSUM if s in (BGZF_ISIZE_MISMATCH, BGZF_CRC_MISMATCH) else E_FORMAT
             err = ZwzError("zwz_bgzf_decompress_dev: member %d at byte offset %d: status %d" % (i, int(d_off[i].item()), s))
-            err.status = code
+            err.status = E_CHECKSUM if s in (BGZF_ISIZE_MISMATCH, BGZF_CRC_MISMATCH) else E_FORMAT
             raise err
         return d_out[:int(d_len.item())]
 
@@ -1305,14 +1129,11 @@ class Codec:
         GPU; members holding a requested byte are decoded and checked.  include/zwz.h says what a valid chunk is."""
         torch, np, d_gz, n, ch, sizes = self._chunks_dev(gz, chunks)
         _check(lib().zwz_bgzf_chunk_sizes_dev(self._h, d_gz.data_ptr(), n, ch.ctypes.data, len(ch), sizes.ctypes.data), "zwz_bgzf_chunk_sizes_dev")
-        total = int(sizes[:len(ch)].sum())
-        d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=d_gz.device)
-        torch.cuda.synchronize(d_gz.device)
-        _check(lib().zwz_bgzf_read_chunks_dev(self._h, d_gz.data_ptr(), n, ch.ctypes.data, len(ch), d_out.data_ptr(), total, sizes.ctypes.data),
-               "zwz_bgzf_read_chunks_dev")
-        if isinstance(gz, torch.Tensor):
-            return d_out[:total], [int(x) for x in sizes[:len(ch)]]
-        return _split(d_out[:total].cpu().numpy().tobytes(), sizes[:len(ch)].reshape(-1, 1))
+        szs, as_tensor = sizes[:len(ch)].reshape(-1, 1), isinstance(gz, torch.Tensor)         # (a view: the read writes the sizes again)
+        total = int(szs.sum())
+        res = self._ranges_dev(torch, szs, as_tensor, lambda d_out: _check(lib().zwz_bgzf_read_chunks_dev(
+            self._h, d_gz.data_ptr(), n, ch.ctypes.data, len(ch), d_out.data_ptr(), total, sizes.ctypes.data), "zwz_bgzf_read_chunks_dev"))
+        return (res, [int(x) for x in szs[:, 0]]) if as_tensor else res
 
     def bgzf_read_chunks_file(self, src, chunks):
         """Chunks of virtual offsets of a BGZF file -> a list of bytes.  Only the file's bytes between a chunk's compressed offsets (and
@@ -1321,11 +1142,10 @@ class Codec:
         ch = _ranges(np, chunks)
         sizes = np.zeros(max(len(ch), 1), dtype=np.uint64)
         _check(lib().zwz_bgzf_chunk_sizes_file(os.fsencode(src), ch.ctypes.data, len(ch), sizes.ctypes.data), "zwz_bgzf_chunk_sizes_file")
-        total = int(sizes[:len(ch)].sum())
-        out = np.empty(max(total, 1), dtype=np.uint8)
-        _check(lib().zwz_bgzf_read_chunks_file(self._h, os.fsencode(src), ch.ctypes.data, len(ch), out.ctypes.data, total, sizes.ctypes.data),
-               "zwz_bgzf_read_chunks_file")
-        return _split(out[:total].tobytes(), sizes[:len(ch)].reshape(-1, 1))
+        szs = sizes[:len(ch)].reshape(-1, 1)
+        total = int(szs.sum())
+        return _ranges_host(np, szs, lambda out: _check(lib().zwz_bgzf_read_chunks_file(
+            self._h, os.fsencode(src), ch.ctypes.data, len(ch), out.ctypes.data, total, sizes.ctypes.data), "zwz_bgzf_read_chunks_file"))
 
     def bgzf_compress_file(self, src, dst):
         """src -> dst as BGZF, streamed through pinned staging (any size); dst appears only on success."""
@@ -1344,28 +1164,18 @@ class Codec:
         if gzi is None:
             gzi = self.bgzf_gzi(gz, _what="zwz_bgzf_gzi") if as_tensor else bgzf_gzi(bytes(gz))
         rng = _ranges(np, ranges)
-        total = int(rng[:, 1].sum()) if len(rng) else 0
-        dev = torch.device("cuda", self.device)
         d_gz = _device_input(torch, gz, self.device)
         n = gz.numel() if as_tensor else len(gz)
-        d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        _check(lib().zwz_bgzf_read_ranges_dev(self._h, d_gz.data_ptr(), n, bytes(gzi), len(gzi), rng.ctypes.data, len(rng), d_out.data_ptr()),
-               "zwz_bgzf_read_ranges_dev")
-        if as_tensor:
-            return d_out[:total]
-        return _split(d_out[:total].cpu().numpy().tobytes(), rng)
+        return self._ranges_dev(torch, rng, as_tensor, lambda d_out: _check(lib().zwz_bgzf_read_ranges_dev(
+            self._h, d_gz.data_ptr(), n, bytes(gzi), len(gzi), rng.ctypes.data, len(rng), d_out.data_ptr()), "zwz_bgzf_read_ranges_dev"))
 
     def bgzf_read_ranges_file(self, src, ranges, gzi=None):
         """Decoded byte ranges of a BGZF file -> a list of bytes.  gzi: path of its .gzi (only the touched members are read); None:
         the member headers are walked up to the last requested byte."""
         import numpy as np
         rng = _ranges(np, ranges)
-        total = int(rng[:, 1].sum()) if len(rng) else 0
-        out = np.empty(max(total, 1), dtype=np.uint8)
-        _check(lib().zwz_bgzf_read_ranges_file(self._h, os.fsencode(src), None if gzi is None else os.fsencode(gzi), rng.ctypes.data, len(rng),
-                                               out.ctypes.data), "zwz_bgzf_read_ranges_file")
-        return _split(out[:total].tobytes(), rng)
+        return _ranges_host(np, rng, lambda out: _check(lib().zwz_bgzf_read_ranges_file(
+            self._h, os.fsencode(src), None if gzi is None else os.fsencode(gzi), rng.ctypes.data, len(rng), out.ctypes.data), "zwz_bgzf_read_ranges_file"))
 
     def set_option(self, name, value):
         """Test / experiment switches of this context (include/zwz.h: zwz_ctx_set_option): "match" = auto | walk | band | lazy |
@@ -1454,6 +1264,78 @@ def _split(blob, rng):
     return out
 
 
+def _ranges_host(np, rng, call):
+    """The tail of the range and chunk reads of a file: room on the host for what the rows' last column sums to, call(out), then the
+    list of the ranges' bytes"""
+    total = int(rng[:, -1].sum()) if len(rng) else 0
+    out = np.empty(max(total, 1), dtype=np.uint8)
+    call(out)
+    return _split(out[:total].tobytes(), rng)
+
+
+def _layout(np, sizes, align=16, slack=0):
+    """Slots one behind the other, slot i of sizes[i] rounded up to `align` plus `slack` bytes -> (uint64 offsets, total bytes; 0
+    without a slot).  The one batch layout of this file: a caller that needs a minimum takes max(total, 16).  Sizes may come from
+    untrusted headers (a ZIP directory), so the sums are Python integers, which do not wrap: OverflowError for a negative slot or a
+    total of 2^64 or more, before anything is sized by an offset."""
+    off, total = [], 0
+    for s in (sizes.tolist() if hasattr(sizes, "tolist") else sizes):
+        slot = (int(s) + align - 1) // align * align + slack
+        if slot < 0:
+            raise OverflowError("batch layout: a slot of %d bytes" % slot)
+        off.append(total)
+        total += slot
+    if total >= 1 << 64:
+        raise OverflowError("batch layout: the slots take %d bytes, which 64 bits do not hold" % total)
+    return np.array(off, dtype=np.uint64), total
+
+
+def _blob(np, size, bufs, offs):
+    """A zeroed uint8 host array of `size` bytes holding bufs[i] at offs[i] (zeroed: the kernels read whole 16-byte vectors past a
+    buffer's end)"""
+    blob = np.zeros(size, dtype=np.uint8)
+    for b, o in zip(bufs, offs.tolist()):
+        blob[o:o + len(b)] = np.frombuffer(bytes(b), dtype=np.uint8)
+    return blob
+
+
+def _pack_host(np, bufs):
+    """[bytes] -> (one zeroed blob of at least 16 bytes holding them at multiples of 16, uint64 offsets, uint64 lengths)"""
+    lens = np.array([len(b) for b in bufs], dtype=np.uint64)
+    offs, total = _layout(np, lens)
+    return _blob(np, max(total, 16), bufs, offs), offs, lens
+
+
+def _cut(host, offs, lens):
+    """[the lens[i] bytes at offs[i] of a host array]"""
+    return [host[o:o + n].tobytes() for o, n in zip(offs.tolist(), lens.tolist())]
+
+
+def _u64_arrays(np, what, seqs, n=None):
+    """Host sequences -> (contiguous uint64 arrays as the C ABI reads them, n); ValueError(what) unless each has n elements (None: as
+    many as the first)"""
+    arr = [np.ascontiguousarray(a, dtype=np.uint64) for a in seqs]
+    n = arr[0].size if n is None else n
+    if any(a.size != n for a in arr):
+        raise ValueError(what)
+    return arr, n
+
+
+def _guess_cap(stream, w):
+    """The decoded capacity to try first for a stream of unknown size: gzip's ISIZE, else max(4 x input, 64 KiB); below 2^32"""
+    guess = max(4 * len(stream), 1 << 16)
+    if w == WRAP_GZIP and len(stream) >= 4:
+        guess = max(int.from_bytes(stream[-4:], "little"), 1)
+    return min(guess, STREAM_MAX_OUT - 1)
+
+
+def _stream_error(who, st, i=None):
+    """The ZwzError of a stream that ended with status st (stream i of a batch; None: the call's only one)"""
+    err = ZwzError("%s: status %d" % (who, st) if i is None else "%s: stream %d: status %d" % (who, i, st))
+    err.status, err.index, err.stream_status = E_FORMAT, i or 0, int(st)
+    return err
+
+
 def sort_files_by_size(path):
     buf = ctypes.create_string_buffer(4096)
     _check(lib().zwz_sort_files_by_size(os.fsencode(path), buf, len(buf)), "zwz_sort_files_by_size")
@@ -1516,17 +1398,12 @@ def pack_indexes(indexes, idx_off=None):
     import numpy as np
     lens = np.array([len(x) for x in indexes], dtype=np.uint64)
     if idx_off is None:
-        off = np.zeros(len(lens), dtype=np.uint64)
-        if len(lens):
-            off[1:] = np.cumsum((lens[:-1] + 15) // 16 * 16)
+        off, _ = _layout(np, lens)
     else:
         off = np.ascontiguousarray(idx_off, dtype=np.uint64)
         if len(off) != len(lens):
             raise ValueError("one offset per index")
-    blob = np.zeros(int((off + lens).max()) + 16 if len(lens) else 16, dtype=np.uint8)
-    for x, o in zip(indexes, off.tolist()):
-        blob[o:o + len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
-    return PackedIndexes(blob, off, lens)
+    return PackedIndexes(_blob(np, int((off + lens).max()) + 16 if len(lens) else 16, indexes, off), off, lens)
 
 
 def index_info(index):
