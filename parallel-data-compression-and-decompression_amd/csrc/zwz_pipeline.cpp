@@ -31,6 +31,7 @@
 #include <thread>
 #include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include <fcntl.h>
@@ -39,6 +40,7 @@
 #include <sys/uio.h>
 #include <unistd.h>
 
+#include "pipeline_core.h"
 #include "zwz_api_internal.h"
 #include "zwz_md5.h"
 
@@ -52,9 +54,7 @@ bool verbose() { static int v = getenv("ZWZ_VERBOSE") ? 1 : 0; return v != 0; }
 // are a load of their own (tools/e2e.py measures with this)
 bool timeline() { static int v = (getenv("ZWZ_TIMELINE") || getenv("ZWZ_VERBOSE")) ? 1 : 0; return v != 0; }
 
-// Chunks per staging slice.  A slice costs 2 x 64 KiB of pinned host memory per chunk, twice (double buffering), and pinning is
-// slow (0.2 s for 4096-chunk slices, a quarter of a 2 GB job); 2048 chunks still give every CU eight chunks a launch.
-constexpr uint32_t kSliceChunks = 2048;
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 bool blank(const std::string& s) {
     return std::all_of(s.begin(), s.end(), [](unsigned char ch) { return std::isspace(ch) != 0; });
@@ -137,8 +137,15 @@ unsigned host_threads() {
 }
 
 // Two staging slices (in / out slots, offsets, lengths, status), pinned on the host and mirrored on
-// the device; reuses the context's staging allocation.
+// the device; reuses the context's staging allocation.  It owns its queues, events and MD5 staging: released when it goes, or
+// earlier by release().  The pool's tasks write into its slots, so DECLARE IT BEFORE THE Drain of the tasks that use it (it is
+// then destroyed after that Drain has waited), whatever the way out of the function.
 struct Slices {
+    Slices() = default;
+    Slices(const Slices&) = delete;
+    Slices& operator=(const Slices&) = delete;
+    ~Slices() { release(); }
+    void release();        // (idempotent)
     uint32_t cap = 0;      // chunks per slice
     uint8_t *h_in[2], *h_out[2], *d_in[2], *d_out[2];
     uint64_t *h_off[2], *d_off[2];
@@ -186,14 +193,11 @@ int make_slices(zwz_ctx* c, uint32_t cap, Slices& s) {
     return ZWZ_OK;
 }
 
-void free_slices(Slices& s) {                 // (idempotent: scope guards call it again behind the timed call of the normal path)
-    if (s.s_in) { (void)hipStreamSynchronize(s.s_in); (void)hipStreamDestroy(s.s_in); s.s_in = nullptr; }
-    if (s.s_out) { (void)hipStreamSynchronize(s.s_out); (void)hipStreamDestroy(s.s_out); s.s_out = nullptr; }
-    for (auto& e : s.done) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    for (auto& e : s.ev_in) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    for (auto& e : s.ev_k) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (s.md5_host) { (void)hipHostFree(s.md5_host); s.md5_host = nullptr; }
-    if (s.md5_dev) { (void)hipFree(s.md5_dev); s.md5_dev = nullptr; }
+void Slices::release() {
+    for (hipStream_t* q : {&s_in, &s_out}) if (*q) { (void)hipStreamSynchronize(*q); (void)hipStreamDestroy(*q); *q = nullptr; }
+    for (auto* evs : {done, ev_in, ev_k}) for (int i = 0; i < 2; i++) if (evs[i]) { (void)hipEventDestroy(evs[i]); evs[i] = nullptr; }
+    if (md5_host) { (void)hipHostFree(md5_host); md5_host = nullptr; }
+    if (md5_dev) { (void)hipFree(md5_dev); md5_dev = nullptr; }
 }
 
 // Waits for every listed task group when its scope is left, however that happens: tasks capture the enclosing function's
@@ -202,6 +206,76 @@ struct Drain {
     Pool& pool; std::vector<Pool::Group*> groups;
     ~Drain() { for (Pool::Group* g : groups) pool.wait(*g); }
 };
+
+// Slice s, m chunks, through buffer pair b = s & 1 and the three queues (see Slices): copy in, `kernels(b, m)` -- which queues the
+// codec and the MD5 kernel on the context's stream and returns a status --, copy out; done[b] then says the slice is back.
+template <class Kernels>
+int slice_through(zwz_ctx* c, Slices& sl, uint32_t s, uint32_t m, Kernels&& kernels) {
+    const int b = (int)(s & 1u);
+    // copy in (its own queue): the pair's device buffers were last read by the kernels of slice s - 2
+    if (s >= 2) HIPCHK(hipStreamWaitEvent(sl.s_in, sl.ev_k[b], 0));
+    HIPCHK(hipMemcpyAsync(sl.d_in[b], sl.h_in[b], (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyHostToDevice, sl.s_in));
+    HIPCHK(hipMemcpyAsync(sl.d_len[b], sl.h_len[b], m * sizeof(uint32_t), hipMemcpyHostToDevice, sl.s_in));
+    HIPCHK(hipMemcpyAsync(sl.d_off[b], sl.h_off[b], m * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s_in));
+    if (sl.n_md5[b]) HIPCHK(hipMemcpyAsync(sl.d_files[b], sl.h_files[b], (size_t)sl.n_md5[b] * 8, hipMemcpyHostToDevice, sl.s_in));
+    HIPCHK(hipEventRecord(sl.ev_in[b], sl.s_in));
+    // the kernels (the codec's stream): behind the copy in, and behind the copy out of slice s - 2, which read d_out[b]
+    HIPCHK(hipStreamWaitEvent(c->stream, sl.ev_in[b], 0));
+    if (s >= 2) HIPCHK(hipStreamWaitEvent(c->stream, sl.done[b], 0));
+    if (int r = kernels(b, m)) return r;
+    HIPCHK(hipEventRecord(sl.ev_k[b], c->stream));
+    // copy out (its own queue)
+    HIPCHK(hipStreamWaitEvent(sl.s_out, sl.ev_k[b], 0));
+    if (sl.n_md5[b]) HIPCHK(hipMemcpyAsync(sl.h_dig[b], sl.d_dig[b], (size_t)sl.n_md5[b] * 16, hipMemcpyDeviceToHost, sl.s_out));
+    HIPCHK(hipMemcpyAsync(sl.h_out[b], sl.d_out[b], (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyDeviceToHost, sl.s_out));
+    HIPCHK(hipMemcpyAsync(sl.h_olen[b], sl.d_olen[b], m * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.s_out));
+    HIPCHK(hipEventRecord(sl.done[b], sl.s_out));
+    return ZWZ_OK;
+}
+
+// The double-buffered slice loop: while slice s is on the GPU, slice s + 1 is filled and slice s - 1 drained.  Per trip: wait for
+// fill s, launch s (which ends by recording done[s & 1]), wait for done of s - 1, after_done(s - 1) (what must read the pair's
+// host slots before the next fill overwrites them), start fill s + 1 into that pair, drain s - 1; the trip s = nslices is the
+// tail, for the last slice.  The first status that is not ZWZ_OK ends it.  t_gpu accumulates the waits for done.
+template <class WaitFill, class Launch, class AfterDone, class StartFill, class DrainSlice>
+int slice_loop(Slices& sl, uint32_t nslices, double& t_gpu, WaitFill&& wait_fill, Launch&& launch, AfterDone&& after_done, StartFill&& start_fill,
+               DrainSlice&& drain) {
+    if (nslices) start_fill(0);
+    for (uint32_t s = 0; nslices && s <= nslices; s++) {
+        if (s < nslices) { wait_fill(s); if (int rc = launch(s)) return rc; }
+        if (s >= 1) {
+            const double t0 = now_s();
+            const hipError_t e = hipEventSynchronize(sl.done[(s - 1) & 1]);
+            t_gpu += now_s() - t0;
+            if (e != hipSuccess) return hip_fail(e, "hipEventSynchronize");
+            after_done(s - 1);
+        }
+        if (s + 1 < nslices) start_fill(s + 1);       // its buffers were last used by slice s - 1, now complete
+        if (s >= 1) drain(s - 1);
+    }
+    return ZWZ_OK;
+}
+
+// The digest of a file as it is on disk, as 32 hex characters + NUL.  False: it could not be opened (the digest is then that of no bytes).
+bool md5_of_path(const std::string& path, char hex[33]) {
+    Md5 m;
+    std::vector<uint8_t> buf(1 << 20);
+    const int fd = open(path.c_str(), O_RDONLY);
+    for (uint64_t off = 0; fd >= 0;) {
+        ssize_t k = pread(fd, buf.data(), buf.size(), (off_t)off);
+        if (k < 0 && errno == EINTR) continue;
+        if (k <= 0) break;
+        m.update(buf.data(), (size_t)k); off += (uint64_t)k;
+    }
+    if (fd >= 0) close(fd);
+    m.hex(hex);
+    return fd >= 0;
+}
+
+// pwritev of the pieces at a known file offset, at most max_pieces a call -> whether all of it was written
+bool pwritev_all(int fd, std::vector<struct iovec>& iov, uint64_t off, size_t max_pieces) {
+    return write_pieces([fd](struct iovec* v, int cnt, uint64_t at) { return pwritev(fd, v, cnt, (off_t)at); }, iov.data(), iov.size(), off, max_pieces);
+}
 
 // Raw bytes per Chunk.  process.hpp:12 fixes 65535 and the shards are bit-exact only with it (the default).  SURVEY.md
 // section 8 f4, opt-in and never default: ZWZ_LOSSLESS=1 cuts files every 65509 bytes instead -- the largest size whose level-6
@@ -258,132 +332,88 @@ int zwz_ctx_set_chunk_size(zwz_ctx* c, uint32_t bytes) {
 
 namespace {
 
-int compress_dir_impl(zwz_ctx* c, const char* src_dir, const char* dst_dir, const char* file_record, int rank, int nranks) {
-    const uint32_t chunk_bytes = chunk_bytes_for(c);
-    const auto t_entry = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {          // ZWZ_VERBOSE: the pipeline's own timeline
-        if (timeline()) fprintf(stderr, "zwz: [%.3f s] %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count(), what);
-    };
-    std::vector<std::string> lines;
-    {
-        std::ifstream f(file_record);
-        if (!f.is_open()) { set_error("cannot open file record %s", file_record); return ZWZ_E_IO; }
-        std::string s;
-        while (std::getline(f, s)) lines.push_back(s);
+// ---- compress: one rank's files into its shard.  compress_dir_impl (below) is the sequence of steps; steps 2 and 3 are members
+// of CompressJob, which holds what the pool's tasks and the caller's thread share.
+struct SrcFile { std::string rel, full; bool ok = false; uint64_t size = 0; uint32_t first_chunk = 0, nchunks = 0; std::string md5;
+                 int32_t gpu_md5 = -1; };   // index into its slice's GPU digest list, or -1: hashed on the host
+struct FileTable { std::vector<SrcFile> files; uint64_t chunks = 0; };
+struct CloseFd { int fd; ~CloseFd() { if (fd >= 0) close(fd); } };
+
+// Step 1: this rank's files (compression.cpp:35-41), sized, laid out as chunks back to back; a file that cannot be opened is
+// logged and skipped (:45-48).
+FileTable list_files(Pool& pool, const std::vector<std::string>& lines, const char* src_dir, int rank, int nranks, uint32_t chunk_bytes) {
+    // Sizes come from stat(), on the pool; a file is opened only by the task that reads it and closed right after.
+    // (Holding every source file open needed one descriptor per file -- 370 k of them in BASELINE's config 4 -- and
+    // grew the descriptor table step by step, each step a synchronize_rcu() in a process the HIP runtime has made
+    // multi-threaded: 80 us per open(), 0.7 s for 8 000 files, more than the rest of the job.  tools/exp/open_hip.cpp)
+    FileTable t;
+    std::vector<SrcFile> cand;
+    for (size_t i = (size_t)rank; i < lines.size(); i += (size_t)nranks) {
+        SrcFile f;
+        f.rel = lines[i];
+        f.full = (fs::path(src_dir) / f.rel).string();
+        cand.push_back(std::move(f));
     }
-    int non_empty = 0;
-    for (const auto& s : lines) if (!s.empty() && !blank(s)) non_empty++;
-    if (rank >= non_empty) return ZWZ_OK;   // main.cpp:47-51: this rank has nothing to do and creates no shard
-
-    // this rank's files (compression.cpp:35-41); a file that cannot be opened is logged and skipped (:45-48)
-    struct File { std::string rel, full; bool ok; uint64_t size; uint32_t first_chunk, nchunks; std::string md5; std::atomic<int>* md5_ready;
-                  int32_t gpu_md5 = -1; };   // index into its slice's GPU digest list, or -1: hashed on the host
-    std::vector<File> files;
-    uint64_t total_chunks = 0;
-    mark("file list read");
-    Pool pool(host_threads());
-    // The pinned staging (0.1 s for 2 x 2 048 chunks: hipHostMalloc pins page by page) is allocated by a helper thread while this one sizes the
-    // files; its size only needs an upper bound of the chunk count, which the list's length gives for the common case (cap is re-derived below).
-    HIPCHK(hipSetDevice(c->device));
-    std::thread staging_thread;
-    int staging_rc = ZWZ_OK;
-    const uint32_t early_cap = std::max(1u, std::min(c->max_batch, kSliceChunks));
-    const bool early_staging = lines.size() / (size_t)nranks >= early_cap;        // at least a slice's worth of files: the full-size staging is what will be asked for
-    if (early_staging) staging_thread = std::thread([&] { (void)hipSetDevice(c->device); staging_rc = ensure_staging(c, 2 * early_cap); });
-    struct JoinStaging { std::thread& t; ~JoinStaging() { if (t.joinable()) t.join(); } } join_staging{staging_thread};
-    {   // Sizes come from stat(), on the pool; a file is opened only by the task that reads it and closed right after.
-        // (Holding every source file open needed one descriptor per file -- 370 k of them in BASELINE's config 4 -- and
-        // grew the descriptor table step by step, each step a synchronize_rcu() in a process the HIP runtime has made
-        // multi-threaded: 80 us per open(), 0.7 s for 8 000 files, more than the rest of the job.  tools/exp/open_hip.cpp)
-        std::vector<File> cand;
-        for (size_t i = (size_t)rank; i < lines.size(); i += (size_t)nranks) {
-            File f;
-            f.rel = lines[i];
-            f.full = (fs::path(src_dir) / f.rel).string();
-            f.ok = false; f.size = 0; f.md5_ready = nullptr;
-            cand.push_back(std::move(f));
-        }
-        Pool::Group stat_group;
-        const size_t stat_per = std::max<size_t>(32, std::min<size_t>(256, cand.size() / (4 * host_threads()) + 1));
-        for (size_t i0 = 0; i0 < cand.size(); i0 += stat_per)
-            pool.submit(stat_group, [&cand, i0, stat_per] {
-                for (size_t i = i0; i < std::min(cand.size(), i0 + stat_per); i++) {
-                    File& f = cand[i];
-                    struct stat sb;
-                    if (stat(f.full.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && access(f.full.c_str(), R_OK) == 0) { f.ok = true; f.size = (uint64_t)sb.st_size; }
-                }
-            });
-        pool.wait(stat_group);
-        for (File& f : cand) {                     // in list order, like the reference's producer
-            if (!f.ok) { fprintf(stderr, "Error opening source file: \"%s\"\n", f.full.c_str()); continue; }
-            f.nchunks = (uint32_t)(f.size / chunk_bytes) + 1;   // a short (possibly empty) read ends the file (:52-58)
-            f.first_chunk = (uint32_t)total_chunks;
-            total_chunks += f.nchunks;
-            files.push_back(std::move(f));
-        }
+    Pool::Group stat_group;
+    const size_t stat_per = std::max<size_t>(32, std::min<size_t>(256, cand.size() / (4 * host_threads()) + 1));
+    for (size_t i0 = 0; i0 < cand.size(); i0 += stat_per)
+        pool.submit(stat_group, [&cand, i0, stat_per] {
+            for (size_t i = i0; i < std::min(cand.size(), i0 + stat_per); i++) {
+                SrcFile& f = cand[i];
+                struct stat sb;
+                if (stat(f.full.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && access(f.full.c_str(), R_OK) == 0) { f.ok = true; f.size = (uint64_t)sb.st_size; }
+            }
+        });
+    pool.wait(stat_group);
+    for (SrcFile& f : cand) {                     // in list order, like the reference's producer
+        if (!f.ok) { fprintf(stderr, "Error opening source file: \"%s\"\n", f.full.c_str()); continue; }
+        f.nchunks = (uint32_t)(f.size / chunk_bytes) + 1;   // a short (possibly empty) read ends the file (:52-58)
+        f.first_chunk = (uint32_t)t.chunks;
+        t.chunks += f.nchunks;
+        t.files.push_back(std::move(f));
     }
-    if (total_chunks > 0xffffffffull) { set_error("too many chunks"); return ZWZ_E_INVALID; }
-    mark("source files sized");
-    std::vector<std::atomic<int>> ready(files.size());
-    for (size_t i = 0; i < files.size(); i++) { ready[i].store(0); files[i].md5_ready = &ready[i]; }
+    return t;
+}
 
-    const std::string out_path = (fs::path(dst_dir) / ("compressed_" + std::to_string(rank) + ".zwz")).string();
-    const int dest = open(out_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (dest < 0) { set_error("cannot create %s", out_path.c_str()); return ZWZ_E_IO; }
-
-    const uint32_t T = (uint32_t)total_chunks;
-    const uint32_t cap = std::max(1u, std::min(c->max_batch, std::min(kSliceChunks, (T + 1) / 2 + 1)));
-    Slices sl;
-    const double t_alloc0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    if (staging_thread.joinable()) staging_thread.join();
-    if (staging_rc) { close(dest); return staging_rc; }
-    int rc = make_slices(c, cap, sl);
-    if (timeline()) fprintf(stderr, "zwz: staging for 2 x %u chunks ready after another %.3f s (pinned beside the file sizing)\n", cap,
-                           std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_alloc0);
-    if (rc) { free_slices(sl); close(dest); return rc; }
-    const uint32_t nslices = (T + cap - 1) / cap;
-
-    // Everything the pool's tasks reach by reference is declared BEFORE the Drain (destroyed after it has waited), the staging and
-    // the shard's descriptor under guards of their own: an exception on this thread (an allocation in a vector) then unwinds
-    // through a function whose tasks have finished and whose resources are released.
-    struct Rec { uint64_t off; uint32_t slot; int32_t path_len, seq, payload; uint8_t last; const std::string* rel; const char* md5; };
-    std::vector<Rec> recs;
-    std::vector<char> hexes;                     // digests that came back from the GPU as 16 raw bytes, as text
-    std::atomic<int> io_error{0}, write_error{0};
-    uint32_t truncated = 0;
-    uint64_t out_pos = 0;                        // shard bytes laid out so far
-    struct Release { Slices& sl; const int& fd; ~Release() { free_slices(sl); if (fd >= 0) close(fd); } };
-    int dest_open = dest;                        // -1 once the normal path has closed it
-    Release release{sl, dest_open};
-    Pool::Group md5_group, read_group[2], write_group;
-    Drain drain{pool, {&md5_group, &read_group[0], &read_group[1], &write_group}};
-    // chunk g -> (file, chunk index in file): files are laid out back to back
-    auto file_of = [&](uint32_t g) -> uint32_t {
-        uint32_t lo = 0, hi = (uint32_t)files.size() - 1;
-        while (lo < hi) { uint32_t mid = (lo + hi + 1) / 2; if (files[mid].first_chunk <= g) lo = mid; else hi = mid - 1; }
-        return lo;
-    };
-    auto hash_whole_file = [&](uint32_t fi) {     // md5_of_file(): re-read (verification.cpp:6-30)
-        Md5 m;
-        std::vector<uint8_t> buf(1 << 20);
-        uint64_t off = 0;
-        const int fd = open(files[fi].full.c_str(), O_RDONLY);
-        if (fd < 0) io_error.store(1);
-        for (; fd >= 0;) {
-            ssize_t k = pread(fd, buf.data(), buf.size(), (off_t)off);
-            if (k < 0 && errno == EINTR) continue;
-            if (k <= 0) break;
-            m.update(buf.data(), (size_t)k); off += (uint64_t)k;
-        }
-        if (fd >= 0) close(fd);
-        char hex[33]; m.hex(hex);
-        files[fi].md5 = hex; files[fi].md5_ready->store(1);
-    };
+struct CompressJob {
+    zwz_ctx* c; Pool& pool; std::vector<SrcFile>& files; const uint32_t chunk_bytes, T, cap; const int dest;
     // a file that lies whole inside a slice is hashed on the GPU from the chunk slots the codec
     // reads anyway (one lane per file); files cut by a slice boundary or read in pieces are hashed by host workers
     // like before.  ZWZ_HOST_MD5=1 keeps everything on the host.
     const bool gpu_md5 = getenv("ZWZ_HOST_MD5") == nullptr;
-    auto start_read = [&](uint32_t s) {
+    const uint32_t consumers = [] { const char* v = getenv("ZWZ_CONSUMERS"); const long k = v ? atol(v) : 1; return (uint32_t)(k < 1 ? 1 : k > 64 ? 64 : k); }();
+    Slices sl;
+    std::vector<char> hexes;                    // digests that came back from the GPU as 16 raw bytes, as text
+    std::vector<std::atomic<int>> md5_ready = std::vector<std::atomic<int>>(files.size());     // per file: its md5 (hashed on the host) is there
+    std::atomic<int> io_error{0}, write_error{0};
+    uint32_t truncated = 0;
+    uint64_t out_pos = 0;                        // shard bytes laid out so far
+    Pool::Group md5_group, read_group[2];
+    Drain drain{pool, {&md5_group, &read_group[0], &read_group[1]}};      // the last member: it waits before anything above goes
+
+    // chunk g -> (file, chunk index in file): files are laid out back to back
+    uint32_t file_of(uint32_t g) const {
+        return (uint32_t)(std::upper_bound(files.begin(), files.end(), g, [](uint32_t v, const SrcFile& f) { return v < f.first_chunk; }) - files.begin()) - 1;
+    }
+    void hash_whole_file(uint32_t fi) {           // md5_of_file(): re-read (verification.cpp:6-30)
+        char hex[33];
+        if (!md5_of_path(files[fi].full, hex)) io_error.store(1);
+        files[fi].md5 = hex; md5_ready[fi].store(1);
+    }
+    // a whole file read as ONE unit is hashed by its reader (or the GPU); every other file -- cut by a slice boundary, or
+    // read in pieces -- by hash_whole_file.  Those tasks only need the source file, and MD5 is one sequential stream per
+    // file (~0.65 GB/s), so they all go out at the start: submitted when the pipeline reached the file, three 384 MiB files were
+    // hashed one after the other with the record writer waiting for each digest in turn.
+    void start_rehashes() {
+        for (uint32_t fi = 0; fi < (uint32_t)files.size(); fi++) {
+            const SrcFile& f = files[fi];
+            const bool whole = f.first_chunk / cap == (f.first_chunk + f.nchunks - 1) / cap;
+            if (!whole || f.nchunks > 64) pool.submit(md5_group, [this, fi] { hash_whole_file(fi); }, /*background=*/true);
+        }
+    }
+
+    // Step 2: the readers of slice s -- chunks pread() into the pinned input slots of buffer pair s & 1.
+    void start_read(uint32_t s) {
         const int b = (int)(s & 1u);
         const uint32_t g0 = s * cap, g1 = std::min(T, g0 + cap);
         uint32_t g = g0;
@@ -397,16 +427,13 @@ int compress_dir_impl(zwz_ctx* c, const char* src_dir, const char* dst_dir, cons
         uint32_t batch_chunks = 0;
         auto flush = [&] {
             if (batch.empty()) return;
-            pool.submit(read_group[b], [&, b, g0, units = std::move(batch)] {
-              for (const Unit& un : units) {
-                const uint32_t fi = un.fi, u0 = un.u0, u1 = un.u1;
-                const bool hash_here = un.hash_here;
-                {
-                    const File& ff = files[fi];
+            pool.submit(read_group[b], [this, b, g0, units = std::move(batch)] {
+                for (const Unit& un : units) {
+                    const SrcFile& ff = files[un.fi];
                     Md5 m;
                     const int fd = open(ff.full.c_str(), O_RDONLY);
                     if (fd < 0) io_error.store(1);
-                    for (uint32_t ci = u0; ci < u1; ci++) {
+                    for (uint32_t ci = un.u0; ci < un.u1; ci++) {
                         const uint32_t slot = ff.first_chunk + ci - g0;
                         uint8_t* dstp = sl.h_in[b] + (size_t)slot * ZWZ_DEV_STRIDE;
                         const uint64_t off = (uint64_t)ci * chunk_bytes;
@@ -421,18 +448,17 @@ int compress_dir_impl(zwz_ctx* c, const char* src_dir, const char* dst_dir, cons
                         if (got != want) io_error.store(1);       // the file shrank under us
                         sl.h_off[b][slot] = (uint64_t)slot * ZWZ_DEV_STRIDE;
                         sl.h_len[b][slot] = (uint32_t)got;
-                        if (hash_here) m.update(dstp, got);
+                        if (un.hash_here) m.update(dstp, got);
                     }
                     if (fd >= 0) close(fd);
-                    if (hash_here) { char hex[33]; m.hex(hex); files[fi].md5 = hex; files[fi].md5_ready->store(1); }
+                    if (un.hash_here) { char hex[33]; m.hex(hex); files[un.fi].md5 = hex; md5_ready[un.fi].store(1); }
                 }
-              }
             });
             batch.clear(); batch_chunks = 0;
         };
         while (g < g1) {
             const uint32_t fi = file_of(g);
-            File& f = files[fi];
+            SrcFile& f = files[fi];
             const uint32_t c0 = g - f.first_chunk, c1 = std::min(f.nchunks, c0 + (g1 - g));
             const bool whole = c0 == 0 && c1 == f.nchunks;
             for (uint32_t u0 = c0; u0 < c1; u0 += 64) {
@@ -450,54 +476,32 @@ int compress_dir_impl(zwz_ctx* c, const char* src_dir, const char* dst_dir, cons
             g += c1 - c0;
         }
         flush();
-    };
-    // a whole file read as ONE unit is hashed by its reader (or the GPU); every other file -- cut by a slice boundary, or
-    // read in pieces -- by hash_whole_file.  Those tasks only need the source file, and MD5 is one sequential stream per
-    // file (~0.65 GB/s), so they all go out NOW: submitted when the pipeline reached the file, three 384 MiB files were
-    // hashed one after the other with the record writer waiting for each digest in turn.
-    for (uint32_t fi = 0; fi < (uint32_t)files.size(); fi++) {
-        const File& f = files[fi];
-        const bool whole = f.first_chunk / cap == (f.first_chunk + f.nchunks - 1) / cap;
-        if (!whole || f.nchunks > 64) pool.submit(md5_group, [&, fi] { hash_whole_file(fi); }, /*background=*/true);
     }
-    auto launch_gpu = [&](uint32_t s) -> int {
+
+    int launch(uint32_t s) {                   // deflate, and MD5 over the input slots (offsets are relative to the slice's d_in)
+        return slice_through(c, sl, s, std::min(T, (s + 1) * cap) - s * cap, [this](int b, uint32_t m) {
+            int r = zwz_deflate_batch_dev(c, sl.d_in[b], sl.d_off[b], sl.d_len[b], m, sl.d_out[b], ZWZ_DEV_STRIDE, sl.d_olen[b]);
+            if (r == ZWZ_OK && sl.n_md5[b]) r = zwz_md5_files_dev(c, sl.d_in[b], sl.d_off[b], sl.d_len[b], sl.d_files[b], sl.n_md5[b], sl.d_dig[b]);
+            return r;
+        });
+    }
+
+    void count_truncated(uint32_t s) {          // payloads that reached the 65535-byte cap: lossy, like the reference
         const int b = (int)(s & 1u);
         const uint32_t m = std::min(T, (s + 1) * cap) - s * cap;
-        // copy in (its own queue): the pair's device buffers were last read by the kernels of slice s - 2
-        if (s >= 2) HIPCHK(hipStreamWaitEvent(sl.s_in, sl.ev_k[b], 0));
-        HIPCHK(hipMemcpyAsync(sl.d_in[b], sl.h_in[b], (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyHostToDevice, sl.s_in));
-        HIPCHK(hipMemcpyAsync(sl.d_len[b], sl.h_len[b], m * sizeof(uint32_t), hipMemcpyHostToDevice, sl.s_in));
-        HIPCHK(hipMemcpyAsync(sl.d_off[b], sl.h_off[b], m * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s_in));
-        if (sl.n_md5[b]) HIPCHK(hipMemcpyAsync(sl.d_files[b], sl.h_files[b], (size_t)sl.n_md5[b] * 8, hipMemcpyHostToDevice, sl.s_in));
-        HIPCHK(hipEventRecord(sl.ev_in[b], sl.s_in));
-        // the kernels (the codec's stream): behind the copy in, and behind the copy out of slice s - 2, which read d_out[b]
-        HIPCHK(hipStreamWaitEvent(c->stream, sl.ev_in[b], 0));
-        if (s >= 2) HIPCHK(hipStreamWaitEvent(c->stream, sl.done[b], 0));
-        // offsets are relative to this slice's d_in
-        int r = zwz_deflate_batch_dev(c, sl.d_in[b], sl.d_off[b], sl.d_len[b], m, sl.d_out[b], ZWZ_DEV_STRIDE, sl.d_olen[b]);
-        if (r) return r;
-        if (sl.n_md5[b]) {
-            r = zwz_md5_files_dev(c, sl.d_in[b], sl.d_off[b], sl.d_len[b], sl.d_files[b], sl.n_md5[b], sl.d_dig[b]);
-            if (r) return r;
-        }
-        HIPCHK(hipEventRecord(sl.ev_k[b], c->stream));
-        // copy out (its own queue)
-        HIPCHK(hipStreamWaitEvent(sl.s_out, sl.ev_k[b], 0));
-        if (sl.n_md5[b]) HIPCHK(hipMemcpyAsync(sl.h_dig[b], sl.d_dig[b], (size_t)sl.n_md5[b] * 16, hipMemcpyDeviceToHost, sl.s_out));
-        HIPCHK(hipMemcpyAsync(sl.h_out[b], sl.d_out[b], (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyDeviceToHost, sl.s_out));
-        HIPCHK(hipMemcpyAsync(sl.h_olen[b], sl.d_olen[b], m * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.s_out));
-        HIPCHK(hipEventRecord(sl.done[b], sl.s_out));
-        return ZWZ_OK;
-    };
-    // data_writer(), compression.cpp:73-104.  The shard is one file, but every record's place in it is known once the
-    // slice's payload lengths are back: the caller's thread lays the slice out (and waits for the digests it needs),
-    // then the pool writes it, each worker its own run of records with pwritev straight from the pinned output slots
-    // -- a single buffered writer copied every payload twice and was the whole pipeline's pace (1.9 GB/s).
-    const uint32_t consumers = [] { const char* v = getenv("ZWZ_CONSUMERS"); const long k = v ? atol(v) : 1; return (uint32_t)(k < 1 ? 1 : k > 64 ? 64 : k); }();
-    auto write_records = [&](uint32_t s) {
+        for (uint32_t i = 0; i < m; i++) if (sl.h_olen[b][i] == ZWZ_CHUNK_SIZE && sl.h_len[b][i] >= 65510u) truncated++;
+    }
+
+    // Step 3: data_writer(), compression.cpp:73-104.  Every record's place in the shard is known once the slice's payload
+    // lengths are back: the caller's thread lays the slice out (and waits for the digests it needs), then writes it with
+    // pwritev straight from the pinned output slots.
+    void write_records(uint32_t s) {
         const int b = (int)(s & 1u);
         const uint32_t g0 = s * cap, g1 = std::min(T, g0 + cap);
-        recs.clear(); recs.reserve(g1 - g0);
+        struct Rec { uint32_t slot; int32_t path_len, seq, payload; uint8_t last; const std::string* rel; const char* md5; };
+        std::vector<Rec> recs;
+        recs.reserve(g1 - g0);
+        const uint64_t off0 = out_pos;           // where this slice's records begin in the shard
         hexes.resize((size_t)cap * 32);          // (sl.n_md5[b] already counts the slice being read into this buffer pair)
         // SURVEY.md section 8 f4, opt-in and never default: ZWZ_CONSUMERS=k writes a slice's records the way k of the reference's
         // consumers (process.hpp:13 NUM_CONSUMERS, shipped as 1) might finish them -- every run of k consecutive chunks of a file
@@ -522,21 +526,18 @@ int compress_dir_impl(zwz_ctx* c, const char* src_dir, const char* dst_dir, cons
         }
         for (uint32_t e = 0; e < g1 - g0; e++) {
             const uint32_t g = order[e];
-            const File& f = files[file_idx[g - g0]];
+            const SrcFile& f = files[file_idx[g - g0]];
             Rec r;
             r.slot = g - g0; r.seq = (int32_t)(g - f.first_chunk); r.last = r.seq + 1 == (int32_t)f.nchunks;
             r.path_len = (int32_t)f.rel.size(); r.payload = (int32_t)sl.h_olen[b][r.slot]; r.rel = &f.rel; r.md5 = nullptr;
-            r.off = out_pos;
             out_pos += 4u + 4u + (uint64_t)r.path_len + 4u + 1u + (uint64_t)r.payload;
             if (r.last) {
                 if (f.gpu_md5 >= 0) {
-                    static const char* dig = "0123456789abcdef";
-                    const uint8_t* d = sl.h_dig[b] + (size_t)f.gpu_md5 * 16;
                     char* hex = hexes.data() + (size_t)f.gpu_md5 * 32;
-                    for (int i = 0; i < 16; i++) { hex[2 * i] = dig[d[i] >> 4]; hex[2 * i + 1] = dig[d[i] & 15]; }
+                    digest_hex(sl.h_dig[b] + (size_t)f.gpu_md5 * 16, hex);
                     r.md5 = hex;
                 } else {
-                    while (!f.md5_ready->load()) std::this_thread::yield();
+                    while (!md5_ready[file_idx[g - g0]].load()) std::this_thread::yield();
                     r.md5 = f.md5.data();          // 32 hex characters (verification.cpp:24-27)
                 }
                 out_pos += 32u;
@@ -547,94 +548,106 @@ int compress_dir_impl(zwz_ctx* c, const char* src_dir, const char* dst_dir, cons
         // pwritev on their own runs of records (rounds 1-4) wrote it at 4 - 8 GB/s, each waiting for the others' lock; one thread writing
         // the records in order reaches 8.5 (tmpfs) to 13 GB/s (the box's overlay file system) -- tools/exp/shard_write.cpp.  The GPU works on
         // the next slice and the pool reads the one after it meanwhile.
-        {
-            const size_t n = recs.size();
-            std::vector<int32_t> hdr;  hdr.reserve(4 * n);                   // total, path_len | seq per record
-            std::vector<struct iovec> iov; iov.reserve(6 * n);
-            for (size_t i = 0; i < n; i++) {
-                const Rec& r = recs[i];
-                hdr.push_back(4 + r.path_len + 4 + 1 + r.payload); hdr.push_back(r.path_len); hdr.push_back(r.seq); hdr.push_back(0);
-            }
-            for (size_t i = 0; i < n; i++) {
-                const Rec& r = recs[i];
-                int32_t* h = hdr.data() + 4 * i;
-                iov.push_back({h, 8});
-                iov.push_back({const_cast<char*>(r.rel->data()), (size_t)r.path_len});
-                iov.push_back({h + 2, 4});
-                iov.push_back({const_cast<uint8_t*>(&r.last), 1});
-                iov.push_back({sl.h_out[b] + (size_t)r.slot * ZWZ_DEV_STRIDE, (size_t)r.payload});
-                if (r.last) iov.push_back({const_cast<char*>(r.md5), 32});
-            }
-            uint64_t off = n ? recs[0].off : 0;
-            size_t k = 0;
-            while (k < iov.size()) {                                         // pwritev: at most IOV_MAX pieces a call, and it may stop short
-                if (iov[k].iov_len == 0) { k++; continue; }
-                const int cnt = (int)std::min<size_t>(1024, iov.size() - k);
-                ssize_t w = pwritev(dest, iov.data() + k, cnt, (off_t)off);
-                if (w < 0 && errno == EINTR) continue;
-                if (w <= 0) { write_error.store(1); break; }
-                off += (uint64_t)w;
-                size_t left = (size_t)w;
-                while (left) {
-                    if (left >= iov[k].iov_len) { left -= iov[k].iov_len; k++; }
-                    else { iov[k].iov_base = static_cast<char*>(iov[k].iov_base) + left; iov[k].iov_len -= left; left = 0; }
-                }
-            }
+        const size_t n = recs.size();
+        std::vector<int32_t> hdr(4 * n);                                 // total, path_len | seq per record
+        std::vector<struct iovec> iov; iov.reserve(6 * n);
+        for (size_t i = 0; i < n; i++) {
+            const Rec& r = recs[i];
+            int32_t* h = hdr.data() + 4 * i;
+            h[0] = 4 + r.path_len + 4 + 1 + r.payload; h[1] = r.path_len; h[2] = r.seq;
+            iov.push_back({h, 8});
+            iov.push_back({const_cast<char*>(r.rel->data()), (size_t)r.path_len});
+            iov.push_back({h + 2, 4});
+            iov.push_back({const_cast<uint8_t*>(&r.last), 1});
+            iov.push_back({sl.h_out[b] + (size_t)r.slot * ZWZ_DEV_STRIDE, (size_t)r.payload});
+            if (r.last) iov.push_back({const_cast<char*>(r.md5), 32});
         }
-        pool.wait(write_group);                 // the slice's buffers go back to the GPU next
-    };
+        if (!pwritev_all(dest, iov, off0, 1024)) write_error.store(1);      // (at most IOV_MAX pieces a call)
+    }
+};
 
-    auto count_truncated = [&](uint32_t s) {      // payloads that reached the 65535-byte cap: lossy, like the reference
-        const int b = (int)(s & 1u);
-        const uint32_t m = std::min(T, (s + 1) * cap) - s * cap;
-        for (uint32_t i = 0; i < m; i++) if (sl.h_olen[b][i] == ZWZ_CHUNK_SIZE && sl.h_len[b][i] >= 65510u) truncated++;
+int compress_dir_impl(zwz_ctx* c, const char* src_dir, const char* dst_dir, const char* file_record, int rank, int nranks) {
+    const uint32_t chunk_bytes = chunk_bytes_for(c);
+    const auto t_entry = std::chrono::steady_clock::now();
+    auto mark = [&](const char* what) {          // ZWZ_VERBOSE: the pipeline's own timeline
+        if (timeline()) fprintf(stderr, "zwz: [%.3f s] %s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count(), what);
     };
-    // (ZWZ_VERBOSE: where the caller's thread spent its time)
+    std::vector<std::string> lines;
+    {
+        std::ifstream f(file_record);
+        if (!f.is_open()) { set_error("cannot open file record %s", file_record); return ZWZ_E_IO; }
+        std::string s;
+        while (std::getline(f, s)) lines.push_back(s);
+    }
+    int non_empty = 0;
+    for (const auto& s : lines) if (!s.empty() && !blank(s)) non_empty++;
+    if (rank >= non_empty) return ZWZ_OK;   // main.cpp:47-51: this rank has nothing to do and creates no shard
+    mark("file list read");
+    Pool pool(host_threads());
+    // The pinned staging (0.1 s for 2 x 2 048 chunks: hipHostMalloc pins page by page) is allocated by a helper thread while this one sizes the
+    // files; its size only needs an upper bound of the chunk count, which the list's length gives for the common case (cap is re-derived below).
+    // The error text is thread-local: the helper hands its own over, for this thread to set again after the join.
+    HIPCHK(hipSetDevice(c->device));
+    int staging_rc = ZWZ_OK;
+    std::string staging_error;
+    std::thread staging_thread;
+    const uint32_t early_cap = std::max(1u, std::min(c->max_batch, kSliceChunks));
+    const bool early_staging = lines.size() / (size_t)nranks >= early_cap;        // at least a slice's worth of files: the full-size staging is what will be asked for
+    if (early_staging) staging_thread = std::thread([&] {
+        (void)hipSetDevice(c->device);
+        staging_rc = ensure_staging(c, 2 * early_cap);
+        if (staging_rc) staging_error = zwz_last_error();
+    });
+    struct JoinStaging { std::thread& t; ~JoinStaging() { if (t.joinable()) t.join(); } } join_staging{staging_thread};
+
+    FileTable table = list_files(pool, lines, src_dir, rank, nranks, chunk_bytes);                  // step 1
+    if (table.chunks > 0xffffffffull) { set_error("too many chunks"); return ZWZ_E_INVALID; }
+    mark("source files sized");
+
+    const std::string out_path = (fs::path(dst_dir) / ("compressed_" + std::to_string(rank) + ".zwz")).string();
+    CloseFd shard{open(out_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666)};
+    if (shard.fd < 0) { set_error("cannot create %s", out_path.c_str()); return ZWZ_E_IO; }
+
+    const uint32_t T = (uint32_t)table.chunks;
+    const uint32_t cap = slice_cap(c->max_batch, T);
+    const double t_alloc0 = now_s();
+    if (staging_thread.joinable()) staging_thread.join();
+    if (staging_rc) { set_error("%s", staging_error.c_str()); return staging_rc; }
+    CompressJob job{c, pool, table.files, chunk_bytes, T, cap, shard.fd};
+    int rc = make_slices(c, cap, job.sl);
+    if (timeline()) fprintf(stderr, "zwz: staging for 2 x %u chunks ready after another %.3f s (pinned beside the file sizing)\n", cap, now_s() - t_alloc0);
+    if (rc) return rc;
+    const uint32_t nslices = (T + cap - 1) / cap;
+    job.start_rehashes();
+
+    // step 4: the loop (ZWZ_VERBOSE: where the caller's thread spent its time)
     double t_read = 0, t_gpu = 0, t_write = 0;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
+    const double t_begin = now_s();
     mark("first slice's reads queued");
-    if (nslices) start_read(0);
-    for (uint32_t s = 0; s < nslices && rc == ZWZ_OK; s++) {
-        double t0 = now();
-        pool.wait(read_group[s & 1]);
-        t_read += now() - t0;
-        rc = launch_gpu(s);
-        if (rc) break;
-        t0 = now();
-        if (s >= 1) { hipError_t e = hipEventSynchronize(sl.done[(s - 1) & 1]); if (e != hipSuccess) { rc = hip_fail(e, "hipEventSynchronize"); break; } }
-        t_gpu += now() - t0;
-        if (s >= 1) count_truncated(s - 1);           // (reads h_len, which the next slice's readers are about to overwrite)
-        if (s + 1 < nslices) start_read(s + 1);       // its buffers were last used by slice s-1, now complete
-        t0 = now();
-        if (s >= 1) write_records(s - 1);
-        t_write += now() - t0;
-    }
-    if (rc == ZWZ_OK && nslices) {
-        double t0 = now();
-        hipError_t e = hipEventSynchronize(sl.done[(nslices - 1) & 1]);
-        t_gpu += now() - t0; t0 = now();
-        if (e != hipSuccess) rc = hip_fail(e, "hipEventSynchronize"); else { count_truncated(nslices - 1); write_records(nslices - 1); }
-        t_write += now() - t0;
-    }
+    rc = slice_loop(job.sl, nslices, t_gpu,
+                    [&](uint32_t s) { const double t0 = now_s(); pool.wait(job.read_group[s & 1]); t_read += now_s() - t0; },
+                    [&](uint32_t s) { return job.launch(s); },
+                    [&](uint32_t s) { job.count_truncated(s); },       // (reads h_len, which the next slice's readers are about to overwrite)
+                    [&](uint32_t s) { job.start_read(s); },                                                          // step 2
+                    [&](uint32_t s) { const double t0 = now_s(); job.write_records(s); t_write += now_s() - t0; });     // step 3
     if (timeline())
         fprintf(stderr, "zwz: %u slices of <= %u chunks in %.3f s: waiting for reads %.3f s, for the GPU %.3f s, writing %.3f s\n",
-                nslices, cap, now() - t_begin, t_read, t_gpu, t_write);
+                nslices, cap, now_s() - t_begin, t_read, t_gpu, t_write);
     mark("last slice written");
-    pool.wait(read_group[0]); pool.wait(read_group[1]); pool.wait(md5_group);
+    // step 5: close
+    pool.wait(job.read_group[0]); pool.wait(job.read_group[1]); pool.wait(job.md5_group);
     (void)hipStreamSynchronize(c->stream);
     mark("workers and stream idle");
-    const double t_free0 = now();
-    free_slices(sl);
-    if (timeline()) fprintf(stderr, "zwz: staging released in %.3f s\n", now() - t_free0);
-    if (write_error.load() && rc == ZWZ_OK) { set_error("writing %s failed", out_path.c_str()); rc = ZWZ_E_IO; }
-    dest_open = -1;
-    if (close(dest) != 0 && rc == ZWZ_OK) rc = ZWZ_E_IO;
+    const double t_free0 = now_s();
+    job.sl.release();
+    if (timeline()) fprintf(stderr, "zwz: staging released in %.3f s\n", now_s() - t_free0);
+    if (job.write_error.load() && rc == ZWZ_OK) { set_error("writing %s failed", out_path.c_str()); rc = ZWZ_E_IO; }
+    if (close(std::exchange(shard.fd, -1)) != 0 && rc == ZWZ_OK) rc = ZWZ_E_IO;
     mark("shard closed");
-    if (io_error.load() && rc == ZWZ_OK) { set_error("a source file changed or vanished while it was being read"); rc = ZWZ_E_IO; }
+    if (job.io_error.load() && rc == ZWZ_OK) { set_error("a source file changed or vanished while it was being read"); rc = ZWZ_E_IO; }
     { std::string why; if (pool.failed(&why) && rc == ZWZ_OK) { set_error("a pipeline task failed: %s", why.c_str()); rc = ZWZ_E_IO; } }
-    if (truncated && timeline())
-        fprintf(stderr, "zwz: %u chunk payload(s) reached the reference's 65535-byte cap (lossy, like the reference)\n", truncated);
+    if (job.truncated && timeline())
+        fprintf(stderr, "zwz: %u chunk payload(s) reached the reference's 65535-byte cap (lossy, like the reference)\n", job.truncated);
     return rc;
 }
 
@@ -743,18 +756,8 @@ struct DecodeSink {
         }
     }
     void hash_from_disk(uint32_t inst) const {                   // md5_of_file(), verification.cpp:6-30
-        Md5 m;
-        const std::string file_path = path_of(inst);
-        const int fd = open(file_path.c_str(), O_RDONLY);
-        std::vector<uint8_t> buf(1 << 20);
-        for (uint64_t off = 0; fd >= 0;) {
-            ssize_t k = pread(fd, buf.data(), buf.size(), (off_t)off);
-            if (k < 0 && errno == EINTR) continue;
-            if (k <= 0) break;
-            m.update(buf.data(), (size_t)k); off += (uint64_t)k;
-        }
-        if (fd >= 0) close(fd);
-        char hex[33]; m.hex(hex);
+        char hex[33];
+        (void)md5_of_path(path_of(inst), hex);
         verdict(inst, hex);
     }
     // The same digest, taken WHILE the file is being written: the hash trails the writers -- it reads what `durable` says is on disk,
@@ -786,20 +789,21 @@ struct DecodeSink {
     }
 };
 
-// pwritev of a run of decoded chunks at a known file offset
-void pwrite_chunks(int fd, uint64_t off, std::vector<struct iovec>& iov) {
-    size_t k = 0;
-    while (k < iov.size()) {
-        if (iov[k].iov_len == 0) { k++; continue; }
-        ssize_t w = pwritev(fd, iov.data() + k, (int)std::min<size_t>(512, iov.size() - k), (off_t)off);
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) break;                            // (a short file then fails its MD5 check)
-        off += (uint64_t)w;
-        size_t left = (size_t)w;
-        while (left) {
-            if (left >= iov[k].iov_len) { left -= iov[k].iov_len; k++; }
-            else { iov[k].iov_base = static_cast<char*>(iov[k].iov_base) + left; iov[k].iov_len -= left; left = 0; }
-        }
+// The copy tasks of a slice's fill: the payloads of records jobs[base, base + count) from the mapped shard into the input slots
+// 0 .. count - 1 of buffer pair b, a payload the shard cuts short filled up with zeros, and the slots' offsets and lengths.
+void start_fill_tasks(Pool& pool, Pool::Group& group, const Mapped& blob, const std::vector<Job>& jobs, uint32_t base, uint32_t count, Slices& sl, int b) {
+    const uint32_t per_task = std::max(32u, std::min(256u, sl.cap / (2u * host_threads())));
+    for (uint32_t u0 = 0; u0 < count; u0 += per_task) {
+        const uint32_t u1 = std::min(count, u0 + per_task);
+        pool.submit(group, [&blob, &jobs, &sl, base, b, u0, u1] {
+            for (uint32_t k = u0; k < u1; k++) {
+                const Rec& r = jobs[base + k].r;
+                uint8_t* slot = sl.h_in[b] + (size_t)k * ZWZ_DEV_STRIDE;
+                memcpy(slot, &blob[r.off], r.avail);
+                if (r.avail < r.len) memset(slot + r.avail, 0, r.len - r.avail);
+                sl.h_off[b][k] = (uint64_t)k * ZWZ_DEV_STRIDE; sl.h_len[b][k] = r.len;
+            }
+        });
     }
 }
 
@@ -836,16 +840,15 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
     double t_gpu_wait = 0, t_write_wait = 0;
     for (uint32_t i = 0; i < insts.size(); i++) outs[i].remaining = (uint32_t)insts[i].order.size();
     const uint32_t T = (uint32_t)jobs.size();
-    const uint32_t cap = std::max(1u, std::min(c->max_batch, std::min(kSliceChunks, (T + 1) / 2 + 1)));
+    const uint32_t cap = slice_cap(c->max_batch, T);
     Slices sl;
     int rc = make_slices(c, cap, sl);
-    if (rc) { free_slices(sl); return rc; }
+    if (rc) return rc;
     const uint32_t nslices = (T + cap - 1) / cap;
-    struct FreeSlices { Slices& s; ~FreeSlices() { free_slices(s); } } free_sl{sl};      // behind the Drain: released once the tasks are done, whatever the way out
     Pool::Group fill_group[2], write_group, md5_group;
     Drain drain{pool, {&fill_group[0], &fill_group[1], &write_group, &md5_group}};
     // A trailing hash ends only when its file is complete.  On every way out of the slice loop that leaves a file incomplete -- an
-    // error `break`, an exception unwinding through write_slice -- its hash is told to give up, BEFORE anything waits for md5_group:
+    // error out of slice_loop, an exception unwinding through write_slice -- its hash is told to give up, BEFORE anything waits for md5_group:
     // called below on an error, and by this guard (declared after the Drain: destroyed, and so run, before the Drain waits).
     auto abandon_hashes = [&outs] { for (OutState& o : outs) if (o.hashing && !o.complete.load()) o.abandoned.store(1, std::memory_order_release); };
     struct Abandon { decltype(abandon_hashes)& f; ~Abandon() { f(); } } abandon{abandon_hashes};
@@ -871,7 +874,7 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
         OutState& o = outs[inst];
         if (o.f) { fclose(o.f); o.f = nullptr; }
         char hex[33];
-        if (digest) { static const char* dig = "0123456789abcdef"; for (int i = 0; i < 16; i++) { hex[2 * i] = dig[digest[i] >> 4]; hex[2 * i + 1] = dig[digest[i] & 15]; } hex[32] = 0; }
+        if (digest) { digest_hex(digest, hex); hex[32] = 0; }
         else o.md5.hex(hex);
         sink.verdict(inst, hex);
     };
@@ -891,45 +894,14 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
                 }
                 g = e;
             }
-        const uint32_t per_task = std::max(32u, std::min(256u, cap / (2u * host_threads())));
-        for (uint32_t u0 = g0; u0 < g1; u0 += per_task) {
-            const uint32_t u1 = std::min(g1, u0 + per_task);
-            pool.submit(fill_group[b], [&, b, g0, u0, u1] {
-                for (uint32_t g = u0; g < u1; g++) {
-                    const Rec& r = jobs[g].r;
-                    uint8_t* slot = sl.h_in[b] + (size_t)(g - g0) * ZWZ_DEV_STRIDE;
-                    memcpy(slot, &blob[r.off], r.avail);
-                    if (r.avail < r.len) memset(slot + r.avail, 0, r.len - r.avail);
-                    sl.h_off[b][g - g0] = (uint64_t)(g - g0) * ZWZ_DEV_STRIDE; sl.h_len[b][g - g0] = r.len;
-                }
-            });
-        }
+        start_fill_tasks(pool, fill_group[b], blob, jobs, g0, g1 - g0, sl, b);
     };
-    auto launch_gpu = [&](uint32_t s) -> int {
-        const int b = (int)(s & 1u);
-        const uint32_t m = std::min(T, (s + 1) * cap) - s * cap;
-        // three queues, as on the compress side (see Slices)
-        if (s >= 2) HIPCHK(hipStreamWaitEvent(sl.s_in, sl.ev_k[b], 0));
-        HIPCHK(hipMemcpyAsync(sl.d_in[b], sl.h_in[b], (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyHostToDevice, sl.s_in));
-        HIPCHK(hipMemcpyAsync(sl.d_len[b], sl.h_len[b], m * sizeof(uint32_t), hipMemcpyHostToDevice, sl.s_in));
-        HIPCHK(hipMemcpyAsync(sl.d_off[b], sl.h_off[b], m * sizeof(uint64_t), hipMemcpyHostToDevice, sl.s_in));
-        if (sl.n_md5[b]) HIPCHK(hipMemcpyAsync(sl.d_files[b], sl.h_files[b], (size_t)sl.n_md5[b] * 8, hipMemcpyHostToDevice, sl.s_in));
-        HIPCHK(hipEventRecord(sl.ev_in[b], sl.s_in));
-        HIPCHK(hipStreamWaitEvent(c->stream, sl.ev_in[b], 0));
-        if (s >= 2) HIPCHK(hipStreamWaitEvent(c->stream, sl.done[b], 0));
-        int r = zwz_inflate_batch_dev(c, sl.d_in[b], sl.d_off[b], sl.d_len[b], m, sl.d_out[b], ZWZ_DEV_STRIDE, sl.d_olen[b], sl.d_st[b]);
-        if (r) return r;
-        if (sl.n_md5[b]) {      // (output slot k sits at k * 65536, which is what d_off holds for the input slots)
-            r = zwz_md5_files_dev(c, sl.d_out[b], sl.d_off[b], sl.d_olen[b], sl.d_files[b], sl.n_md5[b], sl.d_dig[b]);
-            if (r) return r;
-        }
-        HIPCHK(hipEventRecord(sl.ev_k[b], c->stream));
-        HIPCHK(hipStreamWaitEvent(sl.s_out, sl.ev_k[b], 0));
-        if (sl.n_md5[b]) HIPCHK(hipMemcpyAsync(sl.h_dig[b], sl.d_dig[b], (size_t)sl.n_md5[b] * 16, hipMemcpyDeviceToHost, sl.s_out));
-        HIPCHK(hipMemcpyAsync(sl.h_out[b], sl.d_out[b], (size_t)m * ZWZ_DEV_STRIDE, hipMemcpyDeviceToHost, sl.s_out));
-        HIPCHK(hipMemcpyAsync(sl.h_olen[b], sl.d_olen[b], m * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.s_out));
-        HIPCHK(hipEventRecord(sl.done[b], sl.s_out));
-        return ZWZ_OK;
+    auto launch_gpu = [&](uint32_t s) {        // inflate, and MD5 over the output slots (slot k sits at k * 65536, which is what d_off holds for the input slots)
+        return slice_through(c, sl, s, std::min(T, (s + 1) * cap) - s * cap, [&](int b, uint32_t m) {
+            int r = zwz_inflate_batch_dev(c, sl.d_in[b], sl.d_off[b], sl.d_len[b], m, sl.d_out[b], ZWZ_DEV_STRIDE, sl.d_olen[b], sl.d_st[b]);
+            if (r == ZWZ_OK && sl.n_md5[b]) r = zwz_md5_files_dev(c, sl.d_out[b], sl.d_off[b], sl.d_olen[b], sl.d_files[b], sl.n_md5[b], sl.d_dig[b]);
+            return r;
+        });
     };
     // One task per file that has records in this slice -- a file decoded within one slice is written (stdio) and hashed
     // by it.  A file that spans slices is written with pwritev at offsets laid out here, 128 records a task, and
@@ -998,7 +970,7 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
                         std::vector<struct iovec> iov;
                         for (uint32_t k = r0; k < r1; k++)
                             if (sl.h_olen[b][k - g0]) iov.push_back({sl.h_out[b] + (size_t)(k - g0) * ZWZ_DEV_STRIDE, (size_t)sl.h_olen[b][k - g0]});
-                        pwrite_chunks(fd, off0, iov);
+                        (void)pwritev_all(fd, iov, off0, 512);      // (a write that fails leaves a short file, which then fails its MD5 check)
                     });
                 }
                 os.remaining -= a1 - a0;
@@ -1029,28 +1001,14 @@ int decode_whole_shard(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
         finish_spanning();
     };
 
-    if (nslices && rc == ZWZ_OK) start_fill(0);
-    for (uint32_t s = 0; s < nslices && rc == ZWZ_OK; s++) {
-        pool.wait(fill_group[s & 1]);
-        rc = launch_gpu(s);
-        if (rc) break;
-        if (s >= 1) { const double t0 = since(); hipError_t e = hipEventSynchronize(sl.done[(s - 1) & 1]); t_gpu_wait += since() - t0; if (e != hipSuccess) { rc = hip_fail(e, "hipEventSynchronize"); break; } }
-        if (s + 1 < nslices) start_fill(s + 1);
-        if (s >= 1) write_slice(s - 1);
-    }
-    if (rc == ZWZ_OK && nslices) {
-        const double t0 = since();
-        hipError_t e = hipEventSynchronize(sl.done[(nslices - 1) & 1]);
-        t_gpu_wait += since() - t0;
-        if (e != hipSuccess) rc = hip_fail(e, "hipEventSynchronize"); else write_slice(nslices - 1);
-    }
+    rc = slice_loop(sl, nslices, t_gpu_wait, [&](uint32_t s) { pool.wait(fill_group[s & 1]); }, launch_gpu, [](uint32_t) {}, start_fill, write_slice);
     if (rc != ZWZ_OK) abandon_hashes();           // (before the wait for md5_group below)
     const double t_slices = since();
     pool.wait(fill_group[0]); pool.wait(fill_group[1]); pool.wait(md5_group);
     if (timeline()) fprintf(stderr, "zwz: decode: %u records of %zu files in %u slices done at %.3f s (waited %.3f s for the GPU, %.3f s for the writers); "
                                    "spanning files hashed by %.3f s\n", T, insts.size(), nslices, t_slices, t_gpu_wait, t_write_wait, since());
     (void)hipStreamSynchronize(c->stream);
-    free_slices(sl);
+    sl.release();
     // instances that never received a decodable record still get created (the reference opens on the first record of a path)
     for (uint32_t i = 0; i < insts.size(); i++)
         if (insts[i].order.empty()) { open_out(i); finish_out(i, nullptr); }
@@ -1081,6 +1039,8 @@ int decode_shard_split(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
     // (the exchanges' buffers first: once they exist, nothing below can keep this rank from joining its peers)
     std::vector<uint64_t> all((size_t)nranks * kFields), flags((size_t)nranks);
     int rc = rc_in;
+    // (the rule that no way out skips an exchange lives here: both phases run inside `shielded`, and nothing between this point and
+    //  the second exchange returns, except after an exchange that itself failed)
     auto shielded = [&](const char* what, auto&& body) {
         try { body(); }
         catch (const std::bad_alloc&) { if (rc == ZWZ_OK) { set_error("out of host memory while %s", what); rc = ZWZ_E_NOMEM; } }
@@ -1096,19 +1056,18 @@ int decode_shard_split(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
     uint8_t* d_big = nullptr; uint32_t* d_lens = nullptr; uint32_t* d_stat = nullptr;
     std::vector<uint32_t> lens, stats;      // decoded length and end-of-stream status of every chunk of the range (phase 1)
     Slices sl;
-    bool have_slices = false;
-    const uint32_t cap = std::max(1u, std::min(c->max_batch, std::min(kSliceChunks, n ? (n + 1) / 2 + 1 : 1u)));
+    const uint32_t cap = slice_cap(c->max_batch, n);
     const uint32_t nslices = (n + cap - 1) / cap;
     uint32_t res = 0;                            // chunks [0, res) of the range stay in d_big between the phases (whole slices)
     auto cleanup = [&] {                         // (idempotent: also run by the guard below on any way out)
         (void)hipStreamSynchronize(c->stream);
-        if (have_slices) free_slices(sl);
+        sl.release();
         if (d_big) { (void)hipFree(d_big); d_big = nullptr; }
         if (d_lens) { (void)hipFree(d_lens); d_lens = nullptr; }
         if (d_stat) { (void)hipFree(d_stat); d_stat = nullptr; }
     };
     struct Cleanup { decltype(cleanup)& f; ~Cleanup() { f(); } } cleanup_guard{cleanup};
-    // (declared before the Drain -- destroyed after it has waited: the write tasks reach fds and cursor by reference)
+    // (like the Slices above, before the Drain: the write tasks reach fds and cursor by reference)
     std::vector<int> fds;
     struct CloseFds { std::vector<int>& v; ~CloseFds() { for (int& fd : v) if (fd >= 0) { close(fd); fd = -1; } } } close_fds{fds};
     std::vector<uint64_t> cursor;
@@ -1117,19 +1076,7 @@ int decode_shard_split(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
     auto start_fill = [&](uint32_t s) {
         const int b = (int)(s & 1u);
         const uint32_t g0 = s * cap, g1 = std::min(n, g0 + cap);
-        const uint32_t per_task = std::max(32u, std::min(256u, cap / (2u * host_threads())));
-        for (uint32_t u0 = g0; u0 < g1; u0 += per_task) {
-            const uint32_t u1 = std::min(g1, u0 + per_task);
-            pool.submit(fill_group[b], [&, b, g0, u0, u1] {
-                for (uint32_t g = u0; g < u1; g++) {
-                    const Rec& r = jobs[j0 + g].r;
-                    uint8_t* slot = sl.h_in[b] + (size_t)(g - g0) * ZWZ_DEV_STRIDE;
-                    memcpy(slot, &blob[r.off], r.avail);
-                    if (r.avail < r.len) memset(slot + r.avail, 0, r.len - r.avail);
-                    sl.h_off[b][g - g0] = (uint64_t)(g - g0) * ZWZ_DEV_STRIDE; sl.h_len[b][g - g0] = r.len;
-                }
-            });
-        }
+        start_fill_tasks(pool, fill_group[b], blob, jobs, j0 + g0, g1 - g0, sl, b);
     };
     // slice s: payloads to the device, inflated into `target` (cap slots), decoded lengths to d_len_out
     auto inflate_slice = [&](uint32_t s, uint8_t* target, uint32_t* d_len_out, uint32_t* d_stat_out) -> int {
@@ -1149,7 +1096,7 @@ int decode_shard_split(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
             if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_stat), (size_t)n * sizeof(uint32_t));
             // (no early return on any of these: the failure travels through the exchanges below)
             if (e != hipSuccess) { (void)hipGetLastError(); set_error("no device memory for the lengths of %u chunks: %s", n, hipGetErrorString(e)); rc = ZWZ_E_NOMEM; }
-            else { rc = make_slices(c, cap, sl); have_slices = rc == ZWZ_OK; }
+            else rc = make_slices(c, cap, sl);
             if (rc == ZWZ_OK) {
                 // what stays resident between the phases: whole slices, within the budget; a failed allocation halves it, down to nothing
                 uint64_t budget = n;
@@ -1166,6 +1113,8 @@ int decode_shard_split(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
             }
         }
         // ---- phase 1: payloads in, range inflated; the first `res` chunks stay, of the others only the decoded lengths come back
+        // (a loop of its own: nothing is drained and the stream synchronise below waits for the last slice, so slice_loop would bring
+        //  two empty hooks, an unused timer and one more wait)
         if (nslices && rc == ZWZ_OK) start_fill(0);
         for (uint32_t s = 0; s < nslices && rc == ZWZ_OK; s++) {
             const int b = (int)(s & 1u);
@@ -1256,7 +1205,7 @@ int decode_shard_split(zwz_ctx* c, Pool& pool, const Mapped& blob, std::vector<F
                     pool.submit(write_group, [&, b, g0, fd, r0, r1, off0] {
                         std::vector<struct iovec> iov;
                         for (uint32_t k = r0; k < r1; k++) if (lens[k]) iov.push_back({sl.h_out[b] + (size_t)(k - g0) * ZWZ_DEV_STRIDE, (size_t)lens[k]});
-                        pwrite_chunks(fd, off0, iov);
+                        (void)pwritev_all(fd, iov, off0, 512);      // (as in decode_whole_shard: a short file fails its MD5 check)
                     });
                 r0 = r1;
             }

@@ -7,7 +7,7 @@ can show which routes a parameter cell takes, and the CPU suite can check that t
   compress side (the digest stored in the shard)
     compress-gpu       whole inside one slice, at most 64 chunks: md5_files_kernel over the input slots
     compress-reader    the same file under ZWZ_HOST_MD5=1: hashed by the task that reads it
-    compress-rehash    cut by a slice boundary, or more than 64 chunks: hash_whole_file re-reads it
+    compress-rehash    cut by a slice boundary, or more than 64 chunks: CompressJob::hash_whole_file re-reads it
   decode side (the digest checked against the stored one)
     decode-gpu         all records inside one slice, at most 64, path not repeated: md5_files_kernel over the output slots
     decode-writer      inside one slice but more than 64 records, or ZWZ_HOST_MD5=1: the task that writes it
@@ -57,7 +57,7 @@ def sizes(layout=LAYOUT):
 
 
 def cap_for(total, k):
-    """Chunks per slice, as both directory paths size it: min(max_batch, 2048, (T + 1) / 2 + 1)."""
+    """Chunks per slice, as both directory paths size it (csrc/pipeline_core.h: slice_cap): min(max_batch, 2048, (T + 1) / 2 + 1)."""
     return max(1, min(k, SLICE_MAX, (total + 1) // 2 + 1))
 
 
