@@ -237,6 +237,19 @@ class Sequence:
         c, u = self.bgzf_offsets(), self.in_offsets()
         return [(int(c[i]), int(u[i])) for i in range(1, self.n_pieces)]
 
+    def index(self, wrap, span):
+        """The seek index zwz_deflate_streams_index_dev writes with the stream, as host bytes: the points are the piece starts at
+        65 280 k (and the empty one behind the last flush), the entries flush_index_ref.entries_of's, no windows, and the end bit
+        is behind the 03 00 that follows the last marker"""
+        import flush_index_ref
+        import index_ref
+        w = ("raw", "zlib", "gzip").index(wrap)
+        entries = flush_index_ref.entries_of(list(zip(self.out_offsets(wrap).tolist(), self.in_offsets().tolist())), self.in_len, span)
+        n = self.stream_len(wrap)
+        check = self.crc32() if wrap == "gzip" else self.adler32() if wrap == "zlib" else 0
+        end_bit = 8 * (n - len(self.trailer(wrap)) - 2) + 10
+        return index_ref.compose(index_ref.Index(w, span, n, self.in_len, end_bit, check, entries, [b""] * len(entries)))
+
     def _host(self, what, before=b"", after=b""):
         total = len(before) + sum(len(getattr(u, what)) for u in self.units) + len(after)
         assert total <= HOST_LIMIT, "no host buffer of %d bytes" % total
